@@ -22,9 +22,16 @@ Two hosts for the N > 1 island model, same JSON line:
                   host thread per island, ncclCommInitAll + ncclAllGather on the islands' streams).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4}] [--host {process,group}]
+                    [--full] [--dump-outputs DIR]
 
+A plain run does only what the headline needs: set up, settle, W warm-up steps, the K timed steps, and the result
+line (`value`, `ms_per_step`, ...).  `--full` adds everything else, after the timed region: the `sustained` loop,
+the per-kernel event pass behind `roofline` / `kernels`, the reference's full-sort schedule (`full_sort`), the
+population read-back cost, the CPU oracle baseline and the recorded reference-kernel times.
 The K timed steps run with per-kernel timing OFF (the un-instrumented loop); the per-kernel
-events behind `roofline` / `kernels` come from a separate, disclosed pass after the timed region.
+events come from a separate, disclosed pass after the timed region.
+`--dump-outputs DIR` writes the population the last timed step left (values, steps, fitness; float32 .npy),
+read back right after the timed region; inputs are seeded, so runs with the same arguments are comparable.
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -285,6 +292,10 @@ class ProcessHost:
             self.es.read_population()
         return (time.perf_counter() - t) / 5 * 1e3
 
+    def local_islands(self):
+        """(island index, context) of the islands this process owns"""
+        return [(self.rank, self.es)]
+
     def close(self):
         self.es.close()
 
@@ -337,6 +348,9 @@ class GroupHost:
                 es.read_population()
         return (time.perf_counter() - t) / 5 * 1e3
 
+    def local_islands(self):
+        return list(enumerate(self.islands))
+
     def close(self):
         self.g.close()
 
@@ -350,9 +364,30 @@ def timed_steps(host, steps):
     return time.perf_counter() - t0
 
 
-def measure(host, args, kernel_table, sort_full_mode):
-    """settle -> W warm-up steps -> K timed steps (timing off) -> `sustained` (timing off) -> per-kernel event pass
-    (timing on, disclosed) -> the reference's every-generation full sort (timing off)."""
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(host, out_dir, world):
+    """--dump-outputs: each island's population as a caller reads it back (sots_read_population: values, strategy
+    steps, fitness, rows in order) as float32 DIR/<name>.npy - `values` / `steps` / `fitness` for one island,
+    `island<i>_values` ... for several.  Above DUMP_LIMIT_BYTES in all, a fixed seeded sample of the rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    for i, es in host.local_islands():
+        v, s, f = es.read_population()
+        row_bytes = v[0].nbytes + s[0].nbytes + f[:1].nbytes
+        keep = DUMP_LIMIT_BYTES // world // row_bytes
+        if len(f) > keep:
+            rows = np.sort(np.random.default_rng(0x5EED0001).choice(len(f), keep, replace=False))
+            v, s, f = v[rows], s[rows], f[rows]
+        prefix = "" if world == 1 else f"island{i}_"
+        for name, a in (("values", v), ("steps", s), ("fitness", f)):
+            np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def measure(host, args, kernel_table, sort_full_mode, after_timed=None):
+    """settle -> W warm-up steps -> K timed steps (timing off) -> after_timed() -> `sustained` (timing off) ->
+    per-kernel event pass (timing on, disclosed) -> the reference's every-generation full sort (timing off).
+    A plain run (no --full) sets the last three to zero length."""
     clock = host.clock
 
     def harvest():
@@ -385,6 +420,8 @@ def measure(host, args, kernel_table, sort_full_mode):
         host.init_population()
     host.run(args.warmup)
     out["seconds"] = timed_steps(host, args.steps)  # the figure of record: per-kernel timing is off
+    if after_timed is not None:
+        after_timed()  # --dump-outputs: the population the last timed step left, before anything else runs on it
     # `sustained`: the same un-instrumented loop keeps going for >= --sustain seconds: what a long run settles at
     if args.sustain > 0:
         chunk = max(8, args.steps)
@@ -424,8 +461,8 @@ def measure(host, args, kernel_table, sort_full_mode):
     return out
 
 
-def main(argv=None):
-    argv = list(sys.argv[1:] if argv is None else argv)
+def parse_args(argv):
+    """(args, scaling, workload label, config id); without --full the legs beside the headline get zero length"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -456,7 +493,7 @@ def main(argv=None):
     ap.add_argument("--full-sort", action="store_true",
                     help="the HEADLINE region sorts all P rows every generation as the reference does (SOTS_SORT_FULL); default: "
                          "the rows recombination reads are placed each generation, the rest of the order when it is read, and "
-                         "the full-sort schedule is timed beside it (`full_sort`)")
+                         "with --full the full-sort schedule is timed beside it (`full_sort`)")
     ap.add_argument("--full-sort-steps", type=int, default=None,
                     help="timed generations of the `full_sort` record (default: --steps; 0 = skip)")
     ap.add_argument("--event-steps", type=int, default=32,
@@ -467,13 +504,30 @@ def main(argv=None):
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend; gloo + --share-gpu rehearses N > 1 on a 1-GPU box")
     ap.add_argument("--share-gpu", action="store_true", help="map every rank / island to device 0 (rehearsal only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure everything beside the headline: `sustained`, the per-kernel "
+                         "event pass (`kernels`, `roofline`), `full_sort`, `pcie_inclusive`, `cpu_baseline`, the recorded "
+                         "reference-kernel times.  --sustain, --event-steps, --full-sort-steps, --no-cpu-baseline and "
+                         "--cpu-threads shape these legs; without --full none of them runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the population the last timed step left (values, steps, fitness) as float32 DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     (args.parents, args.offspring, args.synth, args.log2n, args.elites, scaling, workload, config_id) = resolve_workload(
         args.config, args.gpus, args.parents, args.offspring, args.synth, args.log2n, args.elites, args.shard_of)
     if args.full_sort_steps is None:
         args.full_sort_steps = args.steps
     if 0 < args.event_steps < 8:
         args.event_steps = 8
+    if not args.full:
+        args.sustain, args.event_steps, args.full_sort_steps = 0.0, 0, 0
+    return args, scaling, workload, config_id
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    args, scaling, workload, config_id = parse_args(argv)
 
     # N > 1 from a plain command line: start the ranks FIRST - nothing above has imported torch or opened libsots_hip
     cmd = self_launch_command(args, argv)
@@ -537,11 +591,12 @@ def main(argv=None):
         ("window+FFT+fitness", c.STAGE_FUSED_SPECTRAL, 4 * N + 4),   # audio row in, fitness out
         ("sortPopulation", c.STAGE_SORT, 16 + 8 * (2 * D + 1)))
 
+    after_timed = (lambda: dump_outputs(host, args.dump_outputs, world)) if args.dump_outputs else None
     if args.host == "process":
         with torch.cuda.stream(stream):
-            m = measure(host, args, KERNELS, c.SORT_FULL)
+            m = measure(host, args, KERNELS, c.SORT_FULL, after_timed)
     else:
-        m = measure(host, args, KERNELS, c.SORT_FULL)
+        m = measure(host, args, KERNELS, c.SORT_FULL, after_timed)
 
     secs = [m["seconds"], m["sustained"]["seconds"] if m["sustained"] else 0.0, m["full_sort"]["seconds"] if m["full_sort"] else 0.0]
     dt_max, dt_sus, dt_full = host.max_over_ranks(secs)
@@ -559,25 +614,10 @@ def main(argv=None):
     # What crossing the boundary with HOST buffers would cost (never part of `value`): a blocking
     # read of the whole population (values, steps, fitness) through the C-ABI, as a caller would do
     # that inspects every generation; the product path itself keeps the population in HBM.
-    readback_ms = host.readback_ms()
+    readback_ms = host.readback_ms() if args.full else None
 
     if rank == 0:
         value = P * world * args.steps / dt_max
-        if not kernels:
-            raise SystemExit("bench.py: no per-kernel events were recorded (--event-steps 0): the roofline record needs them")
-        dom = max(kernels, key=lambda k: kernels[k]["avg_us"])
-        dk = kernels[dom]
-        achieved = dk["alg_bytes_per_candidate"] * P / (dk["avg_us"] * 1e-6) / 1e9
-        # measured HBM bytes per launch from the committed rocprofv3 PMC passes (same workload, same kernel source)
-        wkey = f"P{P}_N{N}_{args.synth}"
-        pmc, traffic_source = load_pmc_traffic(wkey)
-        traffic = pmc.get(dom)
-        per_kernel = {}
-        for name, k in kernels.items():
-            a = k["alg_bytes_per_candidate"] * P / (k["avg_us"] * 1e-6) / 1e9
-            per_kernel[name] = {"achieved_GBs_alg": a, "frac_alg": a / HBM_PEAK_GBS, "traffic": pmc.get(name),
-                                "measured_GBs": (pmc[name] / (k["avg_us"] * 1e-6) / 1e9) if pmc.get(name) else None}
-        b_alg = 24 * N + 16
         parallelism = (f"island x{world}" if world == 1 else
                        f"island x{world}, host = one process per GPU, elites over torch.distributed ({args.backend})" if args.host == "process" else
                        f"island x{world}, host = one process (sots_group_*: a thread per island), elites over "
@@ -604,53 +644,72 @@ def main(argv=None):
                        "timed_region": "per-kernel timing off (SURVEY 8(d): un-instrumented loop)",
                        "sortPopulation": "all P rows every generation (reference behaviour)" if args.full_sort else
                                          "the rows the next recombination reads, in order, every generation; the rest of the "
-                                         "order when the population is read (DESIGN.md 4.1); `full_sort` = the reference's schedule"},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "basis": "bytes this FUSED kernel has to move (DESIGN.md 3.2), not its share of SURVEY 8(d)'s "
-                                  "stage-separated B_alg = 24N+16; that basis is given in achieved_b_alg_share / frac_b_alg_share "
-                                  "and is an effective bandwidth that exceeds 1 once stages are fused",
-                         "achieved_b_alg_share": B_ALG_SHARE[dom](N, D) * P / (dk["avg_us"] * 1e-6) / 1e9,
-                         "frac_b_alg_share": B_ALG_SHARE[dom](N, D) * P / (dk["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                         "traffic_source": traffic_source,
-                         "events": f"separate pass of {args.event_steps} generations with a HIP event pair per launch on the launch "
-                                   f"stream, after the timed region (island 0 of {world})",
-                         "launches": dk["launches"],
-                         "avg_kernel_us": dk["avg_us"],
-                         "alg_bytes_per_launch": dk["alg_bytes_per_candidate"] * P},
-            "pipeline_effective": {"b_alg_unfused_bytes_per_candidate": b_alg,
-                                   "effective_GBs_per_gpu": value / world * b_alg / 1e9,
-                                   "frac_of_hbm_peak": value / world * b_alg / 1e9 / HBM_PEAK_GBS,
-                                   "note": "SURVEY 8(d) prices the reference's stage-separated pipeline at B_alg = 24N+16 bytes per "
-                                           "candidate; the fused loop applies the window on the FFT kernel's load and never "
-                                           "materialises the spectrum, so it moves about 8N. This entry is the whole-loop rate "
-                                           "priced at the unfused B_alg (an effective figure that can exceed 1); `roofline` prices "
-                                           "the dominant kernel at the bytes that kernel itself has to move"},
-            "pcie_inclusive": {"population_readback_ms": readback_ms,
-                               "bytes": P * (2 * D + 1) * 4 * (world if args.host == "group" else 1),
-                               "candidates_per_s_if_read_back_every_generation": P * world / (dt_max / args.steps + readback_ms * 1e-3),
-                               "note": "not `value`: sots_execute_generations keeps every buffer in HBM; hosts cross PCIe only for "
-                                       "the target (4N bytes in) and the final population"},
-            "kernels": kernels,
-            "roofline_per_kernel": per_kernel,
-            "sustained": sustained,
-            "full_sort": full_sort,
+                                         "order when the population is read (DESIGN.md 4.1); `full_sort` = the reference's schedule",
+                       "full": bool(args.full)},
             "settle": m["settle"],
             "best_fitness_sse": best,
             "best_fitness_mse": best / (N // 2),
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args.synth, args.log2n, target, max_threads=args.cpu_threads)
-        # a RECORD, not a measurement of this run: what the reference's own device kernels (kernels/ocl_program.cl compiled as
-        # it stands, tests/ref_kernels_time.py) took on an MI355X at configs[2] - the reference publishes no numbers
-        rec = os.path.join(ROOT, "profiles", "r04_reference_kernels.json")
-        if config_id == 2 and os.path.exists(rec):
-            with open(rec) as f:
-                r = json.load(f)
-            out["reference_kernels_record"] = {"source": "profiles/r04_reference_kernels.json (recorded, not re-run here)",
-                                               "reference_generation_us_without_its_fft": r["reference_generation_us_without_fft"],
-                                               "kernels_us": r["kernels_us"],
-                                               "this_run_generation_us": dt_max / args.steps * 1e6}
+        if args.full:
+            if not kernels:
+                raise SystemExit("bench.py: no per-kernel events were recorded (--event-steps 0): the roofline record needs them")
+            dom = max(kernels, key=lambda k: kernels[k]["avg_us"])
+            dk = kernels[dom]
+            achieved = dk["alg_bytes_per_candidate"] * P / (dk["avg_us"] * 1e-6) / 1e9
+            # measured HBM bytes per launch from the committed rocprofv3 PMC passes (same workload, same kernel source)
+            wkey = f"P{P}_N{N}_{args.synth}"
+            pmc, traffic_source = load_pmc_traffic(wkey)
+            traffic = pmc.get(dom)
+            per_kernel = {}
+            for name, k in kernels.items():
+                a = k["alg_bytes_per_candidate"] * P / (k["avg_us"] * 1e-6) / 1e9
+                per_kernel[name] = {"achieved_GBs_alg": a, "frac_alg": a / HBM_PEAK_GBS, "traffic": pmc.get(name),
+                                    "measured_GBs": (pmc[name] / (k["avg_us"] * 1e-6) / 1e9) if pmc.get(name) else None}
+            b_alg = 24 * N + 16
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                             "basis": "bytes this FUSED kernel has to move (DESIGN.md 3.2), not its share of SURVEY 8(d)'s "
+                                      "stage-separated B_alg = 24N+16; that basis is given in achieved_b_alg_share / frac_b_alg_share "
+                                      "and is an effective bandwidth that exceeds 1 once stages are fused",
+                             "achieved_b_alg_share": B_ALG_SHARE[dom](N, D) * P / (dk["avg_us"] * 1e-6) / 1e9,
+                             "frac_b_alg_share": B_ALG_SHARE[dom](N, D) * P / (dk["avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                             "traffic_source": traffic_source,
+                             "events": f"separate pass of {args.event_steps} generations with a HIP event pair per launch on the launch "
+                                       f"stream, after the timed region (island 0 of {world})",
+                             "launches": dk["launches"],
+                             "avg_kernel_us": dk["avg_us"],
+                             "alg_bytes_per_launch": dk["alg_bytes_per_candidate"] * P},
+                "pipeline_effective": {"b_alg_unfused_bytes_per_candidate": b_alg,
+                                       "effective_GBs_per_gpu": value / world * b_alg / 1e9,
+                                       "frac_of_hbm_peak": value / world * b_alg / 1e9 / HBM_PEAK_GBS,
+                                       "note": "SURVEY 8(d) prices the reference's stage-separated pipeline at B_alg = 24N+16 bytes per "
+                                               "candidate; the fused loop applies the window on the FFT kernel's load and never "
+                                               "materialises the spectrum, so it moves about 8N. This entry is the whole-loop rate "
+                                               "priced at the unfused B_alg (an effective figure that can exceed 1); `roofline` prices "
+                                               "the dominant kernel at the bytes that kernel itself has to move"},
+                "pcie_inclusive": {"population_readback_ms": readback_ms,
+                                   "bytes": P * (2 * D + 1) * 4 * (world if args.host == "group" else 1),
+                                   "candidates_per_s_if_read_back_every_generation": P * world / (dt_max / args.steps + readback_ms * 1e-3),
+                                   "note": "not `value`: sots_execute_generations keeps every buffer in HBM; hosts cross PCIe only for "
+                                           "the target (4N bytes in) and the final population"},
+                "kernels": kernels,
+                "roofline_per_kernel": per_kernel,
+                "sustained": sustained,
+                "full_sort": full_sort,
+            })
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(args.synth, args.log2n, target, max_threads=args.cpu_threads)
+            # a RECORD, not a measurement of this run: what the reference's own device kernels (kernels/ocl_program.cl compiled
+            # as it stands, tests/ref_kernels_time.py) took on an MI355X at configs[2] - the reference publishes no numbers
+            rec = os.path.join(ROOT, "profiles", "r04_reference_kernels.json")
+            if config_id == 2 and os.path.exists(rec):
+                with open(rec) as f:
+                    r = json.load(f)
+                out["reference_kernels_record"] = {"source": "profiles/r04_reference_kernels.json (recorded, not re-run here)",
+                                                   "reference_generation_us_without_its_fft": r["reference_generation_us_without_fft"],
+                                                   "kernels_us": r["kernels_us"],
+                                                   "this_run_generation_us": dt_max / args.steps * 1e6}
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

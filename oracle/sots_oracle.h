@@ -7,7 +7,7 @@
  *
  * PARITY: pinned, stage by stage, by the reference's OWN DEVICE KERNELS since round 4 - kernels/ocl_program.cl
  * compiled as it stands for gfx950 (oracle/build_ref_ocl.py -> code objects under oracle/_ref), run on an MI355X through the HIP
- * module API, inputs and outputs committed as tests/golden/ocl_ref_v1.npz (tests/test_ocl_reference.py): init,
+ * module API, inputs and outputs committed as tests/golden/ocl_ref_v1_<configuration>.npz (tests/test_ocl_reference.py): init,
  * mutation rule (given the kernel's MWC64X words), recombination (the race-free reading of an in-place kernel),
  * the three voices (sots_or_synth_ocl restates the kernels' arithmetic bit for bit; sots_or_synth follows the
  * reference's CPU path - fp32 sample-rate ratio - and stays within table steps of it), window (to the kernel's own fp32

@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Golden vectors from the REFERENCE's own kernels: runs kernels/ocl_program.cl - compiled as it stands by
 oracle/build_ref_ocl.py (build container) - on an MI355X through the HIP module API (tests/_ocl_ref.py) and writes
-inputs and outputs to tests/golden/ocl_ref_v1.npz.
+inputs and outputs to tests/golden/ocl_ref_v1_<tag>.npz, one file per configuration.
 
-Run on a GPU box:  gpurun -- 'python tests/golden/make_ocl_golden.py gpurun_out/ocl_ref_v1.npz'  and copy the file here.
+Run on a machine with an MI355X:  python tests/golden/make_ocl_golden.py OUTDIR  and copy the files here.
 Nothing of the reference travels: the code objects are what the build container compiled; this script holds inputs.
 
 Per configuration (oracle/build_ref_ocl.py CONFIGS); the exact flavour keeps everything, the asrun flavour (six-decimal
@@ -150,7 +150,8 @@ def run_config(tag, wg, d, log2n, parents, offspring, flavour, out, table):
 
 
 def main():
-    dst = sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.path.dirname(os.path.abspath(__file__)), "ocl_ref_v1.npz")
+    dst_dir = sys.argv[1] if len(sys.argv) > 1 else os.path.dirname(os.path.abspath(__file__))
+    os.makedirs(dst_dir, exist_ok=True)
     table = O.wavetable()
     out = {}
     for tag, wg, d, log2n, parents, offspring in B.CONFIGS:
@@ -158,8 +159,10 @@ def main():
             run_config(tag, wg, d, log2n, parents, offspring, flavour, out, table)
             print("ran", tag, flavour, flush=True)
             out["%s/%s/macros" % (tag, flavour)] = np.array([" ".join("%s=%s" % kv for kv in B.macros(wg, d, log2n, parents, offspring, flavour))])
-    np.savez_compressed(dst, **out)
-    print("wrote", dst, os.path.getsize(dst), "bytes")
+    for tag, *_ in B.CONFIGS:
+        dst = os.path.join(dst_dir, "ocl_ref_v1_%s.npz" % tag)
+        np.savez_compressed(dst, **{k: v for k, v in out.items() if k.startswith(tag + "/")})
+        print("wrote", dst, os.path.getsize(dst), "bytes")
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
 """bench.py's CPU-side pieces (no GPU): the cpu_baseline leg is bounded in time and in threads,
-and the roofline accounting tables cover every fused kernel."""
+the roofline accounting tables cover every fused kernel, a plain run measures the headline only
+(the rest behind --full), and --dump-outputs writes what it should."""
 import importlib
 import os
 import sys
@@ -223,3 +224,55 @@ def test_pmc_traffic_is_dropped_when_the_kernel_source_changed(tmp_path, monkeyp
         entry, src = bench.load_pmc_traffic(key)
         assert entry == {} and src.startswith("stale")
     assert bench.load_pmc_traffic("missing") == ({}, None)
+
+
+def test_plain_run_measures_the_headline_only_and_dumps_right_after_the_timed_steps():
+    """Without --full the legs beside the headline get zero length: settle, W warm-up steps, K timed steps between two
+    fences, the --dump-outputs read, and nothing else runs on the device.  --full keeps them at their defaults."""
+    bench = importlib.import_module("bench")
+    args, *_ = bench.parse_args(["--steps", "20", "--warmup", "5"])
+    assert (args.full, args.sustain, args.event_steps, args.full_sort_steps) == (False, 0.0, 0, 0)
+    full, *_ = bench.parse_args(["--steps", "20", "--warmup", "5", "--full"])
+    assert (full.full, full.sustain, full.event_steps, full.full_sort_steps) == (True, 1.0, 32, 20)
+    host = _FakeHost()
+    out = bench.measure(host, args, (("synthesise", 10, 4096),), 1, after_timed=lambda: host.log.append(("dump",)))
+    log = host.log
+    i = log.index(("run", 20))
+    assert log[i - 2:] == [("run", 5), ("fence",), ("run", 20), ("fence",), ("dump",), ("finish",)]
+    assert ("timing", True) not in log and not any(e[0] == "sort_mode" for e in log)
+    assert out["kernels"] == {} and out["sustained"] is None and out["full_sort"] is None
+    # the settle phase ran on a population that was then re-initialised before the warm-up steps
+    assert log[i - 3] == ("init",) and out["settle"]["generations"] >= 32
+
+
+class _FakeIsland:
+    def __init__(self, P, D, seed):
+        rng = np.random.default_rng(seed)
+        self.pop = (rng.random((P, D), dtype=np.float32), rng.random((P, D), dtype=np.float32), rng.random(P, dtype=np.float32))
+
+    def read_population(self):
+        return self.pop
+
+
+def test_dump_outputs_writes_float32_arrays_and_a_fixed_sample_above_the_limit(tmp_path, monkeypatch):
+    bench = importlib.import_module("bench")
+    one = _FakeIsland(100, 4, 1)
+    host = type("H", (), {"local_islands": lambda self: [(0, one)]})()
+    bench.dump_outputs(host, str(tmp_path / "one"), 1)
+    for name, a in zip(("values", "steps", "fitness"), one.pop):
+        got = np.load(tmp_path / "one" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a)
+    # several islands: one file set per island; above the byte limit a seeded, ordered subset of the rows
+    two = [(0, _FakeIsland(100, 4, 2)), (1, _FakeIsland(100, 4, 3))]
+    host = type("H", (), {"local_islands": lambda self: two})()
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 10 * 9 * 4)  # 10 rows of 2D + 1 floats per island
+    for d in ("a", "b"):
+        bench.dump_outputs(host, str(tmp_path / d), 2)
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f"island{i}_{n}.npy" for i in (0, 1) for n in ("values", "steps", "fitness"))
+    for i, isl in two:
+        f = np.load(tmp_path / "a" / f"island{i}_fitness.npy")
+        v = np.load(tmp_path / "a" / f"island{i}_values.npy")
+        assert f.shape == (10,) and v.shape == (10, 4)
+        rows = [int(np.flatnonzero(isl.pop[2] == x)[0]) for x in f]
+        assert rows == sorted(rows) and np.array_equal(v, isl.pop[0][rows])
+        assert np.array_equal(f, np.load(tmp_path / "b" / f"island{i}_fitness.npy"))

@@ -1,6 +1,7 @@
-"""bench.py as the driver calls it, on one MI355X: the plain N = 1 call, and the N = 2 island model through both
-hosts started from the plain command line (`--share-gpu`: both islands on device 0; gloo for the process host,
-since RCCL refuses two ranks on one GPU).  Checks the contract of the ONE JSON line, not the numbers.
+"""bench.py as the driver calls it, on one MI355X: the plain N = 1 call (the headline only, and its --dump-outputs),
+the --full N = 1 call, and the N = 2 island model through both hosts started from the plain command line
+(`--share-gpu`: both islands on device 0; gloo for the process host, since RCCL refuses two ranks on one GPU).
+Checks the contract of the ONE JSON line, not the numbers.
 
 Run with: python -m pytest tests -m gpu
 """
@@ -9,12 +10,17 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SMALL = ["--steps", "12", "--warmup", "3", "--sustain", "0.05", "--settle-ms", "5", "--event-steps", "8"]
+SMALL = ["--steps", "12", "--warmup", "3", "--sustain", "0.05", "--settle-ms", "5", "--event-steps", "8", "--full"]
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+            "vs_baseline", "dtype", "data", "config")
+BESIDE_THE_HEADLINE = ("roofline", "roofline_per_kernel", "kernels", "pipeline_effective", "pcie_inclusive", "sustained",
+                       "full_sort", "cpu_baseline", "reference_kernels_record")
 
 
 def run_bench(args, timeout=600):
@@ -29,8 +35,7 @@ def run_bench(args, timeout=600):
 
 
 def check_contract(d, n_gpus):
-    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-                "vs_baseline", "dtype", "data", "config", "roofline"):
+    for key in HEADLINE + ("roofline",):
         assert key in d, key
     assert d["n_gpus"] == n_gpus and d["steps"] == 12 and d["warmup"] == 3 and d["higher_is_better"] is True
     assert d["dtype"] == "f32" and d["data"] == "synthetic" and d["vs_baseline"] is None and d["value"] > 0
@@ -62,11 +67,16 @@ def test_single_gpu_line_has_roofline_cpu_baseline_and_the_full_sort_leg():
 
 
 @pytest.mark.parametrize("host,extra", [("group", []), ("group", ["--sync-migration"]), ("process", ["--backend", "gloo"])])
-def test_two_islands_from_the_plain_command_line(host, extra):
+def test_two_islands_from_the_plain_command_line(host, extra, tmp_path):
     """`python bench.py --gpus 2 ...` without any rank environment: the process host starts its two ranks itself, the
-    group host drives both islands from one process; either way one line with n_gpus = 2."""
+    group host drives both islands from one process; either way one line with n_gpus = 2, and
+    --dump-outputs writes one file set per island."""
     d = run_bench(SMALL + ["--gpus", "2", "--share-gpu", "--host", host, "--parents", "2048", "--offspring", "6144",
-                           "--no-cpu-baseline"] + extra)
+                           "--no-cpu-baseline", "--dump-outputs", str(tmp_path)] + extra)
+    assert sorted(os.listdir(tmp_path)) == sorted(f"island{i}_{n}.npy" for i in (0, 1) for n in ("fitness", "steps", "values"))
+    for i in (0, 1):
+        v, f = np.load(tmp_path / f"island{i}_values.npy"), np.load(tmp_path / f"island{i}_fitness.npy")
+        assert v.shape == (8192, 4) and f.shape == (8192,) and v.dtype == f.dtype == np.float32
     check_contract(d, 2)
     assert d["config"]["islands"] == 2 and d["config"]["host"] == host and d["config"]["elites_per_island"] == 16
     assert d["config"]["shared_gpu_rehearsal"] is True
@@ -74,3 +84,31 @@ def test_two_islands_from_the_plain_command_line(host, extra):
     assert d["config"]["migration"].startswith("same generation" if "--sync-migration" in extra else "overlapped")
     assert "cpu_baseline" not in d
     assert d["best_fitness_sse"] >= 0
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_timed_step(tmp_path):
+    """Without --full: the headline only (nothing beside it is measured), and --dump-outputs writes the population the
+    K-th timed step left.  Same arguments, same outputs; W warm-up + K timed steps reach the population that W + K
+    timed steps reach, so --steps / --warmup are the generation counts they claim to be."""
+    P = 4096 + 12288
+    common = ["--parents", "4096", "--offspring", "12288"]
+    runs = [("a", ["--steps", "12", "--warmup", "3"]), ("b", ["--steps", "12", "--warmup", "3"]), ("c", ["--steps", "15", "--warmup", "0"])]
+    dumps = {}
+    for tag, counts in runs:
+        d = run_bench(counts + common + ["--dump-outputs", str(tmp_path / tag)])
+        for key in HEADLINE:
+            assert key in d, key
+        assert not set(BESIDE_THE_HEADLINE) & set(d), set(BESIDE_THE_HEADLINE) & set(d)
+        assert d["steps"] == int(counts[1]) and d["warmup"] == int(counts[3]) and d["n_gpus"] == 1
+        assert d["dtype"] == "f32" and d["unit"] == "candidates/s" and d["higher_is_better"] is True and d["value"] > 0
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 / P - 1.0) < 1e-6
+        assert d["config"]["full"] is False
+        dumps[tag] = {name: np.load(tmp_path / tag / f"{name}.npy") for name in ("values", "steps", "fitness")}
+        assert sorted(os.listdir(tmp_path / tag)) == ["fitness.npy", "steps.npy", "values.npy"]
+        assert float(np.nanmin(dumps[tag]["fitness"])) == d["best_fitness_sse"]
+    a = dumps["a"]
+    assert a["values"].shape == (P, 4) and a["steps"].shape == (P, 4) and a["fitness"].shape == (P,)
+    assert all(x.dtype == np.float32 for x in a.values())
+    for tag in ("b", "c"):
+        for name in a:
+            assert np.array_equal(a[name], dumps[tag][name], equal_nan=True), (tag, name)

@@ -1,8 +1,8 @@
 """The oracle - and through it the HIP path - against the REFERENCE'S OWN device kernels.
 
-tests/golden/ocl_ref_v1.npz holds inputs and outputs of /root/reference/kernels/ocl_program.cl, compiled as it stands
-(oracle/build_ref_ocl.py: the image's clang in OpenCL C mode with the macro list of Evolutionary_Strategy_OpenCL.hpp:89-105)
-and run on an MI355X through the HIP module API (tests/golden/make_ocl_golden.py).  The file holds data only.
+tests/golden/ocl_ref_v1_<configuration>.npz hold inputs and outputs of the reference's kernels/ocl_program.cl, compiled as
+it stands (oracle/build_ref_ocl.py: the image's clang in OpenCL C mode with the macro list of Evolutionary_Strategy_OpenCL.hpp:89-105)
+and run on an MI355X through the HIP module API (tests/golden/make_ocl_golden.py).  The files hold data only.
 
 What the vectors pin (CPU tests, `-m "not gpu"`), row of SURVEY 8(a) by row:
   a2  initPopulation     bit-exact, given the kernel's MWC64X words (restated below: the product draws its words from a
@@ -29,7 +29,7 @@ import os
 import numpy as np
 import pytest
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ocl_ref_v1.npz")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ocl_ref_v1_%s.npz")  # one file per configuration
 # (tag, WRKGRPSIZE, D, log2 N, parents, offspring) - oracle/build_ref_ocl.py CONFIGS
 CONFIGS = [
     ("2op_n1024_p512_wg32", 32, 4, 10, 128, 384),
@@ -43,7 +43,12 @@ TABLE_STEP = 2.0 * np.pi / 32768.0  # the largest change of the sine table betwe
 
 @pytest.fixture(scope="module")
 def G():
-    return np.load(GOLDEN)
+    """every configuration's vectors, keyed "<tag>/<flavour>/<name>" as make_ocl_golden.py writes them"""
+    g = {}
+    for tag, *_ in CONFIGS:
+        with np.load(GOLDEN % tag) as z:
+            g.update((k, z[k]) for k in z.files)
+    return g
 
 
 def mwc64x(states):

@@ -3,7 +3,7 @@
 L=survival_of_the_synthesis-gpu_accelerated_frequency_modulation_parameter_matcher_amd/libsots_hip.so
 run() { # lib args...
   local lib=$1; shift
-  SOTS_LIB_PATH=$lib timeout -k 10 300 python3 bench.py --steps 200 --warmup 20 --no-cpu-baseline --full-sort-steps 0 --sustain 0.3 "$@" 2>/dev/null > /tmp/b.log
+  SOTS_LIB_PATH=$lib timeout -k 10 300 python3 bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --full-sort-steps 0 --sustain 0.3 "$@" 2>/dev/null > /tmp/b.log
   echo -n "$(basename $lib)  [$*]  "; python3 tools/show_bench.py /tmp/b.log
 }
 for rep in 1 2 3; do

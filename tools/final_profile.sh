@@ -7,7 +7,7 @@ set -e
 tag=${1:-final}; shift || true
 out=gpurun_out
 mkdir -p $out
-echo "== bench $@"; timeout -k 10 600 python bench.py "$@" > $out/${tag}_bench.json 2> $out/${tag}_bench.err; python tools/show_bench.py $out/${tag}_bench.json
+echo "== bench $@"; timeout -k 10 600 python bench.py --full "$@" > $out/${tag}_bench.json 2> $out/${tag}_bench.err; python tools/show_bench.py $out/${tag}_bench.json
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 echo "== rocprofv3 --kernel-trace --stats"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_stats -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --sustain 0 --full-sort-steps 0 "$@" > $out/${tag}_stats.log 2>&1

@@ -10,8 +10,8 @@ for c in 3 4; do
   echo "== group_overhead --config $c --islands 8"
   timeout -k 10 500 python tools/group_overhead.py --config $c --islands 8 --gens $g --quick > $out/overhead_c$c.jsonl
   echo "== bench --gpus 8 --share-gpu --host group --config $c"
-  timeout -k 10 300 python bench.py --gpus 8 --share-gpu --host group --config $c --steps 30 --warmup 5 --sustain 0.5 --full-sort-steps 0 > $out/bench_group8_c$c.json 2> $out/bench_group8_c$c.err
+  timeout -k 10 300 python bench.py --full --gpus 8 --share-gpu --host group --config $c --steps 30 --warmup 5 --sustain 0.5 --full-sort-steps 0 > $out/bench_group8_c$c.json 2> $out/bench_group8_c$c.err
   echo "== bench --gpus 4 --shard-of 8 --share-gpu --host process --backend gloo --config $c"
-  timeout -k 10 300 python bench.py --gpus 4 --shard-of 8 --share-gpu --host process --backend gloo --config $c --steps 30 --warmup 5 --sustain 0.5 --full-sort-steps 0 > $out/bench_proc4_c$c.json 2> $out/bench_proc4_c$c.err
+  timeout -k 10 300 python bench.py --full --gpus 4 --shard-of 8 --share-gpu --host process --backend gloo --config $c --steps 30 --warmup 5 --sustain 0.5 --full-sort-steps 0 > $out/bench_proc4_c$c.json 2> $out/bench_proc4_c$c.err
 done
 ls -la $out
