@@ -279,6 +279,35 @@ int sots_group_synchronize(sots_group *group);
 /* the island holding the lowest fitness and that fitness (blocking) */
 int sots_group_best(sots_group *group, uint32_t *island, float *fitness);
 
+/* ---- chunks in flight (new; the reference's parameterMatchAudio, Evolutionary_Strategy_OpenCL.hpp:572-610) ----
+ * One handle advances up to max_chunks independent populations, each of the shape cfg describes and each against
+ * its own target, with the launches of ONE population per generation (recombine+mutate | synthesise |
+ * window+FFT+fitness | sort, each over every active chunk's rows).  Chunk c of the batch computes bit for bit what a
+ * sots_ctx of the same cfg computes after sots_init_population(ctx, first_chunk_index + c) and the same calls.
+ * Limits: populationLength <= 1024 per chunk, max_chunks >= 1, max_chunks * populationLength <= 2^26.  Every
+ * generation sorts all rows of every chunk (SOTS_SORT_FULL; at these sizes a context does too).
+ * Rows are chunk-major: chunk c holds rows [c P, (c+1) P) of each rotation half. */
+typedef struct sots_batch sots_batch;
+int sots_batch_create(const sots_config *cfg, uint32_t max_chunks, sots_batch **out);
+void sots_batch_destroy(sots_batch *b);
+/* text of the last failure on b (or of the last failed sots_batch_create when b == NULL) */
+const char *sots_batch_last_error(const sots_batch *b);
+int sots_batch_synchronize(sots_batch *b);
+/* num_chunks (1..max_chunks) targets: chunk c = samples [c N, (c+1) N) / bins [c N/2, (c+1) N/2).  num_samples >=
+ * num_chunks * N; num_bins == num_chunks * N/2.  Sets the number of ACTIVE chunks for the calls below. */
+int sots_batch_set_target_audio(sots_batch *b, const float *audio, uint32_t num_samples, uint32_t num_chunks);
+int sots_batch_set_target_spectra(sots_batch *b, const float *magnitudes, uint32_t num_bins, uint32_t num_chunks);
+/* active chunk c is initialised exactly as sots_init_population(ctx, first_chunk_index + c) would */
+int sots_batch_init_population(sots_batch *b, uint32_t first_chunk_index);
+/* n generations of every active chunk; only enqueues */
+int sots_batch_execute_generations(sots_batch *b, uint32_t n);
+int sots_batch_set_synth_arithmetic(sots_batch *b, uint32_t arith); /* enum sots_synth_arith */
+/* row 0 (the best) of every active chunk: values [active][D], fitness [active] (either may be NULL); blocking */
+int sots_batch_read_best(sots_batch *b, float *values, size_t values_bytes, float *fitness, size_t fitness_bytes);
+/* one active chunk's current half; byte counts as sots_read_population; blocking */
+int sots_batch_read_population(sots_batch *b, uint32_t chunk, float *values, size_t values_bytes,
+                               float *steps, size_t steps_bytes, float *fitness, size_t fitness_bytes);
+
 /* ---- introspection ---- */
 typedef struct sots_info {
     uint32_t population_length, num_dimensions, audio_length, spectrum_row_floats;

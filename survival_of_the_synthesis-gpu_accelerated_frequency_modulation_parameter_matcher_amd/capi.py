@@ -52,7 +52,12 @@ EXPORTS = [
     "sots_group_create", "sots_group_destroy", "sots_group_last_error", "sots_group_size", "sots_group_uses_rccl",
     "sots_group_island", "sots_group_set_target_audio", "sots_group_set_target_spectrum", "sots_group_init_population",
     "sots_group_execute_generations", "sots_group_synchronize", "sots_group_best",
+    "sots_batch_create", "sots_batch_destroy", "sots_batch_last_error", "sots_batch_synchronize",
+    "sots_batch_set_target_audio", "sots_batch_set_target_spectra", "sots_batch_init_population",
+    "sots_batch_execute_generations", "sots_batch_set_synth_arithmetic", "sots_batch_read_best",
+    "sots_batch_read_population",
 ]
+BATCH_MAX_POPULATION = 1024
 GROUP_OVERLAP, GROUP_FORCE_RCCL, GROUP_UNFUSED, GROUP_EVENT_WAITS = 1, 2, 4, 8
 MAX_GROUP_DEVICES = 16
 
@@ -147,6 +152,19 @@ def load():
     L.sots_group_execute_generations.argtypes = [vp, u32]
     L.sots_group_synchronize.argtypes = [vp]
     L.sots_group_best.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_float)]
+    L.sots_batch_create.argtypes = [C.POINTER(Config), u32, C.POINTER(vp)]
+    L.sots_batch_destroy.argtypes = [vp]
+    L.sots_batch_destroy.restype = None
+    L.sots_batch_last_error.argtypes = [vp]
+    L.sots_batch_last_error.restype = C.c_char_p
+    L.sots_batch_synchronize.argtypes = [vp]
+    L.sots_batch_set_target_audio.argtypes = [vp, vp, u32, u32]
+    L.sots_batch_set_target_spectra.argtypes = [vp, vp, u32, u32]
+    L.sots_batch_init_population.argtypes = [vp, u32]
+    L.sots_batch_execute_generations.argtypes = [vp, u32]
+    L.sots_batch_set_synth_arithmetic.argtypes = [vp, u32]
+    L.sots_batch_read_best.argtypes = [vp, vp, sz, vp, sz]
+    L.sots_batch_read_population.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz]
     _lib = L
     return L
 
@@ -408,6 +426,81 @@ class HipES:
     def inject_immigrants(self, rows):
         r = _f32(rows)
         self._check(self.L.sots_inject_immigrants_host(self._h, _ptr(r), r.shape[0]))
+
+
+class HipBatch:
+    """Chunks in flight (sots_batch_* of the C-ABI): up to max_chunks independent populations of one shape, each against
+    its own target, advanced by the launches of one population per generation.  Chunk c computes bit for bit what a
+    HipES of the same arguments computes after init_population(first + c)."""
+
+    def __init__(self, max_chunks, num_parents, num_offspring, synth_kind=SYNTH_2OP, audio_log2=10, param_min=None,
+                 param_max=None, seed=0x5EED0001, workgroup_size=32, device=0, gid_base=0, num_generations=0):
+        self.L = load()
+        self.cfg = make_config(num_parents, num_offspring, synth_kind, audio_log2, param_min, param_max, seed, workgroup_size,
+                               device, gid_base, num_generations)
+        self.P, self.D, self.N = num_parents + num_offspring, SYNTH_DIMS[synth_kind], 1 << audio_log2
+        self.max_chunks = max_chunks
+        self.active = 0
+        h = C.c_void_p()
+        rc = self.L.sots_batch_create(C.byref(self.cfg), max_chunks, C.byref(h))
+        if rc != 0:
+            raise SotsError(rc, self.L.sots_batch_last_error(None).decode())
+        self._h = h
+
+    def _check(self, rc):
+        if rc != 0:
+            raise SotsError(rc, self.L.sots_batch_last_error(self._h).decode())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.L.sots_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def synchronize(self):
+        self._check(self.L.sots_batch_synchronize(self._h))
+
+    def set_target_audio(self, audio):
+        """audio[num_chunks][N] (or a flat signal cut into N-sample chunks): one target per chunk"""
+        a = _f32(audio)
+        chunks = a.shape[0] if a.ndim == 2 else a.size // self.N
+        self._check(self.L.sots_batch_set_target_audio(self._h, _ptr(a), a.size, chunks))
+        self.active = chunks
+
+    def set_target_spectra(self, mags):
+        """mags[num_chunks][N/2]"""
+        m = _f32(mags)
+        chunks = m.shape[0] if m.ndim == 2 else m.size // (self.N // 2)
+        self._check(self.L.sots_batch_set_target_spectra(self._h, _ptr(m), m.size, chunks))
+        self.active = chunks
+
+    def init_population(self, first=0):
+        self._check(self.L.sots_batch_init_population(self._h, first))
+
+    def execute_generations(self, n):
+        self._check(self.L.sots_batch_execute_generations(self._h, n))
+
+    def set_synth_arithmetic(self, arith):
+        self._check(self.L.sots_batch_set_synth_arithmetic(self._h, arith))
+
+    def read_best(self):
+        """(values[active][D], fitness[active]): row 0 of every active chunk"""
+        v = np.empty((self.active, self.D), np.float32)
+        f = np.empty(self.active, np.float32)
+        self._check(self.L.sots_batch_read_best(self._h, _ptr(v), v.nbytes, _ptr(f), f.nbytes))
+        return v, f
+
+    def read_population(self, chunk):
+        v = np.empty((self.P, self.D), np.float32)
+        s = np.empty((self.P, self.D), np.float32)
+        f = np.empty(self.P, np.float32)
+        self._check(self.L.sots_batch_read_population(self._h, chunk, _ptr(v), v.nbytes, _ptr(s), s.nbytes, _ptr(f), f.nbytes))
+        return v, s, f
 
 
 class HipGroup:

@@ -1,0 +1,380 @@
+// sots_batch.hip -- chunks in flight: the sots_batch_* entry points of include/sots_hip.h.  One handle advances C
+// independent chunk populations, each against its own target, with the launches of ONE population per generation
+// (variation | synthesis | window + FFT + fitness | sort, each over every chunk's rows).  Chunk c of a batch computes
+// bit for bit what a sots_ctx of the same configuration computes for chunk first_chunk_index + c ("Chunks in
+// flight").  No CPU fallback: every compute entry point launches gfx950 kernels or fails with an error code.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/sots_hip.h"
+#include "sots_host_math.h"
+#include "sots_kernels.h"
+
+using namespace sots;
+
+namespace {
+thread_local std::string g_batch_create_error;
+constexpr uint32_t kBatchMaxPopulation = 1024; // one k_sort_small workgroup per chunk
+} // namespace
+
+struct sots_batch {
+    sots_config cfg{};
+    PopDims pd{};
+    MutateConsts mc{};
+    SynthParams sp{};
+    int device = 0;
+    uint32_t num_cus = 256;
+    hipStream_t stream = nullptr;
+    uint32_t P = 0, D = 0, N = 0, log2n = 0, pitch = 0;
+    uint32_t max_chunks = 0, active = 0; // active: chunks of the last target call
+    uint32_t rot = 0, generation = 0;
+    uint32_t synth_arith = SOTS_ARITH_CPU_PATH;
+    // device buffers; rows chunk-major, max_chunks * P per rotation half
+    float *values = nullptr, *steps = nullptr, *fitness = nullptr; // [2][C P][D], [2][C P][D], [2][C P]
+    float *audio = nullptr;                                        // [C P][pitch]
+    float *targets = nullptr;                                      // [C][N/2] as uploaded
+    float *seg_image = nullptr;                                    // segmented target image (sots_kernels.h)
+    float *wavetable = nullptr, *window = nullptr, *x_image = nullptr;
+    float2 *twiddle = nullptr;
+    OccCache occ{};
+    std::vector<double> window64;
+    float window_factor = 1.0f, inv_n = 0.0f, inv_wf = 1.0f;
+    mutable std::string err;
+
+    size_t rows() const { return (size_t)max_chunks * P; }
+    float *val(uint32_t half) const { return values + (size_t)half * rows() * D; }
+    float *stp(uint32_t half) const { return steps + (size_t)half * rows() * D; }
+    float *fit(uint32_t half) const { return fitness + (size_t)half * rows(); }
+};
+
+namespace {
+
+int bfail(const sots_batch *b, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (b) b->err = buf;
+    else g_batch_create_error = buf;
+    return code;
+}
+
+#define BATCH_HIP(b, call)                                                                        \
+    do {                                                                                          \
+        hipError_t e_ = (call);                                                                   \
+        if (e_ != hipSuccess) {                                                                   \
+            (void)hipGetLastError();                                                              \
+            return bfail(b, SOTS_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
+                         __FILE__, __LINE__);                                                     \
+        }                                                                                         \
+    } while (0)
+
+#define BATCH_REQUIRE(b) \
+    do {                 \
+        if (!(b)) return bfail(nullptr, SOTS_ERR_INVALID, "null batch"); \
+    } while (0)
+
+uint32_t batch_dims_of(uint32_t kind)
+{
+    switch (kind) {
+    case SOTS_SYNTH_2OP: return 4;
+    case SOTS_SYNTH_3OP_SERIES: return 6;
+    case SOTS_SYNTH_TRIPLE_PAR: return 12;
+    case SOTS_SYNTH_4OP_SERIES: return 8;
+    default: return 0;
+    }
+}
+
+void free_batch(sots_batch *b)
+{
+    if (!b) return;
+    (void)hipSetDevice(b->device);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    void *bufs[] = {b->values, b->steps, b->fitness, b->audio, b->targets, b->seg_image,
+                    b->wavetable, b->window, b->x_image, b->twiddle};
+    for (void *p : bufs)
+        if (p) (void)hipFree(p);
+    if (b->stream) (void)hipStreamDestroy(b->stream);
+    (void)hipGetLastError();
+    delete b;
+}
+
+int bind(const sots_batch *b)
+{
+    BATCH_HIP(b, hipSetDevice(b->device));
+    return SOTS_OK;
+}
+
+int require_active(const sots_batch *b)
+{
+    if (b->active == 0)
+        return bfail(b, SOTS_ERR_STATE, "no target: call sots_batch_set_target_audio or sots_batch_set_target_spectra first");
+    return SOTS_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int sots_batch_create(const sots_config *cfg, uint32_t max_chunks, sots_batch **out)
+{
+    if (!cfg || !out) return bfail(nullptr, SOTS_ERR_INVALID, "sots_batch_create: null argument");
+    *out = nullptr;
+    // the configuration first, as sots_create: a machine without a GPU still tells a bad one from a good one
+    if (cfg->struct_size != sizeof(sots_config))
+        return bfail(nullptr, SOTS_ERR_INVALID, "sots_config.struct_size %u != %zu", cfg->struct_size, sizeof(sots_config));
+    const uint32_t d = batch_dims_of(cfg->synth_kind);
+    if (d == 0) return bfail(nullptr, SOTS_ERR_INVALID, "unknown synth_kind %u", cfg->synth_kind);
+    if (cfg->num_dimensions != d)
+        return bfail(nullptr, SOTS_ERR_INVALID, "synth_kind %u needs numDimensions %u, got %u", cfg->synth_kind, d, cfg->num_dimensions);
+    if (cfg->audio_length_log2 < 8 || cfg->audio_length_log2 > 15)
+        return bfail(nullptr, SOTS_ERR_INVALID, "audioLengthLog2 %u outside 8..15", cfg->audio_length_log2);
+    const uint64_t p64 = (uint64_t)cfg->num_parents + cfg->num_offspring;
+    if (cfg->num_parents == 0 || p64 < 2)
+        return bfail(nullptr, SOTS_ERR_INVALID, "population %llu (parents %u) not supported", (unsigned long long)p64, cfg->num_parents);
+    if (p64 > kBatchMaxPopulation)
+        return bfail(nullptr, SOTS_ERR_INVALID, "a batch takes chunk populations of at most %u, got %llu (larger ones fill the GPU alone: sots_create)",
+                     kBatchMaxPopulation, (unsigned long long)p64);
+    if (cfg->workgroup_size == 0 || p64 % cfg->workgroup_size != 0)
+        return bfail(nullptr, SOTS_ERR_INVALID, "populationLength %llu must be a multiple of workgroupSize %u (the recombination block)",
+                     (unsigned long long)p64, cfg->workgroup_size);
+    if (max_chunks == 0) return bfail(nullptr, SOTS_ERR_INVALID, "max_chunks must be at least 1");
+    if ((uint64_t)max_chunks * p64 > (1ull << 26))
+        return bfail(nullptr, SOTS_ERR_INVALID, "max_chunks %u x population %llu exceeds 2^26 rows", max_chunks, (unsigned long long)p64);
+
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0) return bfail(nullptr, SOTS_ERR_NO_DEVICE, "no HIP device (%s)", hipGetErrorString(e));
+    if (cfg->device < 0 || cfg->device >= ndev)
+        return bfail(nullptr, SOTS_ERR_NO_DEVICE, "device %d not in 0..%d", cfg->device, ndev - 1);
+
+    sots_batch *b = new sots_batch();
+    b->cfg = *cfg;
+    b->device = cfg->device;
+#define CREATE_HIP(call)                                                                          \
+    do {                                                                                          \
+        hipError_t e_ = (call);                                                                   \
+        if (e_ != hipSuccess) {                                                                   \
+            int rc_ = bfail(nullptr, SOTS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
+            free_batch(b);                                                                        \
+            return rc_;                                                                           \
+        }                                                                                         \
+    } while (0)
+    CREATE_HIP(hipSetDevice(b->device));
+    hipDeviceProp_t prop;
+    CREATE_HIP(hipGetDeviceProperties(&prop, b->device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        int rc = bfail(nullptr, SOTS_ERR_NO_DEVICE, "device %d is %s; libsots_hip carries gfx950 code only", b->device, prop.gcnArchName);
+        free_batch(b);
+        return rc;
+    }
+    b->num_cus = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256;
+    CREATE_HIP(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+
+    b->P = (uint32_t)p64;
+    b->D = d;
+    b->log2n = cfg->audio_length_log2;
+    b->N = 1u << b->log2n;
+    b->pitch = b->N + 32; // as sots_create: rows off the power-of-two stride
+    b->max_chunks = max_chunks;
+    b->pd = make_pop_dims(b->P, b->D, cfg->num_parents, cfg->workgroup_size, cfg->gid_base, (uint32_t)cfg->seed,
+                          (uint32_t)(cfg->seed >> 32));
+    // Evolutionary_Strategy.hpp:611-627, as sots_create
+    const float mpi = (float)3.14159265358979323846;
+    b->mc.alpha = 1.4f;
+    b->mc.one_over_alpha = 1.f / b->mc.alpha;
+    b->mc.root_two_over_pi = sqrtf(2.f / (float)mpi);
+    b->mc.beta_scale = 1.f / (float)b->D;
+    const float beta = sqrtf(b->mc.beta_scale);
+    b->mc.pow_alpha_beta = powf(b->mc.alpha, beta);
+    b->mc.pow_inv_alpha_beta = powf(b->mc.one_over_alpha, beta);
+    memcpy(b->sp.pmin, cfg->param_min, sizeof b->sp.pmin);
+    memcpy(b->sp.pmax, cfg->param_max, sizeof b->sp.pmax);
+
+    const size_t pd_bytes = (size_t)2 * b->rows() * b->D * sizeof(float);
+    const size_t audio_bytes = b->rows() * b->pitch * sizeof(float);
+    const size_t targets_bytes = (size_t)max_chunks * (b->N / 2) * sizeof(float);
+    const size_t image_bytes = seg_target_bytes(b->log2n, max_chunks);
+    CREATE_HIP(hipMalloc((void **)&b->values, pd_bytes));
+    CREATE_HIP(hipMalloc((void **)&b->steps, pd_bytes));
+    CREATE_HIP(hipMalloc((void **)&b->fitness, (size_t)2 * b->rows() * sizeof(float)));
+    CREATE_HIP(hipMalloc((void **)&b->audio, audio_bytes));
+    CREATE_HIP(hipMalloc((void **)&b->targets, targets_bytes));
+    CREATE_HIP(hipMalloc((void **)&b->seg_image, image_bytes));
+    CREATE_HIP(hipMalloc((void **)&b->wavetable, (size_t)SOTS_WAVETABLE_SIZE * sizeof(float)));
+    CREATE_HIP(hipMalloc((void **)&b->window, (size_t)b->N * sizeof(float)));
+    CREATE_HIP(hipMalloc((void **)&b->twiddle, (size_t)b->N * sizeof(float2)));
+    if (b->log2n >= 11 && x_table_bytes(b->log2n)) CREATE_HIP(hipMalloc((void **)&b->x_image, x_table_bytes(b->log2n)));
+    CREATE_HIP(hipMemsetAsync(b->values, 0, pd_bytes, b->stream));
+    CREATE_HIP(hipMemsetAsync(b->steps, 0, pd_bytes, b->stream));
+    CREATE_HIP(hipMemsetAsync(b->fitness, 0, (size_t)2 * b->rows() * sizeof(float), b->stream));
+    CREATE_HIP(hipMemsetAsync(b->audio, 0, audio_bytes, b->stream));
+    CREATE_HIP(hipMemsetAsync(b->targets, 0, targets_bytes, b->stream));
+    CREATE_HIP(hipMemsetAsync(b->seg_image, 0, image_bytes, b->stream));
+
+    const std::vector<float> table = make_wavetable();
+    b->window64 = make_window(b->N, &b->window_factor);
+    std::vector<float> window32(b->N);
+    for (uint32_t i = 0; i < b->N; ++i) window32[i] = (float)b->window64[i];
+    const std::vector<float> tw = make_twiddles(b->N);
+    b->inv_n = 1.0f / (float)b->N;
+    b->inv_wf = 1.f / b->window_factor;
+    CREATE_HIP(hipMemcpyAsync(b->wavetable, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    CREATE_HIP(hipMemcpyAsync(b->window, window32.data(), window32.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    CREATE_HIP(hipMemcpyAsync(b->twiddle, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    const uint32_t head = b->P; // the segmented image's word 0: rows per chunk
+    CREATE_HIP(hipMemcpyAsync(b->seg_image, &head, sizeof head, hipMemcpyHostToDevice, b->stream));
+    // k_fft_x's chunk-independent tables (twiddles, window); their target part is not read by the segmented kernels
+    if (b->x_image) {
+        CREATE_HIP(launch_x_tables(b->stream, b->x_image, b->twiddle, b->window, b->targets, b->log2n));
+        b->occ.x_image = b->x_image;
+    }
+    CREATE_HIP(hipStreamSynchronize(b->stream));
+#undef CREATE_HIP
+    *out = b;
+    return SOTS_OK;
+}
+
+void sots_batch_destroy(sots_batch *b) { free_batch(b); }
+
+const char *sots_batch_last_error(const sots_batch *b) { return b ? b->err.c_str() : g_batch_create_error.c_str(); }
+
+int sots_batch_synchronize(sots_batch *b)
+{
+    BATCH_REQUIRE(b);
+    if (int rc = bind(b)) return rc;
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    return SOTS_OK;
+}
+
+int sots_batch_set_target_spectra(sots_batch *b, const float *magnitudes, uint32_t num_bins, uint32_t num_chunks)
+{
+    BATCH_REQUIRE(b);
+    if (num_chunks == 0 || num_chunks > b->max_chunks)
+        return bfail(b, SOTS_ERR_INVALID, "num_chunks %u outside 1..%u", num_chunks, b->max_chunks);
+    const uint64_t need = (uint64_t)num_chunks * (b->N / 2);
+    if (!magnitudes || num_bins != need)
+        return bfail(b, SOTS_ERR_SIZE, "%u target spectra need %llu bins, got %u", num_chunks, (unsigned long long)need, num_bins);
+    if (int rc = bind(b)) return rc;
+    BATCH_HIP(b, hipMemcpyAsync(b->targets, magnitudes, need * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    BATCH_HIP(b, launch_seg_targets(b->stream, b->seg_image, b->targets, b->log2n, num_chunks));
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    b->active = num_chunks;
+    return SOTS_OK;
+}
+
+int sots_batch_set_target_audio(sots_batch *b, const float *audio, uint32_t num_samples, uint32_t num_chunks)
+{
+    BATCH_REQUIRE(b);
+    if (num_chunks == 0 || num_chunks > b->max_chunks)
+        return bfail(b, SOTS_ERR_INVALID, "num_chunks %u outside 1..%u", num_chunks, b->max_chunks);
+    if (!audio || (uint64_t)num_samples < (uint64_t)num_chunks * b->N)
+        return bfail(b, SOTS_ERR_SIZE, "%u chunks of target audio need %llu samples, got %u", num_chunks,
+                     (unsigned long long)num_chunks * b->N, num_samples);
+    const uint32_t m = b->N / 2;
+    std::vector<float> mag((size_t)num_chunks * m);
+    for (uint32_t c = 0; c < num_chunks; ++c) { // the single context's host transform, chunk by chunk
+        const std::vector<float> one = target_spectrum(audio + (size_t)c * b->N, b->N, b->window64, b->window_factor);
+        memcpy(mag.data() + (size_t)c * m, one.data(), (size_t)m * sizeof(float));
+    }
+    return sots_batch_set_target_spectra(b, mag.data(), (uint32_t)mag.size(), num_chunks);
+}
+
+int sots_batch_init_population(sots_batch *b, uint32_t first_chunk_index)
+{
+    BATCH_REQUIRE(b);
+    if (int rc = require_active(b)) return rc;
+    if (int rc = bind(b)) return rc;
+    b->rot = 0;
+    b->generation = 0;
+    BATCH_HIP(b, launch_init_population_seg(b->stream, b->val(0), b->stp(0), b->fit(0), b->pd, first_chunk_index, b->active));
+    return SOTS_OK;
+}
+
+int sots_batch_set_synth_arithmetic(sots_batch *b, uint32_t arith)
+{
+    BATCH_REQUIRE(b);
+    if (arith > SOTS_ARITH_DEVICE_KERNELS) return bfail(b, SOTS_ERR_INVALID, "unknown synthesis arithmetic %u", arith);
+    if (arith == SOTS_ARITH_DEVICE_KERNELS && b->cfg.synth_kind == SOTS_SYNTH_4OP_SERIES)
+        return bfail(b, SOTS_ERR_INVALID, "the reference has no device kernel for the build-defined 4-op voice");
+    b->synth_arith = arith;
+    return SOTS_OK;
+}
+
+int sots_batch_execute_generations(sots_batch *b, uint32_t n)
+{
+    BATCH_REQUIRE(b);
+    if (int rc = require_active(b)) return rc;
+    if (int rc = bind(b)) return rc;
+    const uint32_t rows = b->active * b->P;
+    for (uint32_t g = 0; g < n; ++g) {
+        // recombine + mutate, current half -> other half
+        uint32_t src = b->rot, dst = b->rot ^ 1u;
+        BATCH_HIP(b, launch_recombine_mutate_seg(b->stream, b->val(src), b->stp(src), b->val(dst), b->stp(dst), b->pd, b->mc,
+                                                 b->generation, b->active));
+        b->rot = dst;
+        // synthesis: per row, so the single context's launcher serves every chunk's rows at once
+        if (b->synth_arith == SOTS_ARITH_DEVICE_KERNELS)
+            BATCH_HIP(b, launch_synth_device_arith(b->stream, b->cfg.synth_kind, b->val(b->rot), b->wavetable, b->audio, b->sp, rows,
+                                                   b->log2n, b->pitch));
+        else
+            BATCH_HIP(b, launch_synth(b->stream, b->cfg.synth_kind, b->val(b->rot), b->wavetable, b->audio, b->sp, rows, b->log2n,
+                                      b->pitch, b->num_cus, nullptr, true));
+        // window + FFT + fitness, every row against its chunk's target
+        BATCH_HIP(b, launch_fft_fitness_seg(b->stream, b->audio, b->window, b->seg_image, b->fit(b->rot), b->twiddle, rows, b->log2n,
+                                            b->pitch, b->inv_n, b->inv_wf, b->num_cus, &b->occ));
+        // sortPopulation of every chunk (whole population: P <= 1024), current half -> other half
+        src = b->rot, dst = b->rot ^ 1u;
+        BATCH_HIP(b, launch_sort_seg(b->stream, b->val(src), b->stp(src), b->fit(src), b->val(dst), b->stp(dst), b->fit(dst), b->P,
+                                     b->D, b->active));
+        b->rot = dst;
+        b->generation += 1;
+    }
+    return SOTS_OK;
+}
+
+int sots_batch_read_best(sots_batch *b, float *values, size_t values_bytes, float *fitness, size_t fitness_bytes)
+{
+    BATCH_REQUIRE(b);
+    if (int rc = require_active(b)) return rc;
+    const size_t v_bytes = (size_t)b->active * b->D * sizeof(float), f_bytes = (size_t)b->active * sizeof(float);
+    if ((values && values_bytes != v_bytes) || (fitness && fitness_bytes != f_bytes))
+        return bfail(b, SOTS_ERR_SIZE, "best-row byte counts must be %zu (values) and %zu (fitness)", v_bytes, f_bytes);
+    if (int rc = bind(b)) return rc;
+    if (values)
+        BATCH_HIP(b, hipMemcpy2DAsync(values, (size_t)b->D * sizeof(float), b->val(b->rot), (size_t)b->P * b->D * sizeof(float),
+                                      (size_t)b->D * sizeof(float), b->active, hipMemcpyDeviceToHost, b->stream));
+    if (fitness)
+        BATCH_HIP(b, hipMemcpy2DAsync(fitness, sizeof(float), b->fit(b->rot), (size_t)b->P * sizeof(float), sizeof(float), b->active,
+                                      hipMemcpyDeviceToHost, b->stream));
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    return SOTS_OK;
+}
+
+int sots_batch_read_population(sots_batch *b, uint32_t chunk, float *values, size_t values_bytes, float *steps, size_t steps_bytes,
+                               float *fitness, size_t fitness_bytes)
+{
+    BATCH_REQUIRE(b);
+    if (int rc = require_active(b)) return rc;
+    if (chunk >= b->active) return bfail(b, SOTS_ERR_INVALID, "chunk %u not in 0..%u", chunk, b->active - 1);
+    const size_t pd_bytes = (size_t)b->P * b->D * sizeof(float), f_bytes = (size_t)b->P * sizeof(float);
+    if ((values && values_bytes != pd_bytes) || (steps && steps_bytes != pd_bytes) || (fitness && fitness_bytes != f_bytes))
+        return bfail(b, SOTS_ERR_SIZE, "population byte counts must be %zu (values, steps) and %zu (fitness)", pd_bytes, f_bytes);
+    if (int rc = bind(b)) return rc;
+    const size_t row0 = (size_t)chunk * b->P;
+    if (values) BATCH_HIP(b, hipMemcpyAsync(values, b->val(b->rot) + row0 * b->D, pd_bytes, hipMemcpyDeviceToHost, b->stream));
+    if (steps) BATCH_HIP(b, hipMemcpyAsync(steps, b->stp(b->rot) + row0 * b->D, pd_bytes, hipMemcpyDeviceToHost, b->stream));
+    if (fitness) BATCH_HIP(b, hipMemcpyAsync(fitness, b->fit(b->rot) + row0, f_bytes, hipMemcpyDeviceToHost, b->stream));
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    return SOTS_OK;
+}
+
+} // extern "C"

@@ -153,6 +153,28 @@ hipError_t launch_unpack_rows(hipStream_t st, float *values, float *steps, float
                               const float *rows, uint32_t first_row, uint32_t n_rows, uint32_t d,
                               uint32_t skip_first, uint32_t skip_count);
 
+// ---- chunks in flight (sots_batch) ----
+// `chunks` populations of pd.p rows, chunk-major (row r: chunk r / P, local index r % P); each chunk draws what a context
+// of its own would (init: chunk first_chunk + c; variation: the local index)
+hipError_t launch_init_population_seg(hipStream_t st, float *values, float *steps, float *fitness, const PopDims &pd,
+                                      uint32_t first_chunk, uint32_t chunks);
+hipError_t launch_recombine_mutate_seg(hipStream_t st, const float *vin, const float *sin, float *vout, float *sout,
+                                       const PopDims &pd, const MutateConsts &mc, uint32_t generation, uint32_t chunks);
+// Segmented target image: uint32 rows-per-chunk in word 0, chunk c's target table from float 64 + c * stride on (the N/2
+// bins, or k_fft_x's per-(lane, register) table where that kernel runs).  The caller writes word 0 and zeroes the image
+// once; launch_seg_targets fills the tables from targets[chunks][N/2] (device memory).
+constexpr uint32_t kSegTargetHeadFloats = 64;
+size_t seg_target_stride(uint32_t log2n);
+size_t seg_target_bytes(uint32_t log2n, uint32_t chunks);
+hipError_t launch_seg_targets(hipStream_t st, float *image, const float *targets, uint32_t log2n, uint32_t chunks);
+// launch_fft_fitness (window applied) over rows of consecutive chunks, each row against its chunk's target
+hipError_t launch_fft_fitness_seg(hipStream_t st, const float *audio, const float *window, const float *seg_image, float *fitness,
+                                  const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
+                                  uint32_t num_cus, OccCache *occ);
+// the whole-population sort of each chunk (P <= 1024: k_sort_small, a workgroup per chunk)
+hipError_t launch_sort_seg(hipStream_t st, const float *vin, const float *sin, const float *fin, float *vout, float *sout,
+                           float *fout, uint32_t p, uint32_t d, uint32_t chunks);
+
 uint32_t next_pow2(uint32_t v);
 
 } // namespace sots

@@ -184,6 +184,41 @@ __global__ __launch_bounds__(256) void k_recombine_mutate(const float *__restric
     }
 }
 
+// ------------------------------------------------------------------------------------
+// Chunks in flight (sots_batch): `chunks` populations of pd.p rows each, chunk-major (row r = chunk r / P, local index
+// r % P).  Every chunk draws exactly what a context of its own would: initialisation with the chunk's index in the
+// counter, variation with the LOCAL index (the mutation counter holds no chunk index, as in the single context).
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_init_population_seg(float *__restrict__ values, float *__restrict__ steps,
+                                                             float *__restrict__ fitness, PopDims pd, uint32_t first_chunk,
+                                                             uint32_t chunks)
+{
+    const uint32_t total = chunks * pd.p * pd.d;
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+        const uint32_t r = e / pd.d, g = e - r * pd.d, c = r / pd.p, i = r - c * pd.p;
+        const U4 rn = philox4x32_10(pd.gid_base + i, first_chunk + c, g >> 2, kTagInit, pd.seed_lo, pd.seed_hi);
+        const float u = draw_unit(u4_at(rn, g & 3u));
+        steps[e] = 0.1f;
+        values[e] = (u < 0.0f) ? -u : u;
+        if (g == 0) fitness[r] = 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_recombine_mutate_seg(const float *__restrict__ vin, const float *__restrict__ sin,
+                                                              float *__restrict__ vout, float *__restrict__ sout, PopDims pd,
+                                                              MutateConsts mc, uint32_t generation, uint32_t chunks)
+{
+    const uint32_t total = chunks * pd.p * pd.d;
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+        const uint32_t r = e / pd.d, g = e - r * pd.d, c = r / pd.p, i = r - c * pd.p;
+        const uint32_t src = c * pd.p * pd.d + recombine_source(i, g, pd);
+        float x = vin[src], s = sin[src];
+        mutate_gene(x, s, pd.gid_base + i, g, generation, pd, mc);
+        vout[e] = x;
+        sout[e] = s;
+    }
+}
+
 // Audio rows are read exactly once per generation: non-temporal loads keep them from
 // displacing other data in L2 / Infinity Cache (P = 131072: 151 -> 132 us; neutral at 65536).
 typedef float v4f_t __attribute__((ext_vector_type(4)));
@@ -1706,6 +1741,19 @@ __device__ __forceinline__ float wave_sum(float v)
     return ((r0 + r1) + r2) + r3;
 }
 
+// Segmented target image (chunks in flight): word 0 holds the rows per chunk, the chunks' tables follow from float
+// kSegHead on, `stride` floats each - the N/2 bins for k_fft and k_fft_big, k_fft_x's per-(lane, register) target
+// table for k_fft_x (x_seg_stride).  Row r reads the table of chunk r / rows.
+constexpr uint32_t kSegHead = kSegTargetHeadFloats; // (256 bytes: the tables start aligned)
+__device__ __forceinline__ uint32_t seg_target_rows(const float *image)
+{
+    return __builtin_amdgcn_readfirstlane(reinterpret_cast<const uint32_t *>(image)[0]);
+}
+__device__ __forceinline__ const float *seg_target_chunk(const float *image, uint32_t chunk, uint32_t stride)
+{
+    return image + kSegHead + (size_t)chunk * stride;
+}
+
 // MODE 0: write spectrum rows; MODE 1: accumulate the fitness directly
 // WIN: multiply by the fp32 window while loading (the generation loop then skips the window
 // pass; the product is the same single fp32 rounding either way).
@@ -1716,8 +1764,11 @@ __device__ __forceinline__ float wave_sum(float v)
 // the whole GPU reads one moving window of the audio: a contiguous block of rows per workgroup is 8 % slower).  The SIMD issues for its
 // oldest wavefront first: with a fixed deal the three wavefronts of a SIMD finish their equal shares one after the
 // other and the last one runs alone, far below the issue rate (k_fft_x below has the numbers).
+// SEG (chunks in flight, sots_batch): the rows belong to consecutive chunks of equal size, each with a target of its own;
+// `target` is then a segmented target image (seg_target_rows / seg_target_chunk above) and every row reads its chunk's bins
+// from it in global memory (L2) instead of the workgroup's one target in LDS.  Same arithmetic, same order.
 template <int LOG2N> constexpr int fft_wide_waves() { return LOG2N == 10 ? 12 : 16; }
-template <int LOG2N, int MODE, bool WIN, int W = 1>
+template <int LOG2N, int MODE, bool WIN, int W = 1, bool SEG = false>
 __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audio, float *__restrict__ spectrum,
                                                    const float *__restrict__ target, float *__restrict__ fitness,
                                                    const float2 *__restrict__ tw, const float *__restrict__ window,
@@ -1745,10 +1796,11 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
     for (int q = 0; q < H; ++q) w_split[q] = tw[lane + kWave * q];
     // the target spectrum sits in LDS (2N bytes): eight registers fewer than holding this lane's
     // bins, which is what keeps N = 1024 at three wavefronts per SIMD with two rows in flight
-    __shared__ float tgt_s[MODE == 1 ? M + 1 : 1];
-    if constexpr (MODE == 1) {
+    __shared__ float tgt_s[MODE == 1 && !SEG ? M + 1 : 1];
+    if constexpr (MODE == 1 && !SEG) {
         for (int k = threadIdx.x; k < M; k += W * kWave) tgt_s[k] = target[k];
     }
+    const uint32_t seg_rows = SEG ? seg_target_rows(target) : 1u;
     if constexpr (MODE == 1 || W > 1) __syncthreads(); // (the only workgroup barrier: target and row counter are there)
     if (ind >= p_len) return;
 
@@ -1838,13 +1890,15 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
             if (lane == 0) row[M / 2] = x_half;
         } else {
             v2f_t acc2 = v2f_t{0.0f, 0.0f};
+            const float *__restrict__ tg = SEG ? seg_target_chunk(target, ind / seg_rows, M) : nullptr;
 #pragma unroll
             for (int q = 0; q < H; ++q) {
                 const int k = lane + kWave * q;
                 v2f_t xa2, xbc2;
                 split_pair_2x(z[q], split_partner<M>(z, q, lane, partner_addr), w_split[q], xa2, xbc2); // 2 X[k], 2 conj X[M-k]
                 if (k == 0) xbc2 = v2f_t{2.0f * x_half.x, 2.0f * x_half.y}; // the fitness skips the Nyquist bin and needs bin M/2
-                bin_error2(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tgt_s[k], tgt_s[k == 0 ? M / 2 : M - k], half_scale);
+                if constexpr (SEG) bin_error2(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tg[k], tg[k == 0 ? M / 2 : M - k], half_scale);
+                else bin_error2(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tgt_s[k], tgt_s[k == 0 ? M / 2 : M - k], half_scale);
             }
             float acc = wave_sum(acc2.x + acc2.y);
             if (lane == 0) fitness[ind] = acc;
@@ -2376,12 +2430,18 @@ __global__ __launch_bounds__(kSelTile) void k_sel_tiles(const float *__restrict_
 // small, and there a launch costs as much as the sort): k_sel_tiles' network - one key per lane, 64-key runs sorted in
 // registers, a key's place = its lane + its lower bounds in the other runs - and then the workgroup moves the rows,
 // a lane per output element.  Same order as the full sort: fitness, equal fitness by index, NaN last.
-template <uint32_t RUNS>
+// SEG (chunks in flight): workgroup b sorts the b-th block of p_len rows, the grid one workgroup per chunk.
+template <uint32_t RUNS, bool SEG = false>
 __global__ __launch_bounds__(RUNS *kWave) void k_sort_small(const float *__restrict__ vin, const float *__restrict__ sin,
                                                             const float *__restrict__ fin, float *__restrict__ vout,
                                                             float *__restrict__ sout, float *__restrict__ fout,
                                                             uint32_t p_len, uint32_t d, uint32_t first_row, SortExchange ex)
 {
+    if constexpr (SEG) {
+        const size_t rows = (size_t)blockIdx.x * p_len;
+        vin += rows * d, sin += rows * d, fin += rows;
+        vout += rows * d, sout += rows * d, fout += rows;
+    }
     __shared__ uint32_t runs[RUNS * kWave], from[RUNS * kWave];
     ex_unpack(ex, vout, sout, fout, d, threadIdx.x, RUNS * kWave);
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
@@ -2942,7 +3002,10 @@ template <int LOG2N> constexpr int x_table_floats() { return 3 * 2 * kWave * (x_
 #ifndef SOTS_X_MIN_WAVES // (experiment: minimum wavefronts per SIMD the register allocation must allow, e.g. 5 with two workgroups of ten)
 #define SOTS_X_MIN_WAVES 1
 #endif
-template <int LOG2N, int MODE, bool WIN, int WG = x_waves<LOG2N, MODE>()>
+// floats of one chunk's target table in a segmented target image (SEG): the tgt_s part of the LDS tables, same layout
+template <int LOG2N> constexpr uint32_t x_seg_stride() { return kWave * (x_points<LOG2N>() + 4); }
+// SEG: as k_fft's - every row reads its chunk's target entries (lane, register) from the segmented image in global memory
+template <int LOG2N, int MODE, bool WIN, int WG = x_waves<LOG2N, MODE>(), bool SEG = false>
 __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MIN_WAVES : 1)) void k_fft_x(const float *__restrict__ audio, float *__restrict__ spectrum,
                                                                    const float *__restrict__ target, float *__restrict__ fitness,
                                                                    const float2 *__restrict__ tw, const float *__restrict__ window,
@@ -2974,8 +3037,9 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
         tw2_s[l * S2 + r] = tw[2u * l * q]; // W_M^{l q} = W_N^{2 l q}
         tws_s[l * S2 + r] = tw[k];          // W_N^k
         if constexpr (WIN) win_s[l * S2 + r] = reinterpret_cast<const float2 *>(window)[l + kWave * r]; // r = input register j here
-        if constexpr (MODE == 1) tgt_s[l * S1 + r] = target[x_target_bin<E, EB>(l, r)];
+        if constexpr (MODE == 1 && !SEG) tgt_s[l * S1 + r] = target[x_target_bin<E, EB>(l, r)];
     }
+    const uint32_t seg_rows = SEG ? seg_target_rows(target) : 1u;
     // per-lane constants of the six lane stages
     const float sg8 = (lane & 8u) ? -1.0f : 1.0f;
     const float sg4 = (lane & 4u) ? -1.0f : 1.0f, sg2 = (lane & 2u) ? -1.0f : 1.0f, sg1 = (lane & 1u) ? -1.0f : 1.0f;
@@ -3088,6 +3152,12 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
         };
 #endif
         if constexpr (MODE == 1) {
+            // target entry (this lane, register RR): the workgroup's table in LDS, or (SEG) the row's chunk's in global memory
+            const float *__restrict__ tg = SEG ? seg_target_chunk(target, row / seg_rows, x_seg_stride<LOG2N>()) + lane * S1 : nullptr;
+            auto tgt_at = [&](int rr) -> float {
+                if constexpr (SEG) return tg[rr];
+                else return tgt_s[lane * S1 + rr];
+            };
             // Registers RR and R2 = bitrev(E - bitrev(RR)) need each other and nobody else: the bins are taken in such
             // pairs (this is the summation order, k_fitness_x repeats it), and a pair that is done is free - the NEXT
             // row's loads into those two registers go out at once, so by the end of the split most of the next row is on
@@ -3116,18 +3186,18 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
                     if constexpr (R2 != RR) {
                         v2f_t xa, xb;
                         pair2x(ic<RR>{}, xa, xb);
-                        acc += bin_error(make_float2(xa.x, xa.y), tgt_s[lane * S1 + RR], half_scale);
-                        acc += bin_error(make_float2(xb.x, xb.y), tgt_s[lane * S1 + R2], half_scale); // the partner lane's bin M - k: x_target_bin
+                        acc += bin_error(make_float2(xa.x, xa.y), tgt_at(RR), half_scale);
+                        acc += bin_error(make_float2(xb.x, xb.y), tgt_at(R2), half_scale); // the partner lane's bin M - k: x_target_bin
                     } else {
                         const v2f_t xa = bin2x(ic<RR>{});
-                        acc += bin_error(make_float2(xa.x, xa.y), tgt_s[lane * S1 + RR], half_scale);
+                        acc += bin_error(make_float2(xa.x, xa.y), tgt_at(RR), half_scale);
                     }
 #else
                     const v2f_t xa = bin2x(ic<RR>{});
-                    acc += bin_error(make_float2(xa.x, xa.y), tgt_s[lane * S1 + RR], half_scale);
+                    acc += bin_error(make_float2(xa.x, xa.y), tgt_at(RR), half_scale);
                     if constexpr (R2 != RR) {
                         const v2f_t xb = bin2x(ic<R2>{});
-                        acc += bin_error(make_float2(xb.x, xb.y), tgt_s[lane * S1 + R2], half_scale);
+                        acc += bin_error(make_float2(xb.x, xb.y), tgt_at(R2), half_scale);
                     }
 #endif
 #ifndef SOTS_X_RECYCLE
@@ -3236,7 +3306,8 @@ __device__ __forceinline__ float big_block_sum(float acc, float *__restrict__ re
     return total; // (thread 0's)
 }
 
-template <int LOG2N, int MODE, bool WIN>
+// SEG: `target` is a segmented target image (k_fft's); row r takes its chunk's bins
+template <int LOG2N, int MODE, bool WIN, bool SEG = false>
 __global__ __launch_bounds__(kBigThreads) void k_fft_big(const float *__restrict__ audio, float *__restrict__ spectrum,
                                                          const float *__restrict__ target, float *__restrict__ fitness,
                                                          const float2 *__restrict__ tw, const float *__restrict__ window,
@@ -3284,7 +3355,8 @@ __global__ __launch_bounds__(kBigThreads) void k_fft_big(const float *__restrict
             if (t == 0) dst[M] = make_float2(big_z[0].x - big_z[0].y, 0.0f); // the Nyquist bin X[M] = Re Z0 - Im Z0
         } else {
             float acc = 0.0f;
-            for (uint32_t k = t; k < M; k += T) acc += bin_error(bin(k), target[k], inv_n * inv_wf);
+            const float *__restrict__ tg = SEG ? seg_target_chunk(target, row / seg_target_rows(target), M) : target;
+            for (uint32_t k = t; k < M; k += T) acc += bin_error(bin(k), tg[k], inv_n * inv_wf);
             const float total = big_block_sum(acc, red);
             if (t == 0) fitness[row] = total;
         }
@@ -3351,6 +3423,19 @@ __global__ __launch_bounds__(256) void k_x_tables(float *__restrict__ image, con
         tws_s[l * S2 + r] = tw[k];
         win_s[l * S2 + r] = reinterpret_cast<const float2 *>(window)[l + kWave * r];
         tgt_s[l * S1 + r] = target[x_target_bin<E, EB>(l, r)];
+    }
+}
+// the target part of those tables for every chunk (segmented target image of k_fft_x<.., SEG>): chunk c's table from
+// targets[c][N/2], entry (l, r) at l (E + 4) + r as in tgt_s (the padding entries stay as the caller left them)
+template <int LOG2N>
+__global__ __launch_bounds__(256) void k_x_seg_targets(float *__restrict__ tables, const float *__restrict__ targets, uint32_t chunks)
+{
+    constexpr int E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), S1 = E + 4;
+    constexpr uint32_t M = (1u << LOG2N) / 2;
+    const uint32_t total = chunks * (uint32_t)(kWave * E);
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+        const uint32_t c = e / (kWave * E), le = e - c * (kWave * E), l = le / E, r = le % E;
+        tables[(size_t)c * x_seg_stride<LOG2N>() + l * S1 + r] = targets[(size_t)c * M + x_target_bin<E, EB>(l, r)];
     }
 }
 #pragma clang fp contract(off)
@@ -3737,15 +3822,15 @@ static bool x_from(uint32_t log2n) { return log2n == 8 || (log2n >= SOTS_X_MIN &
     }
 static bool big_from(uint32_t log2n) { return log2n == 14 || log2n == 15; }
 // a workgroup per row: as many workgroups as rows, at most four per CU (they loop)
-template <int L, int MODE, bool WIN>
+template <int L, int MODE, bool WIN, bool SEG = false>
 static hipError_t launch_fft_big(hipStream_t st, uint32_t p, uint32_t num_cus, const float *audio, float *spectrum, const float *target,
                                  float *fitness, const float2 *tw, const float *window, float inv_n, float inv_wf, uint32_t pitch)
 {
     const uint32_t cus = num_cus ? num_cus : 256u, grid = p < 4u * cus ? p : 4u * cus;
     const size_t lds = ((size_t)(1u << L) / 2u) * sizeof(float2) + 64u;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_big<L, MODE, WIN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_big<L, MODE, WIN, SEG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    k_fft_big<L, MODE, WIN><<<grid, kBigThreads, lds, st>>>(audio, spectrum, target, fitness, tw, window, p, inv_n, inv_wf, pitch);
+    k_fft_big<L, MODE, WIN, SEG><<<grid, kBigThreads, lds, st>>>(audio, spectrum, target, fitness, tw, window, p, inv_n, inv_wf, pitch);
     return hipGetLastError();
 }
 template <int L>
@@ -4100,6 +4185,103 @@ hipError_t launch_unpack_rows(hipStream_t st, float *values, float *steps, float
     k_unpack_rows<<<grid_for((uint64_t)n_rows * (2 * d + 1), 256), 256, 0, st>>>(values, steps, fitness, rows,
                                                                                  first_row, n_rows, d, skip_first,
                                                                                  skip_count);
+    return hipGetLastError();
+}
+
+// ---- chunks in flight ----------------------------------------------------------------
+hipError_t launch_init_population_seg(hipStream_t st, float *values, float *steps, float *fitness, const PopDims &pd,
+                                      uint32_t first_chunk, uint32_t chunks)
+{
+    k_init_population_seg<<<grid_for((uint64_t)chunks * pd.p * pd.d, 256), 256, 0, st>>>(values, steps, fitness, pd, first_chunk, chunks);
+    return hipGetLastError();
+}
+
+hipError_t launch_recombine_mutate_seg(hipStream_t st, const float *vin, const float *sin, float *vout, float *sout,
+                                       const PopDims &pd, const MutateConsts &mc, uint32_t generation, uint32_t chunks)
+{
+    k_recombine_mutate_seg<<<grid_for((uint64_t)chunks * pd.p * pd.d, 256), 256, 0, st>>>(vin, sin, vout, sout, pd, mc, generation, chunks);
+    return hipGetLastError();
+}
+
+size_t seg_target_stride(uint32_t log2n)
+{
+    if (x_from(log2n)) {
+        switch (log2n) {
+        case 8: return x_seg_stride<8>();
+        case 11: return x_seg_stride<11>();
+        case 12: return x_seg_stride<12>();
+        default: return x_seg_stride<13>();
+        }
+    }
+    return (1u << log2n) / 2u;
+}
+
+size_t seg_target_bytes(uint32_t log2n, uint32_t chunks)
+{
+    return (kSegHead + (size_t)chunks * seg_target_stride(log2n)) * sizeof(float);
+}
+
+hipError_t launch_seg_targets(hipStream_t st, float *image, const float *targets, uint32_t log2n, uint32_t chunks)
+{
+    float *tables = image + kSegHead;
+    if (!x_from(log2n))
+        return hipMemcpyAsync(tables, targets, (size_t)chunks * ((1u << log2n) / 2u) * sizeof(float), hipMemcpyDeviceToDevice, st);
+    const uint64_t work = (uint64_t)chunks * (1u << log2n) / 2u;
+#define CALL(L) k_x_seg_targets<L><<<grid_for(work, 256), 256, 0, st>>>(tables, targets, chunks)
+    SOTS_DISPATCH_X(log2n, CALL)
+#undef CALL
+    return hipGetLastError();
+}
+
+// launch_fft_fitness with a window, every row against its chunk's target: the same kernel choice for the same row
+// count, each kernel's SEG instantiation
+hipError_t launch_fft_fitness_seg(hipStream_t st, const float *audio, const float *window, const float *seg_image, float *fitness,
+                                  const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
+                                  uint32_t num_cus, OccCache *oc)
+{
+    if (big_from(log2n)) {
+        if (log2n == 14) return launch_fft_big<14, 1, true, true>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch);
+        return launch_fft_big<15, 1, true, true>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch);
+    }
+    if (x_from(log2n)) {
+        int *occ_x = oc->x_fused_win;
+        if ((p + x_waves<12>() - 1) / x_waves<12>() < (num_cus ? num_cus : 256u)) {
+            int *occ_s = oc->x_small;
+#define CALL(L) k_fft_x<L, 1, true, 4, true><<<resident_grid((k_fft_x<L, 1, true, 4, true>), 4 * kWave, (p + 3) / 4, num_cus, &occ_s[L]), 4 * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image)
+            SOTS_DISPATCH_X(log2n, CALL)
+#undef CALL
+            return hipGetLastError();
+        }
+#define CALL(L) k_fft_x<L, 1, true, x_waves<L>(), true><<<SOTS_X_GRID((k_fft_x<L, 1, true, x_waves<L>(), true>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image)
+        SOTS_DISPATCH_X(log2n, CALL)
+#undef CALL
+        return hipGetLastError();
+    }
+    if (fft_wide(p, log2n, num_cus)) {
+        constexpr int W = fft_wide_waves<10>();
+        k_fft<10, 1, true, W, true><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, true>), 1), W * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch);
+        return hipGetLastError();
+    }
+    int *occ_w = oc->fused_win;
+#define CALL(L) k_fft<L, 1, true, 1, true><<<resident_grid(k_fft<L, 1, true, 1, true>, kWave, p, num_cus, &occ_w[L]), kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch)
+    SOTS_DISPATCH_WAVE(log2n, CALL)
+#undef CALL
+    return hipGetLastError();
+}
+
+hipError_t launch_sort_seg(hipStream_t st, const float *vin, const float *sin, const float *fin, float *vout, float *sout,
+                           float *fout, uint32_t p, uint32_t d, uint32_t chunks)
+{
+    const uint32_t n_pad = next_pow2(p < 2 ? 2 : p);
+    if (n_pad > kSortSmall) return hipErrorInvalidValue;
+    const SortExchange ex{};
+    switch ((n_pad + kWave - 1) / kWave) {
+    case 1: k_sort_small<1, true><<<chunks, 1 * kWave, 0, st>>>(vin, sin, fin, vout, sout, fout, p, d, 0, ex); break;
+    case 2: k_sort_small<2, true><<<chunks, 2 * kWave, 0, st>>>(vin, sin, fin, vout, sout, fout, p, d, 0, ex); break;
+    case 4: k_sort_small<4, true><<<chunks, 4 * kWave, 0, st>>>(vin, sin, fin, vout, sout, fout, p, d, 0, ex); break;
+    case 8: k_sort_small<8, true><<<chunks, 8 * kWave, 0, st>>>(vin, sin, fin, vout, sout, fout, p, d, 0, ex); break;
+    default: k_sort_small<16, true><<<chunks, 16 * kWave, 0, st>>>(vin, sin, fin, vout, sout, fout, p, d, 0, ex); break;
+    }
     return hipGetLastError();
 }
 

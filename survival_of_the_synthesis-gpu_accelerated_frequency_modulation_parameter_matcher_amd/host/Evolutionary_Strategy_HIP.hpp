@@ -9,7 +9,8 @@
 //   printBest()                          (:613-631)
 // Stage timers keep the reference's names (:117) and feed the Benchmarker through
 // addTimer(name, ms) with hipEvent-measured durations, like the Vulkan backend feeds its
-// timestamp queries (Evolutionary_Strategy_Vulkan.hpp:1169-1210).  Errors, which the
+// timestamp queries (Evolutionary_Strategy_Vulkan.hpp:1169-1210); with chunksInFlight > 1 (chunks matched in
+// batches, sots_batch) only the "Total Audio Analysis Time" row is produced, no per-stage rows.  Errors, which the
 // reference prints and ignores, throw std::runtime_error here (main.cpp:282 catches it).
 #ifndef SOTS_EVOLUTIONARY_STRATEGY_HIP_HPP
 #define SOTS_EVOLUTIONARY_STRATEGY_HIP_HPP
@@ -65,6 +66,11 @@ struct Evolutionary_Strategy_HIP_Arguments
     uint32_t numElites = 16;
     uint32_t migrationInterval = 1;
     bool overlapMigration = false;    // the all-gather runs underneath the next generation, rows arrive one exchange later
+    // Chunks in flight (type.HIP.chunksInFlight): with more than 1, a single device and populationLength <= 1024,
+    // parameterMatchAudio matches that many chunks at once (sots_batch: every chunk against its own target, the launches
+    // of one population per generation) - same results as the chunk-by-chunk loop.  In that mode the CSV gets only the
+    // "Total Audio Analysis Time" row, no per-stage rows.  Otherwise (numDevices > 1, P > 1024) the chunk-by-chunk loop.
+    uint32_t chunksInFlight = 1;
     bool verbose = true;
     std::string logDirectory = "";    // where hiplog(...).csv goes ("" = cwd)
 };
@@ -78,6 +84,7 @@ private:
 
     sots_ctx *ctx_ = nullptr;       // the context results and timers are read from (island 0 / the best island of a group)
     sots_group *group_ = nullptr;   // owns the islands when numDevices > 1
+    sots_batch *batch_ = nullptr;   // chunks in flight (args_.chunksInFlight > 1), made by the first batched parameterMatchAudio
     sots_config cfg_{};
     Evolutionary_Strategy_HIP_Arguments args_;
 
@@ -173,6 +180,7 @@ public:
     }
     ~Evolutionary_Strategy_HIP() override
     {
+        if (batch_) sots_batch_destroy(batch_);
         if (group_) sots_group_destroy(group_); // owns its islands
         else if (ctx_) sots_destroy(ctx_);
         hipBenchmarker_.close();
@@ -316,16 +324,24 @@ public:
         numChunks_ = aTargetAudioLength / chunkSize_;
         bestPerChunk_.clear();
 
+        const bool batched = args_.chunksInFlight > 1 && !group_ && population.populationLength <= 1024u;
+        if (args_.chunksInFlight > 1 && !batched && args_.verbose)
+            printf("chunksInFlight %u: %s, matching chunk by chunk\n", args_.chunksInFlight,
+                   group_ ? "numDevices > 1" : "populationLength > 1024");
         hipBenchmarker_.startTimer("Total Audio Analysis Time");
-        for (uint32_t i = 0; i < numChunks_; i++) {
-            setTargetAudio(&aTargetAudio[chunkSize_ * i], chunkSize_);
-            initPopulationHIP(i);
-            executeAllGenerations();
-            if (group_) checkGroup(sots_group_synchronize(group_), "synchronize");
-            else check(sots_synchronize(ctx_), "synchronize");
-            if (args_.verbose) printf("Audio chunk %u evaluated:\n", i);
-            printBest();
-            harvestTimers();
+        if (batched) {
+            matchChunksInFlight(aTargetAudio);
+        } else {
+            for (uint32_t i = 0; i < numChunks_; i++) {
+                setTargetAudio(&aTargetAudio[chunkSize_ * i], chunkSize_);
+                initPopulationHIP(i);
+                executeAllGenerations();
+                if (group_) checkGroup(sots_group_synchronize(group_), "synchronize");
+                else check(sots_synchronize(ctx_), "synchronize");
+                if (args_.verbose) printf("Audio chunk %u evaluated:\n", i);
+                printBest();
+                harvestTimers();
+            }
         }
         hipBenchmarker_.pauseTimer("Total Audio Analysis Time");
         const double totalMs = hipBenchmarker_.totalMs("Total Audio Analysis Time");
@@ -346,13 +362,60 @@ public:
         const uint32_t d = population.numDimensions;
         std::vector<float> v((size_t)population.populationLength * d), f(population.populationLength);
         check(sots_read_population(ctx_, v.data(), v.size() * sizeof(float), nullptr, 0, f.data(), f.size() * sizeof(float)), "printBest");
-        std::vector<float> best(v.begin(), v.begin() + d);
+        recordBest(v.data(), f[0]);
+    }
+
+private:
+    // one chunk's result: kept for bestParametersPerChunk() and printed (printBest's lines)
+    void recordBest(const float *bestValues, float bestFitness)
+    {
+        const uint32_t d = population.numDimensions;
+        std::vector<float> best(bestValues, bestValues + d);
         bestPerChunk_.push_back(best);
         if (!args_.verbose) return;
         const std::vector<float> scaled = objective.scaleParams(best);
         printf("Best parameters found:\n");
         for (uint32_t j = 0; j < d && j < scaled.size(); ++j) printf(" p%u = %f\n", j, scaled[j]);
-        printf("Best fitness: %g\n\n", f[0]);
+        printf("Best fitness: %g\n\n", bestFitness);
+    }
+
+    // parameterMatchAudio with chunksInFlight chunks per batch (the last batch may be ragged): per batch the targets
+    // (Objective::calculateFFT, as setTargetAudio), one initialisation, the generations, ONE synchronisation and the best
+    // rows.  Afterwards the context holds the last chunk's population, as after the chunk-by-chunk loop, so that
+    // readPopulationData and printBest read what they read there (the current rotation half).
+    void matchChunksInFlight(const float *aTargetAudio)
+    {
+        const uint32_t half = objective.fftHalfSize, d = population.numDimensions, P = population.populationLength;
+        const uint32_t perBatch = std::min(args_.chunksInFlight, numChunks_);
+        if (perBatch == 0) return;
+        if (!batch_ && sots_batch_create(&cfg_, args_.chunksInFlight, &batch_) != SOTS_OK)
+            throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_batch_create: ") + sots_batch_last_error(nullptr));
+        auto checkBatch = [&](int rc, const char *what) {
+            if (rc != SOTS_OK) throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + what + ": " + sots_batch_last_error(batch_));
+        };
+        if (args_.deviceKernelArithmetic) checkBatch(sots_batch_set_synth_arithmetic(batch_, SOTS_ARITH_DEVICE_KERNELS), "sots_batch_set_synth_arithmetic");
+        std::vector<float> mags((size_t)perBatch * half), values((size_t)perBatch * d), fitness(perBatch);
+        uint32_t last = 0;
+        for (uint32_t first = 0; first < numChunks_; first += perBatch) {
+            const uint32_t n = std::min(perBatch, numChunks_ - first);
+            for (uint32_t c = 0; c < n; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)chunkSize_ * (first + c)], mags.data() + (size_t)c * half);
+            checkBatch(sots_batch_set_target_spectra(batch_, mags.data(), n * half, n), "sots_batch_set_target_spectra");
+            checkBatch(sots_batch_init_population(batch_, first), "sots_batch_init_population");
+            checkBatch(sots_batch_execute_generations(batch_, numGenerations), "sots_batch_execute_generations");
+            checkBatch(sots_batch_synchronize(batch_), "sots_batch_synchronize");
+            checkBatch(sots_batch_read_best(batch_, values.data(), (size_t)n * d * sizeof(float), fitness.data(), (size_t)n * sizeof(float)),
+                       "sots_batch_read_best");
+            for (uint32_t c = 0; c < n; ++c) {
+                if (args_.verbose) printf("Audio chunk %u evaluated:\n", first + c);
+                recordBest(values.data() + (size_t)c * d, fitness[c]);
+            }
+            last = n - 1;
+        }
+        std::vector<float> v((size_t)P * d), s((size_t)P * d), f(P);
+        checkBatch(sots_batch_read_population(batch_, last, v.data(), v.size() * sizeof(float), s.data(), s.size() * sizeof(float), f.data(),
+                                              f.size() * sizeof(float)), "sots_batch_read_population");
+        check(sots_write_population(ctx_, v.data(), v.size() * sizeof(float), s.data(), s.size() * sizeof(float), f.data(), f.size() * sizeof(float)),
+              "writePopulationData");
     }
 };
 

@@ -2,7 +2,7 @@
 //     sots_match -j parameters.json
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
 // "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "numDevices", "numElites",
-// "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic"}},
+// "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
 // N-sample chunk with Evolutionary_Strategy_HIP, writes inputGenerated.wav and the
 // outputAudioPath rendering of the best match, and prints the best parameters.
@@ -190,6 +190,8 @@ int main(int argc, char *argv[])
             if (h.has("overlapMigration")) args.overlapMigration = h["overlapMigration"].b;
             if (h.has("fullSortEveryGeneration")) args.fullSortEveryGeneration = h["fullSortEveryGeneration"].b;
             if (h.has("deviceKernelArithmetic")) args.deviceKernelArithmetic = h["deviceKernelArithmetic"].b;
+            // chunks matched at once (one population per chunk, the launches of one; Evolutionary_Strategy_HIP_Arguments)
+            if (h.has("chunksInFlight")) args.chunksInFlight = (uint32_t)h["chunksInFlight"].number();
             if (h.has("devices"))
                 for (const Json &dv : h["devices"].arr) args.devices.push_back((int32_t)dv.number());
             if (h.has("synth")) {
@@ -233,6 +235,7 @@ int main(int argc, char *argv[])
         std::cout << "Total time to complete: " << secs << "s" << std::endl;
         const double evaluated = (double)es->population.populationLength * args.numDevices * es->numGenerations * (targetAudio.size() / N);
         std::cout << "Candidates evaluated per second: " << evaluated / secs << std::endl;
+        std::cout << "Chunks matched per second: " << (double)(targetAudio.size() / N) / secs << std::endl;
 
         const uint32_t P = es->population.populationLength;
         std::vector<float> v(P * D), s(P * D), f(P);
