@@ -86,6 +86,14 @@ enum sots_sort_mode {
                               * than S elites fails with SOTS_ERR_STATE) */
 };
 
+/* How the selection of rows 0..S-1 (modes 0 and 2 above) is computed; the rows are the same bit for bit.
+ * TILES: two launches, sorted 1024-key tiles and a rank pass over their prefixes.  SPLITTERS: one launch that ranks every
+ * key between stored 64-bit splitters - exact whatever they are, fast when they are the previous selection's (each
+ * selection stores the next one's).  AUTO (default): SPLITTERS from the second generation of a run on, for P <= 65536;
+ * TILES for the first generation after anything replaced rows, fitness, target or sort mode, and from sots_stage_select.
+ * The environment variable SOTS_SELECT_PLAN (auto | tiles | splitters), read by sots_create, sets the initial plan. */
+enum sots_select_plan { SOTS_SELECT_AUTO = 0, SOTS_SELECT_TILES = 1, SOTS_SELECT_SPLITTERS = 2 };
+
 /* Which of the reference's two arithmetics synthesisePopulation uses.  Its CPU path (Evolutionary_Strategy.hpp:203,368-495)
  * keeps the sample-rate ratio in fp32; its device kernels (ocl_program.cl:280-443) write it as a double expression, fuse
  * their multiply-adds and, in the 3-op voice, add params[4] where the CPU path adds params[5]: the same parameters give
@@ -183,6 +191,12 @@ int sots_execute_generation(sots_ctx *ctx);
 int sots_execute_generations(sots_ctx *ctx, uint32_t n);
 
 int sots_set_sort_mode(sots_ctx *ctx, uint32_t mode); /* enum sots_sort_mode */
+int sots_set_select_plan(sots_ctx *ctx, uint32_t plan); /* enum sots_select_plan */
+/* The splitters the next SPLITTERS selection reads (one per compute unit: sots_select_splitter_count), for tests and
+ * diagnostics: keys are (order-preserving fitness bits << 32) | row index; any values are allowed. */
+int sots_select_splitter_count(const sots_ctx *ctx, uint32_t *count);
+int sots_write_select_splitters(sots_ctx *ctx, const uint64_t *keys, uint32_t count);
+int sots_read_select_splitters(sots_ctx *ctx, uint64_t *keys, uint32_t count);
 /* enum sots_synth_arith; applies to sots_stage_synthesise and to both generation loops from the next call on
  * (replaces nothing: the reference picks its arithmetic by picking a backend, main.cpp:105-163) */
 int sots_set_synth_arithmetic(sots_ctx *ctx, uint32_t arith);

@@ -26,6 +26,7 @@ SYNTH_NAMES = {"2op": SYNTH_2OP, "3op_series": SYNTH_3OP_SERIES,
  STAGE_FITNESS, STAGE_SORT, STAGE_ROTATE, STAGE_FUSED_VARIATION, STAGE_FUSED_SYNTH,
  STAGE_FUSED_SPECTRAL, STAGE_SORT_TAIL, STAGE_COUNT) = range(14)
 SORT_LAZY_TAIL, SORT_FULL, SORT_TOP_ONLY = 0, 1, 2
+SELECT_AUTO, SELECT_TILES, SELECT_SPLITTERS = 0, 1, 2
 ARITH_CPU_PATH, ARITH_DEVICE_KERNELS = 0, 1
 
 # the reference's Benchmarker timer names, Evolutionary_Strategy_OpenCL.hpp:117
@@ -42,6 +43,7 @@ EXPORTS = [
     "sots_stage_recombine", "sots_stage_mutate", "sots_stage_synthesise", "sots_stage_window",
     "sots_stage_fft", "sots_stage_fitness", "sots_stage_sort", "sots_stage_select", "sots_stage_rotate",
     "sots_set_sort_mode",
+    "sots_set_select_plan", "sots_select_splitter_count", "sots_write_select_splitters", "sots_read_select_splitters",
     "sots_set_synth_arithmetic",
     "sots_execute_generation", "sots_execute_generations", "sots_get_generation",
     "sots_set_generation", "sots_timing_enable", "sots_timing_reset", "sots_stage_time_ms",
@@ -118,6 +120,10 @@ def load():
     L.sots_write_synth.argtypes = [vp, vp, sz, vp, sz]
     L.sots_read_synth.argtypes = [vp, vp, sz, vp, sz, vp, sz]
     L.sots_set_sort_mode.argtypes = [vp, u32]
+    L.sots_set_select_plan.argtypes = [vp, u32]
+    L.sots_select_splitter_count.argtypes = [vp, C.POINTER(u32)]
+    L.sots_write_select_splitters.argtypes = [vp, vp, u32]
+    L.sots_read_select_splitters.argtypes = [vp, vp, u32]
     L.sots_set_synth_arithmetic.argtypes = [vp, u32]
     for name in ("recombine", "mutate", "synthesise", "window", "fft", "fitness", "sort", "select", "rotate"):
         getattr(L, "sots_stage_" + name).argtypes = [vp]
@@ -355,6 +361,25 @@ class HipES:
 
     def set_sort_mode(self, mode):
         self._check(self.L.sots_set_sort_mode(self._h, mode))
+
+    def set_select_plan(self, plan):
+        """SELECT_AUTO (default), SELECT_TILES or SELECT_SPLITTERS (enum sots_select_plan): the same rows either way"""
+        self._check(self.L.sots_set_select_plan(self._h, plan))
+
+    def select_splitter_count(self):
+        n = C.c_uint32()
+        self._check(self.L.sots_select_splitter_count(self._h, C.byref(n)))
+        return n.value
+
+    def write_select_splitters(self, keys):
+        """the 64-bit keys the next SPLITTERS selection ranks between (any values give the exact rows)"""
+        k = np.ascontiguousarray(keys, dtype=np.uint64)
+        self._check(self.L.sots_write_select_splitters(self._h, k.ctypes.data_as(C.c_void_p), k.size))
+
+    def read_select_splitters(self):
+        k = np.empty(self.select_splitter_count(), np.uint64)
+        self._check(self.L.sots_read_select_splitters(self._h, k.ctypes.data_as(C.c_void_p), k.size))
+        return k
 
     def set_synth_arithmetic(self, arith):
         """ARITH_CPU_PATH (default) or ARITH_DEVICE_KERNELS: the reference's OpenCL kernels' arithmetic (enum sots_synth_arith)"""

@@ -63,6 +63,13 @@ struct sots_ctx {
     uint32_t synth_arith = SOTS_ARITH_CPU_PATH;
     bool tail_pending = false;
     uint32_t tail_first = 0;
+    // the one-launch selection (k_sel_splitters): two slots of splitters, read and written in turn.  spl_valid: the
+    // slot spl_cur was written by the last selection of THIS population (a promise of speed only: any slot content
+    // gives the exact rows)
+    uint64_t *splitters = nullptr;
+    uint32_t spl_cur = 0;
+    bool spl_valid = false;
+    uint32_t select_plan = SOTS_SELECT_AUTO;
     // island exchange folded into the sort of the last generation of the next sots_execute_generations call
     SortExchange next_exchange{};
     bool next_exchange_set = false;
@@ -232,7 +239,7 @@ void free_ctx(sots_ctx *ctx)
         for (hipEvent_t e : all) (void)hipEventDestroy(e);
     }
     void *bufs[] = {ctx->values, ctx->steps, ctx->fitness, ctx->audio, ctx->spectrum, ctx->target,
-                    ctx->wavetable, ctx->window, ctx->rows, ctx->twiddle, ctx->keys, ctx->sort_scratch, ctx->x_image};
+                    ctx->wavetable, ctx->window, ctx->rows, ctx->twiddle, ctx->keys, ctx->sort_scratch, ctx->x_image, ctx->splitters};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -302,6 +309,41 @@ int settle_tail(sots_ctx *ctx)
     if (int rc = complete_tail(ctx)) return rc;
     ctx->tail_pending = false;
     ctx->tail_first = 0;
+    ctx->spl_valid = false; // rows or fitness are about to change under the stored splitters
+    return SOTS_OK;
+}
+
+uint64_t *splitter_slot(const sots_ctx *ctx, uint32_t which)
+{
+    return ctx->splitters + (size_t)which * (select_splitter_slot_bytes() / sizeof(uint64_t));
+}
+
+// does sortPopulation of the fused loop (or sots_stage_select) take the one-launch selection now?  SPLITTERS: always;
+// AUTO: when the slot holds the last selection's splitters and the population is one the two-launch selection
+// handles without its merge pass (P <= 65536; at 131072 the two plans have not been compared)
+bool use_splitters(const sots_ctx *ctx)
+{
+    if (ctx->select_plan == SOTS_SELECT_SPLITTERS) return true;
+    if (ctx->select_plan == SOTS_SELECT_TILES) return false;
+    return ctx->spl_valid && ctx->P <= 65536u;
+}
+
+// the selection of rows 0..need-1 from half src into half dst, by the plan in force
+int run_select(sots_ctx *ctx, uint32_t src, uint32_t dst, uint32_t need, const SortExchange *ex)
+{
+    if (use_splitters(ctx)) {
+        SOTS_HIP(ctx, launch_select_splitters(ctx->stream, ctx->val(src), ctx->stp(src), ctx->fit(src), ctx->val(dst), ctx->stp(dst),
+                                              ctx->fit(dst), ctx->keys, splitter_slot(ctx, ctx->spl_cur), splitter_slot(ctx, ctx->spl_cur ^ 1u),
+                                              ctx->P, ctx->D, need, ctx->num_cus, ex));
+    } else {
+        SOTS_HIP(ctx, launch_select(ctx->stream, ctx->val(src), ctx->stp(src), ctx->fit(src), ctx->val(dst), ctx->stp(dst),
+                                    ctx->fit(dst), ctx->keys, ctx->sort_scratch, ctx->P, ctx->D, need, ctx->num_cus, ex));
+        if (ctx->select_plan == SOTS_SELECT_TILES || ctx->P > 65536u) return SOTS_OK; // nobody will read a slot
+        // the sorted fitness just written seeds the other slot for the next generation
+        SOTS_HIP(ctx, launch_select_seed(ctx->stream, ctx->fit(dst), splitter_slot(ctx, ctx->spl_cur ^ 1u), need, ctx->num_cus));
+    }
+    ctx->spl_cur ^= 1u;
+    ctx->spl_valid = true;
     return SOTS_OK;
 }
 
@@ -422,6 +464,12 @@ int sots_create(const sots_config *cfg, sots_ctx **out)
         const size_t a = sort_scratch_bytes(ctx->P), b = select_scratch_bytes(ctx->P);
         CREATE_HIP(hipMalloc(&ctx->sort_scratch, a > b ? a : b));
     }
+    CREATE_HIP(hipMalloc((void **)&ctx->splitters, 2 * select_splitter_slot_bytes()));
+    CREATE_HIP(hipMemsetAsync(ctx->splitters, 0, 2 * select_splitter_slot_bytes(), ctx->stream));
+    if (const char *e = getenv("SOTS_SELECT_PLAN")) { // one library measured both ways; sots_set_select_plan overrides it
+        if (!strcmp(e, "tiles") || !strcmp(e, "1")) ctx->select_plan = SOTS_SELECT_TILES;
+        else if (!strcmp(e, "splitters") || !strcmp(e, "2")) ctx->select_plan = SOTS_SELECT_SPLITTERS;
+    }
     CREATE_HIP(hipMemsetAsync(ctx->values, 0, pd_bytes, ctx->stream));
     CREATE_HIP(hipMemsetAsync(ctx->steps, 0, pd_bytes, ctx->stream));
     CREATE_HIP(hipMemsetAsync(ctx->fitness, 0, (size_t)2 * ctx->P * sizeof(float), ctx->stream));
@@ -481,6 +529,7 @@ int sots_set_target_spectrum(sots_ctx *ctx, const float *magnitudes, uint32_t nu
     }
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->target_set = true;
+    ctx->spl_valid = false; // the fitness landscape changes
     return SOTS_OK;
 }
 
@@ -503,6 +552,7 @@ int sots_init_population(sots_ctx *ctx, uint32_t chunk_index)
     // a tail the last run's selection left pending belongs to the OLD population: dropped, never completed into the new one
     ctx->tail_pending = false;
     ctx->tail_first = 0;
+    ctx->spl_valid = false;
     ctx->next_exchange_set = false;
     {
         StageScope t(ctx, SOTS_STAGE_INIT);
@@ -697,8 +747,7 @@ int sots_stage_select(sots_ctx *ctx)
     if (ctx->sort_mode == SOTS_SORT_FULL || !select_applies(ctx->P, need)) return sots_stage_sort(ctx);
     {
         StageScope t(ctx, SOTS_STAGE_SORT);
-        SOTS_HIP(ctx, launch_select(ctx->stream, ctx->val(src), ctx->stp(src), ctx->fit(src), ctx->val(dst), ctx->stp(dst),
-                                    ctx->fit(dst), ctx->keys, ctx->sort_scratch, ctx->P, ctx->D, need, ctx->num_cus));
+        if (int rc = run_select(ctx, src, dst, need, nullptr)) return rc;
     }
     ctx->tail_pending = true; // completed from the current (unsorted) half once sots_stage_rotate has flipped
     ctx->tail_first = 0;      // marks "selected into the other half, not rotated yet"
@@ -810,8 +859,7 @@ int sots_execute_generations(sots_ctx *ctx, uint32_t n)
             StageScope t(ctx, SOTS_STAGE_SORT, true);
             if (select) {
                 // the rows recombination reads, in order; the rest of the order is produced on demand
-                SOTS_HIP(ctx, launch_select(ctx->stream, ctx->val(src), ctx->stp(src), ctx->fit(src), ctx->val(dst),
-                                            ctx->stp(dst), ctx->fit(dst), ctx->keys, ctx->sort_scratch, ctx->P, ctx->D, need, ctx->num_cus, ex));
+                if (int rc = run_select(ctx, src, dst, need, ex)) return rc;
             } else {
                 SOTS_HIP(ctx, launch_sort(ctx->stream, ctx->val(src), ctx->stp(src), ctx->fit(src), ctx->val(dst), ctx->stp(dst),
                                           ctx->fit(dst), ctx->keys, ctx->sort_scratch, ctx->P, ctx->D, 0, ex));
@@ -833,7 +881,46 @@ int sots_set_sort_mode(sots_ctx *ctx, uint32_t mode)
     // the new mode decides what happens to a pending tail: leaving SOTS_SORT_TOP_ONLY completes it (the unsorted half
     // is intact as long as the state is pending, settle_tail), entering it keeps the rows unspecified
     ctx->sort_mode = mode;
+    ctx->spl_valid = false;
     return complete_tail(ctx);
+}
+
+int sots_set_select_plan(sots_ctx *ctx, uint32_t plan)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (plan > SOTS_SELECT_SPLITTERS) return fail(ctx, SOTS_ERR_INVALID, "unknown select plan %u", plan);
+    ctx->select_plan = plan;
+    return SOTS_OK;
+}
+
+int sots_select_splitter_count(const sots_ctx *ctx, uint32_t *count)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (!count) return fail(ctx, SOTS_ERR_INVALID, "null count");
+    *count = select_splitter_count(ctx->num_cus);
+    return SOTS_OK;
+}
+
+int sots_write_select_splitters(sots_ctx *ctx, const uint64_t *keys, uint32_t count)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    const uint32_t b = select_splitter_count(ctx->num_cus);
+    if (!keys || count != b) return fail(ctx, SOTS_ERR_SIZE, "select splitters: %u keys needed, got %u", b, count);
+    if (int rc = bind_device(ctx)) return rc;
+    SOTS_HIP(ctx, hipMemcpyAsync(splitter_slot(ctx, ctx->spl_cur), keys, (size_t)b * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SOTS_OK;
+}
+
+int sots_read_select_splitters(sots_ctx *ctx, uint64_t *keys, uint32_t count)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    const uint32_t b = select_splitter_count(ctx->num_cus);
+    if (!keys || count != b) return fail(ctx, SOTS_ERR_SIZE, "select splitters: %u keys needed, got %u", b, count);
+    if (int rc = bind_device(ctx)) return rc;
+    SOTS_HIP(ctx, hipMemcpyAsync(keys, splitter_slot(ctx, ctx->spl_cur), (size_t)b * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SOTS_OK;
 }
 
 int sots_set_synth_arithmetic(sots_ctx *ctx, uint32_t arith)

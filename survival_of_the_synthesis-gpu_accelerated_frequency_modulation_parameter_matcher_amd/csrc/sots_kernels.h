@@ -144,6 +144,17 @@ size_t select_scratch_bytes(uint32_t p); // the sort scratch must hold at least 
 hipError_t launch_select(hipStream_t st, const float *vin, const float *sin, const float *fin, float *vout,
                          float *sout, float *fout, uint64_t *keys, void *scratch, uint32_t p, uint32_t d, uint32_t need,
                          uint32_t num_cus, const SortExchange *exchange = nullptr);
+// The same selection in ONE launch, ranked between the splitters of a slot (k_sel_splitters): spl_in holds
+// select_splitter_count() 64-bit keys - ANY values give the exact rows, the previous generation's give them fast -
+// and spl_out (a different slot) receives this population's.  keys: the sort_keys_bytes(P) buffer (a bucket that
+// outgrows the LDS is ordered there).  launch_select_seed fills a slot from the sorted fitness launch_select wrote.
+uint32_t select_splitter_count(uint32_t num_cus);
+size_t select_splitter_slot_bytes();
+hipError_t launch_select_splitters(hipStream_t st, const float *vin, const float *sin, const float *fin, float *vout,
+                                   float *sout, float *fout, uint64_t *keys, const uint64_t *spl_in, uint64_t *spl_out,
+                                   uint32_t p, uint32_t d, uint32_t need, uint32_t num_cus,
+                                   const SortExchange *exchange = nullptr);
+hipError_t launch_select_seed(hipStream_t st, const float *fsorted, uint64_t *spl_out, uint32_t need, uint32_t num_cus);
 
 // ---- island exchange ----
 hipError_t launch_pack_rows(hipStream_t st, const float *values, const float *steps, const float *fitness,

@@ -30,8 +30,11 @@ entry = {"_round": tag,
          "synthesise": round(nbytes(pick("k_synth"))),
          "window+FFT+fitness": round(nbytes(pick("k_fft"))),
          "recombine+mutate": round(nbytes("k_recombine_mutate")) if "k_recombine_mutate" in d else None,
-         # the fused loop's sortPopulation = the two selection kernels (k_sort_* only run when the order is read)
-         "sortPopulation": round(sum(nbytes(k) for k in d if k.startswith("k_sel")))}
+         # the fused loop's sortPopulation = the selection kernels (k_sort_* only run when the order is read), each weighted
+         # by how often it ran per generation: the one-launch selection runs from the second generation of a run on, the
+         # two-launch one and the seeding of the splitter slot in the first
+         "sortPopulation": round(sum(nbytes(k) * d[k].get("dispatches_seen", 0) for k in d if k.startswith("k_sel")) /
+                                 max(1, d[pick("k_fft")].get("dispatches_seen", 1)))}
 path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "pmc_traffic.json")
 allw = json.load(open(path)) if os.path.exists(path) else {}
 allw.setdefault("_source", "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes (tools/pmc_collect.sh), mean per dispatch; "
