@@ -322,6 +322,72 @@ int sots_batch_read_best(sots_batch *b, float *values, size_t values_bytes, floa
 int sots_batch_read_population(sots_batch *b, uint32_t chunk, float *values, size_t values_bytes,
                                float *steps, size_t steps_bytes, float *fitness, size_t fitness_bytes);
 
+/* ---- run record: best-ever individual, per-generation history, stop rules (new) ----
+ * The strategy is not elitist: recombination rewrites every row, the parent blocks included (ocl_program.cl:99-148), and
+ * mutation then changes every gene of every row, so row 0 after generation g can be worse than row 0 after g-1 - and
+ * the reference's printBest (Evolutionary_Strategy_OpenCL.hpp:612-631) and parameterMatchAudio (:572-610) report row 0 of
+ * the LAST generation, after a fixed number of them.  With tracking on, one small kernel after each generation's
+ * sortPopulation keeps, on the device and without a host round trip,
+ *   - the best individual seen so far (values, steps, fitness, the generation counter when it was seen): a row replaces
+ *     the record only when its fitness is strictly lower - a tie keeps the older record, NaN never wins;
+ *   - a record of the parent rows 0..numParents-1 whenever the generation counter is a multiple of history_every.
+ * It reads the parent rows only (every sort mode places them every generation) and writes nothing the loop reads: the
+ * population is bit for bit what it is with tracking off.  The means are pairwise sums in a fixed order, no atomics: the
+ * same population gives the same record bits run to run, and a batch chunk gives those of a single context.
+ * Both loops record: sots_execute_generations, and sots_execute_generation after its rotate; the single sots_stage_*
+ * calls do not.  A record describes the population as the sort left it, immigrants of a fused exchange
+ * (sots_fuse_exchange_next_sort) included, rows injected by a later launch not.  Off by default; with tracking off the
+ * loops enqueue exactly the launches they always did.  Islands of a group are tracked through sots_group_island. */
+typedef struct sots_gen_record {      /* 96 bytes */
+    uint32_t generation;              /* generations completed when taken (the context's counter after the sort) */
+    float best_fitness;               /* row 0 */
+    float best_ever_fitness;          /* after this generation's update */
+    float parent_worst_fitness;       /* row numParents-1 */
+    float parent_mean_fitness;
+    float reserved[3];                /* 0 */
+    float mean_step[SOTS_MAX_DIMS];   /* arithmetic mean of steps[0..numParents-1][d]; entries >= D are 0 */
+} sots_gen_record;
+enum sots_track_flags { SOTS_TRACK_BEST_EVER = 1, SOTS_TRACK_HISTORY = 2 /* implies SOTS_TRACK_BEST_EVER */ };
+typedef struct sots_stop_rule {
+    uint32_t struct_size;       /* = sizeof(sots_stop_rule) */
+    uint32_t check_interval;    /* generations between looks, >= 1 */
+    float target_fitness;       /* holds when best-ever fitness <= target; negative = off */
+    uint32_t stall_generations; /* holds when generation - best-ever generation >= this (saturating); 0 = off */
+} sots_stop_rule;
+
+/* flags 0 frees the buffers and restores the untracked launch sequence; any other call (re)allocates and starts from
+ * cleared records.  With SOTS_TRACK_HISTORY history_every and history_capacity must be >= 1: the store is a ring of the
+ * newest history_capacity records.  Blocking (synchronises the stream). */
+int sots_track(sots_ctx *ctx, uint32_t flags, uint32_t history_every, uint32_t history_capacity);
+/* any pointer may be NULL; byte counts must equal D*4.  A cleared record is fitness +inf, generation 0, zeroed rows:
+ * sots_init_population and sots_set_target_* clear it (and the history), sots_write_population and
+ * sots_set_generation do not.  SOTS_ERR_STATE without SOTS_TRACK_BEST_EVER.  Blocking. */
+int sots_read_best_ever(sots_ctx *ctx, float *values, size_t values_bytes, float *steps, size_t steps_bytes,
+                        float *fitness, uint32_t *generation);
+/* the newest records, oldest first: *written = min(records held, capacity) (the newest of them when capacity is
+ * smaller), *taken (may be NULL) = records taken since the last clear.  SOTS_ERR_STATE without SOTS_TRACK_HISTORY.  Blocking. */
+int sots_read_history(sots_ctx *ctx, sots_gen_record *out, uint32_t capacity, uint32_t *written, uint64_t *taken);
+/* 1 when the rule holds, 0 when not, SOTS_ERR_INVALID for a null rule, a wrong struct_size or check_interval 0.  A rule
+ * with both conditions off never holds.  Pure host code: no device, no context. */
+int sots_stop_rule_holds(const sots_stop_rule *rule, float best_ever_fitness, uint32_t best_ever_generation,
+                         uint32_t generation);
+/* sots_execute_generations in blocks of rule->check_interval generations (the last one shorter when max_generations is
+ * not a multiple); after each block the best-ever {fitness, generation} come back through a small asynchronous copy to
+ * pinned memory and a stream synchronise, and sots_stop_rule_holds decides.  No look-ahead: *generations_run is the first
+ * block boundary at which the rule holds, or max_generations.  Needs SOTS_TRACK_BEST_EVER (SOTS_ERR_STATE). */
+int sots_execute_until(sots_ctx *ctx, uint32_t max_generations, const sots_stop_rule *rule, uint32_t *generations_run);
+
+/* the same for chunks in flight: every chunk keeps its own record, bit-identical to that of a tracked sots_ctx running
+ * chunk first_chunk_index + c.  sots_batch_init_population and sots_batch_set_target_* clear every chunk's record. */
+int sots_batch_track(sots_batch *b, uint32_t flags, uint32_t history_every, uint32_t history_capacity);
+/* values, steps: [active][D]; fitness, generation: [active]; any pointer may be NULL, byte counts must match */
+int sots_batch_read_best_ever(sots_batch *b, float *values, size_t values_bytes, float *steps, size_t steps_bytes,
+                              float *fitness, size_t fitness_bytes, uint32_t *generation, size_t generation_bytes);
+int sots_batch_read_history(sots_batch *b, uint32_t chunk, sots_gen_record *out, uint32_t capacity, uint32_t *written,
+                            uint64_t *taken);
+/* ends at the first block boundary at which the rule holds for EVERY active chunk (the chunks advance together) */
+int sots_batch_execute_until(sots_batch *b, uint32_t max_generations, const sots_stop_rule *rule, uint32_t *generations_run);
+
 /* ---- introspection ---- */
 typedef struct sots_info {
     uint32_t population_length, num_dimensions, audio_length, spectrum_row_floats;

@@ -58,7 +58,10 @@ EXPORTS = [
     "sots_batch_set_target_audio", "sots_batch_set_target_spectra", "sots_batch_init_population",
     "sots_batch_execute_generations", "sots_batch_set_synth_arithmetic", "sots_batch_read_best",
     "sots_batch_read_population",
+    "sots_track", "sots_read_best_ever", "sots_read_history", "sots_stop_rule_holds", "sots_execute_until",
+    "sots_batch_track", "sots_batch_read_best_ever", "sots_batch_read_history", "sots_batch_execute_until",
 ]
+TRACK_BEST_EVER, TRACK_HISTORY = 1, 2
 BATCH_MAX_POPULATION = 1024
 GROUP_OVERLAP, GROUP_FORCE_RCCL, GROUP_UNFUSED, GROUP_EVENT_WAITS = 1, 2, 4, 8
 MAX_GROUP_DEVICES = 16
@@ -88,6 +91,40 @@ class Info(C.Structure):
         ("compute_units", C.c_uint32), ("reserved", C.c_uint32),
         ("device_name", C.c_char * 128), ("arch", C.c_char * 32),
     ]
+
+
+class GenRecord(C.Structure):
+    """sots_gen_record: one history record of the parent rows (96 bytes)"""
+    _fields_ = [
+        ("generation", C.c_uint32), ("best_fitness", C.c_float), ("best_ever_fitness", C.c_float),
+        ("parent_worst_fitness", C.c_float), ("parent_mean_fitness", C.c_float), ("reserved", C.c_float * 3),
+        ("mean_step", C.c_float * MAX_DIMS),
+    ]
+
+
+GEN_RECORD_DTYPE = np.dtype([("generation", np.uint32), ("best_fitness", np.float32), ("best_ever_fitness", np.float32),
+                             ("parent_worst_fitness", np.float32), ("parent_mean_fitness", np.float32),
+                             ("reserved", np.float32, (3,)), ("mean_step", np.float32, (MAX_DIMS,))])
+
+
+class StopRule(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("check_interval", C.c_uint32), ("target_fitness", C.c_float),
+                ("stall_generations", C.c_uint32)]
+
+
+def make_stop_rule(target=None, stall=0, check_every=32):
+    """target None (or negative) = no fitness target; stall 0 = no stall rule"""
+    r = StopRule()
+    r.struct_size = C.sizeof(StopRule)
+    r.check_interval = check_every
+    r.target_fitness = -1.0 if target is None else float(target)
+    r.stall_generations = stall
+    return r
+
+
+def _track_args(best_ever, history_every, capacity):
+    flags = (TRACK_BEST_EVER if best_ever or history_every else 0) | (TRACK_HISTORY if history_every else 0)
+    return flags, history_every, capacity if history_every else 0
 
 
 _lib = None
@@ -171,6 +208,16 @@ def load():
     L.sots_batch_set_synth_arithmetic.argtypes = [vp, u32]
     L.sots_batch_read_best.argtypes = [vp, vp, sz, vp, sz]
     L.sots_batch_read_population.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz]
+    u64p = C.POINTER(C.c_uint64)
+    L.sots_track.argtypes = [vp, u32, u32, u32]
+    L.sots_read_best_ever.argtypes = [vp, vp, sz, vp, sz, C.POINTER(C.c_float), C.POINTER(u32)]
+    L.sots_read_history.argtypes = [vp, vp, u32, C.POINTER(u32), u64p]
+    L.sots_stop_rule_holds.argtypes = [C.POINTER(StopRule), C.c_float, u32, u32]
+    L.sots_execute_until.argtypes = [vp, u32, C.POINTER(StopRule), C.POINTER(u32)]
+    L.sots_batch_track.argtypes = [vp, u32, u32, u32]
+    L.sots_batch_read_best_ever.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz]
+    L.sots_batch_read_history.argtypes = [vp, u32, vp, u32, C.POINTER(u32), u64p]
+    L.sots_batch_execute_until.argtypes = [vp, u32, C.POINTER(StopRule), C.POINTER(u32)]
     _lib = L
     return L
 
@@ -401,6 +448,36 @@ class HipES:
     def generation(self, g):
         self._check(self.L.sots_set_generation(self._h, g))
 
+    # -- run record: best-ever individual, history, stop rules --
+    def track(self, best_ever=True, history_every=0, capacity=1024):
+        """best-ever record and, with history_every > 0, a ring of the newest `capacity` per-generation records;
+        track(False) switches it off.  Any call starts from cleared records."""
+        self._check(self.L.sots_track(self._h, *_track_args(best_ever, history_every, capacity)))
+        self._history_capacity = capacity if history_every else 0
+
+    def best_ever(self):
+        """(values[D], steps[D], fitness, generation) of the best individual seen since the last clear"""
+        v = np.empty(self.D, np.float32)
+        s = np.empty(self.D, np.float32)
+        f, g = C.c_float(), C.c_uint32()
+        self._check(self.L.sots_read_best_ever(self._h, _ptr(v), v.nbytes, _ptr(s), s.nbytes, C.byref(f), C.byref(g)))
+        return v, s, np.float32(f.value), g.value
+
+    def history(self, with_taken=False):
+        """the records held, oldest first, as a structured array (GEN_RECORD_DTYPE)"""
+        out = np.zeros(max(1, getattr(self, "_history_capacity", 0)), GEN_RECORD_DTYPE)
+        n, taken = C.c_uint32(), C.c_uint64()
+        self._check(self.L.sots_read_history(self._h, _ptr(out), out.size, C.byref(n), C.byref(taken)))
+        return (out[:n.value].copy(), taken.value) if with_taken else out[:n.value].copy()
+
+    def execute_until(self, max_generations, target=None, stall=0, check_every=32):
+        """generations in blocks of check_every until the best-ever fitness is <= target or has not improved for
+        `stall` generations; returns the generations run"""
+        rule = make_stop_rule(target, stall, check_every)
+        run = C.c_uint32()
+        self._check(self.L.sots_execute_until(self._h, max_generations, C.byref(rule), C.byref(run)))
+        return run.value
+
     # -- timing --
     def timing_enable(self, on=True):
         self._check(self.L.sots_timing_enable(self._h, 1 if on else 0))
@@ -526,6 +603,33 @@ class HipBatch:
         f = np.empty(self.P, np.float32)
         self._check(self.L.sots_batch_read_population(self._h, chunk, _ptr(v), v.nbytes, _ptr(s), s.nbytes, _ptr(f), f.nbytes))
         return v, s, f
+
+    # -- run record, per chunk (as HipES) --
+    def track(self, best_ever=True, history_every=0, capacity=1024):
+        self._check(self.L.sots_batch_track(self._h, *_track_args(best_ever, history_every, capacity)))
+        self._history_capacity = capacity if history_every else 0
+
+    def best_ever(self):
+        """(values[active][D], steps[active][D], fitness[active], generation[active])"""
+        v = np.empty((self.active, self.D), np.float32)
+        s = np.empty((self.active, self.D), np.float32)
+        f = np.empty(self.active, np.float32)
+        g = np.empty(self.active, np.uint32)
+        self._check(self.L.sots_batch_read_best_ever(self._h, _ptr(v), v.nbytes, _ptr(s), s.nbytes, _ptr(f), f.nbytes, _ptr(g), g.nbytes))
+        return v, s, f, g
+
+    def history(self, chunk, with_taken=False):
+        out = np.zeros(max(1, getattr(self, "_history_capacity", 0)), GEN_RECORD_DTYPE)
+        n, taken = C.c_uint32(), C.c_uint64()
+        self._check(self.L.sots_batch_read_history(self._h, chunk, _ptr(out), out.size, C.byref(n), C.byref(taken)))
+        return (out[:n.value].copy(), taken.value) if with_taken else out[:n.value].copy()
+
+    def execute_until(self, max_generations, target=None, stall=0, check_every=32):
+        """stops at the first boundary at which the rule holds for every active chunk; returns the generations run"""
+        rule = make_stop_rule(target, stall, check_every)
+        run = C.c_uint32()
+        self._check(self.L.sots_batch_execute_until(self._h, max_generations, C.byref(rule), C.byref(run)))
+        return run.value
 
 
 class HipGroup:

@@ -15,6 +15,7 @@
 #include "../../include/sots_hip.h"
 #include "sots_host_math.h"
 #include "sots_kernels.h"
+#include "sots_track.h"
 
 using namespace sots;
 
@@ -43,6 +44,7 @@ struct sots_batch {
     float *wavetable = nullptr, *window = nullptr, *x_image = nullptr;
     float2 *twiddle = nullptr;
     OccCache occ{};
+    TrackState track{}; // run record of every chunk (sots_batch_track)
     std::vector<double> window64;
     float window_factor = 1.0f, inv_n = 0.0f, inv_wf = 1.0f;
     mutable std::string err;
@@ -102,6 +104,7 @@ void free_batch(sots_batch *b)
                     b->wavetable, b->window, b->x_image, b->twiddle};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
+    track_release(b->track);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     (void)hipGetLastError();
     delete b;
@@ -266,6 +269,7 @@ int sots_batch_set_target_spectra(sots_batch *b, const float *magnitudes, uint32
     if (int rc = bind(b)) return rc;
     BATCH_HIP(b, hipMemcpyAsync(b->targets, magnitudes, need * sizeof(float), hipMemcpyHostToDevice, b->stream));
     BATCH_HIP(b, launch_seg_targets(b->stream, b->seg_image, b->targets, b->log2n, num_chunks));
+    BATCH_HIP(b, track_clear(b->track, b->stream)); // new targets: every chunk's record starts over
     BATCH_HIP(b, hipStreamSynchronize(b->stream));
     b->active = num_chunks;
     return SOTS_OK;
@@ -295,6 +299,7 @@ int sots_batch_init_population(sots_batch *b, uint32_t first_chunk_index)
     if (int rc = bind(b)) return rc;
     b->rot = 0;
     b->generation = 0;
+    BATCH_HIP(b, track_clear(b->track, b->stream));
     BATCH_HIP(b, launch_init_population_seg(b->stream, b->val(0), b->stp(0), b->fit(0), b->pd, first_chunk_index, b->active));
     return SOTS_OK;
 }
@@ -337,6 +342,88 @@ int sots_batch_execute_generations(sots_batch *b, uint32_t n)
                                      b->D, b->active));
         b->rot = dst;
         b->generation += 1;
+        // the run record of every active chunk (nothing when tracking is off)
+        BATCH_HIP(b, track_record(b->track, b->stream, b->val(b->rot), b->stp(b->rot), b->fit(b->rot), b->P, b->D, b->cfg.num_parents,
+                                  b->generation, b->active));
+    }
+    return SOTS_OK;
+}
+
+// ---- run record: as sots_track and its readers, per chunk ----
+int sots_batch_track(sots_batch *b, uint32_t flags, uint32_t history_every, uint32_t history_capacity)
+{
+    BATCH_REQUIRE(b);
+    if (flags & ~(uint32_t)(SOTS_TRACK_BEST_EVER | SOTS_TRACK_HISTORY)) return bfail(b, SOTS_ERR_INVALID, "unknown track flags %u", flags);
+    if (flags & SOTS_TRACK_HISTORY) {
+        flags |= SOTS_TRACK_BEST_EVER;
+        if (history_every == 0 || history_capacity == 0)
+            return bfail(b, SOTS_ERR_INVALID, "history needs history_every >= 1 and history_capacity >= 1 (got %u, %u)", history_every, history_capacity);
+        if ((uint64_t)history_capacity * b->max_chunks > kTrackMaxRecords)
+            return bfail(b, SOTS_ERR_INVALID, "history_capacity %u x max_chunks %u exceeds %llu records", history_capacity, b->max_chunks,
+                         (unsigned long long)kTrackMaxRecords);
+    }
+    if (int rc = bind(b)) return rc;
+    BATCH_HIP(b, hipStreamSynchronize(b->stream)); // a record launch may still be using the old buffers
+    BATCH_HIP(b, track_setup(b->track, flags, history_every, history_capacity, b->max_chunks, b->stream));
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    return SOTS_OK;
+}
+
+int sots_batch_read_best_ever(sots_batch *b, float *values, size_t values_bytes, float *steps, size_t steps_bytes, float *fitness,
+                              size_t fitness_bytes, uint32_t *generation, size_t generation_bytes)
+{
+    BATCH_REQUIRE(b);
+    if (int rc = require_active(b)) return rc;
+    if (!b->track.best_ever()) return bfail(b, SOTS_ERR_STATE, "best-ever tracking is off: call sots_batch_track first");
+    const size_t d_bytes = (size_t)b->D * sizeof(float), v_bytes = b->active * d_bytes, f_bytes = (size_t)b->active * sizeof(float);
+    if ((values && values_bytes != v_bytes) || (steps && steps_bytes != v_bytes) || (fitness && fitness_bytes != f_bytes) ||
+        (generation && generation_bytes != f_bytes))
+        return bfail(b, SOTS_ERR_SIZE, "best-ever byte counts must be %zu (values, steps) and %zu (fitness, generation)", v_bytes, f_bytes);
+    if (int rc = bind(b)) return rc;
+    const size_t pitch = (size_t)kTrackRowFloats * sizeof(float);
+    if (values)
+        BATCH_HIP(b, hipMemcpy2DAsync(values, d_bytes, b->track.rows, pitch, d_bytes, b->active, hipMemcpyDeviceToHost, b->stream));
+    if (steps)
+        BATCH_HIP(b, hipMemcpy2DAsync(steps, d_bytes, b->track.rows + SOTS_MAX_DIMS, pitch, d_bytes, b->active, hipMemcpyDeviceToHost, b->stream));
+    BATCH_HIP(b, track_fetch_meta(b->track, b->stream, b->active));
+    for (uint32_t c = 0; c < b->active; ++c) {
+        if (fitness) fitness[c] = track_fitness(b->track, c);
+        if (generation) generation[c] = b->track.pinned[2 * c + 1];
+    }
+    return SOTS_OK;
+}
+
+int sots_batch_read_history(sots_batch *b, uint32_t chunk, sots_gen_record *out, uint32_t capacity, uint32_t *written, uint64_t *taken)
+{
+    BATCH_REQUIRE(b);
+    if (!b->track.history()) return bfail(b, SOTS_ERR_STATE, "the history is off: call sots_batch_track with SOTS_TRACK_HISTORY first");
+    if (int rc = require_active(b)) return rc;
+    if (chunk >= b->active) return bfail(b, SOTS_ERR_INVALID, "chunk %u not in 0..%u", chunk, b->active - 1);
+    if (!written || (capacity && !out)) return bfail(b, SOTS_ERR_INVALID, "read_history: null argument");
+    if (int rc = bind(b)) return rc;
+    BATCH_HIP(b, track_read_history(b->track, b->stream, chunk, out, capacity, written));
+    if (taken) *taken = b->track.taken;
+    return SOTS_OK;
+}
+
+int sots_batch_execute_until(sots_batch *b, uint32_t max_generations, const sots_stop_rule *rule, uint32_t *generations_run)
+{
+    BATCH_REQUIRE(b);
+    if (generations_run) *generations_run = 0;
+    if (sots_stop_rule_holds(rule, 0.0f, 0, 0) < 0) return bfail(b, SOTS_ERR_INVALID, "stop rule: null, wrong struct_size or check_interval 0");
+    if (!b->track.best_ever()) return bfail(b, SOTS_ERR_STATE, "sots_batch_execute_until needs best-ever tracking: call sots_batch_track first");
+    if (int rc = require_active(b)) return rc;
+    uint32_t done = 0;
+    while (done < max_generations) {
+        const uint32_t block = rule->check_interval < max_generations - done ? rule->check_interval : max_generations - done;
+        if (int rc = sots_batch_execute_generations(b, block)) return rc;
+        done += block;
+        if (generations_run) *generations_run = done;
+        BATCH_HIP(b, track_fetch_meta(b->track, b->stream, b->active));
+        bool all = true; // the chunks advance together: the batch is done when every chunk is
+        for (uint32_t c = 0; c < b->active && all; ++c)
+            all = sots_stop_rule_holds(rule, track_fitness(b->track, c), b->track.pinned[2 * c + 1], b->generation) == 1;
+        if (all) break;
     }
     return SOTS_OK;
 }

@@ -15,6 +15,7 @@
 #include "../../include/sots_hip.h"
 #include "sots_host_math.h"
 #include "sots_kernels.h"
+#include "sots_track.h"
 
 using namespace sots;
 
@@ -71,6 +72,8 @@ struct sots_ctx {
     bool spl_valid = false;
     uint32_t select_plan = SOTS_SELECT_AUTO;
     // island exchange folded into the sort of the last generation of the next sots_execute_generations call
+    // run record (sots_track): best-ever individual and history, updated by one launch after each generation's sort
+    TrackState track{};
     SortExchange next_exchange{};
     bool next_exchange_set = false;
     hipEvent_t next_exchange_gate = nullptr; // the HOST waits for it right before that sort is enqueued
@@ -242,6 +245,7 @@ void free_ctx(sots_ctx *ctx)
                     ctx->wavetable, ctx->window, ctx->rows, ctx->twiddle, ctx->keys, ctx->sort_scratch, ctx->x_image, ctx->splitters};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
+    track_release(ctx->track);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     (void)hipGetLastError(); // nothing sticky survives a context (the launchers read hipGetLastError after each launch)
     delete ctx;
@@ -351,6 +355,21 @@ int require_target(sots_ctx *ctx)
 {
     if (!ctx->target_set)
         return fail(ctx, SOTS_ERR_STATE, "no target: call sots_set_target_audio or sots_set_target_spectrum first");
+    return SOTS_OK;
+}
+
+// the run record of the generation whose sort has just been enqueued: the current half, the counter after it
+int record_generation(sots_ctx *ctx)
+{
+    if (!ctx->track.flags) return SOTS_OK;
+    SOTS_HIP(ctx, track_record(ctx->track, ctx->stream, ctx->val(ctx->rot), ctx->stp(ctx->rot), ctx->fit(ctx->rot), ctx->P, ctx->D,
+                               ctx->cfg.num_parents, ctx->generation, 1));
+    return SOTS_OK;
+}
+
+int check_stop_rule(const sots_stop_rule *rule)
+{
+    if (!rule || rule->struct_size != sizeof(sots_stop_rule) || rule->check_interval == 0) return SOTS_ERR_INVALID;
     return SOTS_OK;
 }
 
@@ -527,6 +546,7 @@ int sots_set_target_spectrum(sots_ctx *ctx, const float *magnitudes, uint32_t nu
         SOTS_HIP(ctx, launch_x_tables(ctx->stream, ctx->x_image, ctx->twiddle, ctx->window, ctx->target, ctx->log2n));
         ctx->occ.x_image = ctx->x_image;
     }
+    SOTS_HIP(ctx, track_clear(ctx->track, ctx->stream)); // a new target: what was best against the old one says nothing
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->target_set = true;
     ctx->spl_valid = false; // the fitness landscape changes
@@ -554,6 +574,7 @@ int sots_init_population(sots_ctx *ctx, uint32_t chunk_index)
     ctx->tail_first = 0;
     ctx->spl_valid = false;
     ctx->next_exchange_set = false;
+    SOTS_HIP(ctx, track_clear(ctx->track, ctx->stream));
     {
         StageScope t(ctx, SOTS_STAGE_INIT);
         SOTS_HIP(ctx, launch_init_population(ctx->stream, ctx->val(0), ctx->stp(0), ctx->fit(0), ctx->pd, chunk_index));
@@ -782,7 +803,8 @@ int sots_execute_generation(sots_ctx *ctx)
     if ((rc = sots_stage_fft(ctx))) return rc;
     if ((rc = sots_stage_fitness(ctx))) return rc;
     if ((rc = sots_stage_sort(ctx))) return rc;
-    return sots_stage_rotate(ctx);
+    if ((rc = sots_stage_rotate(ctx))) return rc;
+    return record_generation(ctx);
 }
 
 int sots_execute_generations(sots_ctx *ctx, uint32_t n)
@@ -869,7 +891,84 @@ int sots_execute_generations(sots_ctx *ctx, uint32_t n)
         ctx->tail_pending = select;
         ctx->tail_first = need;
         ctx->generation += 1;
+        if (int rc = record_generation(ctx)) return rc;
         if (int rc = maybe_drain(ctx)) return rc;
+    }
+    return SOTS_OK;
+}
+
+// ---- run record ---------------------------------------------------------------------------
+int sots_track(sots_ctx *ctx, uint32_t flags, uint32_t history_every, uint32_t history_capacity)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (flags & ~(uint32_t)(SOTS_TRACK_BEST_EVER | SOTS_TRACK_HISTORY)) return fail(ctx, SOTS_ERR_INVALID, "unknown track flags %u", flags);
+    if (flags & SOTS_TRACK_HISTORY) {
+        flags |= SOTS_TRACK_BEST_EVER;
+        if (history_every == 0 || history_capacity == 0)
+            return fail(ctx, SOTS_ERR_INVALID, "history needs history_every >= 1 and history_capacity >= 1 (got %u, %u)", history_every, history_capacity);
+        if (history_capacity > kTrackMaxRecords)
+            return fail(ctx, SOTS_ERR_INVALID, "history_capacity %u exceeds %llu records", history_capacity, (unsigned long long)kTrackMaxRecords);
+    }
+    if (int rc = bind_device(ctx)) return rc;
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // a record launch may still be using the old buffers
+    SOTS_HIP(ctx, track_setup(ctx->track, flags, history_every, history_capacity, 1, ctx->stream));
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SOTS_OK;
+}
+
+int sots_read_best_ever(sots_ctx *ctx, float *values, size_t values_bytes, float *steps, size_t steps_bytes, float *fitness,
+                        uint32_t *generation)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (!ctx->track.best_ever()) return fail(ctx, SOTS_ERR_STATE, "best-ever tracking is off: call sots_track first");
+    const size_t d_bytes = (size_t)ctx->D * sizeof(float);
+    if ((values && values_bytes != d_bytes) || (steps && steps_bytes != d_bytes))
+        return fail(ctx, SOTS_ERR_SIZE, "best-ever byte counts must be %zu (values, steps)", d_bytes);
+    if (int rc = bind_device(ctx)) return rc;
+    if (values) SOTS_HIP(ctx, hipMemcpyAsync(values, ctx->track.rows, d_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (steps) SOTS_HIP(ctx, hipMemcpyAsync(steps, ctx->track.rows + SOTS_MAX_DIMS, d_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SOTS_HIP(ctx, track_fetch_meta(ctx->track, ctx->stream, 1));
+    if (fitness) *fitness = track_fitness(ctx->track, 0);
+    if (generation) *generation = ctx->track.pinned[1];
+    return SOTS_OK;
+}
+
+int sots_read_history(sots_ctx *ctx, sots_gen_record *out, uint32_t capacity, uint32_t *written, uint64_t *taken)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (!ctx->track.history()) return fail(ctx, SOTS_ERR_STATE, "the history is off: call sots_track with SOTS_TRACK_HISTORY first");
+    if (!written || (capacity && !out)) return fail(ctx, SOTS_ERR_INVALID, "read_history: null argument");
+    if (int rc = bind_device(ctx)) return rc;
+    SOTS_HIP(ctx, track_read_history(ctx->track, ctx->stream, 0, out, capacity, written));
+    if (taken) *taken = ctx->track.taken;
+    return SOTS_OK;
+}
+
+int sots_stop_rule_holds(const sots_stop_rule *rule, float best_ever_fitness, uint32_t best_ever_generation, uint32_t generation)
+{
+    if (int rc = check_stop_rule(rule)) return rc;
+    if (rule->target_fitness >= 0.0f && best_ever_fitness <= rule->target_fitness) return 1;
+    if (rule->stall_generations != 0) {
+        const uint32_t since = generation > best_ever_generation ? generation - best_ever_generation : 0u; // saturating
+        if (since >= rule->stall_generations) return 1;
+    }
+    return 0;
+}
+
+int sots_execute_until(sots_ctx *ctx, uint32_t max_generations, const sots_stop_rule *rule, uint32_t *generations_run)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (generations_run) *generations_run = 0;
+    if (check_stop_rule(rule)) return fail(ctx, SOTS_ERR_INVALID, "stop rule: null, wrong struct_size or check_interval 0");
+    if (!ctx->track.best_ever()) return fail(ctx, SOTS_ERR_STATE, "sots_execute_until needs best-ever tracking: call sots_track first");
+    uint32_t done = 0;
+    while (done < max_generations) {
+        const uint32_t block = std::min(rule->check_interval, max_generations - done);
+        if (int rc = sots_execute_generations(ctx, block)) return rc;
+        done += block;
+        if (generations_run) *generations_run = done;
+        SOTS_HIP(ctx, track_fetch_meta(ctx->track, ctx->stream, 1));
+        if (sots_stop_rule_holds(rule, track_fitness(ctx->track, 0), ctx->track.pinned[1], ctx->generation) == 1) break;
     }
     return SOTS_OK;
 }

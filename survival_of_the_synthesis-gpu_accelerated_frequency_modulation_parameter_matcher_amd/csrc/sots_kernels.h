@@ -186,6 +186,24 @@ hipError_t launch_fft_fitness_seg(hipStream_t st, const float *audio, const floa
 hipError_t launch_sort_seg(hipStream_t st, const float *vin, const float *sin, const float *fin, float *vout, float *sout,
                            float *fout, uint32_t p, uint32_t d, uint32_t chunks);
 
+// ---- run record (sots_track / sots_batch_track) ----
+// One launch, a workgroup per chunk, on the half a generation's sortPopulation has just written (rows chunk-major, p rows
+// per chunk; a context is one chunk).  It reads rows 0..parents-1 only.
+//   * best-ever: when fitness[0] is strictly below the chunk's recorded best (NaN never is), row 0 - values, steps,
+//     fitness - and `generation` replace the record.  meta: uint32[chunks][2] = {fitness bits, generation};
+//     rows: float[chunks][kTrackRowFloats] = {values[SOTS_MAX_DIMS], steps[SOTS_MAX_DIMS]}.
+//   * history, when slot != kTrackNoSlot: one sots_gen_record into hist[chunk][slot] of float[chunks][capacity]
+//     [kTrackRecordFloats].  The means are pairwise (tree) sums whose shape depends on `parents` and `d` alone: the same
+//     rows give the same bits in any launch, whatever the number of chunks.  No atomics.
+constexpr uint32_t kTrackRowFloats = 2 * SOTS_MAX_DIMS;
+constexpr uint32_t kTrackRecordFloats = 24; // sizeof(sots_gen_record) / 4
+constexpr uint32_t kTrackNoSlot = 0xFFFFFFFFu;
+// every chunk's record: fitness +inf, generation 0, zeroed rows
+hipError_t launch_track_clear(hipStream_t st, uint32_t *meta, float *rows, uint32_t chunks);
+hipError_t launch_track(hipStream_t st, const float *values, const float *steps, const float *fitness, uint32_t p, uint32_t d,
+                        uint32_t parents, uint32_t generation, uint32_t chunks, uint32_t *meta, float *rows, float *hist,
+                        uint32_t capacity, uint32_t slot);
+
 uint32_t next_pow2(uint32_t v);
 
 } // namespace sots

@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cstdio>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -71,6 +72,25 @@ struct Evolutionary_Strategy_HIP_Arguments
     // of one population per generation) - same results as the chunk-by-chunk loop.  In that mode the CSV gets only the
     // "Total Audio Analysis Time" row, no per-stage rows.  Otherwise (numDevices > 1, P > 1024) the chunk-by-chunk loop.
     uint32_t chunksInFlight = 1;
+    // Run record (type.HIP.{returnBestEver,historyEvery,historyPath,targetFitness,stallGenerations,stopCheckInterval};
+    // extends parameterMatchAudio and printBest, Evolutionary_Strategy_OpenCL.hpp:572-631, which report row 0 of the last
+    // of a fixed number of generations).  The strategy is not elitist, so that row can be worse than one held earlier.
+    // All off by default; single device only.
+    //   returnBestEver   : recordBest(), bestParametersPerChunk() and sots_match's final rendering use the best individual
+    //                      any generation of the chunk produced (kept on the device, sots_track)
+    //   historyEvery > 0 : a record of the parent rows every that many generations; with historyPath, written as CSV
+    //                      (chunk,generation,best,best_ever,parent_mean,parent_worst,step_0..step_{D-1}), one row per record
+    //   targetFitness >= 0 / stallGenerations > 0 : a chunk stops before numGenerations once its best-ever fitness is <= the
+    //                      target, or has not improved for stallGenerations generations; looked at every stopCheckInterval
+    //                      generations (sots_execute_until).  Chunks in flight advance together until every chunk of the
+    //                      batch has stopped; each chunk's result is taken at ITS stopping boundary, so it does not depend
+    //                      on chunksInFlight (its history goes on to the batch's last boundary).
+    bool returnBestEver = false;
+    uint32_t historyEvery = 0;
+    std::string historyPath = "";
+    float targetFitness = -1.0f;
+    uint32_t stallGenerations = 0;
+    uint32_t stopCheckInterval = 32;
     bool verbose = true;
     std::string logDirectory = "";    // where hiplog(...).csv goes ("" = cwd)
 };
@@ -93,6 +113,12 @@ private:
     uint32_t targetAudioLength = 0;
     std::vector<float> targetFFT_;
     std::vector<std::vector<float>> bestPerChunk_;
+    std::vector<float> bestFitnessPerChunk_;
+    std::vector<uint32_t> generationsPerChunk_; // generations each chunk's result was taken after
+    uint64_t generationsRun_ = 0;               // generations really run, over all chunks, by the last parameterMatchAudio
+    uint32_t lastRun_ = 0;                      // ... by the last executeAllGenerations
+    sots_stop_rule rule_{};
+    FILE *historyFile_ = nullptr;
     std::vector<float> launchScratch_;
     uint32_t bestIsland_ = 0;
     double candidatesPerSecond_ = 0.0;
@@ -154,6 +180,21 @@ private:
         }
         if (got < n) hipBenchmarker_.addTimer(name, ms - listed);
     }
+    bool stopRuleSet() const { return args_.targetFitness >= 0.0f || args_.stallGenerations > 0; }
+    bool tracking() const { return args_.returnBestEver || args_.historyEvery > 0 || stopRuleSet(); }
+    uint32_t trackFlags() const { return SOTS_TRACK_BEST_EVER | (args_.historyEvery > 0 ? (uint32_t)SOTS_TRACK_HISTORY : 0u); }
+    uint32_t historyCapacity() const { return args_.historyEvery ? numGenerations / args_.historyEvery + 1 : 0; }
+    void writeHistoryRows(uint32_t chunk, const std::vector<sots_gen_record> &records, uint32_t n)
+    {
+        if (!historyFile_) return;
+        for (uint32_t i = 0; i < n; ++i) {
+            const sots_gen_record &r = records[i];
+            fprintf(historyFile_, "%u,%u,%.9g,%.9g,%.9g,%.9g", chunk, r.generation, r.best_fitness, r.best_ever_fitness, r.parent_mean_fitness,
+                    r.parent_worst_fitness);
+            for (uint32_t j = 0; j < population.numDimensions; ++j) fprintf(historyFile_, ",%.9g", r.mean_step[j]);
+            fprintf(historyFile_, "\n");
+        }
+    }
     void harvestTimers()
     {
         if (!args_.benchmarkStages) return;
@@ -180,6 +221,7 @@ public:
     }
     ~Evolutionary_Strategy_HIP() override
     {
+        if (historyFile_) fclose(historyFile_);
         if (batch_) sots_batch_destroy(batch_);
         if (group_) sots_group_destroy(group_); // owns its islands
         else if (ctx_) sots_destroy(ctx_);
@@ -194,6 +236,11 @@ public:
     uint32_t bestIsland() const { return bestIsland_; }
     Benchmarker &benchmarker() { return hipBenchmarker_; }
     const std::vector<std::vector<float>> &bestParametersPerChunk() const { return bestPerChunk_; }
+    const std::vector<float> &bestFitnessPerChunk() const { return bestFitnessPerChunk_; }
+    // generations after which each chunk's result was taken: numGenerations, or where its stop rule first held
+    const std::vector<uint32_t> &generationsPerChunk() const { return generationsPerChunk_; }
+    // generations really run by the last parameterMatchAudio, summed over its chunks (chunks in flight run to their batch's end)
+    uint64_t generationsRun() const { return generationsRun_; }
     // candidates evaluated per second of the last parameterMatchAudio (population x generations x chunks / wall time)
     double candidatesPerSecond() const { return candidatesPerSecond_; }
 
@@ -239,6 +286,15 @@ public:
             for (uint32_t i = 0; i < numIslands(); ++i)
                 check(sots_set_synth_arithmetic(group_ ? sots_group_island(group_, i) : ctx_, SOTS_ARITH_DEVICE_KERNELS), "sots_set_synth_arithmetic");
         check(sots_timing_enable(ctx_, args_.benchmarkStages ? 1 : 0), "sots_timing_enable");
+        if (tracking()) {
+            if (group_) throw std::runtime_error("Evolutionary_Strategy_HIP: returnBestEver, the history and the stop rules need numDevices = 1");
+            if (args_.stopCheckInterval == 0) throw std::runtime_error("Evolutionary_Strategy_HIP: stopCheckInterval must be at least 1");
+            check(sots_track(ctx_, trackFlags(), args_.historyEvery, historyCapacity()), "sots_track");
+        }
+        rule_.struct_size = sizeof rule_;
+        rule_.check_interval = args_.stopCheckInterval;
+        rule_.target_fitness = args_.targetFitness;
+        rule_.stall_generations = args_.stallGenerations;
     }
     void initTargetAudio() override {}
 
@@ -293,7 +349,10 @@ public:
     }
     void executeAllGenerations() override
     {
-        if (group_) {
+        lastRun_ = numGenerations;
+        if (stopRuleSet()) { // (the fused loop, in blocks of stopCheckInterval generations)
+            check(sots_execute_until(ctx_, numGenerations, &rule_, &lastRun_), "executeAllGenerations");
+        } else if (group_) {
             checkGroup(sots_group_execute_generations(group_, numGenerations), "executeAllGenerations");
         } else if (args_.fusedGenerations) {
             check(sots_execute_generations(ctx_, numGenerations), "executeAllGenerations");
@@ -323,6 +382,18 @@ public:
         chunkSize_ = objective.audioLength;
         numChunks_ = aTargetAudioLength / chunkSize_;
         bestPerChunk_.clear();
+        bestFitnessPerChunk_.clear();
+        generationsPerChunk_.clear();
+        generationsRun_ = 0;
+        if (historyFile_) fclose(historyFile_), historyFile_ = nullptr;
+        if (args_.historyEvery > 0 && !args_.historyPath.empty()) {
+            historyFile_ = fopen(args_.historyPath.c_str(), "w");
+            if (!historyFile_) throw std::runtime_error("Evolutionary_Strategy_HIP: cannot write " + args_.historyPath);
+            fprintf(historyFile_, "chunk,generation,best,best_ever,parent_mean,parent_worst");
+            for (uint32_t j = 0; j < population.numDimensions; ++j) fprintf(historyFile_, ",step_%u", j);
+            fprintf(historyFile_, "\n");
+        }
+        std::vector<sots_gen_record> records(historyCapacity());
 
         const bool batched = args_.chunksInFlight > 1 && !group_ && population.populationLength <= 1024u;
         if (args_.chunksInFlight > 1 && !batched && args_.verbose)
@@ -340,12 +411,22 @@ public:
                 else check(sots_synchronize(ctx_), "synchronize");
                 if (args_.verbose) printf("Audio chunk %u evaluated:\n", i);
                 printBest();
+                generationsPerChunk_.push_back(lastRun_);
+                generationsRun_ += lastRun_;
+                if (stopRuleSet() && args_.verbose) printf("Generations run: %u\n", lastRun_);
+                if (historyFile_) {
+                    uint32_t got = 0;
+                    check(sots_read_history(ctx_, records.data(), (uint32_t)records.size(), &got, nullptr), "sots_read_history");
+                    writeHistoryRows(i, records, got);
+                }
                 harvestTimers();
             }
         }
         hipBenchmarker_.pauseTimer("Total Audio Analysis Time");
         const double totalMs = hipBenchmarker_.totalMs("Total Audio Analysis Time");
-        candidatesPerSecond_ = totalMs > 0.0 ? (double)population.populationLength * numIslands() * numGenerations * numChunks_ / (totalMs * 1e-3) : 0.0;
+        if (historyFile_) fclose(historyFile_), historyFile_ = nullptr;
+        // (generationsRun_ = numGenerations x numChunks_ unless a stop rule ended chunks early)
+        candidatesPerSecond_ = totalMs > 0.0 ? (double)population.populationLength * numIslands() * (double)generationsRun_ / (totalMs * 1e-3) : 0.0;
         if (args_.verbose) printf("Candidates evaluated per second: %.6g\n", candidatesPerSecond_);
 
         for (uint8_t k = 1; k < numKernels_; ++k)
@@ -360,6 +441,13 @@ public:
     {
         selectBestIsland();
         const uint32_t d = population.numDimensions;
+        if (args_.returnBestEver) { // the best individual any generation produced, not row 0 of the last one
+            std::vector<float> best(d);
+            float fitness = 0.0f;
+            check(sots_read_best_ever(ctx_, best.data(), best.size() * sizeof(float), nullptr, 0, &fitness, nullptr), "printBest");
+            recordBest(best.data(), fitness);
+            return;
+        }
         std::vector<float> v((size_t)population.populationLength * d), f(population.populationLength);
         check(sots_read_population(ctx_, v.data(), v.size() * sizeof(float), nullptr, 0, f.data(), f.size() * sizeof(float)), "printBest");
         recordBest(v.data(), f[0]);
@@ -372,6 +460,7 @@ private:
         const uint32_t d = population.numDimensions;
         std::vector<float> best(bestValues, bestValues + d);
         bestPerChunk_.push_back(best);
+        bestFitnessPerChunk_.push_back(bestFitness);
         if (!args_.verbose) return;
         const std::vector<float> scaled = objective.scaleParams(best);
         printf("Best parameters found:\n");
@@ -394,20 +483,67 @@ private:
             if (rc != SOTS_OK) throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + what + ": " + sots_batch_last_error(batch_));
         };
         if (args_.deviceKernelArithmetic) checkBatch(sots_batch_set_synth_arithmetic(batch_, SOTS_ARITH_DEVICE_KERNELS), "sots_batch_set_synth_arithmetic");
+        if (tracking()) checkBatch(sots_batch_track(batch_, trackFlags(), args_.historyEvery, historyCapacity()), "sots_batch_track");
         std::vector<float> mags((size_t)perBatch * half), values((size_t)perBatch * d), fitness(perBatch);
+        std::vector<float> nowValues((size_t)perBatch * d), nowFitness(perBatch), everFitness(perBatch);
+        std::vector<uint32_t> nowGeneration(perBatch), stoppedAt(perBatch);
+        std::vector<sots_gen_record> records(historyCapacity());
+        // every active chunk's result as of now: the best-ever record, or row 0 of the current generation
+        auto readResults = [&](uint32_t n, float *v, float *f) {
+            if (args_.returnBestEver)
+                checkBatch(sots_batch_read_best_ever(batch_, v, (size_t)n * d * sizeof(float), nullptr, 0, f, (size_t)n * sizeof(float), nullptr, 0),
+                           "sots_batch_read_best_ever");
+            else
+                checkBatch(sots_batch_read_best(batch_, v, (size_t)n * d * sizeof(float), f, (size_t)n * sizeof(float)), "sots_batch_read_best");
+        };
         uint32_t last = 0;
         for (uint32_t first = 0; first < numChunks_; first += perBatch) {
             const uint32_t n = std::min(perBatch, numChunks_ - first);
             for (uint32_t c = 0; c < n; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)chunkSize_ * (first + c)], mags.data() + (size_t)c * half);
             checkBatch(sots_batch_set_target_spectra(batch_, mags.data(), n * half, n), "sots_batch_set_target_spectra");
             checkBatch(sots_batch_init_population(batch_, first), "sots_batch_init_population");
-            checkBatch(sots_batch_execute_generations(batch_, numGenerations), "sots_batch_execute_generations");
-            checkBatch(sots_batch_synchronize(batch_), "sots_batch_synchronize");
-            checkBatch(sots_batch_read_best(batch_, values.data(), (size_t)n * d * sizeof(float), fitness.data(), (size_t)n * sizeof(float)),
-                       "sots_batch_read_best");
+            uint32_t done = 0;
+            if (stopRuleSet()) {
+                // one block of stopCheckInterval generations per call; a chunk whose rule holds at a boundary has its result
+                // taken there - what the chunk-by-chunk loop reports for it - and the batch goes on until every chunk has
+                std::fill(stoppedAt.begin(), stoppedAt.begin() + n, 0u);
+                uint32_t open = n;
+                while (done < numGenerations && open) {
+                    uint32_t run = 0;
+                    checkBatch(sots_batch_execute_until(batch_, std::min(args_.stopCheckInterval, numGenerations - done), &rule_, &run),
+                               "sots_batch_execute_until");
+                    done += run;
+                    checkBatch(sots_batch_read_best_ever(batch_, nullptr, 0, nullptr, 0, everFitness.data(), (size_t)n * sizeof(float),
+                                                         nowGeneration.data(), (size_t)n * sizeof(uint32_t)), "sots_batch_read_best_ever");
+                    bool fetched = false;
+                    for (uint32_t c = 0; c < n; ++c) {
+                        if (stoppedAt[c]) continue;
+                        if (sots_stop_rule_holds(&rule_, everFitness[c], nowGeneration[c], done) != 1 && done < numGenerations) continue;
+                        if (!fetched) readResults(n, nowValues.data(), nowFitness.data()), fetched = true;
+                        std::copy(nowValues.begin() + (size_t)c * d, nowValues.begin() + (size_t)(c + 1) * d, values.begin() + (size_t)c * d);
+                        fitness[c] = nowFitness[c];
+                        stoppedAt[c] = done;
+                        --open;
+                    }
+                }
+            } else {
+                checkBatch(sots_batch_execute_generations(batch_, numGenerations), "sots_batch_execute_generations");
+                checkBatch(sots_batch_synchronize(batch_), "sots_batch_synchronize");
+                readResults(n, values.data(), fitness.data());
+                done = numGenerations;
+                std::fill(stoppedAt.begin(), stoppedAt.begin() + n, done);
+            }
+            generationsRun_ += (uint64_t)done * n;
             for (uint32_t c = 0; c < n; ++c) {
                 if (args_.verbose) printf("Audio chunk %u evaluated:\n", first + c);
                 recordBest(values.data() + (size_t)c * d, fitness[c]);
+                generationsPerChunk_.push_back(stoppedAt[c]);
+                if (stopRuleSet() && args_.verbose) printf("Generations run: %u\n", stoppedAt[c]);
+                if (historyFile_) {
+                    uint32_t got = 0;
+                    checkBatch(sots_batch_read_history(batch_, c, records.data(), (uint32_t)records.size(), &got, nullptr), "sots_batch_read_history");
+                    writeHistoryRows(first + c, records, got);
+                }
             }
             last = n - 1;
         }

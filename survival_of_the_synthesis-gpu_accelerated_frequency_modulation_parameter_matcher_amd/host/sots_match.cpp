@@ -2,7 +2,8 @@
 //     sots_match -j parameters.json
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
 // "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "numDevices", "numElites",
-// "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight"}},
+// "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight",
+// "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
 // N-sample chunk with Evolutionary_Strategy_HIP, writes inputGenerated.wav and the
 // outputAudioPath rendering of the best match, and prints the best parameters.
@@ -192,6 +193,14 @@ int main(int argc, char *argv[])
             if (h.has("deviceKernelArithmetic")) args.deviceKernelArithmetic = h["deviceKernelArithmetic"].b;
             // chunks matched at once (one population per chunk, the launches of one; Evolutionary_Strategy_HIP_Arguments)
             if (h.has("chunksInFlight")) args.chunksInFlight = (uint32_t)h["chunksInFlight"].number();
+            // run record (Evolutionary_Strategy_HIP_Arguments): the best individual any generation produced, a history CSV,
+            // and stopping a chunk early on a fitness target or a stall
+            if (h.has("returnBestEver")) args.returnBestEver = h["returnBestEver"].b;
+            if (h.has("historyEvery")) args.historyEvery = (uint32_t)h["historyEvery"].number();
+            if (h.has("historyPath")) args.historyPath = h["historyPath"].str;
+            if (h.has("targetFitness")) args.targetFitness = (float)h["targetFitness"].number();
+            if (h.has("stallGenerations")) args.stallGenerations = (uint32_t)h["stallGenerations"].number();
+            if (h.has("stopCheckInterval")) args.stopCheckInterval = (uint32_t)h["stopCheckInterval"].number();
             if (h.has("devices"))
                 for (const Json &dv : h["devices"].arr) args.devices.push_back((int32_t)dv.number());
             if (h.has("synth")) {
@@ -201,7 +210,8 @@ int main(int argc, char *argv[])
             }
         }
         const uint32_t D = args.es_args.pop.numDimensions;
-        std::unique_ptr<Evolutionary_Strategy> es(new Evolutionary_Strategy_HIP(args));
+        Evolutionary_Strategy_HIP *hipEs = new Evolutionary_Strategy_HIP(args);
+        std::unique_ptr<Evolutionary_Strategy> es(hipEs);
         auto synthesise = [&](Objective &obj, const std::vector<float> &p, float *out) {
             if (D == 4) obj.synthesiseAudio(p, out);
             else if (D == 6) obj.synthesiseAudioDoubleSeries(p, out);
@@ -233,7 +243,8 @@ int main(int argc, char *argv[])
         es->parameterMatchAudio(targetAudio.data(), (uint32_t)targetAudio.size());
         const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
         std::cout << "Total time to complete: " << secs << "s" << std::endl;
-        const double evaluated = (double)es->population.populationLength * args.numDevices * es->numGenerations * (targetAudio.size() / N);
+        const double generations = (double)hipEs->generationsRun(); // over all chunks; fewer than numGenerations each where a stop rule ended them
+        const double evaluated = (double)es->population.populationLength * args.numDevices * generations;
         std::cout << "Candidates evaluated per second: " << evaluated / secs << std::endl;
         std::cout << "Chunks matched per second: " << (double)(targetAudio.size() / N) / secs << std::endl;
 
@@ -241,6 +252,10 @@ int main(int argc, char *argv[])
         std::vector<float> v(P * D), s(P * D), f(P);
         es->readPopulationData(v.data(), nullptr, P * D * sizeof(float), s.data(), nullptr, P * D * sizeof(float), f.data(), nullptr, P * sizeof(float));
         std::vector<float> best(v.begin(), v.begin() + D);
+        if (args.returnBestEver && !hipEs->bestParametersPerChunk().empty()) { // the last chunk's best-ever individual
+            best = hipEs->bestParametersPerChunk().back();
+            f[0] = hipEs->bestFitnessPerChunk().back();
+        }
 
         // render 2^14 samples of the best match (main.cpp:270-275)
         Objective render(P, D, args.es_args.paramMin, args.es_args.paramMax, 14);
