@@ -89,7 +89,8 @@ enum sots_sort_mode {
 /* How the selection of rows 0..S-1 (modes 0 and 2 above) is computed; the rows are the same bit for bit.
  * TILES: two launches, sorted 1024-key tiles and a rank pass over their prefixes.  SPLITTERS: one launch that ranks every
  * key between stored 64-bit splitters - exact whatever they are, fast when they are the previous selection's (each
- * selection stores the next one's).  AUTO (default): SPLITTERS from the second generation of a run on, for P <= 65536;
+ * selection stores the next one's).  AUTO (default): SPLITTERS from the second generation of a run on, for P <= 65536,
+ * and for P <= 131072 where the fused loop's spectral kernel files the keys for it (N = 1024);
  * TILES for the first generation after anything replaced rows, fitness, target or sort mode, and from sots_stage_select.
  * The environment variable SOTS_SELECT_PLAN (auto | tiles | splitters), read by sots_create, sets the initial plan. */
 enum sots_select_plan { SOTS_SELECT_AUTO = 0, SOTS_SELECT_TILES = 1, SOTS_SELECT_SPLITTERS = 2 };
@@ -197,6 +198,12 @@ int sots_set_select_plan(sots_ctx *ctx, uint32_t plan); /* enum sots_select_plan
 int sots_select_splitter_count(const sots_ctx *ctx, uint32_t *count);
 int sots_write_select_splitters(sots_ctx *ctx, const uint64_t *keys, uint32_t count);
 int sots_read_select_splitters(sots_ctx *ctx, uint64_t *keys, uint32_t count);
+/* List mode of the SPLITTERS selection, for tests: files the key of every row of the current half under its bucket
+ * between the splitters the next sots_stage_select reads - what the fused loop's spectral kernel does as it computes the
+ * fitness - so that this sots_stage_select takes its buckets from the lists.  Anything that replaces rows, fitness,
+ * splitters, target, plan or sort mode in between drops the lists again.  SOTS_ERR_STATE where a slot holds more than
+ * 256 splitters, or with SOTS_SELECT_LISTS=0 in the environment of sots_create (the selection then always streams). */
+int sots_stage_bucket_fitness(sots_ctx *ctx);
 /* enum sots_synth_arith; applies to sots_stage_synthesise and to both generation loops from the next call on
  * (replaces nothing: the reference picks its arithmetic by picking a backend, main.cpp:105-163) */
 int sots_set_synth_arithmetic(sots_ctx *ctx, uint32_t arith);

@@ -44,6 +44,7 @@ EXPORTS = [
     "sots_stage_fft", "sots_stage_fitness", "sots_stage_sort", "sots_stage_select", "sots_stage_rotate",
     "sots_set_sort_mode",
     "sots_set_select_plan", "sots_select_splitter_count", "sots_write_select_splitters", "sots_read_select_splitters",
+    "sots_stage_bucket_fitness",
     "sots_set_synth_arithmetic",
     "sots_execute_generation", "sots_execute_generations", "sots_get_generation",
     "sots_set_generation", "sots_timing_enable", "sots_timing_reset", "sots_stage_time_ms",
@@ -161,6 +162,7 @@ def load():
     L.sots_select_splitter_count.argtypes = [vp, C.POINTER(u32)]
     L.sots_write_select_splitters.argtypes = [vp, vp, u32]
     L.sots_read_select_splitters.argtypes = [vp, vp, u32]
+    L.sots_stage_bucket_fitness.argtypes = [vp]
     L.sots_set_synth_arithmetic.argtypes = [vp, u32]
     for name in ("recombine", "mutate", "synthesise", "window", "fft", "fitness", "sort", "select", "rotate"):
         getattr(L, "sots_stage_" + name).argtypes = [vp]
@@ -402,6 +404,10 @@ class HipES:
 
     def select(self):
         self._check(self.L.sots_stage_select(self._h))
+
+    def bucket_fitness(self):
+        """files the current half's keys between the splitters the next select() reads: that select() takes list mode"""
+        self._check(self.L.sots_stage_bucket_fitness(self._h))
 
     def rotate(self):
         self._check(self.L.sots_stage_rotate(self._h))

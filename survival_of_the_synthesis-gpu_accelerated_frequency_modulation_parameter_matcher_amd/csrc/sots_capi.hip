@@ -70,6 +70,16 @@ struct sots_ctx {
     uint64_t *splitters = nullptr;
     uint32_t spl_cur = 0;
     bool spl_valid = false;
+    // list mode of that selection: the spectral kernel files every key under its bucket between the
+    // splitters of slot spl_cur - counter set spl_cur, the key lists - and the selection reads its bucket from there.
+    // A set must be all zero when a launch starts to count into it: the selection that consumes set s clears set s ^ 1
+    // for the next generation, and cnt_dirty (bit s: set s may hold counts) makes the host clear a set that a generation
+    // without lists, an invalidation or a failed call has left behind.  lists_ready: sots_stage_bucket_fitness has
+    // filed the current half's fitness for the next sots_stage_select.
+    uint32_t *sel_cnt = nullptr;
+    uint64_t *sel_lists = nullptr;
+    uint32_t cnt_dirty = 0;
+    bool use_lists = true, lists_ready = false;
     uint32_t select_plan = SOTS_SELECT_AUTO;
     // island exchange folded into the sort of the last generation of the next sots_execute_generations call
     // run record (sots_track): best-ever individual and history, updated by one launch after each generation's sort
@@ -242,7 +252,8 @@ void free_ctx(sots_ctx *ctx)
         for (hipEvent_t e : all) (void)hipEventDestroy(e);
     }
     void *bufs[] = {ctx->values, ctx->steps, ctx->fitness, ctx->audio, ctx->spectrum, ctx->target,
-                    ctx->wavetable, ctx->window, ctx->rows, ctx->twiddle, ctx->keys, ctx->sort_scratch, ctx->x_image, ctx->splitters};
+                    ctx->wavetable, ctx->window, ctx->rows, ctx->twiddle, ctx->keys, ctx->sort_scratch, ctx->x_image, ctx->splitters,
+                    ctx->sel_cnt, ctx->sel_lists};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     track_release(ctx->track);
@@ -314,6 +325,7 @@ int settle_tail(sots_ctx *ctx)
     ctx->tail_pending = false;
     ctx->tail_first = 0;
     ctx->spl_valid = false; // rows or fitness are about to change under the stored splitters
+    ctx->lists_ready = false;
     return SOTS_OK;
 }
 
@@ -322,27 +334,65 @@ uint64_t *splitter_slot(const sots_ctx *ctx, uint32_t which)
     return ctx->splitters + (size_t)which * (select_splitter_slot_bytes() / sizeof(uint64_t));
 }
 
+// list mode: can keys be filed between this context's splitters at all (a slot that fits the filing kernels' LDS)?
+bool lists_possible(const sots_ctx *ctx)
+{
+    return ctx->use_lists && ctx->sel_cnt && ctx->sel_lists && select_splitter_count(ctx->num_cus) <= kSelListMaxBuckets;
+}
+
+// ... and does the fused loop's spectral kernel file them (the wide N = 1024 kernel)?
+bool lists_in_loop(const sots_ctx *ctx)
+{
+    return lists_possible(ctx) && ctx->skip_stage == 0 && select_lists_apply(ctx->P, ctx->log2n, ctx->num_cus);
+}
+
 // does sortPopulation of the fused loop (or sots_stage_select) take the one-launch selection now?  SPLITTERS: always;
-// AUTO: when the slot holds the last selection's splitters and the population is one the two-launch selection
-// handles without its merge pass (P <= 65536; at 131072 the two plans have not been compared)
+// AUTO: when the slot holds the last selection's splitters and P <= 65536 - or P <= 131072, the largest population the
+// two-launch selection handles, where the loop runs in list mode: the streaming kernel's cost grows with P x B and has
+// not been compared with the two launches there, list mode's does not, and at 131072 it won every round of the A/B
+// (profiles/r08_experiments.md)
+#ifndef SOTS_AUTO_MAX_P
+#define SOTS_AUTO_MAX_P 131072u // (65536u: the build variant of the A/B at 131072, profiles/r08_experiments.md)
+#endif
 bool use_splitters(const sots_ctx *ctx)
 {
     if (ctx->select_plan == SOTS_SELECT_SPLITTERS) return true;
     if (ctx->select_plan == SOTS_SELECT_TILES) return false;
-    return ctx->spl_valid && ctx->P <= 65536u;
+    return ctx->spl_valid && (ctx->P <= 65536u || (ctx->P <= SOTS_AUTO_MAX_P && lists_in_loop(ctx)));
 }
 
-// the selection of rows 0..need-1 from half src into half dst, by the plan in force
-int run_select(sots_ctx *ctx, uint32_t src, uint32_t dst, uint32_t need, const SortExchange *ex)
+uint32_t *counter_set(const sots_ctx *ctx, uint32_t which) { return ctx->sel_cnt + (size_t)which * (select_counters_bytes() / sizeof(uint32_t)); }
+
+SelLists lists_of(const sots_ctx *ctx)
+{
+    return SelLists{splitter_slot(ctx, ctx->spl_cur), counter_set(ctx, ctx->spl_cur), counter_set(ctx, ctx->spl_cur ^ 1u), ctx->sel_lists,
+                    select_splitter_count(ctx->num_cus)};
+}
+
+// in front of a launch that files keys between the splitters of slot spl_cur: its counter set is all zero
+int open_lists(sots_ctx *ctx, SelLists *out)
+{
+    const uint32_t bit = 1u << ctx->spl_cur;
+    if (ctx->cnt_dirty & bit) SOTS_HIP(ctx, hipMemsetAsync(counter_set(ctx, ctx->spl_cur), 0, select_counters_bytes(), ctx->stream));
+    ctx->cnt_dirty |= bit;
+    *out = lists_of(ctx);
+    return SOTS_OK;
+}
+
+// the selection of rows 0..need-1 from half src into half dst, by the plan in force.  lists: the keys of half src have
+// been filed between the splitters of slot spl_cur (open_lists) - the one-launch selection only
+int run_select(sots_ctx *ctx, uint32_t src, uint32_t dst, uint32_t need, const SortExchange *ex, bool lists = false)
 {
     if (use_splitters(ctx)) {
+        const SelLists sl = lists_of(ctx);
         SOTS_HIP(ctx, launch_select_splitters(ctx->stream, ctx->val(src), ctx->stp(src), ctx->fit(src), ctx->val(dst), ctx->stp(dst),
                                               ctx->fit(dst), ctx->keys, splitter_slot(ctx, ctx->spl_cur), splitter_slot(ctx, ctx->spl_cur ^ 1u),
-                                              ctx->P, ctx->D, need, ctx->num_cus, ex));
+                                              ctx->P, ctx->D, need, ctx->num_cus, ex, lists ? &sl : nullptr));
+        if (lists) ctx->cnt_dirty &= ~(1u << (ctx->spl_cur ^ 1u)); // cleared by that launch: the next generation counts into it
     } else {
         SOTS_HIP(ctx, launch_select(ctx->stream, ctx->val(src), ctx->stp(src), ctx->fit(src), ctx->val(dst), ctx->stp(dst),
                                     ctx->fit(dst), ctx->keys, ctx->sort_scratch, ctx->P, ctx->D, need, ctx->num_cus, ex));
-        if (ctx->select_plan == SOTS_SELECT_TILES || ctx->P > 65536u) return SOTS_OK; // nobody will read a slot
+        if (ctx->select_plan == SOTS_SELECT_TILES || (ctx->P > 65536u && !(ctx->P <= SOTS_AUTO_MAX_P && lists_in_loop(ctx)))) return SOTS_OK; // nobody will read a slot
         // the sorted fitness just written seeds the other slot for the next generation
         SOTS_HIP(ctx, launch_select_seed(ctx->stream, ctx->fit(dst), splitter_slot(ctx, ctx->spl_cur ^ 1u), need, ctx->num_cus));
     }
@@ -485,6 +535,11 @@ int sots_create(const sots_config *cfg, sots_ctx **out)
     }
     CREATE_HIP(hipMalloc((void **)&ctx->splitters, 2 * select_splitter_slot_bytes()));
     CREATE_HIP(hipMemsetAsync(ctx->splitters, 0, 2 * select_splitter_slot_bytes(), ctx->stream));
+    CREATE_HIP(hipMalloc((void **)&ctx->sel_cnt, 2 * select_counters_bytes()));
+    CREATE_HIP(hipMemsetAsync(ctx->sel_cnt, 0, 2 * select_counters_bytes(), ctx->stream));
+    CREATE_HIP(hipMalloc((void **)&ctx->sel_lists, select_lists_bytes(ctx->num_cus)));
+    CREATE_HIP(hipMemsetAsync(ctx->sel_lists, 0, select_lists_bytes(ctx->num_cus), ctx->stream));
+    if (const char *e = getenv("SOTS_SELECT_LISTS")) ctx->use_lists = strcmp(e, "0") != 0; // 0: the selection streams the fitness (comparisons)
     if (const char *e = getenv("SOTS_SELECT_PLAN")) { // one library measured both ways; sots_set_select_plan overrides it
         if (!strcmp(e, "tiles") || !strcmp(e, "1")) ctx->select_plan = SOTS_SELECT_TILES;
         else if (!strcmp(e, "splitters") || !strcmp(e, "2")) ctx->select_plan = SOTS_SELECT_SPLITTERS;
@@ -550,6 +605,7 @@ int sots_set_target_spectrum(sots_ctx *ctx, const float *magnitudes, uint32_t nu
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->target_set = true;
     ctx->spl_valid = false; // the fitness landscape changes
+    ctx->lists_ready = false;
     return SOTS_OK;
 }
 
@@ -573,6 +629,7 @@ int sots_init_population(sots_ctx *ctx, uint32_t chunk_index)
     ctx->tail_pending = false;
     ctx->tail_first = 0;
     ctx->spl_valid = false;
+    ctx->lists_ready = false;
     ctx->next_exchange_set = false;
     SOTS_HIP(ctx, track_clear(ctx->track, ctx->stream));
     {
@@ -762,23 +819,39 @@ int sots_stage_sort(sots_ctx *ctx)
 int sots_stage_select(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
+    const bool lists = ctx->lists_ready; // (filed from the half this selection reads: settle_tail writes the other one)
     if (int rc = settle_tail(ctx)) return rc;
     if (int rc = bind_device(ctx)) return rc;
     const uint32_t src = ctx->rot, dst = ctx->rot ^ 1u, need = selected_rows(ctx);
     if (ctx->sort_mode == SOTS_SORT_FULL || !select_applies(ctx->P, need)) return sots_stage_sort(ctx);
     {
         StageScope t(ctx, SOTS_STAGE_SORT);
-        if (int rc = run_select(ctx, src, dst, need, nullptr)) return rc;
+        if (int rc = run_select(ctx, src, dst, need, nullptr, lists)) return rc;
     }
     ctx->tail_pending = true; // completed from the current (unsorted) half once sots_stage_rotate has flipped
     ctx->tail_first = 0;      // marks "selected into the other half, not rotated yet"
     return maybe_drain(ctx);
 }
 
+// files the keys of the current half's fitness between the splitters the next sots_stage_select reads, as the fused
+// loop's spectral kernel does (tests: any fitness pattern and any slot reach the selection's list mode)
+int sots_stage_bucket_fitness(sots_ctx *ctx)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (!lists_possible(ctx)) return fail(ctx, SOTS_ERR_STATE, "no key lists here: %u splitters per slot, SOTS_SELECT_LISTS=%d", select_splitter_count(ctx->num_cus), (int)ctx->use_lists);
+    if (int rc = bind_device(ctx)) return rc;
+    SelLists sl;
+    if (int rc = open_lists(ctx, &sl)) return rc;
+    SOTS_HIP(ctx, launch_bucket_fitness(ctx->stream, ctx->fit(ctx->rot), ctx->P, sl));
+    ctx->lists_ready = true;
+    return SOTS_OK;
+}
+
 int sots_stage_rotate(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
     if (int rc = bind_device(ctx)) return rc;
+    ctx->lists_ready = false; // (filed from what was the current half)
     // rotationIndex_ flip, ...OpenCL.hpp:486; a kernel argument here, so no transfer
     StageScope t(ctx, SOTS_STAGE_ROTATE);
     if (ctx->tail_pending && ctx->tail_first == 0) { // sots_stage_select just ran: its rows are in the OTHER half
@@ -823,6 +896,7 @@ int sots_execute_generations(sots_ctx *ctx, uint32_t n)
     if (n > 0) ctx->next_exchange_set = false, ctx->next_exchange_gate = nullptr;
     if (with_exchange && select && exchange.sink && exchange.sink_rows > need)
         return fail(ctx, SOTS_ERR_INVALID, "fused exchange: %u elite rows asked for, sortPopulation places %u per generation here", exchange.sink_rows, need);
+    ctx->lists_ready = false;
     for (uint32_t g = 0; g < n; ++g) {
         // the variation below overwrites the unsorted half a pending tail would be completed from; nobody has
         // asked for those rows, so they are dropped
@@ -862,10 +936,16 @@ int sots_execute_generations(sots_ctx *ctx, uint32_t n)
                                        ctx->audio, ctx->sp, ctx->P, ctx->log2n, ctx->pitch, ctx->num_cus,
                                        fuse_variation ? &var : nullptr, ctx->allow_cut));
         }
+        // Will this generation's selection be the one-launch one, in front of the wide N = 1024 spectral kernel?  Then that
+        // kernel files every row's key under its bucket, and the selection reads lists instead of all P fitness values.
+        const bool lists = select && use_splitters(ctx) && lists_in_loop(ctx);
         if (ctx->skip_stage != 2) {
             StageScope t(ctx, SOTS_STAGE_FUSED_SPECTRAL, true);
+            SelLists sl;
+            if (lists)
+                if (int rc = open_lists(ctx, &sl)) return rc;
             SOTS_HIP(ctx, launch_fft_fitness(ctx->stream, ctx->audio, ctx->window, ctx->target, ctx->fit(ctx->rot), ctx->twiddle, ctx->P,
-                                             ctx->log2n, ctx->pitch, ctx->inv_n, ctx->inv_wf, ctx->num_cus, &ctx->occ));
+                                             ctx->log2n, ctx->pitch, ctx->inv_n, ctx->inv_wf, ctx->num_cus, &ctx->occ, lists ? &sl : nullptr));
         }
         src = ctx->rot;
         dst = ctx->rot ^ 1u;
@@ -881,7 +961,7 @@ int sots_execute_generations(sots_ctx *ctx, uint32_t n)
             StageScope t(ctx, SOTS_STAGE_SORT, true);
             if (select) {
                 // the rows recombination reads, in order; the rest of the order is produced on demand
-                if (int rc = run_select(ctx, src, dst, need, ex)) return rc;
+                if (int rc = run_select(ctx, src, dst, need, ex, lists)) return rc;
             } else {
                 SOTS_HIP(ctx, launch_sort(ctx->stream, ctx->val(src), ctx->stp(src), ctx->fit(src), ctx->val(dst), ctx->stp(dst),
                                           ctx->fit(dst), ctx->keys, ctx->sort_scratch, ctx->P, ctx->D, 0, ex));
@@ -981,6 +1061,7 @@ int sots_set_sort_mode(sots_ctx *ctx, uint32_t mode)
     // is intact as long as the state is pending, settle_tail), entering it keeps the rows unspecified
     ctx->sort_mode = mode;
     ctx->spl_valid = false;
+    ctx->lists_ready = false;
     return complete_tail(ctx);
 }
 
@@ -989,6 +1070,7 @@ int sots_set_select_plan(sots_ctx *ctx, uint32_t plan)
     SOTS_REQUIRE_CTX(ctx);
     if (plan > SOTS_SELECT_SPLITTERS) return fail(ctx, SOTS_ERR_INVALID, "unknown select plan %u", plan);
     ctx->select_plan = plan;
+    ctx->lists_ready = false;
     return SOTS_OK;
 }
 
@@ -1006,6 +1088,7 @@ int sots_write_select_splitters(sots_ctx *ctx, const uint64_t *keys, uint32_t co
     const uint32_t b = select_splitter_count(ctx->num_cus);
     if (!keys || count != b) return fail(ctx, SOTS_ERR_SIZE, "select splitters: %u keys needed, got %u", b, count);
     if (int rc = bind_device(ctx)) return rc;
+    ctx->lists_ready = false; // (filed between the old splitters)
     SOTS_HIP(ctx, hipMemcpyAsync(splitter_slot(ctx, ctx->spl_cur), keys, (size_t)b * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SOTS_OK;

@@ -111,9 +111,32 @@ hipError_t launch_fitness(hipStream_t st, const float *spectrum, const float *ta
 // audio[P][pitch] (x window when window != nullptr) x target -> fitness[P]; no spectrum in memory
 size_t x_table_bytes(uint32_t log2n);
 hipError_t launch_x_tables(hipStream_t st, float *image, const float2 *twiddle, const float *window, const float *target, uint32_t log2n);
+// List mode of the one-launch selection: the kernel that computes a row's fitness also files the row's key under its
+// bucket between the splitters of `slot`, so that the selection reads its bucket from `lists` instead of streaming all
+// P fitness values.  A bucket's list is kSelListShards segments of kSelListSeg places, each with a counter of its own:
+// a filing workgroup uses the segment of its number (one word takes some 88 returning atomics per microsecond on this
+// GPU, and a converged population sends the whole chip to three buckets at a time).  cnt: buckets x kSelListShards
+// counters, ALL ZERO when the filling launch starts, which count every key of the closed buckets, also those their
+// segment has no place for (the open last bucket is P minus their sum); lists: buckets x kSelListCap keys.
+// cnt_other: the other counter set, which the consuming selection leaves zeroed for the next generation.
+constexpr uint32_t kSelListCap = 2048, kSelListShards = 16, kSelListSeg = kSelListCap / kSelListShards;
+constexpr uint32_t kSelListMaxBuckets = 256; // splitters per slot up to which keys can be filed (the bounds sit in LDS)
+struct SelLists {
+    const uint64_t *slot;
+    uint32_t *cnt, *cnt_other;
+    uint64_t *lists;
+    uint32_t buckets;
+};
+// is there a bucketing kernel for this shape (the wide N = 1024 spectral kernel with the window, a slot that fits its LDS)?
+bool select_lists_apply(uint32_t p, uint32_t log2n, uint32_t num_cus);
+size_t select_lists_bytes(uint32_t num_cus);     // the key lists
+size_t select_counters_bytes();                  // ONE counter set
+// files the keys of fitness[0 .. p) as the bucketing spectral kernel would (tests: any fitness, any slot)
+hipError_t launch_bucket_fitness(hipStream_t st, const float *fitness, uint32_t p, const SelLists &lists);
+// lists: also file the keys (only where select_lists_apply(); elsewhere hipErrorInvalidValue)
 hipError_t launch_fft_fitness(hipStream_t st, const float *audio, const float *window, const float *target,
                               float *fitness, const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch,
-                              float inv_n, float inv_wf, uint32_t num_cus, OccCache *occ);
+                              float inv_n, float inv_wf, uint32_t num_cus, OccCache *occ, const SelLists *lists = nullptr);
 
 // Island exchange folded into sortPopulation (one generation of the fused loop, set through
 // sots_fuse_exchange_next_sort): the kernel that moves the sorted rows also
@@ -148,12 +171,14 @@ hipError_t launch_select(hipStream_t st, const float *vin, const float *sin, con
 // select_splitter_count() 64-bit keys - ANY values give the exact rows, the previous generation's give them fast -
 // and spl_out (a different slot) receives this population's.  keys: the sort_keys_bytes(P) buffer (a bucket that
 // outgrows the LDS is ordered there).  launch_select_seed fills a slot from the sorted fitness launch_select wrote.
+// lists (filled between the splitters of spl_in): a workgroup takes its bucket from them, and streams as without
+// them only where its list overflowed or the open bucket has rows or splitters to place.
 uint32_t select_splitter_count(uint32_t num_cus);
 size_t select_splitter_slot_bytes();
 hipError_t launch_select_splitters(hipStream_t st, const float *vin, const float *sin, const float *fin, float *vout,
                                    float *sout, float *fout, uint64_t *keys, const uint64_t *spl_in, uint64_t *spl_out,
                                    uint32_t p, uint32_t d, uint32_t need, uint32_t num_cus,
-                                   const SortExchange *exchange = nullptr);
+                                   const SortExchange *exchange = nullptr, const SelLists *lists = nullptr);
 hipError_t launch_select_seed(hipStream_t st, const float *fsorted, uint64_t *spl_out, uint32_t need, uint32_t num_cus);
 
 // ---- island exchange ----

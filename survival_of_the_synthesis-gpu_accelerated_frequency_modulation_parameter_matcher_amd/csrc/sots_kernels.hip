@@ -1754,6 +1754,113 @@ __device__ __forceinline__ const float *seg_target_chunk(const float *image, uin
     return image + kSegHead + (size_t)chunk * stride;
 }
 
+// ------------------------------------------------------------------------------------
+// Selection keys, and the bucket of a key between the splitters of a slot (list mode).  They stand in
+// front of the spectral kernel because k_fft<.., BUCKET = true> files every row's key under its bucket as soon as it
+// has the row's fitness: the selection then reads its bucket's keys from a list instead of streaming all P.
+// ------------------------------------------------------------------------------------
+// order-preserving bits of a fitness: every number (at most 0xFF800000, +inf) below NaN (0xFFFFFFFD), NaN
+// below the padding key (0xFFFFFFFE); 0xFFFFFFFF stays free so that "bits + 1" never wraps
+constexpr uint32_t kSelPadBits = 0xFFFFFFFEu;
+__device__ __forceinline__ uint32_t order_bits(float f)
+{
+    if (f != f) return 0xFFFFFFFDu;
+    const uint32_t u = __float_as_uint(f == 0.0f ? 0.0f : f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+constexpr uint32_t kSplBitsNegInf = 0x007FFFFFu, kSplBitsPosInf = 0xFF800000u; // order_bits(-inf), order_bits(+inf)
+
+__device__ __forceinline__ uint64_t sel_key(float f, uint32_t idx) { return ((uint64_t)order_bits(f) << 32) | idx; }
+
+// the least key that is >= t and that compares like t against every key that exists: bits below -inf's hold no key, and
+// neither does 0x7FFFFFFF (-0 is keyed as +0)
+__device__ __forceinline__ uint64_t spl_normalise(uint64_t t)
+{
+    const uint32_t b = (uint32_t)(t >> 32);
+    if (b < kSplBitsNegInf) return (uint64_t)kSplBitsNegInf << 32;
+    if (b == 0x7FFFFFFFu) return (uint64_t)0x80000000u << 32;
+    return t;
+}
+
+constexpr uint32_t kBktMaxBuckets = kSelListMaxBuckets; // bounds a bucketing workgroup keeps in LDS (2 KiB)
+static_assert(kBktMaxBuckets % kWave == 0, "a lane looks at kBktMaxBuckets / 64 bounds");
+
+// The slot made non-decreasing exactly as k_sel_splitters makes it (t_0 = 0, running maximum, spl_normalise), into
+// bnd: ONE wavefront, in front of a workgroup barrier.  Bound q's fitness bits lie at bnd[q], its row index at
+// bnd[kBktMaxBuckets + q].  Bound 0 and those from B on are ~0, a bound no key reaches: the bucket of a key is then the
+// number of bounds t_q <= key.
+__device__ __forceinline__ void bkt_bounds(const uint64_t *__restrict__ slot, uint32_t B, uint32_t *__restrict__ bnd, uint32_t lane)
+{
+    constexpr uint32_t C = kBktMaxBuckets / kWave;
+    unsigned long long v[C], carry = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < C; ++c) {
+        const uint32_t q = c * kWave + lane;
+        v[c] = q && q < B ? slot[q] : 0ull;
+    }
+#pragma unroll
+    for (uint32_t c = 0; c < C; ++c) {
+        unsigned long long x = v[c];
+#pragma unroll
+        for (uint32_t m = 1; m < kWave; m <<= 1) {
+            const unsigned long long y = __shfl_up(x, m);
+            if (lane >= m && y > x) x = y;
+        }
+        x = x > carry ? x : carry;
+        carry = __shfl(x, kWave - 1);
+        const uint32_t q = c * kWave + lane;
+        const uint64_t t = q && q < B ? spl_normalise(x) : ~0ull;
+        bnd[q] = (uint32_t)(t >> 32);
+        bnd[kBktMaxBuckets + q] = (uint32_t)t;
+    }
+}
+
+// a key on its way into its bucket's list: key and segment (bucket * kSelListShards + shard) wavefront-uniform, pos lane
+// 0's (the counter's answer)
+struct BktPend {
+    uint64_t key;
+    uint32_t seg, pos;
+};
+constexpr uint32_t kBktNone = 0xFFFFFFFFu; // BktPend::seg: nothing on its way
+
+// the store that a visit left behind: the counter has answered by now
+__device__ __forceinline__ void bkt_flush(const SelLists &bk, const BktPend &pd, uint32_t lane)
+{
+    if (pd.seg != kBktNone && lane == 0 && pd.pos < kSelListSeg) bk.lists[(size_t)pd.seg * kSelListSeg + pd.pos] = pd.key;
+}
+// One wavefront-uniform key: the full 64-bit compare against every bound (in a tie population the row index decides),
+// a lane taking kBktMaxBuckets / 64 of them; the ballots' population counts add up to the bucket.  The fitness bits are
+// compared first, and the row indices only where a bound has the key's fitness bits (wavefront-uniform).  A CLOSED bucket
+// (j < B - 1) counts the key in the caller's shard - every key, also beyond the segment's capacity - and the key is stored
+// at the counter's answer by the NEXT visit (or bkt_flush): the answer then never stalls the caller's loop.  The open
+// last bucket does nothing: it is P minus the closed ones, and while a run improves it is a third of the population.
+// The count is an atomicInc that never wraps, not an atomicAdd: the compiler aggregates additions of a uniform value over
+// the wavefront and WAITS for the answer on the spot (s_waitcnt vmcnt(0): the caller's rows in flight with it).
+__device__ __forceinline__ void bkt_visit(const SelLists &bk, const uint32_t *__restrict__ bnd, uint64_t key, uint32_t shard, uint32_t lane,
+                                          BktPend &pd)
+{
+    bkt_flush(bk, pd, lane);
+    const uint32_t kb = (uint32_t)(key >> 32), ki = (uint32_t)key;
+    uint32_t j = 0;
+    uint64_t ties[kBktMaxBuckets / kWave], any = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < kBktMaxBuckets / kWave; ++c) {
+        const uint32_t hi = bnd[c * kWave + lane];
+        j += (uint32_t)__popcll(__ballot(hi < kb));
+        ties[c] = __ballot(hi == kb);
+        any |= ties[c];
+    }
+    if (any) {
+#pragma unroll
+        for (uint32_t c = 0; c < kBktMaxBuckets / kWave; ++c)
+            j += (uint32_t)__popcll(ties[c] & __ballot(bnd[kBktMaxBuckets + c * kWave + lane] <= ki));
+    }
+    pd.key = key;
+    pd.seg = j < bk.buckets - 1 ? j * kSelListShards + shard : kBktNone; // (buckets >= 2)
+    if (pd.seg != kBktNone && lane == 0) pd.pos = atomicInc(&bk.cnt[pd.seg], 0xFFFFFFFFu);
+}
+
 // MODE 0: write spectrum rows; MODE 1: accumulate the fitness directly
 // WIN: multiply by the fp32 window while loading (the generation loop then skips the window
 // pass; the product is the same single fp32 rounding either way).
@@ -1768,14 +1875,26 @@ __device__ __forceinline__ const float *seg_target_chunk(const float *image, uin
 // `target` is then a segmented target image (seg_target_rows / seg_target_chunk above) and every row reads its chunk's bins
 // from it in global memory (L2) instead of the workgroup's one target in LDS.  Same arithmetic, same order.
 template <int LOG2N> constexpr int fft_wide_waves() { return LOG2N == 10 ? 12 : 16; }
-template <int LOG2N, int MODE, bool WIN, int W = 1, bool SEG = false>
+// The lists are one more kernel argument of the BUCKET instantiation ONLY (LISTS = SelLists): the others keep their
+// argument list, and with it their code, to the byte (an argument in front of the hidden ones moves those).
+struct BktNoLists {};
+__device__ __forceinline__ BktNoLists bkt_lists() { return {}; }
+__device__ __forceinline__ const SelLists &bkt_lists(const SelLists &l) { return l; }
+// BUCKET (the wide fitness kernel in front of a one-launch selection, list mode): every row's key goes into the list of
+// its bucket between the splitters of bk.slot (bkt_visit above) - the slot was written a generation ago, the row's
+// fitness is in a register here, and the selection's 256 workgroups no longer ask all P rows each.
+template <int LOG2N, int MODE, bool WIN, int W = 1, bool SEG = false, bool BUCKET = false, typename... LISTS>
 __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audio, float *__restrict__ spectrum,
                                                    const float *__restrict__ target, float *__restrict__ fitness,
                                                    const float2 *__restrict__ tw, const float *__restrict__ window,
-                                                   uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch)
+                                                   uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch, LISTS... lists)
 {
+    static_assert(sizeof...(LISTS) == (BUCKET ? 1 : 0), "the BUCKET instantiation takes the lists, the others nothing");
+    [[maybe_unused]] const auto bk = bkt_lists(lists...);
     constexpr int N = 1 << LOG2N, M = N / 2, E = M / kWave, H = E / 2;
     static_assert(LOG2N == 9 || LOG2N == 10, "wavefront-per-row FFT is for N <= 1024");
+    static_assert(!BUCKET || (MODE == 1 && W > 1 && !SEG), "keys are filed by the wide fitness kernel only");
+    __shared__ uint32_t bnd_s[BUCKET ? 2 * kBktMaxBuckets : 1];
     __shared__ float2 lds_all[W][M + M / 8 + 1];
     __shared__ uint32_t next_s;
     const int lane = threadIdx.x & (kWave - 1);
@@ -1801,7 +1920,10 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
         for (int k = threadIdx.x; k < M; k += W * kWave) tgt_s[k] = target[k];
     }
     const uint32_t seg_rows = SEG ? seg_target_rows(target) : 1u;
-    if constexpr (MODE == 1 || W > 1) __syncthreads(); // (the only workgroup barrier: target and row counter are there)
+    if constexpr (BUCKET) {
+        if (wave == W - 1) bkt_bounds(bk.slot, bk.buckets, bnd_s, lane); // (a wavefront of the workgroup's last rows)
+    }
+    if constexpr (MODE == 1 || W > 1) __syncthreads(); // (the only workgroup barrier: target, row counter and bounds are there)
     if (ind >= p_len) return;
 
     // rows are read 16 bytes per lane: pair index lane + 64 h holds complex points 2(lane+64h), +1
@@ -1853,6 +1975,7 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
     if constexpr (W > 1) {
         if (lane == 0) pend = atomicAdd(&next_s, 1u);
     }
+    BktPend bkt = {0ull, kBktNone, 0u}; // the key whose place in its list is on its way (BUCKET)
     // transforms the row in `cur` (row `ind`) after requesting this wavefront's next take into `fill`; returns that row
     auto process = [&](float4 (&cur)[Q], float4 (&fill)[Q]) -> uint32_t {
         SOTS_FFT_T(t0);
@@ -1902,6 +2025,11 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
             }
             float acc = wave_sum(acc2.x + acc2.y);
             if (lane == 0) fitness[ind] = acc;
+            if constexpr (BUCKET) {
+                // (uniform by construction; said to the compiler so that key and bucket stay in scalar registers)
+                const uint32_t kb = __builtin_amdgcn_readfirstlane(order_bits(acc));
+                bkt_visit(bk, bnd_s, ((uint64_t)kb << 32) | ind, blockIdx.x % kSelListShards, lane, bkt);
+            }
         }
         wave_lds_sync<W == 1>(); // orders this row's LDS reads before the next row's writes
 #ifdef SOTS_STAMP
@@ -1935,6 +2063,7 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
         ind = r2, r1 = process(b2, b1);
         if (r0 >= p_len) break;
     }
+    if constexpr (BUCKET) bkt_flush(bk, bkt, lane);
 #ifdef SOTS_STAMP_ENDS
     if (lane == 0 && blockIdx.x * W + wave < 4096) {
         unsigned long long *o = g_stamps + (blockIdx.x * W + wave) * 4;
@@ -2322,16 +2451,6 @@ constexpr uint32_t kSelSkew = 4;                    // consecutive tiles start 4
 // four (k_sel_merge4).  Same-box A/B of the un-instrumented loop (profiles/r03_experiments.md): at P = 131072 the selection
 // beats the two-level full sort (237 against 244 us per generation), at 262144 it loses (496 against 482), so it stops at 128 tiles
 constexpr uint32_t kSelMinTiles = 16, kSelMaxTiles = 128, kSelMaxOwn = 512; // kSelMaxTiles: tiles the rank kernel handles (of either size)
-
-// order-preserving bits of a fitness: every number (at most 0xFF800000, +inf) below NaN (0xFFFFFFFD), NaN
-// below the padding key (0xFFFFFFFE); 0xFFFFFFFF stays free so that "bits + 1" never wraps
-constexpr uint32_t kSelPadBits = 0xFFFFFFFEu;
-__device__ __forceinline__ uint32_t order_bits(float f)
-{
-    if (f != f) return 0xFFFFFFFDu;
-    const uint32_t u = __float_as_uint(f == 0.0f ? 0.0f : f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // value of lane (lane ^ J) for J = 1, 2 (DPP quad permutes), 4, 8, 16 (ds_swizzle through the LDS crossbar,
 // no LDS memory), 32 (v_permlane32_swap)
@@ -2852,19 +2971,6 @@ constexpr uint32_t kSplThreads = 1024;
 constexpr uint32_t kSplCap = 8192;       // keys of the LDS list (64 KiB)
 constexpr uint32_t kSplMaxBuckets = 1024; // splitters per slot (the grid is one workgroup per CU)
 constexpr uint32_t kSplAhead = 16;        // 16-byte loads per lane requested up front (64 registers)
-constexpr uint32_t kSplBitsNegInf = 0x007FFFFFu, kSplBitsPosInf = 0xFF800000u; // order_bits(-inf), order_bits(+inf)
-
-__device__ __forceinline__ uint64_t sel_key(float f, uint32_t idx) { return ((uint64_t)order_bits(f) << 32) | idx; }
-
-// the least key that is >= t and that compares like t against every key that exists: bits below -inf's hold no key, and
-// neither does 0x7FFFFFFF (-0 is keyed as +0)
-__device__ __forceinline__ uint64_t spl_normalise(uint64_t t)
-{
-    const uint32_t b = (uint32_t)(t >> 32);
-    if (b < kSplBitsNegInf) return (uint64_t)kSplBitsNegInf << 32;
-    if (b == 0x7FFFFFFFu) return (uint64_t)0x80000000u << 32;
-    return t;
-}
 __device__ __forceinline__ float spl_bound_float(uint64_t t) // of a normalised bound with numeric bits
 {
     const uint32_t b = (uint32_t)(t >> 32);
@@ -3044,7 +3150,7 @@ __global__ __launch_bounds__(kSplThreads) void k_sel_splitters(const float *__re
                                                                 float *__restrict__ sout, float *__restrict__ fout,
                                                                 const uint64_t *__restrict__ spl_in, uint64_t *__restrict__ spl_out,
                                                                 uint64_t *__restrict__ keys_scratch, uint32_t p_len, uint32_t need,
-                                                                uint32_t step, uint32_t d, SortExchange ex, uint32_t vec)
+                                                                uint32_t step, uint32_t d, SortExchange ex, uint32_t vec, SelLists bk)
 {
     __shared__ __attribute__((aligned(16))) uint64_t list[kSplCap];
     __shared__ unsigned long long bound_s[2];
@@ -3056,10 +3162,29 @@ __global__ __launch_bounds__(kSplThreads) void k_sel_splitters(const float *__re
     // the slot, then the stream, are requested before anything else (loads return in order: the bounds are made while the
     // keys arrive)
     const unsigned long long my_spl = tid && tid <= j + 1 && tid < B ? spl_in[tid] : 0ull; // B <= kSplThreads
-    const uint32_t full = (vec & 1u) ? p_len / (4 * kSplThreads) : 0u;
+    // LIST MODE (bk.cnt): the kernel that made the fitness has filed every key under its bucket between these same
+    // splitters.  Instead of the stream: the closed buckets' counters - c is the sum of those in front, n the own one, the
+    // open bucket's the rest of P - and the own list, asked for at its full capacity before n is known (what lies
+    // beyond n is an older generation's and is never looked at).  The set the NEXT generation counts into is cleared here.
+    const bool by_list = bk.cnt != nullptr;
+    constexpr uint32_t kShardWords = kSelListShards / 4; // a bucket's counters, 16 bytes at a time
+    uint4 cnt_q[kShardWords], own_q[kShardWords];        // bucket tid's / this workgroup's own
+#pragma unroll
+    for (uint32_t w = 0; w < kShardWords; ++w) {
+        cnt_q[w] = by_list && tid + 1 < B ? reinterpret_cast<const uint4 *>(bk.cnt)[tid * kShardWords + w] : uint4{0u, 0u, 0u, 0u};
+        own_q[w] = by_list ? reinterpret_cast<const uint4 *>(bk.cnt)[j * kShardWords + w] : uint4{0u, 0u, 0u, 0u};
+    }
+    uint64_t pre_list[kSelListCap / kSplThreads];
+#pragma unroll
+    for (uint32_t u = 0; u < kSelListCap / kSplThreads; ++u) pre_list[u] = by_list ? bk.lists[(size_t)j * kSelListCap + u * kSplThreads + tid] : 0ull;
+    if (by_list && tid < kSelListShards) bk.cnt_other[j * kSelListShards + tid] = 0u;
+    uint32_t my_cnt = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kShardWords; ++w) my_cnt += cnt_q[w].x + cnt_q[w].y + cnt_q[w].z + cnt_q[w].w;
+    const uint32_t full = (vec & 1u) ? p_len / (4 * kSplThreads) : 0u, ahead = by_list ? 0u : full;
     float4 pre[kSplAhead];
 #pragma unroll
-    for (uint32_t u = 0; u < kSplAhead; ++u) pre[u] = u < full ? *reinterpret_cast<const float4 *>(fin + (size_t)u * 4 * kSplThreads + 4 * tid) : float4{0.f, 0.f, 0.f, 0.f};
+    for (uint32_t u = 0; u < kSplAhead; ++u) pre[u] = u < ahead ? *reinterpret_cast<const float4 *>(fin + (size_t)u * 4 * kSplThreads + 4 * tid) : float4{0.f, 0.f, 0.f, 0.f};
 
     // ---- this workgroup's bounds: the running maximum of the slot up to j and up to j + 1, t_0 = 0 --------------
     if (tid < 2) bound_s[tid] = 0;
@@ -3078,6 +3203,14 @@ __global__ __launch_bounds__(kSplThreads) void k_sel_splitters(const float *__re
             atomicMax(&bound_s[1], hi);
         }
     }
+    if (by_list) {
+        uint32_t in_front = tid < j ? my_cnt : 0u;
+#pragma unroll
+        for (int m = kWave / 2; m >= 1; m >>= 1) in_front += __shfl_xor(in_front, m);
+        if (lane == 0 && in_front) atomicAdd(&c_s, in_front);
+        if (tid == j) n_s = my_cnt; // (the open bucket: 0 here, P - c below)
+        static_assert(kSelListSeg * kSelListShards == kSelListCap && kSelListShards % 4 == 0 && kSplThreads % kSelListSeg == 0, "segments");
+    }
     __syncthreads();
     SplScan s;
     s.last = j + 1 == B;
@@ -3092,10 +3225,43 @@ __global__ __launch_bounds__(kSplThreads) void k_sel_splitters(const float *__re
     // The open bucket (the last workgroup) only counts on its way through: it holds whatever lies beyond the last
     // splitter - most of the population when the splitters are good - and is looked at only if positions below `reach`
     // fall into it.
-    const bool count_only = floats && s.last;
-    {
+    const bool count_only = !by_list && floats && s.last;
+    const uint32_t reach = (B - 1) * step + 1 > need ? (B - 1) * step + 1 : need;
+    bool stream = !by_list;
+    if (by_list) {
+        // The list serves unless it overflowed, or the bucket is the open one and has rows to place (nobody files the open
+        // bucket).  Then this workgroup alone streams as without lists - counting and collecting by the 64-bit keys, into
+        // the LDS list while it has room - which is exact for every slot; the counters are a promise of speed only.
+        const uint32_t c0 = c_s, n0 = s.last ? p_len - c0 : n_s;
+        const bool owes = n0 != 0 && c0 < reach && !(s.last && c0 >= need);
+        // the segments one behind the other: place `at` of segment g goes to (keys of the segments in front) + at
+        const uint32_t own[kSelListShards] = {own_q[0].x, own_q[0].y, own_q[0].z, own_q[0].w, own_q[1].x, own_q[1].y, own_q[1].z, own_q[1].w,
+                                              own_q[2].x, own_q[2].y, own_q[2].z, own_q[2].w, own_q[3].x, own_q[3].y, own_q[3].z, own_q[3].w};
+        static_assert(kSelListShards == 16, "own[] spells the sixteen counters out");
+        bool overflow = false;
+#pragma unroll
+        for (uint32_t g = 0; g < kSelListShards; ++g) overflow |= own[g] > kSelListSeg;
+        stream = owes && (s.last || overflow);
+        if (owes && !stream) {
+#pragma unroll
+            for (uint32_t u = 0; u < kSelListCap / kSplThreads; ++u) {
+                const uint32_t g0 = (u * kSplThreads + tid) / kSelListSeg, at = tid % kSelListSeg; // (kSplThreads is a multiple of the segment)
+                uint32_t front = 0, mine = 0;
+#pragma unroll
+                for (uint32_t g = 0; g < kSelListShards; ++g) {
+                    front += g < g0 ? own[g] : 0u;
+                    mine = g == g0 ? own[g] : mine;
+                }
+                if (at < mine) list[front + at] = pre_list[u];
+            }
+        }
+        __syncthreads(); // (everybody has read c_s and n_s)
+        if (stream && tid == 0) n_s = 0, c_s = 0;
+        if (stream) __syncthreads();
+    }
+    if (stream) {
         uint32_t cnt = 0, done = 0;
-        if (floats && (vec & 1u)) {
+        if (!by_list && floats && (vec & 1u)) { // (list mode has not asked for `pre`)
             done = count_only ? spl_stream_fast<true>(s, fin, full, pre, cnt, &n_s, list)
                               : spl_stream_fast<false>(s, fin, full, pre, cnt, &n_s, list);
 #pragma unroll
@@ -3106,9 +3272,8 @@ __global__ __launch_bounds__(kSplThreads) void k_sel_splitters(const float *__re
     }
     __syncthreads();
     SOTS_PHASE(2);
-    const uint32_t c = c_s, n = count_only ? p_len - c : n_s;
+    const uint32_t c = c_s, n = count_only || (by_list && !stream && s.last) ? p_len - c : n_s;
     // positions [c, c + n) are this workgroup's: rows to move below `need`, splitters to write at q * step, q < B
-    const uint32_t reach = (B - 1) * step + 1 > need ? (B - 1) * step + 1 : need;
     if (j == 0 && tid == 0) spl_out[0] = 0;
     if (n == 0 || c >= reach) return;
     if (s.last && c >= need) {
@@ -4373,9 +4538,16 @@ hipError_t launch_x_tables(hipStream_t st, float *image, const float2 *twiddle, 
 
 hipError_t launch_fft_fitness(hipStream_t st, const float *audio, const float *window, const float *target,
                               float *fitness, const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch,
-                              float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc)
+                              float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, const SelLists *lists)
 {
     int *occ_w = oc->fused_win, *occ_n = oc->fused_raw;
+    if (lists) { // the bucketing instantiation, or nothing: a caller that counts on the lists must not get a launch without them
+        if (!window || !select_lists_apply(p, log2n, num_cus) || lists->buckets != select_splitter_count(num_cus) || !lists->slot || !lists->cnt || !lists->lists)
+            return hipErrorInvalidValue;
+        constexpr int W = fft_wide_waves<10>();
+        k_fft<10, 1, true, W, false, true, SelLists><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, false, true, SelLists>), 3), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, *lists);
+        return hipGetLastError();
+    }
     if (big_from(log2n)) {
         if (log2n == 14) {
             if (window) return launch_fft_big<14, 1, true>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch);
@@ -4631,16 +4803,53 @@ static uint32_t select_splitter_step(uint32_t need, uint32_t buckets)
 
 hipError_t launch_select_splitters(hipStream_t st, const float *vin, const float *sin, const float *fin, float *vout,
                                    float *sout, float *fout, uint64_t *keys, const uint64_t *spl_in, uint64_t *spl_out,
-                                   uint32_t p, uint32_t d, uint32_t need, uint32_t num_cus, const SortExchange *exchange)
+                                   uint32_t p, uint32_t d, uint32_t need, uint32_t num_cus, const SortExchange *exchange,
+                                   const SelLists *lists)
 {
     if (!select_applies(p, need)) return hipErrorInvalidValue;
     const SortExchange ex = exchange ? *exchange : SortExchange{};
     const uint32_t buckets = select_splitter_count(num_cus);
+    if (lists && (buckets > kSelListMaxBuckets || lists->buckets != buckets || lists->slot != spl_in || !lists->cnt || !lists->cnt_other || !lists->lists)) return hipErrorInvalidValue;
     // bit 0: the fitness can be read 16 bytes per lane; bit 1: so can rows of four genes
     const uintptr_t row_bits = reinterpret_cast<uintptr_t>(vin) | reinterpret_cast<uintptr_t>(sin) | reinterpret_cast<uintptr_t>(vout) | reinterpret_cast<uintptr_t>(sout);
     const uint32_t vec = ((reinterpret_cast<uintptr_t>(fin) & 15u) == 0 ? 1u : 0u) | ((row_bits & 15u) == 0 ? 2u : 0u);
     k_sel_splitters<<<buckets, kSplThreads, 0, st>>>(vin, sin, fin, vout, sout, fout, spl_in, spl_out, keys, p, need,
-                                                     select_splitter_step(need, buckets), d, ex, vec);
+                                                     select_splitter_step(need, buckets), d, ex, vec, lists ? *lists : SelLists{});
+    return hipGetLastError();
+}
+
+// ---- list mode: who files the keys ----
+bool select_lists_apply(uint32_t p, uint32_t log2n, uint32_t num_cus)
+{
+    return fft_wide(p, log2n, num_cus) && select_splitter_count(num_cus) <= kBktMaxBuckets;
+}
+size_t select_lists_bytes(uint32_t num_cus) { return (size_t)select_splitter_count(num_cus) * kSelListCap * sizeof(uint64_t); }
+size_t select_counters_bytes() { return (size_t)kSelListMaxBuckets * kSelListShards * sizeof(uint32_t); }
+
+// bkt_visit over an array of fitness values: a wavefront takes 64 consecutive keys, one after the other (the visit is
+// a wavefront's, its key uniform)
+constexpr uint32_t kBktThreads = 256;
+static __global__ __launch_bounds__(kBktThreads) void k_bucket_fitness(const float *__restrict__ fin, uint32_t p_len, SelLists bk)
+{
+    __shared__ uint32_t bnd_s[2 * kBktMaxBuckets];
+    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
+    if (tid < kWave) bkt_bounds(bk.slot, bk.buckets, bnd_s, lane);
+    __syncthreads();
+    const uint32_t first = __builtin_amdgcn_readfirstlane(blockIdx.x * kBktThreads + (tid & ~(kWave - 1)));
+    const uint32_t idx = first + lane;
+    const uint32_t bits = idx < p_len ? order_bits(fin[idx]) : 0u;
+    BktPend pd = {0ull, kBktNone, 0u};
+    for (uint32_t l = 0; l < kWave && first + l < p_len; ++l) {
+        const uint32_t kb = (uint32_t)__builtin_amdgcn_readlane((int)bits, (int)l);
+        bkt_visit(bk, bnd_s, ((uint64_t)kb << 32) | (first + l), (first / kWave) % kSelListShards, lane, pd);
+    }
+    bkt_flush(bk, pd, lane);
+}
+
+hipError_t launch_bucket_fitness(hipStream_t st, const float *fitness, uint32_t p, const SelLists &lists)
+{
+    if (lists.buckets < 2 || lists.buckets > kBktMaxBuckets || !lists.slot || !lists.cnt || !lists.lists) return hipErrorInvalidValue;
+    k_bucket_fitness<<<(p + kBktThreads - 1) / kBktThreads, kBktThreads, 0, st>>>(fitness, p, lists);
     return hipGetLastError();
 }
 

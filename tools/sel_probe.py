@@ -1,6 +1,7 @@
 """Diagnostic: phase stamps (shader cycles since workgroup start) of the selection kernels; needs a
--DSOTS_STAMP build.  usage: SOTS_LIB_PATH=variants/libsots_stamp.so python tools/sel_probe.py [P] [pattern] [tiles|splitters]
-(splitters: the one-launch selection, its slot written by a selection of the same fitness one call earlier)"""
+-DSOTS_STAMP build.  usage: SOTS_LIB_PATH=variants/libsots_stamp.so python tools/sel_probe.py [P] [pattern] [tiles|splitters|lists]
+(splitters: the one-launch selection, its slot written by a selection of the same fitness one call earlier; lists: the same
+with the keys filed in front of every selection - sots_stage_bucket_fitness - so that the kernel runs in list mode)"""
 import ctypes as C, importlib, sys, os, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,23 +16,27 @@ if pattern == "skew":
     f *= np.where((np.arange(P) // 1024) % 4 == 0, 0.05, 1.0).astype(np.float32)
 v = rng.random((P, es.D), dtype=np.float32)
 es.set_sort_mode(pkg.capi.SORT_TOP_ONLY)
-es.set_select_plan(pkg.capi.SELECT_SPLITTERS if plan == "splitters" else pkg.capi.SELECT_TILES)
+es.set_select_plan(pkg.capi.SELECT_SPLITTERS if plan in ("splitters", "lists") else pkg.capi.SELECT_TILES)
 es.write_population(v, v, f)
 L = es.L
 L.sots_debug_stamps.argtypes = [C.c_void_p, C.c_size_t]
+def select():
+    if plan == "lists":
+        es.bucket_fitness()
+    es.select()
 for _ in range(200):
-    es.select(); es.rotate(); es.rotate()
+    select(); es.rotate(); es.rotate()
 es.synchronize()
 L.sots_debug_clear_stamps()
-es.select(); es.synchronize()
+select(); es.synchronize()
 buf = (C.c_ulonglong * (2 * 16384))()
 L.sots_debug_stamps(buf, 2 * 16384)
 a = np.frombuffer(buf, dtype=np.uint64)[2 * 8192:].reshape(-1, 16).astype(np.float64)
 names = ["samples in LDS", "v* selected", "off[] scanned", "own keys requested", "copies issued", "copies landed",
          "searched", "rows moved", "T: fitness loaded", "T: runs sorted", "T: ranked", "T: written"]
 print(f"P={P} pattern={pattern} plan={plan}: cycles since workgroup start, median / max over workgroups")
-if plan == "splitters":  # k_sel_splitters: every workgroup streams, those with positions to deliver go on
-    for j, nme in enumerate(["bounds made", "streamed", "bucket ordered", "rows moved"], 1):
+if plan in ("splitters", "lists"):  # k_sel_splitters: every workgroup streams (lists: copies its list), those with positions to deliver go on
+    for j, nme in enumerate(["bounds made", "streamed / list in LDS", "bucket ordered", "rows moved"], 1):
         x = a[:256][a[:256, j] > 0, j]
         if len(x):
             print(f"  {nme:22s} {np.median(x):9.0f} {x.max():9.0f}  ({len(x)} workgroups)")
