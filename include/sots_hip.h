@@ -395,6 +395,57 @@ int sots_batch_read_history(sots_batch *b, uint32_t chunk, sots_gen_record *out,
 /* ends at the first block boundary at which the rule holds for EVERY active chunk (the chunks advance together) */
 int sots_batch_execute_until(sots_batch *b, uint32_t max_generations, const sots_stop_rule *rule, uint32_t *generations_run);
 
+/* ---- chunk queue (new; extends parameterMatchAudio, Evolutionary_Strategy_OpenCL.hpp:572-610) ----
+ * M chunks, any number, go through the S = min(max_chunks, M) slots of a tracked batch.  Every chunk runs under a
+ * generation counter of its own until its own stop rule holds at one of its own check boundaries (multiples of
+ * rule->check_interval, and max_generations) or until it has run max_generations; its result is then stored on the
+ * device and its slot takes the next unstarted chunk, without the stream draining.  Chunk k's result is bit for bit what
+ * a tracked sots_ctx of the same configuration reports after sots_set_target_spectrum(target k),
+ * sots_init_population(ctx, first_chunk_index + k) and sots_execute_until(ctx, max_generations, rule, &run) - whichever
+ * slot the chunk ran in and whenever it started. */
+typedef struct sots_chunk_result {            /* 208 bytes */
+    uint32_t generations_run;                 /* the chunk's own counter when it was retired */
+    uint32_t best_ever_generation;
+    float best_ever_fitness;
+    float last_fitness;                       /* row 0 of the generation it stopped at */
+    float best_ever_values[SOTS_MAX_DIMS];    /* entries >= D are 0 */
+    float best_ever_steps[SOTS_MAX_DIMS];
+    float last_values[SOTS_MAX_DIMS];         /* row 0 of the generation it stopped at */
+} sots_chunk_result;
+typedef struct sots_queue_stats {
+    uint32_t struct_size;                     /* = sizeof(sots_queue_stats), set by the caller */
+    uint32_t slots;                           /* min(max_chunks, num_chunks) */
+    uint64_t global_generations;              /* generations the batch loop ran until the last chunk retired */
+    uint64_t chunk_generations;               /* sum of generations_run */
+} sots_queue_stats;
+#define SOTS_QUEUE_NO_CHUNK 0xFFFFFFFFu
+/* Store the targets of num_chunks >= 1 chunks on the device (as sots_batch_set_target_*: chunk k = bins [k N/2, (k+1) N/2)
+ * / samples [k N, (k+1) N), the audio form through the same host transform, chunk by chunk).  The stored targets and
+ * results are bounded by BYTES: num_chunks * N/2 * 4 <= 2^30 (262144 chunks at N = 2048), SOTS_ERR_INVALID above that.
+ * num_bins == num_chunks * N/2 and num_samples >= num_chunks * N, else SOTS_ERR_SIZE.  Replaces an earlier queue. */
+int sots_batch_queue_targets_spectra(sots_batch *b, const float *magnitudes, uint64_t num_bins, uint32_t num_chunks);
+int sots_batch_queue_targets_audio(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t num_chunks);
+/* Runs the stored queue; blocks until the last chunk is retired.  rule NULL: every chunk runs max_generations (>= 1).
+ * max_generations need not be a multiple of rule->check_interval: a chunk's last block is the shorter one, as in
+ * sots_execute_until.  keep_chunk (SOTS_QUEUE_NO_CHUNK: none; else < num_chunks): that chunk's whole current half, as it
+ * was when the chunk was retired, is kept for sots_batch_queue_read_kept_population.  Needs SOTS_TRACK_BEST_EVER on the
+ * batch and fails with SOTS_TRACK_HISTORY on (both SOTS_ERR_STATE: the slots keep no history rings), and needs targets
+ * stored (SOTS_ERR_STATE).  Afterwards the batch has NO active targets: the ordinary sots_batch_* calls need
+ * sots_batch_set_target_* again and then compute exactly what they compute on a fresh handle; the stored queue stays and
+ * can be run again.  stats may be NULL. */
+int sots_batch_queue_run(sots_batch *b, uint32_t first_chunk_index, uint32_t max_generations, const sots_stop_rule *rule,
+                         uint32_t keep_chunk, sots_queue_stats *stats);
+/* the results of the last run, chunk 0 first: *written = min(num_chunks, capacity).  SOTS_ERR_STATE before a run.  Blocking. */
+int sots_batch_queue_results(sots_batch *b, sots_chunk_result *out, uint32_t capacity, uint32_t *written);
+/* the kept chunk's population; pointers and byte counts as sots_read_population.  SOTS_ERR_STATE when the last run kept none. */
+int sots_batch_queue_read_kept_population(sots_batch *b, float *values, size_t values_bytes, float *steps, size_t steps_bytes,
+                                          float *fitness, size_t fitness_bytes);
+/* The global generations an in-order refill of `slots` slots takes for these per-chunk counts: every slot starts at global
+ * generation 0, chunks start in index order, and a freed slot starts the next chunk at the boundary at which it was freed
+ * (which freed slot takes which chunk does not change the answer).  slots >= 1; num_chunks 0 gives 0.  Pure host code: no
+ * device, no handle. */
+int sots_queue_makespan(const uint32_t *generations_run, uint32_t num_chunks, uint32_t slots, uint64_t *global_generations);
+
 /* ---- introspection ---- */
 typedef struct sots_info {
     uint32_t population_length, num_dimensions, audio_length, spectrum_row_floats;

@@ -61,7 +61,10 @@ EXPORTS = [
     "sots_batch_read_population",
     "sots_track", "sots_read_best_ever", "sots_read_history", "sots_stop_rule_holds", "sots_execute_until",
     "sots_batch_track", "sots_batch_read_best_ever", "sots_batch_read_history", "sots_batch_execute_until",
+    "sots_batch_queue_targets_spectra", "sots_batch_queue_targets_audio", "sots_batch_queue_run", "sots_batch_queue_results",
+    "sots_batch_queue_read_kept_population", "sots_queue_makespan",
 ]
+QUEUE_NO_CHUNK = 0xFFFFFFFF
 TRACK_BEST_EVER, TRACK_HISTORY = 1, 2
 BATCH_MAX_POPULATION = 1024
 GROUP_OVERLAP, GROUP_FORCE_RCCL, GROUP_UNFUSED, GROUP_EVENT_WAITS = 1, 2, 4, 8
@@ -111,6 +114,26 @@ GEN_RECORD_DTYPE = np.dtype([("generation", np.uint32), ("best_fitness", np.floa
 class StopRule(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("check_interval", C.c_uint32), ("target_fitness", C.c_float),
                 ("stall_generations", C.c_uint32)]
+
+
+class ChunkResult(C.Structure):
+    """sots_chunk_result: what the chunk queue stores when it retires a chunk (208 bytes)"""
+    _fields_ = [
+        ("generations_run", C.c_uint32), ("best_ever_generation", C.c_uint32), ("best_ever_fitness", C.c_float),
+        ("last_fitness", C.c_float), ("best_ever_values", C.c_float * MAX_DIMS), ("best_ever_steps", C.c_float * MAX_DIMS),
+        ("last_values", C.c_float * MAX_DIMS),
+    ]
+
+
+CHUNK_RESULT_DTYPE = np.dtype([("generations_run", np.uint32), ("best_ever_generation", np.uint32),
+                               ("best_ever_fitness", np.float32), ("last_fitness", np.float32),
+                               ("best_ever_values", np.float32, (MAX_DIMS,)), ("best_ever_steps", np.float32, (MAX_DIMS,)),
+                               ("last_values", np.float32, (MAX_DIMS,))])
+
+
+class QueueStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("slots", C.c_uint32), ("global_generations", C.c_uint64),
+                ("chunk_generations", C.c_uint64)]
 
 
 def make_stop_rule(target=None, stall=0, check_every=32):
@@ -220,6 +243,12 @@ def load():
     L.sots_batch_read_best_ever.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz]
     L.sots_batch_read_history.argtypes = [vp, u32, vp, u32, C.POINTER(u32), u64p]
     L.sots_batch_execute_until.argtypes = [vp, u32, C.POINTER(StopRule), C.POINTER(u32)]
+    L.sots_batch_queue_targets_spectra.argtypes = [vp, vp, C.c_uint64, u32]
+    L.sots_batch_queue_targets_audio.argtypes = [vp, vp, C.c_uint64, u32]
+    L.sots_batch_queue_run.argtypes = [vp, u32, u32, C.POINTER(StopRule), u32, C.POINTER(QueueStats)]
+    L.sots_batch_queue_results.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.sots_batch_queue_read_kept_population.argtypes = [vp, vp, sz, vp, sz, vp, sz]
+    L.sots_queue_makespan.argtypes = [C.POINTER(u32), u32, u32, u64p]
     _lib = L
     return L
 
@@ -549,6 +578,7 @@ class HipBatch:
         self.P, self.D, self.N = num_parents + num_offspring, SYNTH_DIMS[synth_kind], 1 << audio_log2
         self.max_chunks = max_chunks
         self.active = 0
+        self.queued = 0
         h = C.c_void_p()
         rc = self.L.sots_batch_create(C.byref(self.cfg), max_chunks, C.byref(h))
         if rc != 0:
@@ -636,6 +666,55 @@ class HipBatch:
         run = C.c_uint32()
         self._check(self.L.sots_batch_execute_until(self._h, max_generations, C.byref(rule), C.byref(run)))
         return run.value
+
+    # -- chunk queue: any number of chunks through the handle's slots, a slot refilled when its chunk's rule holds --
+    def queue_targets_audio(self, audio):
+        """audio[M][N] (or a flat signal cut into N-sample chunks): the targets of M queued chunks, any M"""
+        a = _f32(audio)
+        chunks = a.shape[0] if a.ndim == 2 else a.size // self.N
+        self._check(self.L.sots_batch_queue_targets_audio(self._h, _ptr(a), a.size, chunks))
+        self.queued = chunks
+
+    def queue_targets_spectra(self, mags):
+        """mags[M][N/2]"""
+        m = _f32(mags)
+        chunks = m.shape[0] if m.ndim == 2 else m.size // (self.N // 2)
+        self._check(self.L.sots_batch_queue_targets_spectra(self._h, _ptr(m), m.size, chunks))
+        self.queued = chunks
+
+    def queue_run(self, first, max_generations, target=None, stall=0, check_every=32, keep=None):
+        """every queued chunk until ITS rule holds (no target and no stall: max_generations each, rule = NULL); returns
+        (results, stats): a structured array (CHUNK_RESULT_DTYPE), chunk 0 first, and {slots, global_generations,
+        chunk_generations}.  keep: a chunk whose whole population is kept for queue_kept_population()."""
+        no_rule = (target is None or target < 0) and not stall
+        rule = None if no_rule else C.byref(make_stop_rule(target, stall, check_every))
+        stats = QueueStats()
+        stats.struct_size = C.sizeof(QueueStats)
+        self._check(self.L.sots_batch_queue_run(self._h, first, max_generations, rule, QUEUE_NO_CHUNK if keep is None else keep,
+                                                C.byref(stats)))
+        self.active = 0  # the ordinary calls need set_target_* again
+        out = np.zeros(self.queued, CHUNK_RESULT_DTYPE)
+        n = C.c_uint32()
+        self._check(self.L.sots_batch_queue_results(self._h, _ptr(out), out.size, C.byref(n)))
+        return out[:n.value], {"slots": stats.slots, "global_generations": stats.global_generations,
+                               "chunk_generations": stats.chunk_generations}
+
+    def queue_kept_population(self):
+        v = np.empty((self.P, self.D), np.float32)
+        s = np.empty((self.P, self.D), np.float32)
+        f = np.empty(self.P, np.float32)
+        self._check(self.L.sots_batch_queue_read_kept_population(self._h, _ptr(v), v.nbytes, _ptr(s), s.nbytes, _ptr(f), f.nbytes))
+        return v, s, f
+
+    @staticmethod
+    def queue_makespan(generations_run, slots):
+        """the global generations an in-order refill of `slots` slots takes for these per-chunk counts (host only)"""
+        g = np.ascontiguousarray(generations_run, dtype=np.uint32)
+        out = C.c_uint64()
+        rc = load().sots_queue_makespan(g.ctypes.data_as(C.POINTER(C.c_uint32)), g.size, slots, C.byref(out))
+        if rc != 0:
+            raise SotsError(rc, "sots_queue_makespan: slots must be at least 1")
+        return out.value
 
 
 class HipGroup:

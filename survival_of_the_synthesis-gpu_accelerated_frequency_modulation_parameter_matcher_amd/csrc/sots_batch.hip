@@ -15,6 +15,7 @@
 #include "../../include/sots_hip.h"
 #include "sots_host_math.h"
 #include "sots_kernels.h"
+#include "sots_stop_rule.h"
 #include "sots_track.h"
 
 using namespace sots;
@@ -22,6 +23,9 @@ using namespace sots;
 namespace {
 thread_local std::string g_batch_create_error;
 constexpr uint32_t kBatchMaxPopulation = 1024; // one k_sort_small workgroup per chunk
+constexpr uint64_t kQueueMaxTargetBytes = 1ull << 30; // the stored targets of a chunk queue (include/sots_hip.h)
+static_assert(sizeof(sots_chunk_result) == 208 && sizeof(sots_chunk_result) == sots::kQueueResultFloats * sizeof(float),
+              "sots_chunk_result is what k_queue_turnover writes");
 } // namespace
 
 struct sots_batch {
@@ -45,6 +49,15 @@ struct sots_batch {
     float2 *twiddle = nullptr;
     OccCache occ{};
     TrackState track{}; // run record of every chunk (sots_batch_track)
+    // chunk queue (sots_batch_queue_*): the stored targets, the results, the kept population, the slot table
+    uint32_t q_chunks = 0;           // chunks of the stored queue (0: none)
+    bool q_ran = false, q_kept = false;
+    float *q_targets = nullptr;      // [q_chunks][N/2]
+    float *q_results = nullptr;      // [q_chunks][kQueueResultFloats]
+    float *q_kept_rows = nullptr;    // values [P][D], steps [P][D], fitness [P]
+    uint32_t *q_state = nullptr;     // {head, retired, last retirement, 0} and the slot table [max_chunks][2] behind them
+    uint32_t *q_pinned = nullptr;    // host uint32[2][4]: the loop's look at q_state, one per block in flight
+    hipEvent_t q_event[2] = {nullptr, nullptr};
     std::vector<double> window64;
     float window_factor = 1.0f, inv_n = 0.0f, inv_wf = 1.0f;
     mutable std::string err;
@@ -95,6 +108,20 @@ uint32_t batch_dims_of(uint32_t kind)
     }
 }
 
+void queue_release(sots_batch *b)
+{
+    void *bufs[] = {b->q_targets, b->q_results, b->q_kept_rows, b->q_state};
+    for (void *p : bufs)
+        if (p) (void)hipFree(p);
+    if (b->q_pinned) (void)hipHostFree(b->q_pinned);
+    for (hipEvent_t &e : b->q_event)
+        if (e) (void)hipEventDestroy(e), e = nullptr;
+    b->q_targets = b->q_results = b->q_kept_rows = nullptr;
+    b->q_state = b->q_pinned = nullptr;
+    b->q_chunks = 0;
+    b->q_ran = b->q_kept = false;
+}
+
 void free_batch(sots_batch *b)
 {
     if (!b) return;
@@ -105,6 +132,7 @@ void free_batch(sots_batch *b)
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     track_release(b->track);
+    queue_release(b);
     if (b->stream) (void)hipStreamDestroy(b->stream);
     (void)hipGetLastError();
     delete b;
@@ -425,6 +453,221 @@ int sots_batch_execute_until(sots_batch *b, uint32_t max_generations, const sots
             all = sots_stop_rule_holds(rule, track_fitness(b->track, c), b->track.pinned[2 * c + 1], b->generation) == 1;
         if (all) break;
     }
+    return SOTS_OK;
+}
+
+// ---- chunk queue: M chunks through the handle's slots, a slot refilled when its chunk's stop rule holds ----
+int sots_batch_queue_targets_spectra(sots_batch *b, const float *magnitudes, uint64_t num_bins, uint32_t num_chunks)
+{
+    // (what needs no handle is checked first: a machine without a GPU still tells a bad call from a good one)
+    if (num_chunks == 0) return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_targets: num_chunks must be at least 1");
+    BATCH_REQUIRE(b);
+    const uint64_t m = b->N / 2, need = (uint64_t)num_chunks * m;
+    if (need * sizeof(float) > kQueueMaxTargetBytes)
+        return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_targets: %u chunks of %llu bins exceed %llu bytes of stored targets", num_chunks,
+                     (unsigned long long)m, (unsigned long long)kQueueMaxTargetBytes);
+    if (!magnitudes || num_bins != need)
+        return bfail(b, SOTS_ERR_SIZE, "%u queued target spectra need %llu bins, got %llu", num_chunks, (unsigned long long)need,
+                     (unsigned long long)num_bins);
+    if (int rc = bind(b)) return rc;
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    queue_release(b);
+    const size_t pd_floats = (size_t)b->P * b->D;
+#define QUEUE_HIP(call)                         \
+    do {                                        \
+        hipError_t e_ = (call);                 \
+        if (e_ != hipSuccess) {                 \
+            (void)hipGetLastError();            \
+            queue_release(b);                   \
+            return bfail(b, SOTS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
+        }                                       \
+    } while (0)
+    QUEUE_HIP(hipMalloc((void **)&b->q_targets, need * sizeof(float)));
+    QUEUE_HIP(hipMalloc((void **)&b->q_results, (size_t)num_chunks * sizeof(sots_chunk_result)));
+    QUEUE_HIP(hipMalloc((void **)&b->q_kept_rows, (2 * pd_floats + b->P) * sizeof(float)));
+    QUEUE_HIP(hipMalloc((void **)&b->q_state, (4 + 2 * (size_t)b->max_chunks) * sizeof(uint32_t)));
+    QUEUE_HIP(hipHostMalloc((void **)&b->q_pinned, 2 * 4 * sizeof(uint32_t), hipHostMallocDefault));
+    for (hipEvent_t &e : b->q_event) QUEUE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    QUEUE_HIP(hipMemcpyAsync(b->q_targets, magnitudes, need * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    QUEUE_HIP(hipStreamSynchronize(b->stream));
+#undef QUEUE_HIP
+    b->q_chunks = num_chunks;
+    return SOTS_OK;
+}
+
+int sots_batch_queue_targets_audio(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t num_chunks)
+{
+    // (what needs no handle is checked first: a machine without a GPU still tells a bad call from a good one)
+    if (num_chunks == 0) return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_targets: num_chunks must be at least 1");
+    BATCH_REQUIRE(b);
+    const uint64_t m = b->N / 2;
+    if ((uint64_t)num_chunks * m * sizeof(float) > kQueueMaxTargetBytes)
+        return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_targets: %u chunks of %llu bins exceed %llu bytes of stored targets", num_chunks,
+                     (unsigned long long)m, (unsigned long long)kQueueMaxTargetBytes);
+    if (!audio || num_samples < (uint64_t)num_chunks * b->N)
+        return bfail(b, SOTS_ERR_SIZE, "%u queued chunks of target audio need %llu samples, got %llu", num_chunks,
+                     (unsigned long long)num_chunks * b->N, (unsigned long long)num_samples);
+    std::vector<float> mag((size_t)num_chunks * m);
+    for (uint32_t c = 0; c < num_chunks; ++c) { // the host transform of sots_batch_set_target_audio, chunk by chunk
+        const std::vector<float> one = target_spectrum(audio + (size_t)c * b->N, b->N, b->window64, b->window_factor);
+        memcpy(mag.data() + (size_t)c * m, one.data(), (size_t)m * sizeof(float));
+    }
+    return sots_batch_queue_targets_spectra(b, mag.data(), mag.size(), num_chunks);
+}
+
+int sots_batch_queue_run(sots_batch *b, uint32_t first_chunk_index, uint32_t max_generations, const sots_stop_rule *rule,
+                         uint32_t keep_chunk, sots_queue_stats *stats)
+{
+    // (what needs no handle is checked first, as above)
+    if (stats) {
+        if (stats->struct_size != sizeof(sots_queue_stats))
+            return bfail(b, SOTS_ERR_INVALID, "sots_queue_stats.struct_size %u != %zu", stats->struct_size, sizeof(sots_queue_stats));
+        stats->slots = 0;
+        stats->global_generations = stats->chunk_generations = 0;
+    }
+    if (rule && sots_stop_rule_holds(rule, 0.0f, 0, 0) < 0)
+        return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_run: stop rule with a wrong struct_size or check_interval 0");
+    if (max_generations == 0) return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_run: max_generations must be at least 1");
+    BATCH_REQUIRE(b);
+    if (!b->track.best_ever()) return bfail(b, SOTS_ERR_STATE, "sots_batch_queue_run needs best-ever tracking: call sots_batch_track first");
+    if (b->track.history())
+        return bfail(b, SOTS_ERR_STATE, "sots_batch_queue_run keeps no per-slot history: call sots_batch_track without SOTS_TRACK_HISTORY");
+    if (b->q_chunks == 0) return bfail(b, SOTS_ERR_STATE, "no queue: call sots_batch_queue_targets_audio or sots_batch_queue_targets_spectra first");
+    const uint32_t chunks = b->q_chunks, slots = chunks < b->max_chunks ? chunks : b->max_chunks;
+    if (keep_chunk != SOTS_QUEUE_NO_CHUNK && keep_chunk >= chunks)
+        return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_run: keep_chunk %u not in 0..%u", keep_chunk, chunks - 1);
+    // No chunk runs longer than max_generations, so the last one retires within `bound` loop generations: without a rule
+    // every slot turns over together and the loop below enqueues exactly that many.
+    const uint64_t waves = ((uint64_t)chunks + slots - 1) / slots;
+    const uint64_t bound = rule ? ((uint64_t)(chunks - 1) / slots + 2) * max_generations : waves * max_generations;
+    if (bound > 0xFFFFFFFFull) // (the loop generation is a 32-bit kernel argument)
+        return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_run: %u chunks of up to %u generations in %u slots exceed 2^32 loop generations", chunks,
+                     max_generations, slots);
+    if (int rc = bind(b)) return rc;
+
+    // the slots start with chunks 0..slots-1, exactly as sots_batch_set_target_spectra + sots_batch_init_population start them
+    b->active = 0; // whatever happens from here on, the ordinary calls need their targets again
+    b->q_ran = b->q_kept = false;
+    std::vector<uint32_t> start(4 + 2 * (size_t)slots, 0u);
+    start[0] = slots;
+    for (uint32_t c = 0; c < slots; ++c) start[4 + 2 * c] = c;
+    BATCH_HIP(b, hipMemcpyAsync(b->q_state, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
+    BATCH_HIP(b, launch_seg_targets(b->stream, b->seg_image, b->q_targets, b->log2n, slots));
+    BATCH_HIP(b, track_clear(b->track, b->stream));
+    b->rot = 0;
+    b->generation = 0;
+    BATCH_HIP(b, launch_init_population_seg(b->stream, b->val(0), b->stp(0), b->fit(0), b->pd, first_chunk_index, slots));
+    BATCH_HIP(b, hipStreamSynchronize(b->stream)); // `start` leaves scope; the loop below starts from an empty stream
+
+    QueueArgs q{};
+    q.state = b->q_state;
+    q.slot_table = b->q_state + 4;
+    q.results = b->q_results;
+    q.targets = b->q_targets;
+    q.seg_image = b->seg_image;
+    q.kept_values = b->q_kept_rows;
+    q.kept_steps = b->q_kept_rows + (size_t)b->P * b->D;
+    q.kept_fitness = b->q_kept_rows + 2 * (size_t)b->P * b->D;
+    q.num_chunks = chunks;
+    q.first_chunk = first_chunk_index;
+    q.max_generations = max_generations;
+    q.keep_chunk = keep_chunk;
+    q.check_interval = rule ? rule->check_interval : 0u;
+    q.target_fitness = rule ? rule->target_fitness : -1.0f;
+    q.stall_generations = rule ? rule->stall_generations : 0u;
+    q.x_log2n = queue_x_log2n(b->log2n);
+    q.half_bins = b->N / 2;
+
+    // Blocks of check_interval generations; after each the queue's counters come back through a small asynchronous copy
+    // to pinned memory.  The host waits for the copy of the block BEFORE the one it has just enqueued, so the device never
+    // idles on the host; results are captured at retirement, so the block run past the end changes nothing.
+    const uint32_t block = rule ? rule->check_interval : (max_generations < 32u ? max_generations : 32u);
+    const uint32_t rows = slots * b->P;
+    uint64_t global = 0, enqueued = 0, looked = 0; // generations and blocks enqueued, blocks whose counters the host has seen
+    bool drained = false;
+    uint32_t seen[4] = {0, 0, 0, 0};
+    while (!drained) {
+        if (global < bound) {
+            for (uint32_t g = 0; g < block && global < bound; ++g) {
+                uint32_t src = b->rot, dst = b->rot ^ 1u;
+                BATCH_HIP(b, launch_recombine_mutate_queue(b->stream, b->val(src), b->stp(src), b->val(dst), b->stp(dst), b->pd, b->mc,
+                                                           q.slot_table, slots));
+                b->rot = dst;
+                if (b->synth_arith == SOTS_ARITH_DEVICE_KERNELS)
+                    BATCH_HIP(b, launch_synth_device_arith(b->stream, b->cfg.synth_kind, b->val(b->rot), b->wavetable, b->audio, b->sp, rows,
+                                                           b->log2n, b->pitch));
+                else
+                    BATCH_HIP(b, launch_synth(b->stream, b->cfg.synth_kind, b->val(b->rot), b->wavetable, b->audio, b->sp, rows, b->log2n,
+                                              b->pitch, b->num_cus, nullptr, true));
+                BATCH_HIP(b, launch_fft_fitness_seg(b->stream, b->audio, b->window, b->seg_image, b->fit(b->rot), b->twiddle, rows, b->log2n,
+                                                    b->pitch, b->inv_n, b->inv_wf, b->num_cus, &b->occ));
+                src = b->rot, dst = b->rot ^ 1u;
+                BATCH_HIP(b, launch_sort_seg(b->stream, b->val(src), b->stp(src), b->fit(src), b->val(dst), b->stp(dst), b->fit(dst), b->P,
+                                             b->D, slots));
+                b->rot = dst;
+                global += 1;
+                BATCH_HIP(b, launch_queue_turnover(b->stream, b->val(b->rot), b->stp(b->rot), b->fit(b->rot), b->pd, b->track.meta,
+                                                   b->track.rows, q, (uint32_t)global, slots));
+            }
+            const uint32_t k = (uint32_t)(enqueued & 1u);
+            BATCH_HIP(b, hipMemcpyAsync(b->q_pinned + 4 * k, b->q_state, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, b->stream));
+            BATCH_HIP(b, hipEventRecord(b->q_event[k], b->stream));
+            enqueued += 1;
+            if (enqueued - looked < 2 && global < bound) continue; // stay one block ahead of the block looked at
+        } else if (looked == enqueued) {
+            return bfail(b, SOTS_ERR_STATE, "sots_batch_queue_run: %u of %u chunks retired after %llu generations", seen[1], chunks,
+                         (unsigned long long)global);
+        }
+        const uint32_t k = (uint32_t)(looked & 1u);
+        BATCH_HIP(b, hipEventSynchronize(b->q_event[k]));
+        memcpy(seen, b->q_pinned + 4 * k, sizeof seen);
+        looked += 1;
+        drained = seen[1] >= chunks;
+    }
+    BATCH_HIP(b, hipStreamSynchronize(b->stream)); // the block enqueued ahead: nothing of it is kept
+    b->generation = 0;
+    b->q_ran = true;
+    b->q_kept = keep_chunk != SOTS_QUEUE_NO_CHUNK;
+    if (stats) {
+        std::vector<uint32_t> run(chunks);
+        BATCH_HIP(b, hipMemcpy2D(run.data(), sizeof(uint32_t), b->q_results, sizeof(sots_chunk_result), sizeof(uint32_t), chunks, hipMemcpyDeviceToHost));
+        stats->slots = slots;
+        stats->global_generations = seen[2];
+        for (uint32_t r : run) stats->chunk_generations += r;
+    }
+    return SOTS_OK;
+}
+
+int sots_batch_queue_results(sots_batch *b, sots_chunk_result *out, uint32_t capacity, uint32_t *written)
+{
+    BATCH_REQUIRE(b);
+    if (written) *written = 0;
+    if (!written || (capacity && !out)) return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_results: null argument");
+    if (!b->q_ran) return bfail(b, SOTS_ERR_STATE, "no results: call sots_batch_queue_run first");
+    if (int rc = bind(b)) return rc;
+    const uint32_t n = capacity < b->q_chunks ? capacity : b->q_chunks;
+    if (n) {
+        BATCH_HIP(b, hipMemcpyAsync(out, b->q_results, (size_t)n * sizeof(sots_chunk_result), hipMemcpyDeviceToHost, b->stream));
+        BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    }
+    *written = n;
+    return SOTS_OK;
+}
+
+int sots_batch_queue_read_kept_population(sots_batch *b, float *values, size_t values_bytes, float *steps, size_t steps_bytes,
+                                          float *fitness, size_t fitness_bytes)
+{
+    BATCH_REQUIRE(b);
+    if (!b->q_ran || !b->q_kept) return bfail(b, SOTS_ERR_STATE, "no kept population: call sots_batch_queue_run with a keep_chunk first");
+    const size_t pd_bytes = (size_t)b->P * b->D * sizeof(float), f_bytes = (size_t)b->P * sizeof(float);
+    if ((values && values_bytes != pd_bytes) || (steps && steps_bytes != pd_bytes) || (fitness && fitness_bytes != f_bytes))
+        return bfail(b, SOTS_ERR_SIZE, "population byte counts must be %zu (values, steps) and %zu (fitness)", pd_bytes, f_bytes);
+    if (int rc = bind(b)) return rc;
+    const size_t pd_floats = (size_t)b->P * b->D;
+    if (values) BATCH_HIP(b, hipMemcpyAsync(values, b->q_kept_rows, pd_bytes, hipMemcpyDeviceToHost, b->stream));
+    if (steps) BATCH_HIP(b, hipMemcpyAsync(steps, b->q_kept_rows + pd_floats, pd_bytes, hipMemcpyDeviceToHost, b->stream));
+    if (fitness) BATCH_HIP(b, hipMemcpyAsync(fitness, b->q_kept_rows + 2 * pd_floats, f_bytes, hipMemcpyDeviceToHost, b->stream));
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
     return SOTS_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "../../include/sots_hip.h"
 #include "sots_host_math.h"
 #include "sots_kernels.h"
+#include "sots_stop_rule.h"
 #include "sots_track.h"
 
 using namespace sots;
@@ -1027,12 +1028,8 @@ int sots_read_history(sots_ctx *ctx, sots_gen_record *out, uint32_t capacity, ui
 int sots_stop_rule_holds(const sots_stop_rule *rule, float best_ever_fitness, uint32_t best_ever_generation, uint32_t generation)
 {
     if (int rc = check_stop_rule(rule)) return rc;
-    if (rule->target_fitness >= 0.0f && best_ever_fitness <= rule->target_fitness) return 1;
-    if (rule->stall_generations != 0) {
-        const uint32_t since = generation > best_ever_generation ? generation - best_ever_generation : 0u; // saturating
-        if (since >= rule->stall_generations) return 1;
-    }
-    return 0;
+    // (one copy of the arithmetic for the host and for the chunk queue's turnover kernel: sots_stop_rule.h)
+    return stop_rule_holds(rule->target_fitness, rule->stall_generations, best_ever_fitness, best_ever_generation, generation) ? 1 : 0;
 }
 
 int sots_execute_until(sots_ctx *ctx, uint32_t max_generations, const sots_stop_rule *rule, uint32_t *generations_run)

@@ -229,6 +229,35 @@ hipError_t launch_track(hipStream_t st, const float *values, const float *steps,
                         uint32_t parents, uint32_t generation, uint32_t chunks, uint32_t *meta, float *rows, float *hist,
                         uint32_t capacity, uint32_t slot);
 
+// ---- chunk queue (sots_batch_queue_run) ----
+// M chunks go through `slots` slots of a batch; a slot runs its chunk under a generation counter of its own.  Device
+// state: state = uint32[4] {queue head (next unstarted chunk), chunks retired, loop generation of the last retirement, 0};
+// slot_table = uint32[slots][2] {chunk index or kQueueNoChunk, generations completed}; results = float[M]
+// [kQueueResultFloats] (sots_chunk_result); targets = float[M][N/2]; kept_*: one chunk's current half as it was retired.
+constexpr uint32_t kQueueNoChunk = 0xFFFFFFFFu;
+constexpr uint32_t kQueueResultFloats = 4 + 3 * SOTS_MAX_DIMS; // sizeof(sots_chunk_result) / 4
+struct QueueArgs {
+    uint32_t *state, *slot_table;
+    float *results;
+    const float *targets;
+    float *seg_image; // the batch's segmented target image: slot c's table is rewritten when the slot is refilled
+    float *kept_values, *kept_steps, *kept_fitness;
+    uint32_t num_chunks, first_chunk, max_generations, keep_chunk;
+    uint32_t check_interval; // 0: no rule, every chunk runs max_generations
+    float target_fitness;
+    uint32_t stall_generations;
+    uint32_t x_log2n;   // queue_x_log2n(): log2 N where the image holds k_fft_x's tables, 0 where it holds the N/2 bins
+    uint32_t half_bins; // N/2
+};
+uint32_t queue_x_log2n(uint32_t log2n);
+// k_recombine_mutate_seg with the generation of row r's slot read from slot_table
+hipError_t launch_recombine_mutate_queue(hipStream_t st, const float *vin, const float *sin, float *vout, float *sout, const PopDims &pd,
+                                         const MutateConsts &mc, const uint32_t *slot_table, uint32_t slots);
+// after a generation's sort, on the half it wrote: the best-ever record of every busy slot (meta, rows: as launch_track) and
+// the turnover of those whose chunk ends here; global_generation = generations the queue loop has run, this one included
+hipError_t launch_queue_turnover(hipStream_t st, float *values, float *steps, float *fitness, const PopDims &pd, uint32_t *meta,
+                                 float *rows, const QueueArgs &q, uint32_t global_generation, uint32_t slots);
+
 uint32_t next_pow2(uint32_t v);
 
 } // namespace sots

@@ -14,6 +14,7 @@
 //
 // Reference citations are file:line in the reference tree.
 #include "sots_kernels.h"
+#include "sots_stop_rule.h"
 #include <type_traits>
 
 #include <cstdlib>
@@ -214,6 +215,24 @@ __global__ __launch_bounds__(256) void k_recombine_mutate_seg(const float *__res
         const uint32_t src = c * pd.p * pd.d + recombine_source(i, g, pd);
         float x = vin[src], s = sin[src];
         mutate_gene(x, s, pd.gid_base + i, g, generation, pd, mc);
+        vout[e] = x;
+        sout[e] = s;
+    }
+}
+
+// Chunk queue (sots_batch_queue_run): slot c runs under a generation counter of its own, slot_table[c] = {chunk index or
+// kQueueNoChunk, generations completed}; everything else is k_recombine_mutate_seg.  An idle slot (its chunk retired, the
+// queue empty) goes on being varied under its old counter: nothing reads its rows any more.
+__global__ __launch_bounds__(256) void k_recombine_mutate_queue(const float *__restrict__ vin, const float *__restrict__ sin,
+                                                                float *__restrict__ vout, float *__restrict__ sout, PopDims pd,
+                                                                MutateConsts mc, const uint32_t *__restrict__ slot_table, uint32_t slots)
+{
+    const uint32_t total = slots * pd.p * pd.d;
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+        const uint32_t r = e / pd.d, g = e - r * pd.d, c = r / pd.p, i = r - c * pd.p;
+        const uint32_t src = c * pd.p * pd.d + recombine_source(i, g, pd);
+        float x = vin[src], s = sin[src];
+        mutate_gene(x, s, pd.gid_base + i, g, slot_table[2u * c + 1u], pd, mc);
         vout[e] = x;
         sout[e] = s;
     }
@@ -4036,15 +4055,24 @@ __global__ __launch_bounds__(256) void k_x_tables(float *__restrict__ image, con
 }
 // the target part of those tables for every chunk (segmented target image of k_fft_x<.., SEG>): chunk c's table from
 // targets[c][N/2], entry (l, r) at l (E + 4) + r as in tgt_s (the padding entries stay as the caller left them)
+// (one chunk's table, entry le = l E + r of its kWave E entries: the one copy both writers use - k_x_seg_targets for every chunk of a
+// batch, the chunk queue's turnover for the slot it refills)
+template <int LOG2N>
+__device__ __forceinline__ void x_seg_target_entry(float *__restrict__ table, const float *__restrict__ target, uint32_t le)
+{
+    constexpr int E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), S1 = E + 4;
+    const uint32_t l = le / E, r = le % E;
+    table[l * S1 + r] = target[x_target_bin<E, EB>(l, r)];
+}
 template <int LOG2N>
 __global__ __launch_bounds__(256) void k_x_seg_targets(float *__restrict__ tables, const float *__restrict__ targets, uint32_t chunks)
 {
-    constexpr int E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), S1 = E + 4;
+    constexpr int E = x_points<LOG2N>();
     constexpr uint32_t M = (1u << LOG2N) / 2;
     const uint32_t total = chunks * (uint32_t)(kWave * E);
     for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-        const uint32_t c = e / (kWave * E), le = e - c * (kWave * E), l = le / E, r = le % E;
-        tables[(size_t)c * x_seg_stride<LOG2N>() + l * S1 + r] = targets[(size_t)c * M + x_target_bin<E, EB>(l, r)];
+        const uint32_t c = e / (kWave * E), le = e - c * (kWave * E);
+        x_seg_target_entry<LOG2N>(tables + (size_t)c * x_seg_stride<LOG2N>(), targets + (size_t)c * M, le);
     }
 }
 #pragma clang fp contract(off)
@@ -5144,7 +5172,139 @@ __global__ __launch_bounds__(256) void k_track_clear(uint32_t *__restrict__ meta
     }
 }
 
+// ------------------------------------------------------------------------------------
+// Chunk queue (sots_batch_queue_run): the run record of k_track (best-ever only) and the TURNOVER in one launch, a
+// workgroup per slot, after every generation's sort.  A slot whose chunk's stop rule holds at one of the chunk's own
+// check boundaries - or whose counter has reached max_generations - stores the chunk's result, draws the next unstarted
+// chunk (ONE returning atomic on the queue head; nothing else passes between workgroups inside the launch, kernel
+// boundaries on the stream order the rest), and is re-initialised for it: rows as k_init_population_seg draws them,
+// record cleared, counter zeroed, target table rewritten from the stored targets.  With the queue empty the slot goes idle.
+// values / steps / fitness: the half the sort has just written (the turnover writes the new chunk's rows there: it is the
+// half the next generation's variation reads).
+// ------------------------------------------------------------------------------------
+template <int LOG2N>
+__device__ __forceinline__ void queue_fill_x_table(float *__restrict__ image, const float *__restrict__ target, uint32_t slot,
+                                                   uint32_t t, uint32_t threads)
+{
+    float *table = image + kSegHead + (size_t)slot * x_seg_stride<LOG2N>();
+    for (uint32_t le = t; le < (uint32_t)(kWave * x_points<LOG2N>()); le += threads) x_seg_target_entry<LOG2N>(table, target, le);
+}
+
+__global__ __launch_bounds__(256) void k_queue_turnover(float *__restrict__ values, float *__restrict__ steps, float *__restrict__ fitness,
+                                                        PopDims pd, uint32_t *__restrict__ meta, float *__restrict__ rows, QueueArgs q,
+                                                        uint32_t global_generation)
+{
+    __shared__ uint32_t next_s;
+    const uint32_t c = blockIdx.x, t = threadIdx.x, threads = blockDim.x, p = pd.p, d = pd.d;
+    uint32_t *slot = q.slot_table + 2u * (size_t)c;
+    const uint32_t chunk = slot[0];
+    if (chunk == kQueueNoChunk) return; // idle (uniform over the workgroup)
+    const uint32_t g = slot[1] + 1u;    // the chunk's own counter after this generation
+    float *v = values + (size_t)c * p * d, *s = steps + (size_t)c * p * d, *f = fitness + (size_t)c * p;
+    uint32_t *m = meta + 2u * (size_t)c;
+    float *row = rows + (size_t)kTrackRowFloats * c;
+
+    // best-ever, as k_track: strictly better only
+    const float f0 = f[0], old = __uint_as_float(m[0]);
+    const bool wins = f0 < old;
+    const float ever_f = wins ? f0 : old;
+    const uint32_t ever_g = wins ? g : m[1];
+    float rec = 0.0f; // thread t < kTrackRowFloats: word t of the record's row {values[16], steps[16]} after this generation
+    if (t < kTrackRowFloats) {
+        const uint32_t j = t % SOTS_MAX_DIMS;
+        rec = wins && j < d ? (t < SOTS_MAX_DIMS ? v[j] : s[j]) : row[t];
+    }
+    const bool look = q.check_interval != 0u && g % q.check_interval == 0u;
+    const bool retire = g >= q.max_generations || (look && stop_rule_holds(q.target_fitness, q.stall_generations, ever_f, ever_g, g));
+    __syncthreads(); // every thread holds the slot's words and the old record before anybody replaces them
+    if (!retire) {
+        if (wins) {
+            if (t < kTrackRowFloats) row[t] = rec;
+            if (t == 0) {
+                m[0] = __float_as_uint(f0);
+                m[1] = g;
+            }
+        }
+        if (t == 0) slot[1] = g;
+        return;
+    }
+
+    // ---- retire: the result (sots_chunk_result), the kept population ----
+    float *res = q.results + (size_t)chunk * kQueueResultFloats;
+    if (t == 0) {
+        reinterpret_cast<uint32_t *>(res)[0] = g;
+        reinterpret_cast<uint32_t *>(res)[1] = ever_g;
+        res[2] = ever_f;
+        res[3] = f0;
+    }
+    if (t < kTrackRowFloats) res[4 + t] = rec;
+    if (t < SOTS_MAX_DIMS) res[4 + kTrackRowFloats + t] = t < d ? v[t] : 0.0f;
+    if (chunk == q.keep_chunk) {
+        for (uint32_t e = t; e < p * d; e += threads) {
+            q.kept_values[e] = v[e];
+            q.kept_steps[e] = s[e];
+        }
+        for (uint32_t e = t; e < p; e += threads) q.kept_fitness[e] = f[e];
+    }
+    if (t == 0) {
+        atomicAdd(&q.state[1], 1u);                    // retired
+        atomicMax(&q.state[2], global_generation);     // the loop generation of the last retirement
+        next_s = atomicAdd(&q.state[0], 1u);           // the queue head: the next unstarted chunk
+    }
+    __syncthreads(); // the draw is in LDS, and the old rows have been read
+    const uint32_t next = next_s;
+    if (next >= q.num_chunks) {
+        if (t == 0) slot[0] = kQueueNoChunk;
+        return;
+    }
+
+    // ---- refill: k_init_population_seg's draws for chunk first_chunk + next, a cleared record, the target table ----
+    for (uint32_t e = t; e < p * d; e += threads) {
+        const uint32_t i = e / d, gene = e - i * d;
+        const U4 rn = philox4x32_10(pd.gid_base + i, q.first_chunk + next, gene >> 2, kTagInit, pd.seed_lo, pd.seed_hi);
+        const float u = draw_unit(u4_at(rn, gene & 3u));
+        s[e] = 0.1f;
+        v[e] = (u < 0.0f) ? -u : u;
+        if (gene == 0) f[i] = 0.0f;
+    }
+    if (t < kTrackRowFloats) row[t] = 0.0f;
+    if (t == 0) {
+        m[0] = 0x7F800000u;
+        m[1] = 0u;
+        slot[0] = next;
+        slot[1] = 0u;
+    }
+    const float *tg = q.targets + (size_t)next * q.half_bins;
+    switch (q.x_log2n) {
+    case 8: queue_fill_x_table<8>(q.seg_image, tg, c, t, threads); break;
+    case 11: queue_fill_x_table<11>(q.seg_image, tg, c, t, threads); break;
+    case 12: queue_fill_x_table<12>(q.seg_image, tg, c, t, threads); break;
+    case 13: queue_fill_x_table<13>(q.seg_image, tg, c, t, threads); break;
+    default: { // k_fft / k_fft_big: the N/2 bins
+        float *table = q.seg_image + kSegHead + (size_t)c * q.half_bins;
+        for (uint32_t k = t; k < q.half_bins; k += threads) table[k] = tg[k];
+    }
+    }
+}
+
 } // namespace
+
+hipError_t launch_recombine_mutate_queue(hipStream_t st, const float *vin, const float *sin, float *vout, float *sout, const PopDims &pd,
+                                         const MutateConsts &mc, const uint32_t *slot_table, uint32_t slots)
+{
+    k_recombine_mutate_queue<<<grid_for((uint64_t)slots * pd.p * pd.d, 256), 256, 0, st>>>(vin, sin, vout, sout, pd, mc, slot_table, slots);
+    return hipGetLastError();
+}
+
+uint32_t queue_x_log2n(uint32_t log2n) { return x_from(log2n) && log2n != 10 ? log2n : 0u; }
+
+hipError_t launch_queue_turnover(hipStream_t st, float *values, float *steps, float *fitness, const PopDims &pd, uint32_t *meta,
+                                 float *rows, const QueueArgs &q, uint32_t global_generation, uint32_t slots)
+{
+    if (slots == 0 || pd.d == 0 || pd.d > SOTS_MAX_DIMS || q.num_chunks == 0 || q.max_generations == 0) return hipErrorInvalidValue;
+    k_queue_turnover<<<slots, 256, 0, st>>>(values, steps, fitness, pd, meta, rows, q, global_generation);
+    return hipGetLastError();
+}
 
 hipError_t launch_track_clear(hipStream_t st, uint32_t *meta, float *rows, uint32_t chunks)
 {

@@ -85,6 +85,12 @@ struct Evolutionary_Strategy_HIP_Arguments
     //                      generations (sots_execute_until).  Chunks in flight advance together until every chunk of the
     //                      batch has stopped; each chunk's result is taken at ITS stopping boundary, so it does not depend
     //                      on chunksInFlight (its history goes on to the batch's last boundary).
+    // Chunk queue (type.HIP.chunkQueue; sots_batch_queue_run): with chunksInFlight > 1 and no historyPath, parameterMatchAudio
+    // sends ALL its chunks through the chunksInFlight slots of one batch - a chunk whose stop rule holds (or that has run
+    // numGenerations) is retired on the device and its slot starts the next chunk at once, instead of idling until the slowest
+    // chunk of its batch is done.  Same per-chunk results, same lines printed.  With a historyPath (the slots keep no history
+    // rings) today's batch-by-batch path runs.  Off by default: nothing changes.
+    bool chunkQueue = false;
     bool returnBestEver = false;
     uint32_t historyEvery = 0;
     std::string historyPath = "";
@@ -400,7 +406,12 @@ public:
             printf("chunksInFlight %u: %s, matching chunk by chunk\n", args_.chunksInFlight,
                    group_ ? "numDevices > 1" : "populationLength > 1024");
         hipBenchmarker_.startTimer("Total Audio Analysis Time");
-        if (batched) {
+        const bool queued = batched && args_.chunkQueue && !historyFile_ && numGenerations > 0 && numChunks_ > 0;
+        if (batched && args_.chunkQueue && historyFile_ && args_.verbose)
+            printf("chunkQueue: a history file is written, matching batch by batch\n");
+        if (queued) {
+            matchChunkQueue(aTargetAudio);
+        } else if (batched) {
             matchChunksInFlight(aTargetAudio);
         } else {
             for (uint32_t i = 0; i < numChunks_; i++) {
@@ -466,6 +477,46 @@ private:
         printf("Best parameters found:\n");
         for (uint32_t j = 0; j < d && j < scaled.size(); ++j) printf(" p%u = %f\n", j, scaled[j]);
         printf("Best fitness: %g\n\n", bestFitness);
+    }
+
+    // parameterMatchAudio through the chunk queue: every chunk's target (Objective::calculateFFT, as setTargetAudio) goes to the
+    // device, ONE sots_batch_queue_run matches them all in chunksInFlight slots, and the results come back together.  The
+    // last chunk's population, as it was when that chunk stopped, is kept and written into the context, so that
+    // readPopulationData and printBest read what they read after the chunk-by-chunk loop.
+    void matchChunkQueue(const float *aTargetAudio)
+    {
+        const uint32_t half = objective.fftHalfSize, d = population.numDimensions, P = population.populationLength;
+        if (!batch_ && sots_batch_create(&cfg_, args_.chunksInFlight, &batch_) != SOTS_OK)
+            throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_batch_create: ") + sots_batch_last_error(nullptr));
+        auto checkBatch = [&](int rc, const char *what) {
+            if (rc != SOTS_OK) throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + what + ": " + sots_batch_last_error(batch_));
+        };
+        if (args_.deviceKernelArithmetic) checkBatch(sots_batch_set_synth_arithmetic(batch_, SOTS_ARITH_DEVICE_KERNELS), "sots_batch_set_synth_arithmetic");
+        checkBatch(sots_batch_track(batch_, SOTS_TRACK_BEST_EVER, 0, 0), "sots_batch_track"); // (the queue keeps the best-ever record itself)
+        std::vector<float> mags((size_t)numChunks_ * half);
+        for (uint32_t c = 0; c < numChunks_; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)chunkSize_ * c], mags.data() + (size_t)c * half);
+        checkBatch(sots_batch_queue_targets_spectra(batch_, mags.data(), (uint64_t)mags.size(), numChunks_), "sots_batch_queue_targets_spectra");
+        sots_queue_stats stats{};
+        stats.struct_size = sizeof stats;
+        checkBatch(sots_batch_queue_run(batch_, 0, numGenerations, stopRuleSet() ? &rule_ : nullptr, numChunks_ - 1, &stats), "sots_batch_queue_run");
+        std::vector<sots_chunk_result> results(numChunks_);
+        uint32_t got = 0;
+        checkBatch(sots_batch_queue_results(batch_, results.data(), numChunks_, &got), "sots_batch_queue_results");
+        if (got != numChunks_) throw std::runtime_error("Evolutionary_Strategy_HIP: sots_batch_queue_results: results missing");
+        generationsRun_ = stats.chunk_generations;
+        for (uint32_t c = 0; c < numChunks_; ++c) {
+            const sots_chunk_result &r = results[c];
+            if (args_.verbose) printf("Audio chunk %u evaluated:\n", c);
+            if (args_.returnBestEver) recordBest(r.best_ever_values, r.best_ever_fitness);
+            else recordBest(r.last_values, r.last_fitness);
+            generationsPerChunk_.push_back(r.generations_run);
+            if (stopRuleSet() && args_.verbose) printf("Generations run: %u\n", r.generations_run);
+        }
+        std::vector<float> v((size_t)P * d), s((size_t)P * d), f(P);
+        checkBatch(sots_batch_queue_read_kept_population(batch_, v.data(), v.size() * sizeof(float), s.data(), s.size() * sizeof(float), f.data(),
+                                                         f.size() * sizeof(float)), "sots_batch_queue_read_kept_population");
+        check(sots_write_population(ctx_, v.data(), v.size() * sizeof(float), s.data(), s.size() * sizeof(float), f.data(), f.size() * sizeof(float)),
+              "writePopulationData");
     }
 
     // parameterMatchAudio with chunksInFlight chunks per batch (the last batch may be ragged): per batch the targets
