@@ -207,6 +207,22 @@ int sots_stage_bucket_fitness(sots_ctx *ctx);
 /* enum sots_synth_arith; applies to sots_stage_synthesise and to both generation loops from the next call on
  * (replaces nothing: the reference picks its arithmetic by picking a backend, main.cpp:105-163) */
 int sots_set_synth_arithmetic(sots_ctx *ctx, uint32_t arith);
+/* Elitist survival (new; replaces nothing: the reference's strategy keeps no row, ocl_program.cl:99-190).  With n > 0 the
+ * variation that makes the new half - sots_stage_recombine + sots_stage_mutate, and the variation of both generation
+ * loops, whichever kernel performs it - does this for row i:
+ *   i <  n : values and steps are bit copies of row i of the sorted current half; nothing is drawn, nothing is mutated;
+ *   i >= n : exactly what is computed with n = 0 (the PRNG is counter-based: the survivors' draws are left out, nobody
+ *            else's change).
+ * Everything after variation is unchanged: survivors are synthesised and evaluated again like any other row - no fitness
+ * is carried that a new target could make stale - and compete in the sort, at a lower row index than any offspring of
+ * equal fitness.  n = numParents is plus-selection.  0 <= n <= numParents (rows every sort mode and both selection plans
+ * place every generation); above that SOTS_ERR_INVALID, and the old setting stays.  Default 0: the launches and bits of
+ * the reference's strategy.  A setting, not population state: sots_init_population, sots_set_target_* and
+ * sots_write_population keep it; it applies from the next variation on and neither completes nor drops a pending
+ * lazy tail (enum sots_sort_mode).  The rows carried are whatever rows 0..n-1 of the current half hold when variation
+ * runs, immigrants of a fused or separate inject included.  Islands of a group are set through sots_group_island. */
+int sots_set_survivors(sots_ctx *ctx, uint32_t n);
+int sots_get_survivors(const sots_ctx *ctx, uint32_t *n);
 int sots_get_generation(const sots_ctx *ctx, uint32_t *generation);
 int sots_set_generation(sots_ctx *ctx, uint32_t generation);
 
@@ -323,6 +339,9 @@ int sots_batch_init_population(sots_batch *b, uint32_t first_chunk_index);
 /* n generations of every active chunk; only enqueues */
 int sots_batch_execute_generations(sots_batch *b, uint32_t n);
 int sots_batch_set_synth_arithmetic(sots_batch *b, uint32_t arith); /* enum sots_synth_arith */
+/* sots_set_survivors for every chunk of the batch, in sots_batch_execute_* and sots_batch_queue_run alike (a refilled
+ * slot's first variation carries the initialised rows 0..n-1, as a fresh context's does); same limits, same default */
+int sots_batch_set_survivors(sots_batch *b, uint32_t n);
 /* row 0 (the best) of every active chunk: values [active][D], fitness [active] (either may be NULL); blocking */
 int sots_batch_read_best(sots_batch *b, float *values, size_t values_bytes, float *fitness, size_t fitness_bytes);
 /* one active chunk's current half; byte counts as sots_read_population; blocking */

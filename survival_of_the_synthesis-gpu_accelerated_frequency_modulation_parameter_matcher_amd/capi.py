@@ -45,7 +45,7 @@ EXPORTS = [
     "sots_set_sort_mode",
     "sots_set_select_plan", "sots_select_splitter_count", "sots_write_select_splitters", "sots_read_select_splitters",
     "sots_stage_bucket_fitness",
-    "sots_set_synth_arithmetic",
+    "sots_set_synth_arithmetic", "sots_set_survivors", "sots_get_survivors", "sots_batch_set_survivors",
     "sots_execute_generation", "sots_execute_generations", "sots_get_generation",
     "sots_set_generation", "sots_timing_enable", "sots_timing_reset", "sots_stage_time_ms",
     "sots_stage_launch_times_ms",
@@ -191,6 +191,8 @@ def load():
         getattr(L, "sots_stage_" + name).argtypes = [vp]
     L.sots_execute_generation.argtypes = [vp]
     L.sots_execute_generations.argtypes = [vp, u32]
+    L.sots_set_survivors.argtypes = [vp, u32]
+    L.sots_get_survivors.argtypes = [vp, C.POINTER(u32)]
     L.sots_get_generation.argtypes = [vp, C.POINTER(u32)]
     L.sots_set_generation.argtypes = [vp, u32]
     L.sots_timing_enable.argtypes = [vp, C.c_int]
@@ -231,6 +233,7 @@ def load():
     L.sots_batch_init_population.argtypes = [vp, u32]
     L.sots_batch_execute_generations.argtypes = [vp, u32]
     L.sots_batch_set_synth_arithmetic.argtypes = [vp, u32]
+    L.sots_batch_set_survivors.argtypes = [vp, u32]
     L.sots_batch_read_best.argtypes = [vp, vp, sz, vp, sz]
     L.sots_batch_read_population.argtypes = [vp, u32, vp, sz, vp, sz, vp, sz]
     u64p = C.POINTER(C.c_uint64)
@@ -467,6 +470,17 @@ class HipES:
         """ARITH_CPU_PATH (default) or ARITH_DEVICE_KERNELS: the reference's OpenCL kernels' arithmetic (enum sots_synth_arith)"""
         self._check(self.L.sots_set_synth_arithmetic(self._h, arith))
 
+    def set_survivors(self, n):
+        """rows 0..n-1 of the sorted half pass through variation unchanged (0 <= n <= numParents; 0, the default, is the
+        reference's non-elitist strategy); a setting: init_population and set_target_* keep it"""
+        self._check(self.L.sots_set_survivors(self._h, n))
+
+    @property
+    def survivors(self):
+        n = C.c_uint32()
+        self._check(self.L.sots_get_survivors(self._h, C.byref(n)))
+        return n.value
+
     def execute_generation(self):
         self._check(self.L.sots_execute_generation(self._h))
 
@@ -625,6 +639,10 @@ class HipBatch:
 
     def set_synth_arithmetic(self, arith):
         self._check(self.L.sots_batch_set_synth_arithmetic(self._h, arith))
+
+    def set_survivors(self, n):
+        """HipES.set_survivors for every chunk, in execute_generations / execute_until and queue_run alike"""
+        self._check(self.L.sots_batch_set_survivors(self._h, n))
 
     def read_best(self):
         """(values[active][D], fitness[active]): row 0 of every active chunk"""

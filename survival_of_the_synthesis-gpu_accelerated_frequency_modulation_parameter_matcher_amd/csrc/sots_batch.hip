@@ -342,6 +342,15 @@ int sots_batch_set_synth_arithmetic(sots_batch *b, uint32_t arith)
     return SOTS_OK;
 }
 
+int sots_batch_set_survivors(sots_batch *b, uint32_t n)
+{
+    BATCH_REQUIRE(b);
+    if (n > b->cfg.num_parents)
+        return bfail(b, SOTS_ERR_INVALID, "%u survivors asked for, at most numParents = %u can be kept", n, b->cfg.num_parents);
+    b->pd.survivors = n;
+    return SOTS_OK;
+}
+
 int sots_batch_execute_generations(sots_batch *b, uint32_t n)
 {
     BATCH_REQUIRE(b);

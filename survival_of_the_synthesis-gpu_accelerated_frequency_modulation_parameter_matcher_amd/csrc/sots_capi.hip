@@ -1112,6 +1112,25 @@ int sots_set_synth_arithmetic(sots_ctx *ctx, uint32_t arith)
     return SOTS_OK;
 }
 
+// A setting, like the sort mode: it changes what the NEXT variation computes and nothing now - a pending lazy tail stays
+// pending (rows 0..numParents-1, all that variation takes survivors from, are placed whatever the tail's state).
+int sots_set_survivors(sots_ctx *ctx, uint32_t n)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (n > ctx->cfg.num_parents)
+        return fail(ctx, SOTS_ERR_INVALID, "%u survivors asked for, at most numParents = %u can be kept", n, ctx->cfg.num_parents);
+    ctx->pd.survivors = n;
+    return SOTS_OK;
+}
+
+int sots_get_survivors(const sots_ctx *ctx, uint32_t *n)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (!n) return fail(ctx, SOTS_ERR_INVALID, "null survivors pointer");
+    *n = ctx->pd.survivors;
+    return SOTS_OK;
+}
+
 int sots_get_generation(const sots_ctx *ctx, uint32_t *generation)
 {
     SOTS_REQUIRE_CTX(ctx);

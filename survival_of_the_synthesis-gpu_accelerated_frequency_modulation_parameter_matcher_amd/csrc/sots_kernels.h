@@ -37,12 +37,15 @@ struct PopDims {
     uint32_t block_shift;  // log2(block) when block is a power of two, else kNoPow2
     uint32_t npb;          // parent blocks: max(1, num_parents / block)
     uint32_t npb_mask;     // npb - 1 when npb is a power of two, else kNoPow2
+    // rows 0 .. survivors-1 of the sorted half pass through variation as they are (make_gene, sots_kernels.hip); a
+    // setting of the context or batch (sots_set_survivors), 0 = the reference's strategy
+    uint32_t survivors;
 };
 constexpr uint32_t kNoPow2 = 0xFFFFFFFFu;
 inline PopDims make_pop_dims(uint32_t p, uint32_t d, uint32_t num_parents, uint32_t block, uint32_t gid_base, uint32_t seed_lo,
                              uint32_t seed_hi)
 {
-    PopDims pd{p, d, num_parents, block, gid_base, seed_lo, seed_hi, kNoPow2, 1u, kNoPow2};
+    PopDims pd{p, d, num_parents, block, gid_base, seed_lo, seed_hi, kNoPow2, 1u, kNoPow2, 0u};
     if (block && (block & (block - 1u)) == 0u)
         for (uint32_t sh = 0; sh < 32; ++sh)
             if ((1u << sh) == block) pd.block_shift = sh;

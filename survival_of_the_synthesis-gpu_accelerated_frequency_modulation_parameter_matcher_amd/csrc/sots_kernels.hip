@@ -110,20 +110,6 @@ __device__ __forceinline__ uint32_t recombine_source(uint32_t i, uint32_t g, con
     return (pb * pd.block + l) * pd.d + g;
 }
 
-__global__ __launch_bounds__(256) void k_recombine(const float *__restrict__ vin,
-                                                   const float *__restrict__ sin,
-                                                   float *__restrict__ vout,
-                                                   float *__restrict__ sout, PopDims pd)
-{
-    const uint32_t total = pd.p * pd.d;
-    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-        const uint32_t i = e / pd.d, g = e - i * pd.d;
-        const uint32_t src = recombine_source(i, g, pd);
-        vout[e] = vin[src];
-        sout[e] = sin[src];
-    }
-}
-
 // ------------------------------------------------------------------------------------
 // mutatePopulation, ocl_program.cl:155-190.  13 draws per gene = Philox blocks 4g..4g+3.
 // ------------------------------------------------------------------------------------
@@ -155,14 +141,50 @@ __device__ __forceinline__ void mutate_gene(float &x, float &s, uint32_t gid, ui
     x = new_x;
 }
 
+// ------------------------------------------------------------------------------------
+// Gene g of individual i of the new half: THE rule of variation, used by every kernel that makes individuals.
+// Rows i < pd.survivors (sots_set_survivors; 0 = the reference's strategy) are carried: value and step are bit copies of
+// the row's own entry in the sorted current half, nothing is drawn, nothing is mutated.  Every other row is what it is
+// without survivors - Philox is counter-based, so the draws the survivors leave out are nobody else's.
+// row_base: first element of the individual's population in vin / sin (a batch chunk; 0 in a context).  WHAT: the stage
+// kernels do one half each (kVaryMutate alone works in place: the source is the gene's own entry).
+// ------------------------------------------------------------------------------------
+constexpr uint32_t kVaryRecombine = 1u, kVaryMutate = 2u;
+template <uint32_t WHAT = kVaryRecombine | kVaryMutate>
+__device__ __forceinline__ void make_gene(float &x, float &s, const float *__restrict__ vin, const float *__restrict__ sin,
+                                          uint32_t row_base, uint32_t i, uint32_t g, uint32_t generation, const PopDims &pd,
+                                          const MutateConsts &mc)
+{
+    const bool survivor = i < pd.survivors;
+    const uint32_t src = row_base + ((WHAT & kVaryRecombine) && !survivor ? recombine_source(i, g, pd) : i * pd.d + g);
+    x = vin[src];
+    s = sin[src];
+    if ((WHAT & kVaryMutate) && !survivor) mutate_gene(x, s, pd.gid_base + i, g, generation, pd, mc);
+}
+
+__global__ __launch_bounds__(256) void k_recombine(const float *__restrict__ vin,
+                                                   const float *__restrict__ sin,
+                                                   float *__restrict__ vout,
+                                                   float *__restrict__ sout, PopDims pd)
+{
+    const uint32_t total = pd.p * pd.d;
+    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
+        const uint32_t i = e / pd.d, g = e - i * pd.d;
+        float x, s;
+        make_gene<kVaryRecombine>(x, s, vin, sin, 0u, i, g, 0u, pd, MutateConsts{});
+        vout[e] = x;
+        sout[e] = s;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_mutate(float *__restrict__ values, float *__restrict__ steps,
                                                 PopDims pd, MutateConsts mc, uint32_t generation)
 {
     const uint32_t total = pd.p * pd.d;
     for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
         const uint32_t i = e / pd.d, g = e - i * pd.d;
-        float x = values[e], s = steps[e];
-        mutate_gene(x, s, pd.gid_base + i, g, generation, pd, mc);
+        float x, s;
+        make_gene<kVaryMutate>(x, s, values, steps, 0u, i, g, generation, pd, mc);
         values[e] = x;
         steps[e] = s;
     }
@@ -177,9 +199,8 @@ __global__ __launch_bounds__(256) void k_recombine_mutate(const float *__restric
     const uint32_t total = pd.p * pd.d;
     for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
         const uint32_t i = e / pd.d, g = e - i * pd.d;
-        const uint32_t src = recombine_source(i, g, pd);
-        float x = vin[src], s = sin[src];
-        mutate_gene(x, s, pd.gid_base + i, g, generation, pd, mc);
+        float x, s;
+        make_gene(x, s, vin, sin, 0u, i, g, generation, pd, mc);
         vout[e] = x;
         sout[e] = s;
     }
@@ -212,9 +233,8 @@ __global__ __launch_bounds__(256) void k_recombine_mutate_seg(const float *__res
     const uint32_t total = chunks * pd.p * pd.d;
     for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
         const uint32_t r = e / pd.d, g = e - r * pd.d, c = r / pd.p, i = r - c * pd.p;
-        const uint32_t src = c * pd.p * pd.d + recombine_source(i, g, pd);
-        float x = vin[src], s = sin[src];
-        mutate_gene(x, s, pd.gid_base + i, g, generation, pd, mc);
+        float x, s;
+        make_gene(x, s, vin, sin, c * pd.p * pd.d, i, g, generation, pd, mc);
         vout[e] = x;
         sout[e] = s;
     }
@@ -230,9 +250,8 @@ __global__ __launch_bounds__(256) void k_recombine_mutate_queue(const float *__r
     const uint32_t total = slots * pd.p * pd.d;
     for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
         const uint32_t r = e / pd.d, g = e - r * pd.d, c = r / pd.p, i = r - c * pd.p;
-        const uint32_t src = c * pd.p * pd.d + recombine_source(i, g, pd);
-        float x = vin[src], s = sin[src];
-        mutate_gene(x, s, pd.gid_base + i, g, slot_table[2u * c + 1u], pd, mc);
+        float x, s;
+        make_gene(x, s, vin, sin, c * pd.p * pd.d, i, g, slot_table[2u * c + 1u], pd, mc);
         vout[e] = x;
         sout[e] = s;
     }
@@ -489,9 +508,8 @@ __global__ __launch_bounds__((HELP ? (SPLIT ? 8 : 16) : SPLIT3 ? 8 : SPLIT2 ? 6 
             const uint32_t i1 = (blockIdx.x + kt * gridDim.x) * (pairs * kWave) + li;
             if (i1 < p_len) {
                 for (uint32_t g1 = t % HT; g1 < (uint32_t)D; g1 += HT) {
-                    const uint32_t src = recombine_source(i1, g1, var.pd);
-                    float x = var.vin[src], st = var.sin[src];
-                    mutate_gene(x, st, var.pd.gid_base + i1, g1, var.generation, var.pd, var.mc);
+                    float x, st;
+                    make_gene(x, st, var.vin, var.sin, 0u, i1, g1, var.generation, var.pd, var.mc);
                     var.vout[(size_t)i1 * D + g1] = x;
                     var.sout[(size_t)i1 * D + g1] = st;
                     made[kt * (pairs * kWave * D) + li * D + g1] = x;
@@ -553,9 +571,8 @@ __global__ __launch_bounds__((HELP ? (SPLIT ? 8 : 16) : SPLIT3 ? 8 : SPLIT2 ? 6 
             const bool owner = !front && row0 + lane < p_len;
 #pragma unroll 1
             for (int g = 0; g < D; ++g) {
-                const uint32_t src = recombine_source(ind, (uint32_t)g, var.pd);
-                float x = var.vin[src], st = var.sin[src];
-                mutate_gene(x, st, var.pd.gid_base + ind, (uint32_t)g, var.generation, var.pd, var.mc);
+                float x, st;
+                make_gene(x, st, var.vin, var.sin, 0u, ind, (uint32_t)g, var.generation, var.pd, var.mc);
                 if (owner) {
                     var.vout[(size_t)ind * D + g] = x;
                     var.sout[(size_t)ind * D + g] = st;
@@ -968,9 +985,8 @@ __global__ __launch_bounds__(ol_max_waves<VoiceShape<KIND>::OPS>() * kWave) void
             for (uint32_t t = threadIdx.x; t < rows_per_block * D; t += blockDim.x) {
                 const uint32_t i1 = base + t / D, g1 = t % D;
                 if (i1 < p_len) {
-                    const uint32_t src = recombine_source(i1, g1, var.pd);
-                    float x = var.vin[src], st = var.sin[src];
-                    mutate_gene(x, st, var.pd.gid_base + i1, g1, var.generation, var.pd, var.mc);
+                    float x, st;
+                    make_gene(x, st, var.vin, var.sin, 0u, i1, g1, var.generation, var.pd, var.mc);
                     var.vout[(size_t)i1 * D + g1] = x;
                     var.sout[(size_t)i1 * D + g1] = st;
                     made[t] = x;
@@ -1250,9 +1266,8 @@ __global__ __launch_bounds__(tp_waves<KIND>() * kWave) void k_synth_tp(const flo
     if (var.vin) {
         for (uint32_t t = threadIdx.x; t < count * D; t += THREADS) {
             const uint32_t i1 = first + t / D, g1 = t % D;
-            const uint32_t src = recombine_source(i1, g1, var.pd);
-            float x = var.vin[src], st = var.sin[src];
-            mutate_gene(x, st, var.pd.gid_base + i1, g1, var.generation, var.pd, var.mc);
+            float x, st;
+            make_gene(x, st, var.vin, var.sin, 0u, i1, g1, var.generation, var.pd, var.mc);
             var.vout[(size_t)i1 * D + g1] = x;
             var.sout[(size_t)i1 * D + g1] = st;
             made[t] = x;

@@ -91,6 +91,11 @@ struct Evolutionary_Strategy_HIP_Arguments
     // chunk of its batch is done.  Same per-chunk results, same lines printed.  With a historyPath (the slots keep no history
     // rings) today's batch-by-batch path runs.  Off by default: nothing changes.
     bool chunkQueue = false;
+    // Elitist survival (type.HIP.survivors; sots_set_survivors): rows 0..survivors-1 of the sorted population pass through
+    // recombination and mutation unchanged and are evaluated again with the offspring.  0 (default) is the reference's
+    // strategy; at most numParents, above that the constructor / parameterMatchAudio throws with the library's text.
+    // Applied to the context, to every island of a group and to the chunks in flight (batched and queued alike).
+    uint32_t survivors = 0;
     bool returnBestEver = false;
     uint32_t historyEvery = 0;
     std::string historyPath = "";
@@ -291,6 +296,9 @@ public:
         if (args_.deviceKernelArithmetic)
             for (uint32_t i = 0; i < numIslands(); ++i)
                 check(sots_set_synth_arithmetic(group_ ? sots_group_island(group_, i) : ctx_, SOTS_ARITH_DEVICE_KERNELS), "sots_set_synth_arithmetic");
+        if (args_.survivors)
+            for (uint32_t i = 0; i < numIslands(); ++i)
+                check(sots_set_survivors(group_ ? sots_group_island(group_, i) : ctx_, args_.survivors), "sots_set_survivors");
         check(sots_timing_enable(ctx_, args_.benchmarkStages ? 1 : 0), "sots_timing_enable");
         if (tracking()) {
             if (group_) throw std::runtime_error("Evolutionary_Strategy_HIP: returnBestEver, the history and the stop rules need numDevices = 1");
@@ -492,6 +500,7 @@ private:
             if (rc != SOTS_OK) throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + what + ": " + sots_batch_last_error(batch_));
         };
         if (args_.deviceKernelArithmetic) checkBatch(sots_batch_set_synth_arithmetic(batch_, SOTS_ARITH_DEVICE_KERNELS), "sots_batch_set_synth_arithmetic");
+        checkBatch(sots_batch_set_survivors(batch_, args_.survivors), "sots_batch_set_survivors");
         checkBatch(sots_batch_track(batch_, SOTS_TRACK_BEST_EVER, 0, 0), "sots_batch_track"); // (the queue keeps the best-ever record itself)
         std::vector<float> mags((size_t)numChunks_ * half);
         for (uint32_t c = 0; c < numChunks_; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)chunkSize_ * c], mags.data() + (size_t)c * half);
@@ -534,6 +543,7 @@ private:
             if (rc != SOTS_OK) throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + what + ": " + sots_batch_last_error(batch_));
         };
         if (args_.deviceKernelArithmetic) checkBatch(sots_batch_set_synth_arithmetic(batch_, SOTS_ARITH_DEVICE_KERNELS), "sots_batch_set_synth_arithmetic");
+        checkBatch(sots_batch_set_survivors(batch_, args_.survivors), "sots_batch_set_survivors");
         if (tracking()) checkBatch(sots_batch_track(batch_, trackFlags(), args_.historyEvery, historyCapacity()), "sots_batch_track");
         std::vector<float> mags((size_t)perBatch * half), values((size_t)perBatch * d), fitness(perBatch);
         std::vector<float> nowValues((size_t)perBatch * d), nowFitness(perBatch), everFitness(perBatch);

@@ -3,7 +3,7 @@
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
 // "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "numDevices", "numElites",
 // "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight", "chunkQueue",
-// "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
+// "survivors", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
 // N-sample chunk with Evolutionary_Strategy_HIP, writes inputGenerated.wav and the
 // outputAudioPath rendering of the best match, and prints the best parameters.
@@ -195,6 +195,13 @@ int main(int argc, char *argv[])
             if (h.has("chunksInFlight")) args.chunksInFlight = (uint32_t)h["chunksInFlight"].number();
             // ... through one queue: a slot takes the next chunk as soon as its chunk's stop rule holds
             if (h.has("chunkQueue")) args.chunkQueue = h["chunkQueue"].b;
+            // elitist survival: the best `survivors` rows are carried unchanged into each generation (0: the reference's strategy)
+            if (h.has("survivors")) {
+                // a value above every population goes to the library as the largest count, which refuses it with its own text
+                const double k = h["survivors"].number();
+                if (!(k >= 0.0)) throw std::runtime_error("parameters.json: type.HIP.survivors must not be negative");
+                args.survivors = k >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)k;
+            }
             // run record (Evolutionary_Strategy_HIP_Arguments): the best individual any generation produced, a history CSV,
             // and stopping a chunk early on a fitness target or a stall
             if (h.has("returnBestEver")) args.returnBestEver = h["returnBestEver"].b;
