@@ -223,6 +223,22 @@ int sots_set_synth_arithmetic(sots_ctx *ctx, uint32_t arith);
  * runs, immigrants of a fused or separate inject included.  Islands of a group are set through sots_group_island. */
 int sots_set_survivors(sots_ctx *ctx, uint32_t n);
 int sots_get_survivors(const sots_ctx *ctx, uint32_t *n);
+/* The spectral objective (new; replaces nothing: the reference has the one fitness, Evolutionary_Strategy.hpp:517-519 /
+ * ocl_program.cl:608-611).  With m_k = |X_k| / N / windowFactor, the candidate's normalised magnitude of bin k, and t_k
+ * the target's, over the bins k = 0 .. N/2-1 of the reference's sum:
+ *   SOTS_OBJECTIVE_MAGNITUDE      F = sum_k (m_k - t_k)^2                            (the reference's; the default)
+ *   SOTS_OBJECTIVE_LOG_MAGNITUDE  F = sum_k (ln(m_k + floor) - ln(t_k + floor))^2
+ * floor, in the unit of the normalised magnitudes, must be finite with 1e-30 <= floor <= 1 (m + floor is then a normal
+ * fp32 number); it is ignored for MAGNITUDE and reported as 0.  An unknown objective or a floor outside the range is
+ * SOTS_ERR_INVALID, and the old setting stays.  Setting the objective - to any value, the current one included - acts
+ * like a new target: the run record is cleared, the stored splitters and key lists are dropped.  It may come before or
+ * after the target, with the same result; sots_read_synth still returns the raw target magnitudes.  NaN rows
+ * get NaN fitness and sort last, as ever.  Fitness values, history records and stop-rule thresholds
+ * (sots_stop_rule.target_fitness) are in the units of the active objective: squared nepers summed over the bins under
+ * LOG_MAGNITUDE.  A setting: sots_init_population and sots_set_target_* keep it. */
+enum sots_objective { SOTS_OBJECTIVE_MAGNITUDE = 0, SOTS_OBJECTIVE_LOG_MAGNITUDE = 1 };
+int sots_set_objective(sots_ctx *ctx, uint32_t objective, float floor);
+int sots_get_objective(const sots_ctx *ctx, uint32_t *objective, float *floor);
 int sots_get_generation(const sots_ctx *ctx, uint32_t *generation);
 int sots_set_generation(sots_ctx *ctx, uint32_t generation);
 
@@ -302,6 +318,8 @@ int sots_group_uses_rccl(const sots_group *group);
 sots_ctx *sots_group_island(sots_group *group, uint32_t i);
 int sots_group_set_target_audio(sots_group *group, const float *audio, uint32_t num_samples);
 int sots_group_set_target_spectrum(sots_group *group, const float *magnitudes, uint32_t num_bins);
+/* sots_set_objective on every island (new; the reference has one fitness, ocl_program.cl:608-611); the first failure is returned */
+int sots_group_set_objective(sots_group *group, uint32_t objective, float floor);
 int sots_group_init_population(sots_group *group, uint32_t chunk_index);
 /* n generations on every island with the elite exchange; returns once everything is ENQUEUED.  In the overlapped
  * schedule (SOTS_GROUP_OVERLAP without SOTS_GROUP_EVENT_WAITS, "host-gated") every island's thread waits, before it
@@ -342,6 +360,10 @@ int sots_batch_set_synth_arithmetic(sots_batch *b, uint32_t arith); /* enum sots
 /* sots_set_survivors for every chunk of the batch, in sots_batch_execute_* and sots_batch_queue_run alike (a refilled
  * slot's first variation carries the initialised rows 0..n-1, as a fresh context's does); same limits, same default */
 int sots_batch_set_survivors(sots_batch *b, uint32_t n);
+/* sots_set_objective for every chunk of the batch (new; the reference has one fitness, ocl_program.cl:608-611), in
+ * sots_batch_execute_* and sots_batch_queue_run alike: the active targets' and the stored queue targets' tables are
+ * rebuilt for it, every chunk's run record is cleared.  Before or after the targets, with the same result. */
+int sots_batch_set_objective(sots_batch *b, uint32_t objective, float floor);
 /* row 0 (the best) of every active chunk: values [active][D], fitness [active] (either may be NULL); blocking */
 int sots_batch_read_best(sots_batch *b, float *values, size_t values_bytes, float *fitness, size_t fitness_bytes);
 /* one active chunk's current half; byte counts as sots_read_population; blocking */

@@ -28,6 +28,8 @@ SYNTH_NAMES = {"2op": SYNTH_2OP, "3op_series": SYNTH_3OP_SERIES,
 SORT_LAZY_TAIL, SORT_FULL, SORT_TOP_ONLY = 0, 1, 2
 SELECT_AUTO, SELECT_TILES, SELECT_SPLITTERS = 0, 1, 2
 ARITH_CPU_PATH, ARITH_DEVICE_KERNELS = 0, 1
+OBJECTIVE_MAGNITUDE, OBJECTIVE_LOG_MAGNITUDE = 0, 1  # enum sots_objective
+OBJECTIVE_FLOOR_MIN, OBJECTIVE_FLOOR_MAX = 1e-30, 1.0
 
 # the reference's Benchmarker timer names, Evolutionary_Strategy_OpenCL.hpp:117
 STAGE_NAMES = ["initPopulation", "recombinePopulation", "mutatePopulation", "synthesisePopulation",
@@ -63,6 +65,7 @@ EXPORTS = [
     "sots_batch_track", "sots_batch_read_best_ever", "sots_batch_read_history", "sots_batch_execute_until",
     "sots_batch_queue_targets_spectra", "sots_batch_queue_targets_audio", "sots_batch_queue_run", "sots_batch_queue_results",
     "sots_batch_queue_read_kept_population", "sots_queue_makespan",
+    "sots_set_objective", "sots_get_objective", "sots_batch_set_objective", "sots_group_set_objective",
 ]
 QUEUE_NO_CHUNK = 0xFFFFFFFF
 TRACK_BEST_EVER, TRACK_HISTORY = 1, 2
@@ -193,6 +196,10 @@ def load():
     L.sots_execute_generations.argtypes = [vp, u32]
     L.sots_set_survivors.argtypes = [vp, u32]
     L.sots_get_survivors.argtypes = [vp, C.POINTER(u32)]
+    L.sots_set_objective.argtypes = [vp, u32, C.c_float]
+    L.sots_get_objective.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_float)]
+    L.sots_batch_set_objective.argtypes = [vp, u32, C.c_float]
+    L.sots_group_set_objective.argtypes = [vp, u32, C.c_float]
     L.sots_get_generation.argtypes = [vp, C.POINTER(u32)]
     L.sots_set_generation.argtypes = [vp, u32]
     L.sots_timing_enable.argtypes = [vp, C.c_int]
@@ -481,6 +488,20 @@ class HipES:
         self._check(self.L.sots_get_survivors(self._h, C.byref(n)))
         return n.value
 
+    def set_objective(self, objective, floor=0.0):
+        """OBJECTIVE_MAGNITUDE (default: sum (m - t)^2, the reference's) or OBJECTIVE_LOG_MAGNITUDE: sum (ln(m + floor) -
+        ln(t + floor))^2 with 1e-30 <= floor <= 1 in the unit of the normalised magnitudes.  Acts like a new target (the
+        run record starts over); before or after set_target_*, with the same result.  Fitness, history and stop-rule
+        thresholds are in the units of the active objective."""
+        self._check(self.L.sots_set_objective(self._h, objective, floor))
+
+    @property
+    def objective(self):
+        """(objective, floor); the floor reads 0 under OBJECTIVE_MAGNITUDE"""
+        o, f = C.c_uint32(), C.c_float()
+        self._check(self.L.sots_get_objective(self._h, C.byref(o), C.byref(f)))
+        return o.value, f.value
+
     def execute_generation(self):
         self._check(self.L.sots_execute_generation(self._h))
 
@@ -644,6 +665,10 @@ class HipBatch:
         """HipES.set_survivors for every chunk, in execute_generations / execute_until and queue_run alike"""
         self._check(self.L.sots_batch_set_survivors(self._h, n))
 
+    def set_objective(self, objective, floor=0.0):
+        """HipES.set_objective for every chunk, in execute_generations / execute_until and queue_run alike"""
+        self._check(self.L.sots_batch_set_objective(self._h, objective, floor))
+
     def read_best(self):
         """(values[active][D], fitness[active]): row 0 of every active chunk"""
         v = np.empty((self.active, self.D), np.float32)
@@ -767,6 +792,10 @@ class HipGroup:
     def set_target_audio(self, audio):
         a = _f32(audio)
         self._check(self.L.sots_group_set_target_audio(self._h, _ptr(a), a.size))
+
+    def set_objective(self, objective, floor=0.0):
+        """HipES.set_objective on every island"""
+        self._check(self.L.sots_group_set_objective(self._h, objective, floor))
 
     def init_population(self, chunk=0):
         self._check(self.L.sots_group_init_population(self._h, chunk))

@@ -44,6 +44,11 @@ struct sots_batch {
     float *values = nullptr, *steps = nullptr, *fitness = nullptr; // [2][C P][D], [2][C P][D], [2][C P]
     float *audio = nullptr;                                        // [C P][pitch]
     float *targets = nullptr;                                      // [C][N/2] as uploaded
+    // the objective of every chunk (sots_batch_set_objective).  Under LOG_MAGNITUDE the segmented image is laid out from
+    // targets_ln = ln(targets + floor) and the queue's turnover reads q_targets_ln, both made on the device from the
+    // uploaded magnitudes (batch_derive / queue_derive) and allocated with the first log objective that needs them
+    Objective obj{};
+    float *targets_ln = nullptr;                                   // [C][N/2]
     float *seg_image = nullptr;                                    // segmented target image (sots_kernels.h)
     float *wavetable = nullptr, *window = nullptr, *x_image = nullptr;
     float2 *twiddle = nullptr;
@@ -53,6 +58,7 @@ struct sots_batch {
     uint32_t q_chunks = 0;           // chunks of the stored queue (0: none)
     bool q_ran = false, q_kept = false;
     float *q_targets = nullptr;      // [q_chunks][N/2]
+    float *q_targets_ln = nullptr;   // [q_chunks][N/2], log objective only
     float *q_results = nullptr;      // [q_chunks][kQueueResultFloats]
     float *q_kept_rows = nullptr;    // values [P][D], steps [P][D], fitness [P]
     uint32_t *q_state = nullptr;     // {head, retired, last retirement, 0} and the slot table [max_chunks][2] behind them
@@ -110,13 +116,13 @@ uint32_t batch_dims_of(uint32_t kind)
 
 void queue_release(sots_batch *b)
 {
-    void *bufs[] = {b->q_targets, b->q_results, b->q_kept_rows, b->q_state};
+    void *bufs[] = {b->q_targets, b->q_targets_ln, b->q_results, b->q_kept_rows, b->q_state};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (b->q_pinned) (void)hipHostFree(b->q_pinned);
     for (hipEvent_t &e : b->q_event)
         if (e) (void)hipEventDestroy(e), e = nullptr;
-    b->q_targets = b->q_results = b->q_kept_rows = nullptr;
+    b->q_targets = b->q_targets_ln = b->q_results = b->q_kept_rows = nullptr;
     b->q_state = b->q_pinned = nullptr;
     b->q_chunks = 0;
     b->q_ran = b->q_kept = false;
@@ -127,7 +133,7 @@ void free_batch(sots_batch *b)
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    void *bufs[] = {b->values, b->steps, b->fitness, b->audio, b->targets, b->seg_image,
+    void *bufs[] = {b->values, b->steps, b->fitness, b->audio, b->targets, b->targets_ln, b->seg_image,
                     b->wavetable, b->window, b->x_image, b->twiddle};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
@@ -143,6 +149,36 @@ int bind(const sots_batch *b)
     BATCH_HIP(b, hipSetDevice(b->device));
     return SOTS_OK;
 }
+
+bool log_objective(const sots_batch *b) { return b->obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE; }
+
+// the segmented target image of chunks 0 .. num_chunks-1 from b->targets under b->obj; every chunk's record starts over
+int batch_derive(sots_batch *b, uint32_t num_chunks)
+{
+    const float *src = b->targets;
+    if (log_objective(b)) {
+        const size_t m = b->N / 2;
+        if (!b->targets_ln) BATCH_HIP(b, hipMalloc((void **)&b->targets_ln, (size_t)b->max_chunks * m * sizeof(float)));
+        BATCH_HIP(b, launch_objective_map(b->stream, b->targets_ln, b->targets, (size_t)num_chunks * m, b->obj.floor));
+        src = b->targets_ln;
+    }
+    BATCH_HIP(b, launch_seg_targets(b->stream, b->seg_image, src, b->log2n, num_chunks));
+    BATCH_HIP(b, track_clear(b->track, b->stream));
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    return SOTS_OK;
+}
+
+// the stored queue targets as the turnover copies them into the image: the magnitudes, or their log image
+int queue_derive(sots_batch *b)
+{
+    if (b->q_chunks == 0 || !log_objective(b)) return SOTS_OK;
+    const size_t n = (size_t)b->q_chunks * (b->N / 2);
+    if (!b->q_targets_ln) BATCH_HIP(b, hipMalloc((void **)&b->q_targets_ln, n * sizeof(float)));
+    BATCH_HIP(b, launch_objective_map(b->stream, b->q_targets_ln, b->q_targets, n, b->obj.floor));
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    return SOTS_OK;
+}
+const float *queue_targets(const sots_batch *b) { return log_objective(b) ? b->q_targets_ln : b->q_targets; }
 
 int require_active(const sots_batch *b)
 {
@@ -296,9 +332,7 @@ int sots_batch_set_target_spectra(sots_batch *b, const float *magnitudes, uint32
         return bfail(b, SOTS_ERR_SIZE, "%u target spectra need %llu bins, got %u", num_chunks, (unsigned long long)need, num_bins);
     if (int rc = bind(b)) return rc;
     BATCH_HIP(b, hipMemcpyAsync(b->targets, magnitudes, need * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    BATCH_HIP(b, launch_seg_targets(b->stream, b->seg_image, b->targets, b->log2n, num_chunks));
-    BATCH_HIP(b, track_clear(b->track, b->stream)); // new targets: every chunk's record starts over
-    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    if (int rc = batch_derive(b, num_chunks)) return rc; // (new targets: every chunk's record starts over)
     b->active = num_chunks;
     return SOTS_OK;
 }
@@ -351,6 +385,24 @@ int sots_batch_set_survivors(sots_batch *b, uint32_t n)
     return SOTS_OK;
 }
 
+int sots_batch_set_objective(sots_batch *b, uint32_t objective, float floor)
+{
+    BATCH_REQUIRE(b);
+    if (objective != SOTS_OBJECTIVE_MAGNITUDE && objective != SOTS_OBJECTIVE_LOG_MAGNITUDE)
+        return bfail(b, SOTS_ERR_INVALID, "unknown objective %u (0 = magnitude, 1 = log magnitude)", objective);
+    if (objective == SOTS_OBJECTIVE_LOG_MAGNITUDE && !objective_floor_ok(floor))
+        return bfail(b, SOTS_ERR_INVALID, "log-magnitude floor %g outside 1e-30 .. 1", (double)floor);
+    if (int rc = bind(b)) return rc;
+    const Objective old = b->obj;
+    b->obj.kind = objective;
+    b->obj.floor = objective == SOTS_OBJECTIVE_LOG_MAGNITUDE ? floor : 0.0f;
+    if (b->obj.kind != old.kind) occ_forget(b->occ); // (other kernels, other occupancies)
+    int rc = b->active ? batch_derive(b, b->active) : SOTS_OK;
+    if (rc == SOTS_OK) rc = queue_derive(b);
+    if (rc != SOTS_OK) b->obj = old, b->active = 0; // (the image may be half made: the ordinary calls need their targets again)
+    return rc;
+}
+
 int sots_batch_execute_generations(sots_batch *b, uint32_t n)
 {
     BATCH_REQUIRE(b);
@@ -372,7 +424,7 @@ int sots_batch_execute_generations(sots_batch *b, uint32_t n)
                                       b->pitch, b->num_cus, nullptr, true));
         // window + FFT + fitness, every row against its chunk's target
         BATCH_HIP(b, launch_fft_fitness_seg(b->stream, b->audio, b->window, b->seg_image, b->fit(b->rot), b->twiddle, rows, b->log2n,
-                                            b->pitch, b->inv_n, b->inv_wf, b->num_cus, &b->occ));
+                                            b->pitch, b->inv_n, b->inv_wf, b->num_cus, &b->occ, b->obj));
         // sortPopulation of every chunk (whole population: P <= 1024), current half -> other half
         src = b->rot, dst = b->rot ^ 1u;
         BATCH_HIP(b, launch_sort_seg(b->stream, b->val(src), b->stp(src), b->fit(src), b->val(dst), b->stp(dst), b->fit(dst), b->P,
@@ -501,6 +553,10 @@ int sots_batch_queue_targets_spectra(sots_batch *b, const float *magnitudes, uin
     QUEUE_HIP(hipStreamSynchronize(b->stream));
 #undef QUEUE_HIP
     b->q_chunks = num_chunks;
+    if (int rc = queue_derive(b)) {
+        queue_release(b);
+        return rc;
+    }
     return SOTS_OK;
 }
 
@@ -561,7 +617,7 @@ int sots_batch_queue_run(sots_batch *b, uint32_t first_chunk_index, uint32_t max
     start[0] = slots;
     for (uint32_t c = 0; c < slots; ++c) start[4 + 2 * c] = c;
     BATCH_HIP(b, hipMemcpyAsync(b->q_state, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-    BATCH_HIP(b, launch_seg_targets(b->stream, b->seg_image, b->q_targets, b->log2n, slots));
+    BATCH_HIP(b, launch_seg_targets(b->stream, b->seg_image, queue_targets(b), b->log2n, slots));
     BATCH_HIP(b, track_clear(b->track, b->stream));
     b->rot = 0;
     b->generation = 0;
@@ -572,7 +628,7 @@ int sots_batch_queue_run(sots_batch *b, uint32_t first_chunk_index, uint32_t max
     q.state = b->q_state;
     q.slot_table = b->q_state + 4;
     q.results = b->q_results;
-    q.targets = b->q_targets;
+    q.targets = queue_targets(b);
     q.seg_image = b->seg_image;
     q.kept_values = b->q_kept_rows;
     q.kept_steps = b->q_kept_rows + (size_t)b->P * b->D;
@@ -609,7 +665,7 @@ int sots_batch_queue_run(sots_batch *b, uint32_t first_chunk_index, uint32_t max
                     BATCH_HIP(b, launch_synth(b->stream, b->cfg.synth_kind, b->val(b->rot), b->wavetable, b->audio, b->sp, rows, b->log2n,
                                               b->pitch, b->num_cus, nullptr, true));
                 BATCH_HIP(b, launch_fft_fitness_seg(b->stream, b->audio, b->window, b->seg_image, b->fit(b->rot), b->twiddle, rows, b->log2n,
-                                                    b->pitch, b->inv_n, b->inv_wf, b->num_cus, &b->occ));
+                                                    b->pitch, b->inv_n, b->inv_wf, b->num_cus, &b->occ, b->obj));
                 src = b->rot, dst = b->rot ^ 1u;
                 BATCH_HIP(b, launch_sort_seg(b->stream, b->val(src), b->stp(src), b->fit(src), b->val(dst), b->stp(dst), b->fit(dst), b->P,
                                              b->D, slots));

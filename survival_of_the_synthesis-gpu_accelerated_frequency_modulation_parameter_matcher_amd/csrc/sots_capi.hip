@@ -59,6 +59,11 @@ struct sots_ctx {
     uint32_t rows_capacity = 0;
     OccCache occ{};
     float *x_image = nullptr; // k_fft_x's tables (N >= 2048), rebuilt with every target
+    // the objective (sots_set_objective).  Under LOG_MAGNITUDE the spectral kernels read target_ln = ln(target + floor),
+    // made on the device from `target` (which stays the raw magnitudes) whenever the target or the objective changes;
+    // allocated with the first log objective
+    Objective obj{};
+    float *target_ln = nullptr;
     // selection state: after the fused loop's partial sort only rows [0, tail_first) of the current half
     // are in place; the unsorted half it came from is intact until the next generation starts
     uint32_t sort_mode = SOTS_SORT_LAZY_TAIL;
@@ -252,7 +257,7 @@ void free_ctx(sots_ctx *ctx)
         all.erase(std::unique(all.begin(), all.end()), all.end());
         for (hipEvent_t e : all) (void)hipEventDestroy(e);
     }
-    void *bufs[] = {ctx->values, ctx->steps, ctx->fitness, ctx->audio, ctx->spectrum, ctx->target,
+    void *bufs[] = {ctx->values, ctx->steps, ctx->fitness, ctx->audio, ctx->spectrum, ctx->target, ctx->target_ln,
                     ctx->wavetable, ctx->window, ctx->rows, ctx->twiddle, ctx->keys, ctx->sort_scratch, ctx->x_image, ctx->splitters,
                     ctx->sel_cnt, ctx->sel_lists};
     for (void *b : bufs)
@@ -399,6 +404,31 @@ int run_select(sots_ctx *ctx, uint32_t src, uint32_t dst, uint32_t need, const S
     }
     ctx->spl_cur ^= 1u;
     ctx->spl_valid = true;
+    return SOTS_OK;
+}
+
+// the bins the fitness kernels read: the magnitudes, or their image under the log objective
+const float *fitness_target(const sots_ctx *ctx)
+{
+    return ctx->obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE ? ctx->target_ln : ctx->target;
+}
+
+// What follows from ctx->target and ctx->obj: the log image, the long rows' tables in the layout the fused kernel reads
+// them in.  Also what a new target or objective makes stale: the run record, the stored splitters, the key lists.
+int derive_target(sots_ctx *ctx)
+{
+    if (ctx->obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE) {
+        if (!ctx->target_ln) SOTS_HIP(ctx, hipMalloc((void **)&ctx->target_ln, (size_t)(ctx->N / 2) * sizeof(float)));
+        SOTS_HIP(ctx, launch_objective_map(ctx->stream, ctx->target_ln, ctx->target, ctx->N / 2, ctx->obj.floor));
+    }
+    if (ctx->x_image) { // long rows: the fused spectral kernel's tables, in the layout it reads them in
+        SOTS_HIP(ctx, launch_x_tables(ctx->stream, ctx->x_image, ctx->twiddle, ctx->window, fitness_target(ctx), ctx->log2n));
+        ctx->occ.x_image = ctx->x_image;
+    }
+    SOTS_HIP(ctx, track_clear(ctx->track, ctx->stream)); // a new target: what was best against the old one says nothing
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->spl_valid = false; // the fitness landscape changes
+    ctx->lists_ready = false;
     return SOTS_OK;
 }
 
@@ -598,15 +628,8 @@ int sots_set_target_spectrum(sots_ctx *ctx, const float *magnitudes, uint32_t nu
         return fail(ctx, SOTS_ERR_SIZE, "target spectrum needs %u bins, got %u", ctx->N / 2, num_bins);
     if (int rc = bind_device(ctx)) return rc;
     SOTS_HIP(ctx, hipMemcpyAsync(ctx->target, magnitudes, (size_t)num_bins * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->x_image) { // long rows: the fused spectral kernel's tables, in the layout it reads them in
-        SOTS_HIP(ctx, launch_x_tables(ctx->stream, ctx->x_image, ctx->twiddle, ctx->window, ctx->target, ctx->log2n));
-        ctx->occ.x_image = ctx->x_image;
-    }
-    SOTS_HIP(ctx, track_clear(ctx->track, ctx->stream)); // a new target: what was best against the old one says nothing
-    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = derive_target(ctx)) return rc;
     ctx->target_set = true;
-    ctx->spl_valid = false; // the fitness landscape changes
-    ctx->lists_ready = false;
     return SOTS_OK;
 }
 
@@ -797,8 +820,8 @@ int sots_stage_fitness(sots_ctx *ctx)
     if (int rc = bind_device(ctx)) return rc;
     {
         StageScope t(ctx, SOTS_STAGE_FITNESS);
-        SOTS_HIP(ctx, launch_fitness(ctx->stream, ctx->spectrum, ctx->target, ctx->fit(ctx->rot), ctx->P, ctx->log2n,
-                                     ctx->inv_n, ctx->inv_wf, ctx->num_cus, &ctx->occ));
+        SOTS_HIP(ctx, launch_fitness(ctx->stream, ctx->spectrum, fitness_target(ctx), ctx->fit(ctx->rot), ctx->P, ctx->log2n,
+                                     ctx->inv_n, ctx->inv_wf, ctx->num_cus, &ctx->occ, ctx->obj));
     }
     return maybe_drain(ctx);
 }
@@ -945,8 +968,8 @@ int sots_execute_generations(sots_ctx *ctx, uint32_t n)
             SelLists sl;
             if (lists)
                 if (int rc = open_lists(ctx, &sl)) return rc;
-            SOTS_HIP(ctx, launch_fft_fitness(ctx->stream, ctx->audio, ctx->window, ctx->target, ctx->fit(ctx->rot), ctx->twiddle, ctx->P,
-                                             ctx->log2n, ctx->pitch, ctx->inv_n, ctx->inv_wf, ctx->num_cus, &ctx->occ, lists ? &sl : nullptr));
+            SOTS_HIP(ctx, launch_fft_fitness(ctx->stream, ctx->audio, ctx->window, fitness_target(ctx), ctx->fit(ctx->rot), ctx->twiddle, ctx->P,
+                                             ctx->log2n, ctx->pitch, ctx->inv_n, ctx->inv_wf, ctx->num_cus, &ctx->occ, lists ? &sl : nullptr, ctx->obj));
         }
         src = ctx->rot;
         dst = ctx->rot ^ 1u;
@@ -1128,6 +1151,36 @@ int sots_get_survivors(const sots_ctx *ctx, uint32_t *n)
     SOTS_REQUIRE_CTX(ctx);
     if (!n) return fail(ctx, SOTS_ERR_INVALID, "null survivors pointer");
     *n = ctx->pd.survivors;
+    return SOTS_OK;
+}
+
+// Like a new target (derive_target): same population, another landscape.  A pending lazy tail is an order under the OLD
+// fitness values, which stay in place until the next evaluation: it is kept, as sots_set_target_* keeps it.
+int sots_set_objective(sots_ctx *ctx, uint32_t objective, float floor)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (objective != SOTS_OBJECTIVE_MAGNITUDE && objective != SOTS_OBJECTIVE_LOG_MAGNITUDE)
+        return fail(ctx, SOTS_ERR_INVALID, "unknown objective %u (0 = magnitude, 1 = log magnitude)", objective);
+    if (objective == SOTS_OBJECTIVE_LOG_MAGNITUDE && !objective_floor_ok(floor))
+        return fail(ctx, SOTS_ERR_INVALID, "log-magnitude floor %g outside 1e-30 .. 1", (double)floor);
+    if (int rc = bind_device(ctx)) return rc;
+    const Objective old = ctx->obj;
+    ctx->obj.kind = objective;
+    ctx->obj.floor = objective == SOTS_OBJECTIVE_LOG_MAGNITUDE ? floor : 0.0f;
+    if (ctx->obj.kind != old.kind) occ_forget(ctx->occ); // (other kernels, other occupancies)
+    if (int rc = derive_target(ctx)) {
+        ctx->obj = old;
+        return rc;
+    }
+    return SOTS_OK;
+}
+
+int sots_get_objective(const sots_ctx *ctx, uint32_t *objective, float *floor)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (!objective && !floor) return fail(ctx, SOTS_ERR_INVALID, "null objective and floor pointers");
+    if (objective) *objective = ctx->obj.kind;
+    if (floor) *floor = ctx->obj.floor;
     return SOTS_OK;
 }
 

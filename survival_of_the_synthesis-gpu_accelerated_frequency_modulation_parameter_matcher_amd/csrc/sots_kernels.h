@@ -77,6 +77,26 @@ struct OccCache {
     const float *x_image;
 };
 
+// The objective of a spectral launch (sots_set_objective): SOTS_OBJECTIVE_MAGNITUDE, the reference's squared distance of
+// the magnitudes, or SOTS_OBJECTIVE_LOG_MAGNITUDE, sum (ln(m + floor) - ln(t + floor))^2.  Under the log objective every
+// target the launchers below are given - plain bins, table image, segmented image - holds ln(t + floor) instead of t:
+// launch_objective_map makes the plain bins, the layouts are copied from them as they are from magnitudes.
+struct Objective {
+    uint32_t kind = SOTS_OBJECTIVE_MAGNITUDE;
+    float floor = 0.0f;
+};
+// 1e-30 <= floor <= 1: m + floor is then a normal fp32 number for every magnitude m >= 0
+inline bool objective_floor_ok(float floor) { return floor >= 1e-30f && floor <= 1.0f; } // (false for NaN)
+// dst[i] = ln(src[i] + floor) with the device routine the fitness epilogues apply to the candidate's bins
+hipError_t launch_objective_map(hipStream_t st, float *dst, const float *src, size_t n, float floor);
+// the cached occupancies belong to the kernels of one objective: forgotten when it changes (the image pointer stays)
+inline void occ_forget(OccCache &oc)
+{
+    const float *image = oc.x_image;
+    oc = OccCache{};
+    oc.x_image = image;
+}
+
 // ---- variation ----
 hipError_t launch_init_population(hipStream_t st, float *values, float *steps, float *fitness,
                                   const PopDims &pd, uint32_t chunk);
@@ -110,7 +130,8 @@ hipError_t launch_fft(hipStream_t st, const float *audio, float *spectrum, const
                       uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus, OccCache *occ);
 // spectrum[P][N+8] x target[N/2] -> fitness[P]
 hipError_t launch_fitness(hipStream_t st, const float *spectrum, const float *target, float *fitness,
-                          uint32_t p, uint32_t log2n, float inv_n, float inv_wf, uint32_t num_cus, OccCache *occ);
+                          uint32_t p, uint32_t log2n, float inv_n, float inv_wf, uint32_t num_cus, OccCache *occ,
+                          const Objective &obj = Objective{});
 // audio[P][pitch] (x window when window != nullptr) x target -> fitness[P]; no spectrum in memory
 size_t x_table_bytes(uint32_t log2n);
 hipError_t launch_x_tables(hipStream_t st, float *image, const float2 *twiddle, const float *window, const float *target, uint32_t log2n);
@@ -139,7 +160,8 @@ hipError_t launch_bucket_fitness(hipStream_t st, const float *fitness, uint32_t 
 // lists: also file the keys (only where select_lists_apply(); elsewhere hipErrorInvalidValue)
 hipError_t launch_fft_fitness(hipStream_t st, const float *audio, const float *window, const float *target,
                               float *fitness, const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch,
-                              float inv_n, float inv_wf, uint32_t num_cus, OccCache *occ, const SelLists *lists = nullptr);
+                              float inv_n, float inv_wf, uint32_t num_cus, OccCache *occ, const SelLists *lists = nullptr,
+                              const Objective &obj = Objective{});
 
 // Island exchange folded into sortPopulation (one generation of the fused loop, set through
 // sots_fuse_exchange_next_sort): the kernel that moves the sorted rows also
@@ -209,7 +231,7 @@ hipError_t launch_seg_targets(hipStream_t st, float *image, const float *targets
 // launch_fft_fitness (window applied) over rows of consecutive chunks, each row against its chunk's target
 hipError_t launch_fft_fitness_seg(hipStream_t st, const float *audio, const float *window, const float *seg_image, float *fitness,
                                   const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
-                                  uint32_t num_cus, OccCache *occ);
+                                  uint32_t num_cus, OccCache *occ, const Objective &obj = Objective{});
 // the whole-population sort of each chunk (P <= 1024: k_sort_small, a workgroup per chunk)
 hipError_t launch_sort_seg(hipStream_t st, const float *vin, const float *sin, const float *fin, float *vout, float *sout,
                            float *fout, uint32_t p, uint32_t d, uint32_t chunks);

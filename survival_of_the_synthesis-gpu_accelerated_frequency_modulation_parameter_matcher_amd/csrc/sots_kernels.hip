@@ -1753,6 +1753,60 @@ __device__ __forceinline__ void bin_error2(v2f_t &acc2, float2 xa, float2 xb, fl
     acc2 = acc2 + e * e;
 }
 
+// ---- the selectable objective (sots_set_objective) ----
+// OBJ is a template parameter of every kernel that turns bins into fitness.  kObjMagnitude is the reference's sum above,
+// and its instantiations are the kernels as they were: no extra argument, no extra instruction.  kObjLogMagnitude:
+// sum_k (ln(m_k + floor) - ln(t_k + floor))^2 with m_k = |X_k| scale.  The kernels read a target table that already holds
+// ln(t_k + floor), in whatever layout they read the magnitudes in (k_objective_map below made it with obj_ln_floor, the
+// routine of the epilogues: a bin whose magnitude equals the target's contributes exactly 0, and nobody's log but
+// v_log_f32's is involved).  The floor is one more kernel argument of the log instantiations only, behind all others.
+constexpr int kObjMagnitude = SOTS_OBJECTIVE_MAGNITUDE, kObjLogMagnitude = SOTS_OBJECTIVE_LOG_MAGNITUDE;
+#pragma clang fp contract(off) // (m + floor and log2 x ln 2 round one by one, here and in the table's kernel)
+// ln(m + floor): v_log_f32 (log2, 1 ulp) times ln 2.  m >= 0 and 1e-30 <= floor <= 1 keep the argument a normal number,
+// which is all that instruction handles; NaN and +inf pass through.
+__device__ __forceinline__ float obj_ln_floor(float m, float floor)
+{
+    return __builtin_amdgcn_logf(m + floor) * 0.693147180559945f;
+}
+__device__ __forceinline__ float bin_error_log(float raw, float target_ln, float scale, float floor)
+{
+    const float e = obj_ln_floor(raw * scale, floor) - target_ln;
+    return e * e;
+}
+// (the packed form, as bin_error2: scale, floor, ln 2, the subtraction and the squared accumulation are packed; lane by
+// lane the operations and their order are obj_ln_floor's)
+__device__ __forceinline__ void bin_error2_log(v2f_t &acc2, v2f_t raw, float ta, float tb, float scale, float floor)
+{
+    const v2f_t a = raw * v2f_t{scale, scale} + v2f_t{floor, floor};
+    const v2f_t l = v2f_t{__builtin_amdgcn_logf(a.x), __builtin_amdgcn_logf(a.y)} * v2f_t{0.693147180559945f, 0.693147180559945f};
+    const v2f_t e = l - v2f_t{ta, tb};
+    acc2 = acc2 + e * e;
+}
+#pragma clang fp contract(on)
+template <int OBJ>
+__device__ __forceinline__ float bin_error_o(float2 x, float target, float scale, [[maybe_unused]] float floor)
+{
+    if constexpr (OBJ == kObjLogMagnitude) return bin_error_log(__builtin_amdgcn_sqrtf(x.x * x.x + x.y * x.y), target, scale, floor);
+    else return bin_error(x, target, scale);
+}
+template <int OBJ>
+__device__ __forceinline__ void bin_error2_o(v2f_t &acc2, float2 xa, float2 xb, float ta, float tb, float scale, [[maybe_unused]] float floor)
+{
+    if constexpr (OBJ == kObjLogMagnitude)
+        bin_error2_log(acc2, v2f_t{__builtin_amdgcn_sqrtf(xa.x * xa.x + xa.y * xa.y), __builtin_amdgcn_sqrtf(xb.x * xb.x + xb.y * xb.y)}, ta, tb, scale, floor);
+    else bin_error2(acc2, xa, xb, ta, tb, scale);
+}
+// the floor out of a kernel's trailing arguments: (), (lists) - magnitude - or (floor), (lists, floor)
+__device__ __forceinline__ float obj_floor() { return 0.0f; }
+__device__ __forceinline__ float obj_floor(float floor) { return floor; }
+__device__ __forceinline__ float obj_floor(const SelLists &) { return 0.0f; }
+__device__ __forceinline__ float obj_floor(const SelLists &, float floor) { return floor; }
+// target[i] -> ln(target[i] + floor): the derived table of the log objective, plain bins (every other layout is copied from it)
+__global__ __launch_bounds__(256) void k_objective_map(float *__restrict__ dst, const float *__restrict__ src, size_t n, float floor)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = obj_ln_floor(src[i], floor);
+}
+
 // Wavefront sum without LDS traffic: DPP swaps inside each row of 16 lanes (every lane of a
 // row ends with the row total), then the four row totals are added in row order.
 template <int CTRL>
@@ -1913,18 +1967,23 @@ template <int LOG2N> constexpr int fft_wide_waves() { return LOG2N == 10 ? 12 : 
 // argument list, and with it their code, to the byte (an argument in front of the hidden ones moves those).
 struct BktNoLists {};
 __device__ __forceinline__ BktNoLists bkt_lists() { return {}; }
+__device__ __forceinline__ BktNoLists bkt_lists(float) { return {}; }
 __device__ __forceinline__ const SelLists &bkt_lists(const SelLists &l) { return l; }
+__device__ __forceinline__ const SelLists &bkt_lists(const SelLists &l, float) { return l; }
 // BUCKET (the wide fitness kernel in front of a one-launch selection, list mode): every row's key goes into the list of
 // its bucket between the splitters of bk.slot (bkt_visit above) - the slot was written a generation ago, the row's
 // fitness is in a register here, and the selection's 256 workgroups no longer ask all P rows each.
-template <int LOG2N, int MODE, bool WIN, int W = 1, bool SEG = false, bool BUCKET = false, typename... LISTS>
+// OBJ (MODE 1): the objective; the log instantiations take the floor as their last argument (bin_error_o above)
+template <int LOG2N, int MODE, bool WIN, int W = 1, bool SEG = false, bool BUCKET = false, int OBJ = kObjMagnitude, typename... LISTS>
 __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audio, float *__restrict__ spectrum,
                                                    const float *__restrict__ target, float *__restrict__ fitness,
                                                    const float2 *__restrict__ tw, const float *__restrict__ window,
                                                    uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch, LISTS... lists)
 {
-    static_assert(sizeof...(LISTS) == (BUCKET ? 1 : 0), "the BUCKET instantiation takes the lists, the others nothing");
+    static_assert(sizeof...(LISTS) == (BUCKET ? 1 : 0) + (OBJ == kObjLogMagnitude ? 1 : 0), "the BUCKET instantiation takes the lists, the log ones the floor, the others nothing");
+    static_assert(OBJ == kObjMagnitude || MODE == 1, "the objective belongs to the fitness epilogue");
     [[maybe_unused]] const auto bk = bkt_lists(lists...);
+    [[maybe_unused]] const float floor_eps = obj_floor(lists...);
     constexpr int N = 1 << LOG2N, M = N / 2, E = M / kWave, H = E / 2;
     static_assert(LOG2N == 9 || LOG2N == 10, "wavefront-per-row FFT is for N <= 1024");
     static_assert(!BUCKET || (MODE == 1 && W > 1 && !SEG), "keys are filed by the wide fitness kernel only");
@@ -2054,8 +2113,8 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
                 v2f_t xa2, xbc2;
                 split_pair_2x(z[q], split_partner<M>(z, q, lane, partner_addr), w_split[q], xa2, xbc2); // 2 X[k], 2 conj X[M-k]
                 if (k == 0) xbc2 = v2f_t{2.0f * x_half.x, 2.0f * x_half.y}; // the fitness skips the Nyquist bin and needs bin M/2
-                if constexpr (SEG) bin_error2(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tg[k], tg[k == 0 ? M / 2 : M - k], half_scale);
-                else bin_error2(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tgt_s[k], tgt_s[k == 0 ? M / 2 : M - k], half_scale);
+                if constexpr (SEG) bin_error2_o<OBJ>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tg[k], tg[k == 0 ? M / 2 : M - k], half_scale, floor_eps);
+                else bin_error2_o<OBJ>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tgt_s[k], tgt_s[k == 0 ? M / 2 : M - k], half_scale, floor_eps);
             }
             float acc = wave_sum(acc2.x + acc2.y);
             if (lane == 0) fitness[ind] = acc;
@@ -2108,12 +2167,14 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
 
 // fitnessPopulation on materialised spectrum rows; same bin -> lane assignment and
 // summation order as k_fft<.., 1>, so both paths give the same fp32 sum.
-template <int LOG2N>
+template <int LOG2N, int OBJ = kObjMagnitude, typename... FLOOR>
 __global__ __launch_bounds__(kWave) void k_fitness(const float *__restrict__ spectrum,
                                                    const float *__restrict__ target,
                                                    float *__restrict__ fitness, uint32_t p_len, float inv_n,
-                                                   float inv_wf)
+                                                   float inv_wf, FLOOR... floor)
 {
+    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0), "the log instantiation takes the floor");
+    [[maybe_unused]] const float floor_eps = obj_floor(floor...);
     constexpr int N = 1 << LOG2N, M = N / 2, E = M / kWave;
     const int lane = threadIdx.x;
     for (uint32_t ind = blockIdx.x; ind < p_len; ind += gridDim.x) {
@@ -2123,7 +2184,7 @@ __global__ __launch_bounds__(kWave) void k_fitness(const float *__restrict__ spe
         for (int q = 0; q < E / 2; ++q) {
             const int k = lane + kWave * q;
             const int kb = k == 0 ? M / 2 : M - k;
-            bin_error2(acc2, row[k], row[kb], target[k], target[kb], inv_n * inv_wf);
+            bin_error2_o<OBJ>(acc2, row[k], row[kb], target[k], target[kb], inv_n * inv_wf, floor_eps);
         }
         float acc = wave_sum(acc2.x + acc2.y);
         if (lane == 0) fitness[ind] = acc;
@@ -3648,13 +3709,15 @@ template <int LOG2N> constexpr int x_table_floats() { return 3 * 2 * kWave * (x_
 // floats of one chunk's target table in a segmented target image (SEG): the tgt_s part of the LDS tables, same layout
 template <int LOG2N> constexpr uint32_t x_seg_stride() { return kWave * (x_points<LOG2N>() + 4); }
 // SEG: as k_fft's - every row reads its chunk's target entries (lane, register) from the segmented image in global memory
-template <int LOG2N, int MODE, bool WIN, int WG = x_waves<LOG2N, MODE>(), bool SEG = false>
+template <int LOG2N, int MODE, bool WIN, int WG = x_waves<LOG2N, MODE>(), bool SEG = false, int OBJ = kObjMagnitude, typename... FLOOR>
 __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MIN_WAVES : 1)) void k_fft_x(const float *__restrict__ audio, float *__restrict__ spectrum,
                                                                    const float *__restrict__ target, float *__restrict__ fitness,
                                                                    const float2 *__restrict__ tw, const float *__restrict__ window,
                                                                    uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch,
-                                                                   const float *__restrict__ image)
+                                                                   const float *__restrict__ image, FLOOR... floor)
 {
+    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) && (OBJ == kObjMagnitude || MODE == 1), "the log instantiation (fitness epilogue only) takes the floor");
+    [[maybe_unused]] const float floor_eps = obj_floor(floor...);
     constexpr int N = 1 << LOG2N, M = N / 2, E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), W = WG;
     constexpr int S2 = E + 2, S1 = E + 4; // lane strides of the float2 / float tables (16-byte reads, spread over the banks)
     __shared__ __attribute__((aligned(16))) float xt_s[x_table_floats<LOG2N>()]; // (the variants without window or target leave theirs unused)
@@ -3829,18 +3892,18 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
                     if constexpr (R2 != RR) {
                         v2f_t xa, xb;
                         pair2x(ic<RR>{}, xa, xb);
-                        acc += bin_error(make_float2(xa.x, xa.y), tgt_at(RR), half_scale);
-                        acc += bin_error(make_float2(xb.x, xb.y), tgt_at(R2), half_scale); // the partner lane's bin M - k: x_target_bin
+                        acc += bin_error_o<OBJ>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps);
+                        acc += bin_error_o<OBJ>(make_float2(xb.x, xb.y), tgt_at(R2), half_scale, floor_eps); // the partner lane's bin M - k: x_target_bin
                     } else {
                         const v2f_t xa = bin2x(ic<RR>{});
-                        acc += bin_error(make_float2(xa.x, xa.y), tgt_at(RR), half_scale);
+                        acc += bin_error_o<OBJ>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps);
                     }
 #else
                     const v2f_t xa = bin2x(ic<RR>{});
-                    acc += bin_error(make_float2(xa.x, xa.y), tgt_at(RR), half_scale);
+                    acc += bin_error_o<OBJ>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps);
                     if constexpr (R2 != RR) {
                         const v2f_t xb = bin2x(ic<R2>{});
-                        acc += bin_error(make_float2(xb.x, xb.y), tgt_at(R2), half_scale);
+                        acc += bin_error_o<OBJ>(make_float2(xb.x, xb.y), tgt_at(R2), half_scale, floor_eps);
                     }
 #endif
 #ifndef SOTS_X_RECYCLE
@@ -3895,7 +3958,7 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
                 if constexpr (Q % 2 == 0) out_even = x2 * v2f_t{0.5f, 0.5f};
                 else *reinterpret_cast<float4 *>(dst + Q - 1) = make_float4(out_even.x, out_even.y, 0.5f * x2.x, 0.5f * x2.y);
             } else {
-                acc += bin_error(make_float2(x2.x, x2.y), tgt_s[lane * S1 + RR], half_scale);
+                acc += bin_error_o<OBJ>(make_float2(x2.x, x2.y), tgt_s[lane * S1 + RR], half_scale, floor_eps);
             }
             if constexpr (I % 4 == 3) __builtin_amdgcn_sched_barrier(0);
         });
@@ -3950,12 +4013,14 @@ __device__ __forceinline__ float big_block_sum(float acc, float *__restrict__ re
 }
 
 // SEG: `target` is a segmented target image (k_fft's); row r takes its chunk's bins
-template <int LOG2N, int MODE, bool WIN, bool SEG = false>
+template <int LOG2N, int MODE, bool WIN, bool SEG = false, int OBJ = kObjMagnitude, typename... FLOOR>
 __global__ __launch_bounds__(kBigThreads) void k_fft_big(const float *__restrict__ audio, float *__restrict__ spectrum,
                                                          const float *__restrict__ target, float *__restrict__ fitness,
                                                          const float2 *__restrict__ tw, const float *__restrict__ window,
-                                                         uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch)
+                                                         uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch, FLOOR... floor)
 {
+    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) && (OBJ == kObjMagnitude || MODE == 1), "the log instantiation (fitness epilogue only) takes the floor");
+    [[maybe_unused]] const float floor_eps = obj_floor(floor...);
     constexpr uint32_t N = 1u << LOG2N, M = N / 2, LM = LOG2N - 1, T = kBigThreads;
     extern __shared__ float2 big_z[]; // M complex points (the launch asks for M * 8 + 64 bytes)
     float *__restrict__ red = reinterpret_cast<float *>(big_z + M);
@@ -3999,7 +4064,7 @@ __global__ __launch_bounds__(kBigThreads) void k_fft_big(const float *__restrict
         } else {
             float acc = 0.0f;
             const float *__restrict__ tg = SEG ? seg_target_chunk(target, row / seg_target_rows(target), M) : target;
-            for (uint32_t k = t; k < M; k += T) acc += bin_error(bin(k), tg[k], inv_n * inv_wf);
+            for (uint32_t k = t; k < M; k += T) acc += bin_error_o<OBJ>(bin(k), tg[k], inv_n * inv_wf, floor_eps);
             const float total = big_block_sum(acc, red);
             if (t == 0) fitness[row] = total;
         }
@@ -4007,16 +4072,18 @@ __global__ __launch_bounds__(kBigThreads) void k_fft_big(const float *__restrict
     }
 }
 
-template <int LOG2N>
+template <int LOG2N, int OBJ = kObjMagnitude, typename... FLOOR>
 __global__ __launch_bounds__(kBigThreads) void k_fitness_big(const float *__restrict__ spectrum, const float *__restrict__ target,
-                                                             float *__restrict__ fitness, uint32_t p_len, float inv_n, float inv_wf)
+                                                             float *__restrict__ fitness, uint32_t p_len, float inv_n, float inv_wf, FLOOR... floor)
 {
+    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0), "the log instantiation takes the floor");
+    [[maybe_unused]] const float floor_eps = obj_floor(floor...);
     constexpr uint32_t N = 1u << LOG2N, M = N / 2, T = kBigThreads;
     __shared__ float red[kBigThreads / kWave];
     for (uint32_t row = blockIdx.x; row < p_len; row += gridDim.x) {
         const float2 *__restrict__ src = reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8));
         float acc = 0.0f;
-        for (uint32_t k = threadIdx.x; k < M; k += T) acc += bin_error(src[k], target[k], inv_n * inv_wf);
+        for (uint32_t k = threadIdx.x; k < M; k += T) acc += bin_error_o<OBJ>(src[k], target[k], inv_n * inv_wf, floor_eps);
         const float total = big_block_sum(acc, red);
         if (threadIdx.x == 0) fitness[row] = total;
         __syncthreads();
@@ -4024,10 +4091,12 @@ __global__ __launch_bounds__(kBigThreads) void k_fitness_big(const float *__rest
 }
 
 // fitnessPopulation on materialised rows with k_fft_x's bin -> (lane, register) map and summation order
-template <int LOG2N>
+template <int LOG2N, int OBJ = kObjMagnitude, typename... FLOOR>
 __global__ __launch_bounds__(x_waves<LOG2N>() * kWave) void k_fitness_x(const float *__restrict__ spectrum, const float *__restrict__ target,
-                                                                       float *__restrict__ fitness, uint32_t p_len, float inv_n, float inv_wf)
+                                                                       float *__restrict__ fitness, uint32_t p_len, float inv_n, float inv_wf, FLOOR... floor)
 {
+    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0), "the log instantiation takes the floor");
+    [[maybe_unused]] const float floor_eps = obj_floor(floor...);
     constexpr int N = 1 << LOG2N, E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), W = x_waves<LOG2N>();
     const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const uint32_t pp = __brev(lane) >> 26;
@@ -4037,13 +4106,13 @@ __global__ __launch_bounds__(x_waves<LOG2N>() * kWave) void k_fitness_x(const fl
         static_for<0, E>([&](auto r_tag) { // k_fft_x's order: register pairs (RR, R2 = bitrev(E - bitrev(RR)))
             constexpr int RR = decltype(r_tag)::value, Q = x_bitrev(RR, EB), R2 = Q == 0 ? 0 : x_bitrev(E - Q, EB);
             if constexpr (R2 >= RR) {
-                acc += bin_error(src[Q], target[E * pp + Q], inv_n * inv_wf);
+                acc += bin_error_o<OBJ>(src[Q], target[E * pp + Q], inv_n * inv_wf, floor_eps);
 #if SOTS_X_PAIR_SPLIT
                 // the pair's second bin is the PARTNER lane's: M - k (k_fft_x's pair2x)
                 if constexpr (R2 != RR)
-                    acc += bin_error(reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8))[N / 2 - (E * pp + Q)], target[N / 2 - (E * pp + Q)], inv_n * inv_wf);
+                    acc += bin_error_o<OBJ>(reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8))[N / 2 - (E * pp + Q)], target[N / 2 - (E * pp + Q)], inv_n * inv_wf, floor_eps);
 #else
-                if constexpr (R2 != RR) acc += bin_error(src[x_bitrev(R2, EB)], target[E * pp + x_bitrev(R2, EB)], inv_n * inv_wf);
+                if constexpr (R2 != RR) acc += bin_error_o<OBJ>(src[x_bitrev(R2, EB)], target[E * pp + x_bitrev(R2, EB)], inv_n * inv_wf, floor_eps);
 #endif
             }
         });
@@ -4474,23 +4543,23 @@ static bool x_from(uint32_t log2n) { return log2n == 8 || (log2n >= SOTS_X_MIN &
     }
 static bool big_from(uint32_t log2n) { return log2n == 14 || log2n == 15; }
 // a workgroup per row: as many workgroups as rows, at most four per CU (they loop)
-template <int L, int MODE, bool WIN, bool SEG = false>
+template <int L, int MODE, bool WIN, bool SEG = false, int OBJ = kObjMagnitude, typename... FL>
 static hipError_t launch_fft_big(hipStream_t st, uint32_t p, uint32_t num_cus, const float *audio, float *spectrum, const float *target,
-                                 float *fitness, const float2 *tw, const float *window, float inv_n, float inv_wf, uint32_t pitch)
+                                 float *fitness, const float2 *tw, const float *window, float inv_n, float inv_wf, uint32_t pitch, FL... fl)
 {
     const uint32_t cus = num_cus ? num_cus : 256u, grid = p < 4u * cus ? p : 4u * cus;
     const size_t lds = ((size_t)(1u << L) / 2u) * sizeof(float2) + 64u;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_big<L, MODE, WIN, SEG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_big<L, MODE, WIN, SEG, OBJ, FL...>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    k_fft_big<L, MODE, WIN, SEG><<<grid, kBigThreads, lds, st>>>(audio, spectrum, target, fitness, tw, window, p, inv_n, inv_wf, pitch);
+    k_fft_big<L, MODE, WIN, SEG, OBJ, FL...><<<grid, kBigThreads, lds, st>>>(audio, spectrum, target, fitness, tw, window, p, inv_n, inv_wf, pitch, fl...);
     return hipGetLastError();
 }
-template <int L>
+template <int L, int OBJ = kObjMagnitude, typename... FL>
 static hipError_t launch_fitness_big(hipStream_t st, uint32_t p, uint32_t num_cus, const float *spectrum, const float *target, float *fitness,
-                                     float inv_n, float inv_wf)
+                                     float inv_n, float inv_wf, FL... fl)
 {
     const uint32_t cus = num_cus ? num_cus : 256u, grid = p < 4u * cus ? p : 4u * cus;
-    k_fitness_big<L><<<grid, kBigThreads, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf);
+    k_fitness_big<L, OBJ, FL...><<<grid, kBigThreads, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...);
     return hipGetLastError();
 }
 #define SOTS_X_GRID(K, L, MODE) resident_grid(K, x_waves<L, MODE>() * kWave, (p + x_waves<L, MODE>() - 1) / x_waves<L, MODE>(), num_cus, &occ_x[L])
@@ -4536,24 +4605,43 @@ hipError_t launch_fft(hipStream_t st, const float *audio, float *spectrum, const
     return hipGetLastError();
 }
 
-hipError_t launch_fitness(hipStream_t st, const float *spectrum, const float *target, float *fitness,
-                          uint32_t p, uint32_t log2n, float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc)
+// OBJ, FL: the objective and, for the log one, its floor (the kernels' last argument); the magnitude instantiations are
+// launched exactly as before
+template <int OBJ, typename... FL>
+static hipError_t launch_fitness_o(hipStream_t st, const float *spectrum, const float *target, float *fitness,
+                                   uint32_t p, uint32_t log2n, float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, FL... fl)
 {
     int *occ = oc->fitness;
     if (big_from(log2n)) {
-        if (log2n == 14) return launch_fitness_big<14>(st, p, num_cus, spectrum, target, fitness, inv_n, inv_wf);
-        return launch_fitness_big<15>(st, p, num_cus, spectrum, target, fitness, inv_n, inv_wf);
+        if (log2n == 14) return launch_fitness_big<14, OBJ, FL...>(st, p, num_cus, spectrum, target, fitness, inv_n, inv_wf, fl...);
+        return launch_fitness_big<15, OBJ, FL...>(st, p, num_cus, spectrum, target, fitness, inv_n, inv_wf, fl...);
     }
     if (x_from(log2n)) {
         int *occ_x = oc->x_fitness;
-#define CALL(L) k_fitness_x<L><<<SOTS_X_GRID(k_fitness_x<L>, L, 1), x_waves<L>() * kWave, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf)
+#define CALL(L) k_fitness_x<L, OBJ, FL...><<<SOTS_X_GRID((k_fitness_x<L, OBJ, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...)
         SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
         return hipGetLastError();
     }
-#define CALL(L) k_fitness<L><<<resident_grid(k_fitness<L>, kWave, p, num_cus, &occ[L]), kWave, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf)
+#define CALL(L) k_fitness<L, OBJ, FL...><<<resident_grid(k_fitness<L, OBJ, FL...>, kWave, p, num_cus, &occ[L]), kWave, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...)
     SOTS_DISPATCH_WAVE(log2n, CALL)
 #undef CALL
+    return hipGetLastError();
+}
+
+hipError_t launch_fitness(hipStream_t st, const float *spectrum, const float *target, float *fitness,
+                          uint32_t p, uint32_t log2n, float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, const Objective &obj)
+{
+    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE)
+        return launch_fitness_o<kObjLogMagnitude>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc, obj.floor);
+    if (obj.kind != SOTS_OBJECTIVE_MAGNITUDE) return hipErrorInvalidValue;
+    return launch_fitness_o<kObjMagnitude>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc);
+}
+
+hipError_t launch_objective_map(hipStream_t st, float *dst, const float *src, size_t n, float floor)
+{
+    if (n == 0) return hipSuccess;
+    k_objective_map<<<grid_for(n, 256, 8192), 256, 0, st>>>(dst, src, n, floor);
     return hipGetLastError();
 }
 
@@ -4579,25 +4667,31 @@ hipError_t launch_x_tables(hipStream_t st, float *image, const float2 *twiddle, 
     return hipGetLastError();
 }
 
-hipError_t launch_fft_fitness(hipStream_t st, const float *audio, const float *window, const float *target,
-                              float *fitness, const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch,
-                              float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, const SelLists *lists)
+template <int OBJ, typename... FL>
+static hipError_t launch_fft_fitness_o(hipStream_t st, const float *audio, const float *window, const float *target,
+                                       float *fitness, const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch,
+                                       float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, const SelLists *lists, FL... fl)
 {
-    int *occ_w = oc->fused_win, *occ_n = oc->fused_raw;
+    // The forms without a window exist for the magnitude objective only (the library itself always passes its window; the
+    // log N = 4096 form without one would not fit its 128 registers): elsewhere a missing window is an error, not another kernel
+    constexpr bool RAW = OBJ == kObjMagnitude;
+    if (!RAW && !window) return hipErrorInvalidValue;
+    int *occ_w = oc->fused_win;
+    [[maybe_unused]] int *occ_n = oc->fused_raw;
     if (lists) { // the bucketing instantiation, or nothing: a caller that counts on the lists must not get a launch without them
         if (!window || !select_lists_apply(p, log2n, num_cus) || lists->buckets != select_splitter_count(num_cus) || !lists->slot || !lists->cnt || !lists->lists)
             return hipErrorInvalidValue;
         constexpr int W = fft_wide_waves<10>();
-        k_fft<10, 1, true, W, false, true, SelLists><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, false, true, SelLists>), 3), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, *lists);
+        k_fft<10, 1, true, W, false, true, OBJ, SelLists, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, false, true, OBJ, SelLists, FL...>), 3), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, *lists, fl...);
         return hipGetLastError();
     }
     if (big_from(log2n)) {
         if (log2n == 14) {
-            if (window) return launch_fft_big<14, 1, true>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch);
-            return launch_fft_big<14, 1, false>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, nullptr, inv_n, inv_wf, pitch);
+            if (window) return launch_fft_big<14, 1, true, false, OBJ, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
+            if constexpr (RAW) return launch_fft_big<14, 1, false, false, OBJ, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, nullptr, inv_n, inv_wf, pitch, fl...);
         }
-        if (window) return launch_fft_big<15, 1, true>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch);
-        return launch_fft_big<15, 1, false>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, nullptr, inv_n, inv_wf, pitch);
+        if (window) return launch_fft_big<15, 1, true, false, OBJ, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
+        if constexpr (RAW) return launch_fft_big<15, 1, false, false, OBJ, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, nullptr, inv_n, inv_wf, pitch, fl...);
     }
     if (x_from(log2n)) {
         if (window) {
@@ -4606,17 +4700,17 @@ hipError_t launch_fft_fitness(hipStream_t st, const float *audio, const float *w
             // N = 4096 and 2048, where x_waves is 16; N = 8192 (x_waves 8) follows it unmeasured
             if ((p + x_waves<12>() - 1) / x_waves<12>() < (num_cus ? num_cus : 256u)) {
                 int *occ_s = oc->x_small;
-#define CALL(L) k_fft_x<L, 1, true, 4><<<resident_grid((k_fft_x<L, 1, true, 4>), 4 * kWave, (p + 3) / 4, num_cus, &occ_s[L]), 4 * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image)
+#define CALL(L) k_fft_x<L, 1, true, 4, false, OBJ, FL...><<<resident_grid((k_fft_x<L, 1, true, 4, false, OBJ, FL...>), 4 * kWave, (p + 3) / 4, num_cus, &occ_s[L]), 4 * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
                 SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
                 return hipGetLastError();
             }
-#define CALL(L) k_fft_x<L, 1, true><<<SOTS_X_GRID((k_fft_x<L, 1, true>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image)
+#define CALL(L) k_fft_x<L, 1, true, x_waves<L>(), false, OBJ, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, true, x_waves<L>(), false, OBJ, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
             SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
-        } else {
+        } else if constexpr (RAW) {
             int *occ_x = oc->x_fused_raw;
-#define CALL(L) k_fft_x<L, 1, false><<<SOTS_X_GRID((k_fft_x<L, 1, false>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, nullptr)
+#define CALL(L) k_fft_x<L, 1, false, x_waves<L>(), false, OBJ, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, false, x_waves<L>(), false, OBJ, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, nullptr, fl...)
             SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
         }
@@ -4624,20 +4718,32 @@ hipError_t launch_fft_fitness(hipStream_t st, const float *audio, const float *w
     }
     if (fft_wide(p, log2n, num_cus)) {
         constexpr int W = fft_wide_waves<10>();
-        if (window) k_fft<10, 1, true, W><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W>), 1), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch);
-        else k_fft<10, 1, false, W><<<SOTS_WIDE_GRID((k_fft<10, 1, false, W>), 2), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch);
+        if (window) k_fft<10, 1, true, W, false, false, OBJ, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, false, false, OBJ, FL...>), 1), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...);
+        else if constexpr (RAW) k_fft<10, 1, false, W, false, false, OBJ, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, false, W, false, false, OBJ, FL...>), 2), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, fl...);
         return hipGetLastError();
     }
     if (window) {
-#define CALL(L) k_fft<L, 1, true><<<resident_grid(k_fft<L, 1, true>, kWave, p, num_cus, &occ_w[L]), kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch)
+#define CALL(L) k_fft<L, 1, true, 1, false, false, OBJ, FL...><<<resident_grid((k_fft<L, 1, true, 1, false, false, OBJ, FL...>), kWave, p, num_cus, &occ_w[L]), kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...)
         SOTS_DISPATCH_WAVE(log2n, CALL)
 #undef CALL
         return hipGetLastError();
     }
-#define CALL(L) k_fft<L, 1, false><<<resident_grid(k_fft<L, 1, false>, kWave, p, num_cus, &occ_n[L]), kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch)
-    SOTS_DISPATCH_WAVE(log2n, CALL)
+    if constexpr (RAW) {
+#define CALL(L) k_fft<L, 1, false, 1, false, false, OBJ, FL...><<<resident_grid((k_fft<L, 1, false, 1, false, false, OBJ, FL...>), kWave, p, num_cus, &occ_n[L]), kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, fl...)
+        SOTS_DISPATCH_WAVE(log2n, CALL)
 #undef CALL
+    }
     return hipGetLastError();
+}
+
+hipError_t launch_fft_fitness(hipStream_t st, const float *audio, const float *window, const float *target,
+                              float *fitness, const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch,
+                              float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, const SelLists *lists, const Objective &obj)
+{
+    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE)
+        return launch_fft_fitness_o<kObjLogMagnitude>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists, obj.floor);
+    if (obj.kind != SOTS_OBJECTIVE_MAGNITUDE) return hipErrorInvalidValue;
+    return launch_fft_fitness_o<kObjMagnitude>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists);
 }
 
 constexpr uint32_t kSortMaxTiles = 256;
@@ -4970,38 +5076,49 @@ hipError_t launch_seg_targets(hipStream_t st, float *image, const float *targets
 
 // launch_fft_fitness with a window, every row against its chunk's target: the same kernel choice for the same row
 // count, each kernel's SEG instantiation
-hipError_t launch_fft_fitness_seg(hipStream_t st, const float *audio, const float *window, const float *seg_image, float *fitness,
-                                  const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
-                                  uint32_t num_cus, OccCache *oc)
+template <int OBJ, typename... FL>
+static hipError_t launch_fft_fitness_seg_o(hipStream_t st, const float *audio, const float *window, const float *seg_image, float *fitness,
+                                           const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
+                                           uint32_t num_cus, OccCache *oc, FL... fl)
 {
     if (big_from(log2n)) {
-        if (log2n == 14) return launch_fft_big<14, 1, true, true>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch);
-        return launch_fft_big<15, 1, true, true>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch);
+        if (log2n == 14) return launch_fft_big<14, 1, true, true, OBJ, FL...>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
+        return launch_fft_big<15, 1, true, true, OBJ, FL...>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
     }
     if (x_from(log2n)) {
         int *occ_x = oc->x_fused_win;
         if ((p + x_waves<12>() - 1) / x_waves<12>() < (num_cus ? num_cus : 256u)) {
             int *occ_s = oc->x_small;
-#define CALL(L) k_fft_x<L, 1, true, 4, true><<<resident_grid((k_fft_x<L, 1, true, 4, true>), 4 * kWave, (p + 3) / 4, num_cus, &occ_s[L]), 4 * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image)
+#define CALL(L) k_fft_x<L, 1, true, 4, true, OBJ, FL...><<<resident_grid((k_fft_x<L, 1, true, 4, true, OBJ, FL...>), 4 * kWave, (p + 3) / 4, num_cus, &occ_s[L]), 4 * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
             SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
             return hipGetLastError();
         }
-#define CALL(L) k_fft_x<L, 1, true, x_waves<L>(), true><<<SOTS_X_GRID((k_fft_x<L, 1, true, x_waves<L>(), true>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image)
+#define CALL(L) k_fft_x<L, 1, true, x_waves<L>(), true, OBJ, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, true, x_waves<L>(), true, OBJ, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
         SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
         return hipGetLastError();
     }
     if (fft_wide(p, log2n, num_cus)) {
         constexpr int W = fft_wide_waves<10>();
-        k_fft<10, 1, true, W, true><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, true>), 1), W * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch);
+        k_fft<10, 1, true, W, true, false, OBJ, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, true, false, OBJ, FL...>), 1), W * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...);
         return hipGetLastError();
     }
     int *occ_w = oc->fused_win;
-#define CALL(L) k_fft<L, 1, true, 1, true><<<resident_grid(k_fft<L, 1, true, 1, true>, kWave, p, num_cus, &occ_w[L]), kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch)
+#define CALL(L) k_fft<L, 1, true, 1, true, false, OBJ, FL...><<<resident_grid((k_fft<L, 1, true, 1, true, false, OBJ, FL...>), kWave, p, num_cus, &occ_w[L]), kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...)
     SOTS_DISPATCH_WAVE(log2n, CALL)
 #undef CALL
     return hipGetLastError();
+}
+
+hipError_t launch_fft_fitness_seg(hipStream_t st, const float *audio, const float *window, const float *seg_image, float *fitness,
+                                  const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
+                                  uint32_t num_cus, OccCache *oc, const Objective &obj)
+{
+    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE)
+        return launch_fft_fitness_seg_o<kObjLogMagnitude>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, obj.floor);
+    if (obj.kind != SOTS_OBJECTIVE_MAGNITUDE) return hipErrorInvalidValue;
+    return launch_fft_fitness_seg_o<kObjMagnitude>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc);
 }
 
 hipError_t launch_sort_seg(hipStream_t st, const float *vin, const float *sin, const float *fin, float *vout, float *sout,

@@ -96,6 +96,15 @@ struct Evolutionary_Strategy_HIP_Arguments
     // strategy; at most numParents, above that the constructor / parameterMatchAudio throws with the library's text.
     // Applied to the context, to every island of a group and to the chunks in flight (batched and queued alike).
     uint32_t survivors = 0;
+    // The spectral objective (type.HIP.objective, type.HIP.objectiveFloor; sots_set_objective): SOTS_OBJECTIVE_MAGNITUDE, the
+    // reference's sum of squared magnitude differences (default), or SOTS_OBJECTIVE_LOG_MAGNITUDE, the sum over the same
+    // bins of (ln(m + objectiveFloor) - ln(t + objectiveFloor))^2 with 1e-30 <= objectiveFloor <= 1.  Applied to the context,
+    // to every island of a group and to the chunks in flight (batched and queued alike).  Every fitness printed, the
+    // history's columns and targetFitness are in the units of the objective in force.  objectiveGiven: sots_match
+    // names the objective in its output (one line) only when parameters.json named it.
+    uint32_t objective = SOTS_OBJECTIVE_MAGNITUDE;
+    float objectiveFloor = 0.0f;
+    bool objectiveGiven = false;
     bool returnBestEver = false;
     uint32_t historyEvery = 0;
     std::string historyPath = "";
@@ -299,6 +308,12 @@ public:
         if (args_.survivors)
             for (uint32_t i = 0; i < numIslands(); ++i)
                 check(sots_set_survivors(group_ ? sots_group_island(group_, i) : ctx_, args_.survivors), "sots_set_survivors");
+        if (args_.objective != SOTS_OBJECTIVE_MAGNITUDE) {
+            if (group_) {
+                if (sots_group_set_objective(group_, args_.objective, args_.objectiveFloor) != SOTS_OK)
+                    throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_group_set_objective: ") + sots_group_last_error(group_));
+            } else check(sots_set_objective(ctx_, args_.objective, args_.objectiveFloor), "sots_set_objective");
+        }
         check(sots_timing_enable(ctx_, args_.benchmarkStages ? 1 : 0), "sots_timing_enable");
         if (tracking()) {
             if (group_) throw std::runtime_error("Evolutionary_Strategy_HIP: returnBestEver, the history and the stop rules need numDevices = 1");
@@ -501,6 +516,7 @@ private:
         };
         if (args_.deviceKernelArithmetic) checkBatch(sots_batch_set_synth_arithmetic(batch_, SOTS_ARITH_DEVICE_KERNELS), "sots_batch_set_synth_arithmetic");
         checkBatch(sots_batch_set_survivors(batch_, args_.survivors), "sots_batch_set_survivors");
+        checkBatch(sots_batch_set_objective(batch_, args_.objective, args_.objectiveFloor), "sots_batch_set_objective");
         checkBatch(sots_batch_track(batch_, SOTS_TRACK_BEST_EVER, 0, 0), "sots_batch_track"); // (the queue keeps the best-ever record itself)
         std::vector<float> mags((size_t)numChunks_ * half);
         for (uint32_t c = 0; c < numChunks_; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)chunkSize_ * c], mags.data() + (size_t)c * half);
@@ -544,6 +560,7 @@ private:
         };
         if (args_.deviceKernelArithmetic) checkBatch(sots_batch_set_synth_arithmetic(batch_, SOTS_ARITH_DEVICE_KERNELS), "sots_batch_set_synth_arithmetic");
         checkBatch(sots_batch_set_survivors(batch_, args_.survivors), "sots_batch_set_survivors");
+        checkBatch(sots_batch_set_objective(batch_, args_.objective, args_.objectiveFloor), "sots_batch_set_objective");
         if (tracking()) checkBatch(sots_batch_track(batch_, trackFlags(), args_.historyEvery, historyCapacity()), "sots_batch_track");
         std::vector<float> mags((size_t)perBatch * half), values((size_t)perBatch * d), fitness(perBatch);
         std::vector<float> nowValues((size_t)perBatch * d), nowFitness(perBatch), everFitness(perBatch);

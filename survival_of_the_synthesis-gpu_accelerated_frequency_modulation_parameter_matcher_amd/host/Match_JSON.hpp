@@ -1,0 +1,150 @@
+// Match_JSON.hpp -- sots_match's reading of parameters.json, apart from the driver so that it can be compiled and tested
+// without the library: the minimal JSON reader and the keys whose values need checking before anything touches a device.
+// Header-only, plain C++17, no HIP.
+#ifndef SOTS_MATCH_JSON_HPP
+#define SOTS_MATCH_JSON_HPP
+
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <map>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+// ---------------------------------------------------------------------------------------
+// minimal JSON (objects, arrays, numbers, strings, true/false/null)
+// ---------------------------------------------------------------------------------------
+struct Json {
+    enum Kind { Null, Bool, Number, String, Array, Object } kind = Null;
+    bool b = false;
+    double num = 0.0;
+    std::string str;
+    std::vector<Json> arr;
+    std::map<std::string, Json> obj;
+
+    const Json &operator[](const std::string &k) const
+    {
+        auto it = obj.find(k);
+        if (kind != Object || it == obj.end()) throw std::runtime_error("parameters.json: missing key \"" + k + "\"");
+        return it->second;
+    }
+    bool has(const std::string &k) const { return kind == Object && obj.count(k); }
+    double number() const
+    {
+        if (kind != Number) throw std::runtime_error("parameters.json: number expected");
+        return num;
+    }
+    std::vector<float> floats() const
+    {
+        std::vector<float> out;
+        for (const Json &e : arr) out.push_back((float)e.number());
+        return out;
+    }
+};
+
+class JsonParser
+{
+    const std::string &s_;
+    size_t i_ = 0;
+    void ws()
+    {
+        while (i_ < s_.size() && (s_[i_] == ' ' || s_[i_] == '\n' || s_[i_] == '\t' || s_[i_] == '\r')) ++i_;
+    }
+    [[noreturn]] void bad(const char *what) { throw std::runtime_error(std::string("parameters.json: ") + what + " at offset " + std::to_string(i_)); }
+    std::string string()
+    {
+        std::string out;
+        ++i_;
+        while (i_ < s_.size() && s_[i_] != '"') {
+            if (s_[i_] == '\\' && i_ + 1 < s_.size()) ++i_;
+            out.push_back(s_[i_++]);
+        }
+        if (i_ >= s_.size()) bad("unterminated string");
+        ++i_;
+        return out;
+    }
+
+public:
+    explicit JsonParser(const std::string &s) : s_(s) {}
+    Json value()
+    {
+        ws();
+        if (i_ >= s_.size()) bad("unexpected end");
+        Json j;
+        const char c = s_[i_];
+        if (c == '{') {
+            j.kind = Json::Object;
+            ++i_;
+            ws();
+            if (s_[i_] == '}') { ++i_; return j; }
+            for (;;) {
+                ws();
+                if (s_[i_] != '"') bad("key expected");
+                const std::string k = string();
+                ws();
+                if (s_[i_++] != ':') bad("':' expected");
+                j.obj[k] = value();
+                ws();
+                if (s_[i_] == ',') { ++i_; continue; }
+                if (s_[i_] == '}') { ++i_; return j; }
+                bad("',' or '}' expected");
+            }
+        }
+        if (c == '[') {
+            j.kind = Json::Array;
+            ++i_;
+            ws();
+            if (s_[i_] == ']') { ++i_; return j; }
+            for (;;) {
+                j.arr.push_back(value());
+                ws();
+                if (s_[i_] == ',') { ++i_; continue; }
+                if (s_[i_] == ']') { ++i_; return j; }
+                bad("',' or ']' expected");
+            }
+        }
+        if (c == '"') { j.kind = Json::String; j.str = string(); return j; }
+        if (s_.compare(i_, 4, "true") == 0) { j.kind = Json::Bool; j.b = true; i_ += 4; return j; }
+        if (s_.compare(i_, 5, "false") == 0) { j.kind = Json::Bool; j.b = false; i_ += 5; return j; }
+        if (s_.compare(i_, 4, "null") == 0) { i_ += 4; return j; }
+        char *end = nullptr;
+        j.num = strtod(s_.c_str() + i_, &end);
+        if (end == s_.c_str() + i_) bad("value expected");
+        j.kind = Json::Number;
+        i_ = (size_t)(end - s_.c_str());
+        return j;
+    }
+};
+
+// type.HIP.objective / type.HIP.objectiveFloor (enum sots_objective, sots_set_objective): "magnitude" (0, the default: the
+// reference's squared distance of the magnitudes) or "logMagnitude" (1: squared distance of ln(magnitude + objectiveFloor),
+// which then must be given, 1e-30 <= objectiveFloor <= 1).  Returns whether either key was there; throws on an unknown
+// name, a floor without the log objective's range, or a log objective without a floor.
+inline bool readObjectiveKeys(const Json &h, uint32_t &objective, float &floor)
+{
+    if (!h.has("objective") && !h.has("objectiveFloor")) return false;
+    uint32_t o = 0;
+    if (h.has("objective")) {
+        const Json &name = h["objective"];
+        if (name.kind != Json::String || (name.str != "magnitude" && name.str != "logMagnitude"))
+            throw std::runtime_error("parameters.json: type.HIP.objective must be \"magnitude\" or \"logMagnitude\"" +
+                                     (name.kind == Json::String ? ", not \"" + name.str + "\"" : std::string()));
+        o = name.str == "logMagnitude" ? 1u : 0u;
+    }
+    float f = 0.0f;
+    if (o == 1u) {
+        if (!h.has("objectiveFloor")) throw std::runtime_error("parameters.json: type.HIP.objective \"logMagnitude\" needs type.HIP.objectiveFloor");
+        const double v = h["objectiveFloor"].number();
+        if (!(v >= 1e-30 && v <= 1.0) || !((float)v >= 1e-30f)) // (NaN fails both; the float the library gets must be in range too)
+            throw std::runtime_error("parameters.json: type.HIP.objectiveFloor must lie in 1e-30 .. 1");
+        f = (float)v;
+    } else if (h.has("objectiveFloor")) {
+        (void)h["objectiveFloor"].number(); // a number, and ignored: the magnitude objective has no floor
+    }
+    objective = o;
+    floor = f;
+    return true;
+}
+
+#endif

@@ -3,7 +3,7 @@
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
 // "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "numDevices", "numElites",
 // "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight", "chunkQueue",
-// "survivors", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
+// "survivors", "objective", "objectiveFloor", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
 // N-sample chunk with Evolutionary_Strategy_HIP, writes inputGenerated.wav and the
 // outputAudioPath rendering of the best match, and prints the best parameters.
@@ -23,112 +23,8 @@
 #include <vector>
 
 #include "Evolutionary_Strategy_HIP.hpp"
+#include "Match_JSON.hpp"
 #include "Wav_IO.hpp"
-
-// ---------------------------------------------------------------------------------------
-// minimal JSON (objects, arrays, numbers, strings, true/false/null)
-// ---------------------------------------------------------------------------------------
-struct Json {
-    enum Kind { Null, Bool, Number, String, Array, Object } kind = Null;
-    bool b = false;
-    double num = 0.0;
-    std::string str;
-    std::vector<Json> arr;
-    std::map<std::string, Json> obj;
-
-    const Json &operator[](const std::string &k) const
-    {
-        auto it = obj.find(k);
-        if (kind != Object || it == obj.end()) throw std::runtime_error("parameters.json: missing key \"" + k + "\"");
-        return it->second;
-    }
-    bool has(const std::string &k) const { return kind == Object && obj.count(k); }
-    double number() const
-    {
-        if (kind != Number) throw std::runtime_error("parameters.json: number expected");
-        return num;
-    }
-    std::vector<float> floats() const
-    {
-        std::vector<float> out;
-        for (const Json &e : arr) out.push_back((float)e.number());
-        return out;
-    }
-};
-
-class JsonParser
-{
-    const std::string &s_;
-    size_t i_ = 0;
-    void ws()
-    {
-        while (i_ < s_.size() && (s_[i_] == ' ' || s_[i_] == '\n' || s_[i_] == '\t' || s_[i_] == '\r')) ++i_;
-    }
-    [[noreturn]] void bad(const char *what) { throw std::runtime_error(std::string("parameters.json: ") + what + " at offset " + std::to_string(i_)); }
-    std::string string()
-    {
-        std::string out;
-        ++i_;
-        while (i_ < s_.size() && s_[i_] != '"') {
-            if (s_[i_] == '\\' && i_ + 1 < s_.size()) ++i_;
-            out.push_back(s_[i_++]);
-        }
-        if (i_ >= s_.size()) bad("unterminated string");
-        ++i_;
-        return out;
-    }
-
-public:
-    explicit JsonParser(const std::string &s) : s_(s) {}
-    Json value()
-    {
-        ws();
-        if (i_ >= s_.size()) bad("unexpected end");
-        Json j;
-        const char c = s_[i_];
-        if (c == '{') {
-            j.kind = Json::Object;
-            ++i_;
-            ws();
-            if (s_[i_] == '}') { ++i_; return j; }
-            for (;;) {
-                ws();
-                if (s_[i_] != '"') bad("key expected");
-                const std::string k = string();
-                ws();
-                if (s_[i_++] != ':') bad("':' expected");
-                j.obj[k] = value();
-                ws();
-                if (s_[i_] == ',') { ++i_; continue; }
-                if (s_[i_] == '}') { ++i_; return j; }
-                bad("',' or '}' expected");
-            }
-        }
-        if (c == '[') {
-            j.kind = Json::Array;
-            ++i_;
-            ws();
-            if (s_[i_] == ']') { ++i_; return j; }
-            for (;;) {
-                j.arr.push_back(value());
-                ws();
-                if (s_[i_] == ',') { ++i_; continue; }
-                if (s_[i_] == ']') { ++i_; return j; }
-                bad("',' or ']' expected");
-            }
-        }
-        if (c == '"') { j.kind = Json::String; j.str = string(); return j; }
-        if (s_.compare(i_, 4, "true") == 0) { j.kind = Json::Bool; j.b = true; i_ += 4; return j; }
-        if (s_.compare(i_, 5, "false") == 0) { j.kind = Json::Bool; j.b = false; i_ += 5; return j; }
-        if (s_.compare(i_, 4, "null") == 0) { i_ += 4; return j; }
-        char *end = nullptr;
-        j.num = strtod(s_.c_str() + i_, &end);
-        if (end == s_.c_str() + i_) bad("value expected");
-        j.kind = Json::Number;
-        i_ = (size_t)(end - s_.c_str());
-        return j;
-    }
-};
 
 static void show_usage(const std::string &name)
 {
@@ -202,6 +98,8 @@ int main(int argc, char *argv[])
                 if (!(k >= 0.0)) throw std::runtime_error("parameters.json: type.HIP.survivors must not be negative");
                 args.survivors = k >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)k;
             }
+            // the spectral objective: "magnitude" (the reference's, the default) or "logMagnitude" with its floor (Match_JSON.hpp)
+            args.objectiveGiven = readObjectiveKeys(h, args.objective, args.objectiveFloor);
             // run record (Evolutionary_Strategy_HIP_Arguments): the best individual any generation produced, a history CSV,
             // and stopping a chunk early on a fitness target or a stall
             if (h.has("returnBestEver")) args.returnBestEver = h["returnBestEver"].b;
@@ -248,6 +146,8 @@ int main(int argc, char *argv[])
             outputAudioFile("inputGenerated.wav", targetAudio.data(), N);
         }
 
+        if (args.objectiveGiven) // (without the keys: not a byte more than before)
+            printf("Objective: %s, floor %g\n", args.objective == SOTS_OBJECTIVE_LOG_MAGNITUDE ? "logMagnitude" : "magnitude", (double)args.objectiveFloor);
         const auto start = std::chrono::steady_clock::now();
         es->parameterMatchAudio(targetAudio.data(), (uint32_t)targetAudio.size());
         const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
