@@ -239,6 +239,21 @@ int sots_get_survivors(const sots_ctx *ctx, uint32_t *n);
 enum sots_objective { SOTS_OBJECTIVE_MAGNITUDE = 0, SOTS_OBJECTIVE_LOG_MAGNITUDE = 1 };
 int sots_set_objective(sots_ctx *ctx, uint32_t objective, float floor);
 int sots_get_objective(const sots_ctx *ctx, uint32_t *objective, float *floor);
+/* Per-bin weights of the objective (new; the reference weighs every bin alike, ocl_program.cl:608-611).  With weights
+ * w_k, k = 0 .. N/2-1, the fitness under either objective is F = sum_k (u_k e_k)^2 = sum_k w_k e_k^2, where e_k is the
+ * bin's signed error as the active objective computes it (m_k - t_k, or ln(m_k + floor) - ln(t_k + floor)) and
+ * u_k = sqrtf(w_k), made once.  A weight of 1 leaves the bin's contribution as it is without weights, bit for bit; a weight
+ * of 0 makes a finite bin contribute exactly 0.  num_bins must be N/2, every w_k finite and >= 0, at least one > 0:
+ * anything else is SOTS_ERR_INVALID and the old setting stays.  NULL with 0 bins removes the weights (the default).
+ * Setting or removing them acts like a new target, as sots_set_objective does: the run record is cleared, the stored
+ * splitters and key lists are dropped.  Before or after the target and the objective, with the same result;
+ * sots_read_synth still returns the raw target magnitudes.  Fitness values, history records and stop-rule thresholds
+ * (sots_stop_rule.target_fitness) are in the units of the WEIGHTED sum.  A setting: sots_init_population, sots_set_target_*
+ * and sots_set_objective keep it.
+ * sots_get_objective_weights: *is_set (may be NULL) says whether weights are set; weights (may be NULL; otherwise
+ * num_bins must be N/2) receives the w_k as they were passed, and is left alone when none are set. */
+int sots_set_objective_weights(sots_ctx *ctx, const float *weights, uint32_t num_bins);
+int sots_get_objective_weights(const sots_ctx *ctx, float *weights, uint32_t num_bins, uint32_t *is_set);
 int sots_get_generation(const sots_ctx *ctx, uint32_t *generation);
 int sots_set_generation(sots_ctx *ctx, uint32_t generation);
 
@@ -320,6 +335,8 @@ int sots_group_set_target_audio(sots_group *group, const float *audio, uint32_t 
 int sots_group_set_target_spectrum(sots_group *group, const float *magnitudes, uint32_t num_bins);
 /* sots_set_objective on every island (new; the reference has one fitness, ocl_program.cl:608-611); the first failure is returned */
 int sots_group_set_objective(sots_group *group, uint32_t objective, float floor);
+/* sots_set_objective_weights on every island (new); the first failure is returned */
+int sots_group_set_objective_weights(sots_group *group, const float *weights, uint32_t num_bins);
 int sots_group_init_population(sots_group *group, uint32_t chunk_index);
 /* n generations on every island with the elite exchange; returns once everything is ENQUEUED.  In the overlapped
  * schedule (SOTS_GROUP_OVERLAP without SOTS_GROUP_EVENT_WAITS, "host-gated") every island's thread waits, before it
@@ -364,6 +381,10 @@ int sots_batch_set_survivors(sots_batch *b, uint32_t n);
  * sots_batch_execute_* and sots_batch_queue_run alike: the active targets' and the stored queue targets' tables are
  * rebuilt for it, every chunk's run record is cleared.  Before or after the targets, with the same result. */
 int sots_batch_set_objective(sots_batch *b, uint32_t objective, float floor);
+/* sots_set_objective_weights for every chunk of the batch (new), in sots_batch_execute_* and sots_batch_queue_run alike:
+ * one table for all chunks, active and queued.  Every chunk's run record is cleared.  Before or after the targets and
+ * the objective, with the same result. */
+int sots_batch_set_objective_weights(sots_batch *b, const float *weights, uint32_t num_bins);
 /* row 0 (the best) of every active chunk: values [active][D], fitness [active] (either may be NULL); blocking */
 int sots_batch_read_best(sots_batch *b, float *values, size_t values_bytes, float *fitness, size_t fitness_bytes);
 /* one active chunk's current half; byte counts as sots_read_population; blocking */

@@ -66,6 +66,8 @@ EXPORTS = [
     "sots_batch_queue_targets_spectra", "sots_batch_queue_targets_audio", "sots_batch_queue_run", "sots_batch_queue_results",
     "sots_batch_queue_read_kept_population", "sots_queue_makespan",
     "sots_set_objective", "sots_get_objective", "sots_batch_set_objective", "sots_group_set_objective",
+    "sots_set_objective_weights", "sots_get_objective_weights", "sots_batch_set_objective_weights",
+    "sots_group_set_objective_weights",
 ]
 QUEUE_NO_CHUNK = 0xFFFFFFFF
 TRACK_BEST_EVER, TRACK_HISTORY = 1, 2
@@ -200,6 +202,10 @@ def load():
     L.sots_get_objective.argtypes = [vp, C.POINTER(u32), C.POINTER(C.c_float)]
     L.sots_batch_set_objective.argtypes = [vp, u32, C.c_float]
     L.sots_group_set_objective.argtypes = [vp, u32, C.c_float]
+    L.sots_set_objective_weights.argtypes = [vp, vp, u32]
+    L.sots_get_objective_weights.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.sots_batch_set_objective_weights.argtypes = [vp, vp, u32]
+    L.sots_group_set_objective_weights.argtypes = [vp, vp, u32]
     L.sots_get_generation.argtypes = [vp, C.POINTER(u32)]
     L.sots_set_generation.argtypes = [vp, u32]
     L.sots_timing_enable.argtypes = [vp, C.c_int]
@@ -502,6 +508,24 @@ class HipES:
         self._check(self.L.sots_get_objective(self._h, C.byref(o), C.byref(f)))
         return o.value, f.value
 
+    def set_objective_weights(self, weights):
+        """Per-bin weights w[N/2] of the objective, F = sum_k w_k e_k^2 with e_k the active objective's signed error of bin k
+        (finite, >= 0, not all zero), or None for none (the default).  Acts like a new target; before or after
+        set_target_* and set_objective, with the same result.  Fitness, history and stop-rule thresholds are in the units
+        of the weighted sum."""
+        if weights is None:
+            self._check(self.L.sots_set_objective_weights(self._h, None, 0))
+            return
+        w = _f32(weights)
+        self._check(self.L.sots_set_objective_weights(self._h, _ptr(w), w.size))
+
+    def get_objective_weights(self):
+        """the weights as they were set, or None"""
+        is_set = C.c_uint32()
+        w = np.empty(self.N // 2, np.float32)
+        self._check(self.L.sots_get_objective_weights(self._h, _ptr(w), w.size, C.byref(is_set)))
+        return w if is_set.value else None
+
     def execute_generation(self):
         self._check(self.L.sots_execute_generation(self._h))
 
@@ -669,6 +693,14 @@ class HipBatch:
         """HipES.set_objective for every chunk, in execute_generations / execute_until and queue_run alike"""
         self._check(self.L.sots_batch_set_objective(self._h, objective, floor))
 
+    def set_objective_weights(self, weights):
+        """HipES.set_objective_weights for every chunk (one table), in execute_generations / execute_until and queue_run alike"""
+        if weights is None:
+            self._check(self.L.sots_batch_set_objective_weights(self._h, None, 0))
+            return
+        w = _f32(weights)
+        self._check(self.L.sots_batch_set_objective_weights(self._h, _ptr(w), w.size))
+
     def read_best(self):
         """(values[active][D], fitness[active]): row 0 of every active chunk"""
         v = np.empty((self.active, self.D), np.float32)
@@ -796,6 +828,14 @@ class HipGroup:
     def set_objective(self, objective, floor=0.0):
         """HipES.set_objective on every island"""
         self._check(self.L.sots_group_set_objective(self._h, objective, floor))
+
+    def set_objective_weights(self, weights):
+        """HipES.set_objective_weights on every island"""
+        if weights is None:
+            self._check(self.L.sots_group_set_objective_weights(self._h, None, 0))
+            return
+        w = _f32(weights)
+        self._check(self.L.sots_group_set_objective_weights(self._h, _ptr(w), w.size))
 
     def init_population(self, chunk=0):
         self._check(self.L.sots_group_init_population(self._h, chunk))

@@ -49,6 +49,9 @@ struct sots_batch {
     // uploaded magnitudes (batch_derive / queue_derive) and allocated with the first log objective that needs them
     Objective obj{};
     float *targets_ln = nullptr;                                   // [C][N/2]
+    // per-bin weights of every chunk (sots_batch_set_objective_weights): one table, u = sqrt(w), as plain bins and as the
+    // SEG kernels read it; b->obj points at the two while weights are set.  The targets' images do not depend on it.
+    float *weights_u = nullptr, *weights_image = nullptr;
     float *seg_image = nullptr;                                    // segmented target image (sots_kernels.h)
     float *wavetable = nullptr, *window = nullptr, *x_image = nullptr;
     float2 *twiddle = nullptr;
@@ -133,7 +136,7 @@ void free_batch(sots_batch *b)
     if (!b) return;
     (void)hipSetDevice(b->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    void *bufs[] = {b->values, b->steps, b->fitness, b->audio, b->targets, b->targets_ln, b->seg_image,
+    void *bufs[] = {b->values, b->steps, b->fitness, b->audio, b->targets, b->targets_ln, b->weights_u, b->weights_image, b->seg_image,
                     b->wavetable, b->window, b->x_image, b->twiddle};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
@@ -401,6 +404,41 @@ int sots_batch_set_objective(sots_batch *b, uint32_t objective, float floor)
     if (rc == SOTS_OK) rc = queue_derive(b);
     if (rc != SOTS_OK) b->obj = old, b->active = 0; // (the image may be half made: the ordinary calls need their targets again)
     return rc;
+}
+
+int sots_batch_set_objective_weights(sots_batch *b, const float *weights, uint32_t num_bins)
+{
+    BATCH_REQUIRE(b);
+    if ((weights == nullptr) != (num_bins == 0))
+        return bfail(b, SOTS_ERR_INVALID, "objective weights: a table and its length, or NULL and 0");
+    std::vector<float> u;
+    if (weights) {
+        uint32_t bad = 0;
+        switch (objective_weights_check(weights, num_bins, b->N / 2, u, &bad)) {
+        case 1: return bfail(b, SOTS_ERR_INVALID, "objective weights need %u bins, got %u", b->N / 2, num_bins);
+        case 2: return bfail(b, SOTS_ERR_INVALID, "objective weight %u is %g: every weight must be finite and >= 0", bad, (double)weights[bad]);
+        case 3: return bfail(b, SOTS_ERR_INVALID, "objective weights are all zero");
+        default: break;
+        }
+    }
+    if (int rc = bind(b)) return rc;
+    const Objective old = b->obj;
+    if (weights) {
+        if (!b->weights_u) BATCH_HIP(b, hipMalloc((void **)&b->weights_u, (size_t)num_bins * sizeof(float)));
+        if (!b->weights_image) BATCH_HIP(b, hipMalloc((void **)&b->weights_image, weight_image_bytes(b->log2n)));
+        BATCH_HIP(b, hipMemcpyAsync(b->weights_u, u.data(), (size_t)num_bins * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        BATCH_HIP(b, launch_weight_image(b->stream, b->weights_image, b->weights_u, b->log2n));
+        BATCH_HIP(b, hipStreamSynchronize(b->stream)); // (u goes out of scope)
+        b->obj.weights = b->weights_u;
+        b->obj.weights_image = b->weights_image;
+    } else {
+        b->obj.weights = b->obj.weights_image = nullptr;
+    }
+    if ((b->obj.weights != nullptr) != (old.weights != nullptr)) occ_forget(b->occ); // (other kernels, other occupancies)
+    // (the targets' images stay; what the chunks had found under the old weights says nothing: every record starts over)
+    BATCH_HIP(b, track_clear(b->track, b->stream));
+    BATCH_HIP(b, hipStreamSynchronize(b->stream));
+    return SOTS_OK;
 }
 
 int sots_batch_execute_generations(sots_batch *b, uint32_t n)

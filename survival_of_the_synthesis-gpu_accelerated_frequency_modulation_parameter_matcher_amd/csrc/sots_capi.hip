@@ -64,6 +64,10 @@ struct sots_ctx {
     // allocated with the first log objective
     Objective obj{};
     float *target_ln = nullptr;
+    // per-bin weights (sots_set_objective_weights): w as passed, u = sqrt(w) on the device as plain bins and as the fused
+    // kernels read it; ctx->obj points at the two while weights are set
+    std::vector<float> weights_w;
+    float *weights_u = nullptr, *weights_image = nullptr;
     // selection state: after the fused loop's partial sort only rows [0, tail_first) of the current half
     // are in place; the unsorted half it came from is intact until the next generation starts
     uint32_t sort_mode = SOTS_SORT_LAZY_TAIL;
@@ -257,7 +261,7 @@ void free_ctx(sots_ctx *ctx)
         all.erase(std::unique(all.begin(), all.end()), all.end());
         for (hipEvent_t e : all) (void)hipEventDestroy(e);
     }
-    void *bufs[] = {ctx->values, ctx->steps, ctx->fitness, ctx->audio, ctx->spectrum, ctx->target, ctx->target_ln,
+    void *bufs[] = {ctx->values, ctx->steps, ctx->fitness, ctx->audio, ctx->spectrum, ctx->target, ctx->target_ln, ctx->weights_u, ctx->weights_image,
                     ctx->wavetable, ctx->window, ctx->rows, ctx->twiddle, ctx->keys, ctx->sort_scratch, ctx->x_image, ctx->splitters,
                     ctx->sel_cnt, ctx->sel_lists};
     for (void *b : bufs)
@@ -1172,6 +1176,55 @@ int sots_set_objective(sots_ctx *ctx, uint32_t objective, float floor)
         ctx->obj = old;
         return rc;
     }
+    return SOTS_OK;
+}
+
+// Like a new objective: another landscape for the same population.  Everything is checked before anything changes.
+int sots_set_objective_weights(sots_ctx *ctx, const float *weights, uint32_t num_bins)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if ((weights == nullptr) != (num_bins == 0))
+        return fail(ctx, SOTS_ERR_INVALID, "objective weights: a table and its length, or NULL and 0");
+    std::vector<float> u;
+    if (weights) {
+        uint32_t bad = 0;
+        switch (objective_weights_check(weights, num_bins, ctx->N / 2, u, &bad)) {
+        case 1: return fail(ctx, SOTS_ERR_INVALID, "objective weights need %u bins, got %u", ctx->N / 2, num_bins);
+        case 2: return fail(ctx, SOTS_ERR_INVALID, "objective weight %u is %g: every weight must be finite and >= 0", bad, (double)weights[bad]);
+        case 3: return fail(ctx, SOTS_ERR_INVALID, "objective weights are all zero");
+        default: break;
+        }
+    }
+    if (int rc = bind_device(ctx)) return rc;
+    const Objective old = ctx->obj;
+    if (weights) {
+        if (!ctx->weights_u) SOTS_HIP(ctx, hipMalloc((void **)&ctx->weights_u, (size_t)num_bins * sizeof(float)));
+        if (!ctx->weights_image) SOTS_HIP(ctx, hipMalloc((void **)&ctx->weights_image, weight_image_bytes(ctx->log2n)));
+        SOTS_HIP(ctx, hipMemcpyAsync(ctx->weights_u, u.data(), (size_t)num_bins * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        SOTS_HIP(ctx, launch_weight_image(ctx->stream, ctx->weights_image, ctx->weights_u, ctx->log2n));
+        SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (u goes out of scope)
+        ctx->obj.weights = ctx->weights_u;
+        ctx->obj.weights_image = ctx->weights_image;
+    } else {
+        ctx->obj.weights = ctx->obj.weights_image = nullptr;
+    }
+    if ((ctx->obj.weights != nullptr) != (old.weights != nullptr)) occ_forget(ctx->occ); // (other kernels, other occupancies)
+    if (int rc = derive_target(ctx)) {
+        ctx->obj = old;
+        return rc;
+    }
+    if (weights) ctx->weights_w.assign(weights, weights + num_bins);
+    else ctx->weights_w.clear();
+    return SOTS_OK;
+}
+
+int sots_get_objective_weights(const sots_ctx *ctx, float *weights, uint32_t num_bins, uint32_t *is_set)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (!weights && !is_set) return fail(ctx, SOTS_ERR_INVALID, "null weights and is_set pointers");
+    if (weights && num_bins != ctx->N / 2) return fail(ctx, SOTS_ERR_INVALID, "objective weights have %u bins, room for %u", ctx->N / 2, num_bins);
+    if (is_set) *is_set = ctx->weights_w.empty() ? 0u : 1u;
+    if (weights && !ctx->weights_w.empty()) std::copy(ctx->weights_w.begin(), ctx->weights_w.end(), weights);
     return SOTS_OK;
 }
 

@@ -487,6 +487,15 @@ int sots_group_set_objective(sots_group *g, uint32_t objective, float floor)
     return SOTS_OK;
 }
 
+int sots_group_set_objective_weights(sots_group *g, const float *weights, uint32_t num_bins)
+{
+    if (!g) return gfail(nullptr, SOTS_ERR_INVALID, "null group");
+    for (size_t i = 0; i < g->islands.size(); ++i)
+        if (int rc = sots_set_objective_weights(g->islands[i].ctx, weights, num_bins))
+            return gfail(g, rc, "island %zu: %s", i, sots_last_error(g->islands[i].ctx));
+    return SOTS_OK;
+}
+
 int sots_group_synchronize(sots_group *g)
 {
     if (!g) return gfail(nullptr, SOTS_ERR_INVALID, "null group");

@@ -3,7 +3,9 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
+#include <vector>
 
 #include "../../include/sots_hip.h"
 
@@ -81,10 +83,33 @@ struct OccCache {
 // the magnitudes, or SOTS_OBJECTIVE_LOG_MAGNITUDE, sum (ln(m + floor) - ln(t + floor))^2.  Under the log objective every
 // target the launchers below are given - plain bins, table image, segmented image - holds ln(t + floor) instead of t:
 // launch_objective_map makes the plain bins, the layouts are copied from them as they are from magnitudes.
+// Per-bin weights (sots_set_objective_weights): F = sum_k (u_k e_k)^2 with e_k the signed error of the objective above and
+// u_k = sqrt(w_k).  `weights` is u[N/2] on the device, plain bins (the staged fitness kernels read it); `weights_image` is
+// the same table as the fused kernels read it (launch_weight_image: laid out as one chunk's target table).  Both null: no
+// weights, and the launchers enqueue the unweighted kernels.
 struct Objective {
     uint32_t kind = SOTS_OBJECTIVE_MAGNITUDE;
     float floor = 0.0f;
+    const float *weights = nullptr;
+    const float *weights_image = nullptr;
 };
+// w[n] as sots_set_objective_weights takes it: n == bins, every entry finite and >= 0, one at least > 0.  0: fine, and
+// u[k] = sqrtf(w[k]) (correctly rounded); 1: wrong length; 2: entry *bad is negative or not finite; 3: all zero
+inline int objective_weights_check(const float *w, uint32_t n, uint32_t bins, std::vector<float> &u, uint32_t *bad)
+{
+    if (n != bins) return 1;
+    bool any = false;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (!(w[k] >= 0.0f) || !std::isfinite(w[k])) return *bad = k, 2;
+        any = any || w[k] > 0.0f;
+    }
+    if (!any) return 3;
+    u.resize(n);
+    for (uint32_t k = 0; k < n; ++k) u[k] = std::sqrt(w[k]);
+    return 0;
+}
+size_t weight_image_bytes(uint32_t log2n);
+hipError_t launch_weight_image(hipStream_t st, float *image, const float *u, uint32_t log2n);
 // 1e-30 <= floor <= 1: m + floor is then a normal fp32 number for every magnitude m >= 0
 inline bool objective_floor_ok(float floor) { return floor >= 1e-30f && floor <= 1.0f; } // (false for NaN)
 // dst[i] = ln(src[i] + floor) with the device routine the fitness epilogues apply to the candidate's bins

@@ -1752,6 +1752,21 @@ __device__ __forceinline__ void bin_error2(v2f_t &acc2, float2 xa, float2 xb, fl
     const v2f_t e = raw * v2f_t{scale, scale} - v2f_t{ta, tb};
     acc2 = acc2 + e * e;
 }
+// The weighted forms (bin_error_w / bin_error2_w below): the same signed error e, times u = sqrt(w) of the
+// bin - one product, rounded once - and the squared accumulation as it stands above.  u = 1 gives the unweighted bits,
+// u = 0 makes a finite bin contribute exactly 0.
+__device__ __forceinline__ float bin_error_wt(float2 x, float target, float scale, float u)
+{
+    const float raw = __builtin_amdgcn_sqrtf(x.x * x.x + x.y * x.y);
+    const float e = (raw * scale - target) * u;
+    return e * e;
+}
+__device__ __forceinline__ void bin_error2_wt(v2f_t &acc2, float2 xa, float2 xb, float ta, float tb, float scale, float ua, float ub)
+{
+    const v2f_t raw = v2f_t{__builtin_amdgcn_sqrtf(xa.x * xa.x + xa.y * xa.y), __builtin_amdgcn_sqrtf(xb.x * xb.x + xb.y * xb.y)};
+    const v2f_t e = (raw * v2f_t{scale, scale} - v2f_t{ta, tb}) * v2f_t{ua, ub};
+    acc2 = acc2 + e * e;
+}
 
 // ---- the selectable objective (sots_set_objective) ----
 // OBJ is a template parameter of every kernel that turns bins into fitness.  kObjMagnitude is the reference's sum above,
@@ -1761,6 +1776,8 @@ __device__ __forceinline__ void bin_error2(v2f_t &acc2, float2 xa, float2 xb, fl
 // routine of the epilogues: a bin whose magnitude equals the target's contributes exactly 0, and nobody's log but
 // v_log_f32's is involved).  The floor is one more kernel argument of the log instantiations only, behind all others.
 constexpr int kObjMagnitude = SOTS_OBJECTIVE_MAGNITUDE, kObjLogMagnitude = SOTS_OBJECTIVE_LOG_MAGNITUDE;
+// (host side: the table inside a weight image, launch_weight_image)
+static inline const float *weight_table(const float *image) { return image + kSegTargetHeadFloats; }
 #pragma clang fp contract(off) // (m + floor and log2 x ln 2 round one by one, here and in the table's kernel)
 // ln(m + floor): v_log_f32 (log2, 1 ulp) times ln 2.  m >= 0 and 1e-30 <= floor <= 1 keep the argument a normal number,
 // which is all that instruction handles; NaN and +inf pass through.
@@ -1782,6 +1799,19 @@ __device__ __forceinline__ void bin_error2_log(v2f_t &acc2, v2f_t raw, float ta,
     const v2f_t e = l - v2f_t{ta, tb};
     acc2 = acc2 + e * e;
 }
+// (weighted: bin_error_wt's note)
+__device__ __forceinline__ float bin_error_log_wt(float raw, float target_ln, float scale, float floor, float u)
+{
+    const float e = (obj_ln_floor(raw * scale, floor) - target_ln) * u;
+    return e * e;
+}
+__device__ __forceinline__ void bin_error2_log_wt(v2f_t &acc2, v2f_t raw, float ta, float tb, float scale, float floor, float ua, float ub)
+{
+    const v2f_t a = raw * v2f_t{scale, scale} + v2f_t{floor, floor};
+    const v2f_t l = v2f_t{__builtin_amdgcn_logf(a.x), __builtin_amdgcn_logf(a.y)} * v2f_t{0.693147180559945f, 0.693147180559945f};
+    const v2f_t e = (l - v2f_t{ta, tb}) * v2f_t{ua, ub};
+    acc2 = acc2 + e * e;
+}
 #pragma clang fp contract(on)
 template <int OBJ>
 __device__ __forceinline__ float bin_error_o(float2 x, float target, float scale, [[maybe_unused]] float floor)
@@ -1796,11 +1826,42 @@ __device__ __forceinline__ void bin_error2_o(v2f_t &acc2, float2 xa, float2 xb, 
         bin_error2_log(acc2, v2f_t{__builtin_amdgcn_sqrtf(xa.x * xa.x + xa.y * xa.y), __builtin_amdgcn_sqrtf(xb.x * xb.x + xb.y * xb.y)}, ta, tb, scale, floor);
     else bin_error2(acc2, xa, xb, ta, tb, scale);
 }
-// the floor out of a kernel's trailing arguments: (), (lists) - magnitude - or (floor), (lists, floor)
+// ---- per-bin weights (sots_set_objective_weights) ----
+// WGT is the second template parameter of those kernels: F = sum_k (u_k e_k)^2 with e_k the signed error of the objective
+// and u_k = sqrt(w_k), a table made once on the host.  The weighted instantiations take the table as one more trailing
+// argument, behind the floor; the others are the kernels as they were.  This pair is the one statement of it: every fused
+// and staged kernel calls it, so fused fitness equals staged fitness bit for bit.
+template <int OBJ, bool WGT>
+__device__ __forceinline__ float bin_error_w(float2 x, float target, float scale, [[maybe_unused]] float floor, [[maybe_unused]] float u)
+{
+    if constexpr (!WGT) return bin_error_o<OBJ>(x, target, scale, floor);
+    else if constexpr (OBJ == kObjLogMagnitude) return bin_error_log_wt(__builtin_amdgcn_sqrtf(x.x * x.x + x.y * x.y), target, scale, floor, u);
+    else return bin_error_wt(x, target, scale, u);
+}
+template <int OBJ, bool WGT>
+__device__ __forceinline__ void bin_error2_w(v2f_t &acc2, float2 xa, float2 xb, float ta, float tb, float scale, [[maybe_unused]] float floor,
+                                             [[maybe_unused]] float ua, [[maybe_unused]] float ub)
+{
+    if constexpr (!WGT) bin_error2_o<OBJ>(acc2, xa, xb, ta, tb, scale, floor);
+    else if constexpr (OBJ == kObjLogMagnitude)
+        bin_error2_log_wt(acc2, v2f_t{__builtin_amdgcn_sqrtf(xa.x * xa.x + xa.y * xa.y), __builtin_amdgcn_sqrtf(xb.x * xb.x + xb.y * xb.y)}, ta, tb, scale, floor, ua, ub);
+    else bin_error2_wt(acc2, xa, xb, ta, tb, scale, ua, ub);
+}
+// the floor out of a kernel's trailing arguments: (), (lists) - magnitude - or (floor), (lists, floor); a weighted
+// instantiation's table stands behind them
 __device__ __forceinline__ float obj_floor() { return 0.0f; }
 __device__ __forceinline__ float obj_floor(float floor) { return floor; }
 __device__ __forceinline__ float obj_floor(const SelLists &) { return 0.0f; }
 __device__ __forceinline__ float obj_floor(const SelLists &, float floor) { return floor; }
+__device__ __forceinline__ float obj_floor(const float *) { return 0.0f; }
+__device__ __forceinline__ float obj_floor(float floor, const float *) { return floor; }
+__device__ __forceinline__ float obj_floor(const SelLists &, const float *) { return 0.0f; }
+__device__ __forceinline__ float obj_floor(const SelLists &, float floor, const float *) { return floor; }
+// the weight table out of them: the last argument where it is a pointer
+__device__ __forceinline__ const float *obj_weights() { return nullptr; }
+__device__ __forceinline__ const float *obj_weights(const float *u) { return u; }
+template <typename T, typename... R>
+__device__ __forceinline__ const float *obj_weights(const T &, R... r) { return obj_weights(r...); }
 // target[i] -> ln(target[i] + floor): the derived table of the log objective, plain bins (every other layout is copied from it)
 __global__ __launch_bounds__(256) void k_objective_map(float *__restrict__ dst, const float *__restrict__ src, size_t n, float floor)
 {
@@ -1970,20 +2031,30 @@ __device__ __forceinline__ BktNoLists bkt_lists() { return {}; }
 __device__ __forceinline__ BktNoLists bkt_lists(float) { return {}; }
 __device__ __forceinline__ const SelLists &bkt_lists(const SelLists &l) { return l; }
 __device__ __forceinline__ const SelLists &bkt_lists(const SelLists &l, float) { return l; }
+__device__ __forceinline__ BktNoLists bkt_lists(const float *) { return {}; }
+__device__ __forceinline__ BktNoLists bkt_lists(float, const float *) { return {}; }
+__device__ __forceinline__ const SelLists &bkt_lists(const SelLists &l, const float *) { return l; }
+__device__ __forceinline__ const SelLists &bkt_lists(const SelLists &l, float, const float *) { return l; }
 // BUCKET (the wide fitness kernel in front of a one-launch selection, list mode): every row's key goes into the list of
 // its bucket between the splitters of bk.slot (bkt_visit above) - the slot was written a generation ago, the row's
 // fitness is in a register here, and the selection's 256 workgroups no longer ask all P rows each.
 // OBJ (MODE 1): the objective; the log instantiations take the floor as their last argument (bin_error_o above)
-template <int LOG2N, int MODE, bool WIN, int W = 1, bool SEG = false, bool BUCKET = false, int OBJ = kObjMagnitude, typename... LISTS>
+// WGT (MODE 1): per-bin weights; the table u[N/2] is then the very last argument (bin_error_w above).  Without SEG it sits
+// in LDS beside the target, one float2 {target, u} per bin; with SEG the chunk's target is read from global memory as
+// ever and u - one table for all chunks - sits in LDS on its own (read from global memory beside the target, the
+// one-wavefront form needed 188 registers and lost its third wavefront per SIMD).
+template <int LOG2N, int MODE, bool WIN, int W = 1, bool SEG = false, bool BUCKET = false, int OBJ = kObjMagnitude, bool WGT = false, typename... LISTS>
 __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audio, float *__restrict__ spectrum,
                                                    const float *__restrict__ target, float *__restrict__ fitness,
                                                    const float2 *__restrict__ tw, const float *__restrict__ window,
                                                    uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch, LISTS... lists)
 {
-    static_assert(sizeof...(LISTS) == (BUCKET ? 1 : 0) + (OBJ == kObjLogMagnitude ? 1 : 0), "the BUCKET instantiation takes the lists, the log ones the floor, the others nothing");
-    static_assert(OBJ == kObjMagnitude || MODE == 1, "the objective belongs to the fitness epilogue");
+    static_assert(sizeof...(LISTS) == (BUCKET ? 1 : 0) + (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the BUCKET instantiation takes the lists, the log ones the floor, the weighted ones their table, the others nothing");
+    static_assert((OBJ == kObjMagnitude && !WGT) || MODE == 1, "the objective belongs to the fitness epilogue");
+    static_assert(!WGT || WIN, "the weighted forms exist with a window only");
     [[maybe_unused]] const auto bk = bkt_lists(lists...);
     [[maybe_unused]] const float floor_eps = obj_floor(lists...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(lists...);
     constexpr int N = 1 << LOG2N, M = N / 2, E = M / kWave, H = E / 2;
     static_assert(LOG2N == 9 || LOG2N == 10, "wavefront-per-row FFT is for N <= 1024");
     static_assert(!BUCKET || (MODE == 1 && W > 1 && !SEG), "keys are filed by the wide fitness kernel only");
@@ -2008,8 +2079,15 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
     for (int q = 0; q < H; ++q) w_split[q] = tw[lane + kWave * q];
     // the target spectrum sits in LDS (2N bytes): eight registers fewer than holding this lane's
     // bins, which is what keeps N = 1024 at three wavefronts per SIMD with two rows in flight
-    __shared__ float tgt_s[MODE == 1 && !SEG ? M + 1 : 1];
-    if constexpr (MODE == 1 && !SEG) {
+    __shared__ float tgt_s[MODE == 1 && !SEG && !WGT ? M + 1 : 1];
+    __shared__ float2 tu_s[MODE == 1 && !SEG && WGT ? M + 1 : 1]; // (weighted: {target, u} of a bin in one 8-byte read)
+    __shared__ float u_s[MODE == 1 && SEG && WGT ? M + 1 : 1];
+    if constexpr (MODE == 1 && SEG && WGT) {
+        for (int k = threadIdx.x; k < M; k += W * kWave) u_s[k] = wgt_u[k];
+    }
+    if constexpr (MODE == 1 && !SEG && WGT) {
+        for (int k = threadIdx.x; k < M; k += W * kWave) tu_s[k] = make_float2(target[k], wgt_u[k]);
+    } else if constexpr (MODE == 1 && !SEG) {
         for (int k = threadIdx.x; k < M; k += W * kWave) tgt_s[k] = target[k];
     }
     const uint32_t seg_rows = SEG ? seg_target_rows(target) : 1u;
@@ -2113,6 +2191,17 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
                 v2f_t xa2, xbc2;
                 split_pair_2x(z[q], split_partner<M>(z, q, lane, partner_addr), w_split[q], xa2, xbc2); // 2 X[k], 2 conj X[M-k]
                 if (k == 0) xbc2 = v2f_t{2.0f * x_half.x, 2.0f * x_half.y}; // the fitness skips the Nyquist bin and needs bin M/2
+                if constexpr (WGT) {
+                    const int k2 = k == 0 ? M / 2 : M - k;
+                    if constexpr (SEG) {
+                        bin_error2_w<OBJ, true>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tg[k], tg[k2], half_scale, floor_eps, u_s[k], u_s[k2]);
+                        if constexpr (W == 1) __builtin_amdgcn_sched_barrier(0); // (the one-wavefront form: read ahead, the weights cost the third wavefront per SIMD)
+                    }
+                    else {
+                        const float2 ta = tu_s[k], tb = tu_s[k2];
+                        bin_error2_w<OBJ, true>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), ta.x, tb.x, half_scale, floor_eps, ta.y, tb.y);
+                    }
+                } else
                 if constexpr (SEG) bin_error2_o<OBJ>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tg[k], tg[k == 0 ? M / 2 : M - k], half_scale, floor_eps);
                 else bin_error2_o<OBJ>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tgt_s[k], tgt_s[k == 0 ? M / 2 : M - k], half_scale, floor_eps);
             }
@@ -2167,14 +2256,15 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
 
 // fitnessPopulation on materialised spectrum rows; same bin -> lane assignment and
 // summation order as k_fft<.., 1>, so both paths give the same fp32 sum.
-template <int LOG2N, int OBJ = kObjMagnitude, typename... FLOOR>
+template <int LOG2N, int OBJ = kObjMagnitude, bool WGT = false, typename... FLOOR>
 __global__ __launch_bounds__(kWave) void k_fitness(const float *__restrict__ spectrum,
                                                    const float *__restrict__ target,
                                                    float *__restrict__ fitness, uint32_t p_len, float inv_n,
                                                    float inv_wf, FLOOR... floor)
 {
-    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0), "the log instantiation takes the floor");
+    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the log instantiation takes the floor, the weighted one its table");
     [[maybe_unused]] const float floor_eps = obj_floor(floor...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(floor...);
     constexpr int N = 1 << LOG2N, M = N / 2, E = M / kWave;
     const int lane = threadIdx.x;
     for (uint32_t ind = blockIdx.x; ind < p_len; ind += gridDim.x) {
@@ -2184,7 +2274,7 @@ __global__ __launch_bounds__(kWave) void k_fitness(const float *__restrict__ spe
         for (int q = 0; q < E / 2; ++q) {
             const int k = lane + kWave * q;
             const int kb = k == 0 ? M / 2 : M - k;
-            bin_error2_o<OBJ>(acc2, row[k], row[kb], target[k], target[kb], inv_n * inv_wf, floor_eps);
+            bin_error2_w<OBJ, WGT>(acc2, row[k], row[kb], target[k], target[kb], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f, WGT ? wgt_u[kb] : 0.0f);
         }
         float acc = wave_sum(acc2.x + acc2.y);
         if (lane == 0) fitness[ind] = acc;
@@ -3709,15 +3799,19 @@ template <int LOG2N> constexpr int x_table_floats() { return 3 * 2 * kWave * (x_
 // floats of one chunk's target table in a segmented target image (SEG): the tgt_s part of the LDS tables, same layout
 template <int LOG2N> constexpr uint32_t x_seg_stride() { return kWave * (x_points<LOG2N>() + 4); }
 // SEG: as k_fft's - every row reads its chunk's target entries (lane, register) from the segmented image in global memory
-template <int LOG2N, int MODE, bool WIN, int WG = x_waves<LOG2N, MODE>(), bool SEG = false, int OBJ = kObjMagnitude, typename... FLOOR>
+// WGT: the weight table u in the layout of the target table (entry (l, r) at l (E + 4) + r: a one-chunk segmented image
+// made from u[N/2]), read by (lane, register) from global memory - the LDS tables and their image stay as they are
+template <int LOG2N, int MODE, bool WIN, int WG = x_waves<LOG2N, MODE>(), bool SEG = false, int OBJ = kObjMagnitude, bool WGT = false, typename... FLOOR>
 __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MIN_WAVES : 1)) void k_fft_x(const float *__restrict__ audio, float *__restrict__ spectrum,
                                                                    const float *__restrict__ target, float *__restrict__ fitness,
                                                                    const float2 *__restrict__ tw, const float *__restrict__ window,
                                                                    uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch,
                                                                    const float *__restrict__ image, FLOOR... floor)
 {
-    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) && (OBJ == kObjMagnitude || MODE == 1), "the log instantiation (fitness epilogue only) takes the floor");
+    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0) && ((OBJ == kObjMagnitude && !WGT) || MODE == 1), "the log instantiation (fitness epilogue only) takes the floor, the weighted one its table");
+    static_assert(!WGT || WIN, "the weighted forms exist with a window only");
     [[maybe_unused]] const float floor_eps = obj_floor(floor...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(floor...);
     constexpr int N = 1 << LOG2N, M = N / 2, E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), W = WG;
     constexpr int S2 = E + 2, S1 = E + 4; // lane strides of the float2 / float tables (16-byte reads, spread over the banks)
     __shared__ __attribute__((aligned(16))) float xt_s[x_table_floats<LOG2N>()]; // (the variants without window or target leave theirs unused)
@@ -3864,6 +3958,11 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
                 if constexpr (SEG) return tg[rr];
                 else return tgt_s[lane * S1 + rr];
             };
+            [[maybe_unused]] const float *__restrict__ ul = WGT ? wgt_u + lane * S1 : nullptr;
+            [[maybe_unused]] auto u_at = [&](int rr) -> float {
+                if constexpr (WGT) return ul[rr];
+                else return 0.0f;
+            };
             // Registers RR and R2 = bitrev(E - bitrev(RR)) need each other and nobody else: the bins are taken in such
             // pairs (this is the summation order, k_fitness_x repeats it), and a pair that is done is free - the NEXT
             // row's loads into those two registers go out at once, so by the end of the split most of the next row is on
@@ -3892,18 +3991,18 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
                     if constexpr (R2 != RR) {
                         v2f_t xa, xb;
                         pair2x(ic<RR>{}, xa, xb);
-                        acc += bin_error_o<OBJ>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps);
-                        acc += bin_error_o<OBJ>(make_float2(xb.x, xb.y), tgt_at(R2), half_scale, floor_eps); // the partner lane's bin M - k: x_target_bin
+                        acc += bin_error_w<OBJ, WGT>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps, u_at(RR));
+                        acc += bin_error_w<OBJ, WGT>(make_float2(xb.x, xb.y), tgt_at(R2), half_scale, floor_eps, u_at(R2)); // the partner lane's bin M - k: x_target_bin
                     } else {
                         const v2f_t xa = bin2x(ic<RR>{});
-                        acc += bin_error_o<OBJ>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps);
+                        acc += bin_error_w<OBJ, WGT>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps, u_at(RR));
                     }
 #else
                     const v2f_t xa = bin2x(ic<RR>{});
-                    acc += bin_error_o<OBJ>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps);
+                    acc += bin_error_w<OBJ, WGT>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps, u_at(RR));
                     if constexpr (R2 != RR) {
                         const v2f_t xb = bin2x(ic<R2>{});
-                        acc += bin_error_o<OBJ>(make_float2(xb.x, xb.y), tgt_at(R2), half_scale, floor_eps);
+                        acc += bin_error_w<OBJ, WGT>(make_float2(xb.x, xb.y), tgt_at(R2), half_scale, floor_eps, u_at(R2));
                     }
 #endif
 #ifndef SOTS_X_RECYCLE
@@ -3958,7 +4057,7 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
                 if constexpr (Q % 2 == 0) out_even = x2 * v2f_t{0.5f, 0.5f};
                 else *reinterpret_cast<float4 *>(dst + Q - 1) = make_float4(out_even.x, out_even.y, 0.5f * x2.x, 0.5f * x2.y);
             } else {
-                acc += bin_error_o<OBJ>(make_float2(x2.x, x2.y), tgt_s[lane * S1 + RR], half_scale, floor_eps);
+                acc += bin_error_w<OBJ, WGT>(make_float2(x2.x, x2.y), tgt_s[lane * S1 + RR], half_scale, floor_eps, WGT ? wgt_u[lane * S1 + RR] : 0.0f);
             }
             if constexpr (I % 4 == 3) __builtin_amdgcn_sched_barrier(0);
         });
@@ -4013,14 +4112,16 @@ __device__ __forceinline__ float big_block_sum(float acc, float *__restrict__ re
 }
 
 // SEG: `target` is a segmented target image (k_fft's); row r takes its chunk's bins
-template <int LOG2N, int MODE, bool WIN, bool SEG = false, int OBJ = kObjMagnitude, typename... FLOOR>
+template <int LOG2N, int MODE, bool WIN, bool SEG = false, int OBJ = kObjMagnitude, bool WGT = false, typename... FLOOR>
 __global__ __launch_bounds__(kBigThreads) void k_fft_big(const float *__restrict__ audio, float *__restrict__ spectrum,
                                                          const float *__restrict__ target, float *__restrict__ fitness,
                                                          const float2 *__restrict__ tw, const float *__restrict__ window,
                                                          uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch, FLOOR... floor)
 {
-    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) && (OBJ == kObjMagnitude || MODE == 1), "the log instantiation (fitness epilogue only) takes the floor");
+    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0) && ((OBJ == kObjMagnitude && !WGT) || MODE == 1), "the log instantiation (fitness epilogue only) takes the floor, the weighted one its table");
+    static_assert(!WGT || WIN, "the weighted forms exist with a window only");
     [[maybe_unused]] const float floor_eps = obj_floor(floor...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(floor...);
     constexpr uint32_t N = 1u << LOG2N, M = N / 2, LM = LOG2N - 1, T = kBigThreads;
     extern __shared__ float2 big_z[]; // M complex points (the launch asks for M * 8 + 64 bytes)
     float *__restrict__ red = reinterpret_cast<float *>(big_z + M);
@@ -4064,7 +4165,7 @@ __global__ __launch_bounds__(kBigThreads) void k_fft_big(const float *__restrict
         } else {
             float acc = 0.0f;
             const float *__restrict__ tg = SEG ? seg_target_chunk(target, row / seg_target_rows(target), M) : target;
-            for (uint32_t k = t; k < M; k += T) acc += bin_error_o<OBJ>(bin(k), tg[k], inv_n * inv_wf, floor_eps);
+            for (uint32_t k = t; k < M; k += T) acc += bin_error_w<OBJ, WGT>(bin(k), tg[k], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f);
             const float total = big_block_sum(acc, red);
             if (t == 0) fitness[row] = total;
         }
@@ -4072,18 +4173,19 @@ __global__ __launch_bounds__(kBigThreads) void k_fft_big(const float *__restrict
     }
 }
 
-template <int LOG2N, int OBJ = kObjMagnitude, typename... FLOOR>
+template <int LOG2N, int OBJ = kObjMagnitude, bool WGT = false, typename... FLOOR>
 __global__ __launch_bounds__(kBigThreads) void k_fitness_big(const float *__restrict__ spectrum, const float *__restrict__ target,
                                                              float *__restrict__ fitness, uint32_t p_len, float inv_n, float inv_wf, FLOOR... floor)
 {
-    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0), "the log instantiation takes the floor");
+    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the log instantiation takes the floor, the weighted one its table");
     [[maybe_unused]] const float floor_eps = obj_floor(floor...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(floor...);
     constexpr uint32_t N = 1u << LOG2N, M = N / 2, T = kBigThreads;
     __shared__ float red[kBigThreads / kWave];
     for (uint32_t row = blockIdx.x; row < p_len; row += gridDim.x) {
         const float2 *__restrict__ src = reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8));
         float acc = 0.0f;
-        for (uint32_t k = threadIdx.x; k < M; k += T) acc += bin_error_o<OBJ>(src[k], target[k], inv_n * inv_wf, floor_eps);
+        for (uint32_t k = threadIdx.x; k < M; k += T) acc += bin_error_w<OBJ, WGT>(src[k], target[k], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f);
         const float total = big_block_sum(acc, red);
         if (threadIdx.x == 0) fitness[row] = total;
         __syncthreads();
@@ -4091,28 +4193,49 @@ __global__ __launch_bounds__(kBigThreads) void k_fitness_big(const float *__rest
 }
 
 // fitnessPopulation on materialised rows with k_fft_x's bin -> (lane, register) map and summation order
-template <int LOG2N, int OBJ = kObjMagnitude, typename... FLOOR>
+template <int LOG2N, int OBJ = kObjMagnitude, bool WGT = false, typename... FLOOR>
 __global__ __launch_bounds__(x_waves<LOG2N>() * kWave) void k_fitness_x(const float *__restrict__ spectrum, const float *__restrict__ target,
                                                                        float *__restrict__ fitness, uint32_t p_len, float inv_n, float inv_wf, FLOOR... floor)
 {
-    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0), "the log instantiation takes the floor");
+    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the log instantiation takes the floor, the weighted one its table");
     [[maybe_unused]] const float floor_eps = obj_floor(floor...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(floor...);
     constexpr int N = 1 << LOG2N, E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), W = x_waves<LOG2N>();
     const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const uint32_t pp = __brev(lane) >> 26;
     for (uint32_t row = blockIdx.x * W + wave; row < p_len; row += gridDim.x * W) {
         const float2 *__restrict__ src = reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8)) + E * pp;
         float acc = 0.0f;
+        if constexpr (WGT) {
+            // The same pairs in the same order, as a loop: unrolled like the form below, the compiler reads row, target and
+            // weights of all E registers ahead, and the third set of E registers spilled at N = 4096 and 8192.
+            const float2 *__restrict__ bins = reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8));
+#pragma unroll 2
+            for (int rr = 0; rr < E; ++rr) {
+                const int q = x_bitrev(rr, EB), r2 = q == 0 ? 0 : x_bitrev(E - q, EB);
+                if (r2 < rr) continue;
+                const int k = E * pp + q;
+                acc += bin_error_w<OBJ, true>(bins[k], target[k], inv_n * inv_wf, floor_eps, wgt_u[k]);
+                if (r2 != rr) {
+#if SOTS_X_PAIR_SPLIT
+                    const int k2 = N / 2 - k;
+#else
+                    const int k2 = E * pp + x_bitrev(r2, EB);
+#endif
+                    acc += bin_error_w<OBJ, true>(bins[k2], target[k2], inv_n * inv_wf, floor_eps, wgt_u[k2]);
+                }
+            }
+        } else
         static_for<0, E>([&](auto r_tag) { // k_fft_x's order: register pairs (RR, R2 = bitrev(E - bitrev(RR)))
             constexpr int RR = decltype(r_tag)::value, Q = x_bitrev(RR, EB), R2 = Q == 0 ? 0 : x_bitrev(E - Q, EB);
             if constexpr (R2 >= RR) {
-                acc += bin_error_o<OBJ>(src[Q], target[E * pp + Q], inv_n * inv_wf, floor_eps);
+                acc += bin_error_w<OBJ, WGT>(src[Q], target[E * pp + Q], inv_n * inv_wf, floor_eps, WGT ? wgt_u[E * pp + Q] : 0.0f);
 #if SOTS_X_PAIR_SPLIT
                 // the pair's second bin is the PARTNER lane's: M - k (k_fft_x's pair2x)
                 if constexpr (R2 != RR)
-                    acc += bin_error_o<OBJ>(reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8))[N / 2 - (E * pp + Q)], target[N / 2 - (E * pp + Q)], inv_n * inv_wf, floor_eps);
+                    acc += bin_error_w<OBJ, WGT>(reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8))[N / 2 - (E * pp + Q)], target[N / 2 - (E * pp + Q)], inv_n * inv_wf, floor_eps, WGT ? wgt_u[N / 2 - (E * pp + Q)] : 0.0f);
 #else
-                if constexpr (R2 != RR) acc += bin_error_o<OBJ>(src[x_bitrev(R2, EB)], target[E * pp + x_bitrev(R2, EB)], inv_n * inv_wf, floor_eps);
+                if constexpr (R2 != RR) acc += bin_error_w<OBJ, WGT>(src[x_bitrev(R2, EB)], target[E * pp + x_bitrev(R2, EB)], inv_n * inv_wf, floor_eps, WGT ? wgt_u[E * pp + x_bitrev(R2, EB)] : 0.0f);
 #endif
             }
         });
@@ -4543,23 +4666,23 @@ static bool x_from(uint32_t log2n) { return log2n == 8 || (log2n >= SOTS_X_MIN &
     }
 static bool big_from(uint32_t log2n) { return log2n == 14 || log2n == 15; }
 // a workgroup per row: as many workgroups as rows, at most four per CU (they loop)
-template <int L, int MODE, bool WIN, bool SEG = false, int OBJ = kObjMagnitude, typename... FL>
+template <int L, int MODE, bool WIN, bool SEG = false, int OBJ = kObjMagnitude, bool WGT = false, typename... FL>
 static hipError_t launch_fft_big(hipStream_t st, uint32_t p, uint32_t num_cus, const float *audio, float *spectrum, const float *target,
                                  float *fitness, const float2 *tw, const float *window, float inv_n, float inv_wf, uint32_t pitch, FL... fl)
 {
     const uint32_t cus = num_cus ? num_cus : 256u, grid = p < 4u * cus ? p : 4u * cus;
     const size_t lds = ((size_t)(1u << L) / 2u) * sizeof(float2) + 64u;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_big<L, MODE, WIN, SEG, OBJ, FL...>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_big<L, MODE, WIN, SEG, OBJ, WGT, FL...>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    k_fft_big<L, MODE, WIN, SEG, OBJ, FL...><<<grid, kBigThreads, lds, st>>>(audio, spectrum, target, fitness, tw, window, p, inv_n, inv_wf, pitch, fl...);
+    k_fft_big<L, MODE, WIN, SEG, OBJ, WGT, FL...><<<grid, kBigThreads, lds, st>>>(audio, spectrum, target, fitness, tw, window, p, inv_n, inv_wf, pitch, fl...);
     return hipGetLastError();
 }
-template <int L, int OBJ = kObjMagnitude, typename... FL>
+template <int L, int OBJ = kObjMagnitude, bool WGT = false, typename... FL>
 static hipError_t launch_fitness_big(hipStream_t st, uint32_t p, uint32_t num_cus, const float *spectrum, const float *target, float *fitness,
                                      float inv_n, float inv_wf, FL... fl)
 {
     const uint32_t cus = num_cus ? num_cus : 256u, grid = p < 4u * cus ? p : 4u * cus;
-    k_fitness_big<L, OBJ, FL...><<<grid, kBigThreads, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...);
+    k_fitness_big<L, OBJ, WGT, FL...><<<grid, kBigThreads, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...);
     return hipGetLastError();
 }
 #define SOTS_X_GRID(K, L, MODE) resident_grid(K, x_waves<L, MODE>() * kWave, (p + x_waves<L, MODE>() - 1) / x_waves<L, MODE>(), num_cus, &occ_x[L])
@@ -4605,25 +4728,25 @@ hipError_t launch_fft(hipStream_t st, const float *audio, float *spectrum, const
     return hipGetLastError();
 }
 
-// OBJ, FL: the objective and, for the log one, its floor (the kernels' last argument); the magnitude instantiations are
-// launched exactly as before
-template <int OBJ, typename... FL>
+// OBJ, WGT, FL: the objective and the weights; FL holds the log objective's floor and then the weighted kernels' table
+// (the kernels' last arguments); the unweighted magnitude instantiations are launched exactly as before
+template <int OBJ, bool WGT, typename... FL>
 static hipError_t launch_fitness_o(hipStream_t st, const float *spectrum, const float *target, float *fitness,
                                    uint32_t p, uint32_t log2n, float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, FL... fl)
 {
     int *occ = oc->fitness;
     if (big_from(log2n)) {
-        if (log2n == 14) return launch_fitness_big<14, OBJ, FL...>(st, p, num_cus, spectrum, target, fitness, inv_n, inv_wf, fl...);
-        return launch_fitness_big<15, OBJ, FL...>(st, p, num_cus, spectrum, target, fitness, inv_n, inv_wf, fl...);
+        if (log2n == 14) return launch_fitness_big<14, OBJ, WGT, FL...>(st, p, num_cus, spectrum, target, fitness, inv_n, inv_wf, fl...);
+        return launch_fitness_big<15, OBJ, WGT, FL...>(st, p, num_cus, spectrum, target, fitness, inv_n, inv_wf, fl...);
     }
     if (x_from(log2n)) {
         int *occ_x = oc->x_fitness;
-#define CALL(L) k_fitness_x<L, OBJ, FL...><<<SOTS_X_GRID((k_fitness_x<L, OBJ, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...)
+#define CALL(L) k_fitness_x<L, OBJ, WGT, FL...><<<SOTS_X_GRID((k_fitness_x<L, OBJ, WGT, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...)
         SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
         return hipGetLastError();
     }
-#define CALL(L) k_fitness<L, OBJ, FL...><<<resident_grid(k_fitness<L, OBJ, FL...>, kWave, p, num_cus, &occ[L]), kWave, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...)
+#define CALL(L) k_fitness<L, OBJ, WGT, FL...><<<resident_grid(k_fitness<L, OBJ, WGT, FL...>, kWave, p, num_cus, &occ[L]), kWave, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...)
     SOTS_DISPATCH_WAVE(log2n, CALL)
 #undef CALL
     return hipGetLastError();
@@ -4632,10 +4755,14 @@ static hipError_t launch_fitness_o(hipStream_t st, const float *spectrum, const 
 hipError_t launch_fitness(hipStream_t st, const float *spectrum, const float *target, float *fitness,
                           uint32_t p, uint32_t log2n, float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, const Objective &obj)
 {
-    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE)
-        return launch_fitness_o<kObjLogMagnitude>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc, obj.floor);
+    const float *const u = obj.weights; // (the staged kernels index the plain table by bin)
+    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE) {
+        if (u) return launch_fitness_o<kObjLogMagnitude, true>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc, obj.floor, u);
+        return launch_fitness_o<kObjLogMagnitude, false>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc, obj.floor);
+    }
     if (obj.kind != SOTS_OBJECTIVE_MAGNITUDE) return hipErrorInvalidValue;
-    return launch_fitness_o<kObjMagnitude>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc);
+    if (u) return launch_fitness_o<kObjMagnitude, true>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc, u);
+    return launch_fitness_o<kObjMagnitude, false>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc);
 }
 
 hipError_t launch_objective_map(hipStream_t st, float *dst, const float *src, size_t n, float floor)
@@ -4667,14 +4794,14 @@ hipError_t launch_x_tables(hipStream_t st, float *image, const float2 *twiddle, 
     return hipGetLastError();
 }
 
-template <int OBJ, typename... FL>
+template <int OBJ, bool WGT, typename... FL>
 static hipError_t launch_fft_fitness_o(hipStream_t st, const float *audio, const float *window, const float *target,
                                        float *fitness, const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch,
                                        float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, const SelLists *lists, FL... fl)
 {
     // The forms without a window exist for the magnitude objective only (the library itself always passes its window; the
     // log N = 4096 form without one would not fit its 128 registers): elsewhere a missing window is an error, not another kernel
-    constexpr bool RAW = OBJ == kObjMagnitude;
+    constexpr bool RAW = OBJ == kObjMagnitude && !WGT; // (nor for a weighted launch)
     if (!RAW && !window) return hipErrorInvalidValue;
     int *occ_w = oc->fused_win;
     [[maybe_unused]] int *occ_n = oc->fused_raw;
@@ -4682,16 +4809,16 @@ static hipError_t launch_fft_fitness_o(hipStream_t st, const float *audio, const
         if (!window || !select_lists_apply(p, log2n, num_cus) || lists->buckets != select_splitter_count(num_cus) || !lists->slot || !lists->cnt || !lists->lists)
             return hipErrorInvalidValue;
         constexpr int W = fft_wide_waves<10>();
-        k_fft<10, 1, true, W, false, true, OBJ, SelLists, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, false, true, OBJ, SelLists, FL...>), 3), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, *lists, fl...);
+        k_fft<10, 1, true, W, false, true, OBJ, WGT, SelLists, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, false, true, OBJ, WGT, SelLists, FL...>), 3), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, *lists, fl...);
         return hipGetLastError();
     }
     if (big_from(log2n)) {
         if (log2n == 14) {
-            if (window) return launch_fft_big<14, 1, true, false, OBJ, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
-            if constexpr (RAW) return launch_fft_big<14, 1, false, false, OBJ, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, nullptr, inv_n, inv_wf, pitch, fl...);
+            if (window) return launch_fft_big<14, 1, true, false, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
+            if constexpr (RAW) return launch_fft_big<14, 1, false, false, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, nullptr, inv_n, inv_wf, pitch, fl...);
         }
-        if (window) return launch_fft_big<15, 1, true, false, OBJ, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
-        if constexpr (RAW) return launch_fft_big<15, 1, false, false, OBJ, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, nullptr, inv_n, inv_wf, pitch, fl...);
+        if (window) return launch_fft_big<15, 1, true, false, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
+        if constexpr (RAW) return launch_fft_big<15, 1, false, false, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, nullptr, inv_n, inv_wf, pitch, fl...);
     }
     if (x_from(log2n)) {
         if (window) {
@@ -4700,17 +4827,17 @@ static hipError_t launch_fft_fitness_o(hipStream_t st, const float *audio, const
             // N = 4096 and 2048, where x_waves is 16; N = 8192 (x_waves 8) follows it unmeasured
             if ((p + x_waves<12>() - 1) / x_waves<12>() < (num_cus ? num_cus : 256u)) {
                 int *occ_s = oc->x_small;
-#define CALL(L) k_fft_x<L, 1, true, 4, false, OBJ, FL...><<<resident_grid((k_fft_x<L, 1, true, 4, false, OBJ, FL...>), 4 * kWave, (p + 3) / 4, num_cus, &occ_s[L]), 4 * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
+#define CALL(L) k_fft_x<L, 1, true, 4, false, OBJ, WGT, FL...><<<resident_grid((k_fft_x<L, 1, true, 4, false, OBJ, WGT, FL...>), 4 * kWave, (p + 3) / 4, num_cus, &occ_s[L]), 4 * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
                 SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
                 return hipGetLastError();
             }
-#define CALL(L) k_fft_x<L, 1, true, x_waves<L>(), false, OBJ, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, true, x_waves<L>(), false, OBJ, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
+#define CALL(L) k_fft_x<L, 1, true, x_waves<L>(), false, OBJ, WGT, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, true, x_waves<L>(), false, OBJ, WGT, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
             SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
         } else if constexpr (RAW) {
             int *occ_x = oc->x_fused_raw;
-#define CALL(L) k_fft_x<L, 1, false, x_waves<L>(), false, OBJ, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, false, x_waves<L>(), false, OBJ, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, nullptr, fl...)
+#define CALL(L) k_fft_x<L, 1, false, x_waves<L>(), false, OBJ, WGT, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, false, x_waves<L>(), false, OBJ, WGT, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, nullptr, fl...)
             SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
         }
@@ -4718,18 +4845,18 @@ static hipError_t launch_fft_fitness_o(hipStream_t st, const float *audio, const
     }
     if (fft_wide(p, log2n, num_cus)) {
         constexpr int W = fft_wide_waves<10>();
-        if (window) k_fft<10, 1, true, W, false, false, OBJ, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, false, false, OBJ, FL...>), 1), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...);
-        else if constexpr (RAW) k_fft<10, 1, false, W, false, false, OBJ, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, false, W, false, false, OBJ, FL...>), 2), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, fl...);
+        if (window) k_fft<10, 1, true, W, false, false, OBJ, WGT, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, false, false, OBJ, WGT, FL...>), 1), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...);
+        else if constexpr (RAW) k_fft<10, 1, false, W, false, false, OBJ, WGT, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, false, W, false, false, OBJ, WGT, FL...>), 2), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, fl...);
         return hipGetLastError();
     }
     if (window) {
-#define CALL(L) k_fft<L, 1, true, 1, false, false, OBJ, FL...><<<resident_grid((k_fft<L, 1, true, 1, false, false, OBJ, FL...>), kWave, p, num_cus, &occ_w[L]), kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...)
+#define CALL(L) k_fft<L, 1, true, 1, false, false, OBJ, WGT, FL...><<<resident_grid((k_fft<L, 1, true, 1, false, false, OBJ, WGT, FL...>), kWave, p, num_cus, &occ_w[L]), kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...)
         SOTS_DISPATCH_WAVE(log2n, CALL)
 #undef CALL
         return hipGetLastError();
     }
     if constexpr (RAW) {
-#define CALL(L) k_fft<L, 1, false, 1, false, false, OBJ, FL...><<<resident_grid((k_fft<L, 1, false, 1, false, false, OBJ, FL...>), kWave, p, num_cus, &occ_n[L]), kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, fl...)
+#define CALL(L) k_fft<L, 1, false, 1, false, false, OBJ, WGT, FL...><<<resident_grid((k_fft<L, 1, false, 1, false, false, OBJ, WGT, FL...>), kWave, p, num_cus, &occ_n[L]), kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, fl...)
         SOTS_DISPATCH_WAVE(log2n, CALL)
 #undef CALL
     }
@@ -4740,10 +4867,15 @@ hipError_t launch_fft_fitness(hipStream_t st, const float *audio, const float *w
                               float *fitness, const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch,
                               float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, const SelLists *lists, const Objective &obj)
 {
-    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE)
-        return launch_fft_fitness_o<kObjLogMagnitude>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists, obj.floor);
+    if (obj.weights && !obj.weights_image) return hipErrorInvalidValue;
+    const float *const u = obj.weights ? weight_table(obj.weights_image) : nullptr; // (in the layout of the kernel's target table)
+    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE) {
+        if (u) return launch_fft_fitness_o<kObjLogMagnitude, true>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists, obj.floor, u);
+        return launch_fft_fitness_o<kObjLogMagnitude, false>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists, obj.floor);
+    }
     if (obj.kind != SOTS_OBJECTIVE_MAGNITUDE) return hipErrorInvalidValue;
-    return launch_fft_fitness_o<kObjMagnitude>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists);
+    if (u) return launch_fft_fitness_o<kObjMagnitude, true>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists, u);
+    return launch_fft_fitness_o<kObjMagnitude, false>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists);
 }
 
 constexpr uint32_t kSortMaxTiles = 256;
@@ -5074,38 +5206,48 @@ hipError_t launch_seg_targets(hipStream_t st, float *image, const float *targets
     return hipGetLastError();
 }
 
+// The weight table of the fused kernels: u[N/2] laid out as ONE chunk's target table (plain bins for k_fft and k_fft_big,
+// the per-(lane, register) table for k_fft_x), so the weighted kernels read u wherever they read the target
+size_t weight_image_bytes(uint32_t log2n) { return seg_target_bytes(log2n, 1); }
+hipError_t launch_weight_image(hipStream_t st, float *image, const float *u, uint32_t log2n)
+{
+    const hipError_t e = hipMemsetAsync(image, 0, weight_image_bytes(log2n), st); // (the padding entries are never read; they are defined all the same)
+    if (e != hipSuccess) return e;
+    return launch_seg_targets(st, image, u, log2n, 1);
+}
+
 // launch_fft_fitness with a window, every row against its chunk's target: the same kernel choice for the same row
 // count, each kernel's SEG instantiation
-template <int OBJ, typename... FL>
+template <int OBJ, bool WGT, typename... FL>
 static hipError_t launch_fft_fitness_seg_o(hipStream_t st, const float *audio, const float *window, const float *seg_image, float *fitness,
                                            const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
                                            uint32_t num_cus, OccCache *oc, FL... fl)
 {
     if (big_from(log2n)) {
-        if (log2n == 14) return launch_fft_big<14, 1, true, true, OBJ, FL...>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
-        return launch_fft_big<15, 1, true, true, OBJ, FL...>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
+        if (log2n == 14) return launch_fft_big<14, 1, true, true, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
+        return launch_fft_big<15, 1, true, true, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
     }
     if (x_from(log2n)) {
         int *occ_x = oc->x_fused_win;
         if ((p + x_waves<12>() - 1) / x_waves<12>() < (num_cus ? num_cus : 256u)) {
             int *occ_s = oc->x_small;
-#define CALL(L) k_fft_x<L, 1, true, 4, true, OBJ, FL...><<<resident_grid((k_fft_x<L, 1, true, 4, true, OBJ, FL...>), 4 * kWave, (p + 3) / 4, num_cus, &occ_s[L]), 4 * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
+#define CALL(L) k_fft_x<L, 1, true, 4, true, OBJ, WGT, FL...><<<resident_grid((k_fft_x<L, 1, true, 4, true, OBJ, WGT, FL...>), 4 * kWave, (p + 3) / 4, num_cus, &occ_s[L]), 4 * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
             SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
             return hipGetLastError();
         }
-#define CALL(L) k_fft_x<L, 1, true, x_waves<L>(), true, OBJ, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, true, x_waves<L>(), true, OBJ, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
+#define CALL(L) k_fft_x<L, 1, true, x_waves<L>(), true, OBJ, WGT, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, true, x_waves<L>(), true, OBJ, WGT, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
         SOTS_DISPATCH_X(log2n, CALL)
 #undef CALL
         return hipGetLastError();
     }
     if (fft_wide(p, log2n, num_cus)) {
         constexpr int W = fft_wide_waves<10>();
-        k_fft<10, 1, true, W, true, false, OBJ, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, true, false, OBJ, FL...>), 1), W * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...);
+        k_fft<10, 1, true, W, true, false, OBJ, WGT, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, true, false, OBJ, WGT, FL...>), 1), W * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...);
         return hipGetLastError();
     }
     int *occ_w = oc->fused_win;
-#define CALL(L) k_fft<L, 1, true, 1, true, false, OBJ, FL...><<<resident_grid((k_fft<L, 1, true, 1, true, false, OBJ, FL...>), kWave, p, num_cus, &occ_w[L]), kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...)
+#define CALL(L) k_fft<L, 1, true, 1, true, false, OBJ, WGT, FL...><<<resident_grid((k_fft<L, 1, true, 1, true, false, OBJ, WGT, FL...>), kWave, p, num_cus, &occ_w[L]), kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...)
     SOTS_DISPATCH_WAVE(log2n, CALL)
 #undef CALL
     return hipGetLastError();
@@ -5115,10 +5257,16 @@ hipError_t launch_fft_fitness_seg(hipStream_t st, const float *audio, const floa
                                   const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
                                   uint32_t num_cus, OccCache *oc, const Objective &obj)
 {
-    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE)
-        return launch_fft_fitness_seg_o<kObjLogMagnitude>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, obj.floor);
+    if (obj.weights && !obj.weights_image) return hipErrorInvalidValue;
+    if (obj.weights && !window) return hipErrorInvalidValue;
+    const float *const u = obj.weights ? weight_table(obj.weights_image) : nullptr; // (one table for all chunks)
+    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE) {
+        if (u) return launch_fft_fitness_seg_o<kObjLogMagnitude, true>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, obj.floor, u);
+        return launch_fft_fitness_seg_o<kObjLogMagnitude, false>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, obj.floor);
+    }
     if (obj.kind != SOTS_OBJECTIVE_MAGNITUDE) return hipErrorInvalidValue;
-    return launch_fft_fitness_seg_o<kObjMagnitude>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc);
+    if (u) return launch_fft_fitness_seg_o<kObjMagnitude, true>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, u);
+    return launch_fft_fitness_seg_o<kObjMagnitude, false>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc);
 }
 
 hipError_t launch_sort_seg(hipStream_t st, const float *vin, const float *sin, const float *fin, float *vout, float *sout,

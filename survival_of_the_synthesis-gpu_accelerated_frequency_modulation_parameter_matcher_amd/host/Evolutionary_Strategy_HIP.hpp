@@ -26,6 +26,7 @@
 #include "../../include/sots_hip.h"
 #include "Benchmarker.hpp"
 #include "Evolutionary_Strategy.hpp"
+#include "Objective_weights.hpp"
 
 struct Evolutionary_Strategy_HIP_Arguments
 {
@@ -105,6 +106,13 @@ struct Evolutionary_Strategy_HIP_Arguments
     uint32_t objective = SOTS_OBJECTIVE_MAGNITUDE;
     float objectiveFloor = 0.0f;
     bool objectiveGiven = false;
+    // Per-bin weights of the objective (type.HIP.objectiveWeights; sots_set_objective_weights, Objective_weights.hpp): a
+    // band in Hz, the A-curve or a table of N/2 numbers; the fitness is then sum_k w_k e_k^2 over the bins, and every
+    // fitness printed, the history's columns and targetFitness are in the units of that weighted sum.  The table is made
+    // for N and the class's sampleRate in the constructor, which throws - before any device work - where it cannot be.
+    // Applied to the context, to every island of a group and to the chunks in flight (batched and queued alike).
+    // sots_match names the weighting in its output (one line) only when parameters.json named it.
+    Objective_Weights_Spec objectiveWeights;
     bool returnBestEver = false;
     uint32_t historyEvery = 0;
     std::string historyPath = "";
@@ -132,6 +140,7 @@ private:
     uint32_t chunkSize_ = 0;
     uint32_t targetAudioLength = 0;
     std::vector<float> targetFFT_;
+    std::vector<float> objectiveWeights_;       // the table of args_.objectiveWeights for this N; empty: no weights
     std::vector<std::vector<float>> bestPerChunk_;
     std::vector<float> bestFitnessPerChunk_;
     std::vector<uint32_t> generationsPerChunk_; // generations each chunk's result was taken after
@@ -261,6 +270,12 @@ public:
     const std::vector<uint32_t> &generationsPerChunk() const { return generationsPerChunk_; }
     // generations really run by the last parameterMatchAudio, summed over its chunks (chunks in flight run to their batch's end)
     uint64_t generationsRun() const { return generationsRun_; }
+    // bins with a positive weight (all N/2 of them without weights)
+    uint32_t objectiveWeightBins() const
+    {
+        if (objectiveWeights_.empty()) return objective.fftHalfSize;
+        return (uint32_t)std::count_if(objectiveWeights_.begin(), objectiveWeights_.end(), [](float w) { return w > 0.0f; });
+    }
     // candidates evaluated per second of the last parameterMatchAudio (population x generations x chunks / wall time)
     double candidatesPerSecond() const { return candidatesPerSecond_; }
 
@@ -285,6 +300,7 @@ public:
             cfg_.param_min[i] = i < objective.paramMins.size() ? objective.paramMins[i] : 0.0f;
             cfg_.param_max[i] = i < objective.paramMaxs.size() ? objective.paramMaxs[i] : 0.0f;
         }
+        objectiveWeights_ = makeObjectiveWeights(args_.objectiveWeights, objective.audioLength, (double)objective.sampleRate); // (throws before any device work)
         if (args_.numDevices > 1) {
             std::vector<int32_t> devs = args_.devices;
             if (devs.empty())
@@ -313,6 +329,12 @@ public:
                 if (sots_group_set_objective(group_, args_.objective, args_.objectiveFloor) != SOTS_OK)
                     throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_group_set_objective: ") + sots_group_last_error(group_));
             } else check(sots_set_objective(ctx_, args_.objective, args_.objectiveFloor), "sots_set_objective");
+        }
+        if (!objectiveWeights_.empty()) {
+            if (group_) {
+                if (sots_group_set_objective_weights(group_, objectiveWeights_.data(), (uint32_t)objectiveWeights_.size()) != SOTS_OK)
+                    throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_group_set_objective_weights: ") + sots_group_last_error(group_));
+            } else check(sots_set_objective_weights(ctx_, objectiveWeights_.data(), (uint32_t)objectiveWeights_.size()), "sots_set_objective_weights");
         }
         check(sots_timing_enable(ctx_, args_.benchmarkStages ? 1 : 0), "sots_timing_enable");
         if (tracking()) {
@@ -517,6 +539,8 @@ private:
         if (args_.deviceKernelArithmetic) checkBatch(sots_batch_set_synth_arithmetic(batch_, SOTS_ARITH_DEVICE_KERNELS), "sots_batch_set_synth_arithmetic");
         checkBatch(sots_batch_set_survivors(batch_, args_.survivors), "sots_batch_set_survivors");
         checkBatch(sots_batch_set_objective(batch_, args_.objective, args_.objectiveFloor), "sots_batch_set_objective");
+        if (!objectiveWeights_.empty())
+            checkBatch(sots_batch_set_objective_weights(batch_, objectiveWeights_.data(), (uint32_t)objectiveWeights_.size()), "sots_batch_set_objective_weights");
         checkBatch(sots_batch_track(batch_, SOTS_TRACK_BEST_EVER, 0, 0), "sots_batch_track"); // (the queue keeps the best-ever record itself)
         std::vector<float> mags((size_t)numChunks_ * half);
         for (uint32_t c = 0; c < numChunks_; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)chunkSize_ * c], mags.data() + (size_t)c * half);
@@ -561,6 +585,8 @@ private:
         if (args_.deviceKernelArithmetic) checkBatch(sots_batch_set_synth_arithmetic(batch_, SOTS_ARITH_DEVICE_KERNELS), "sots_batch_set_synth_arithmetic");
         checkBatch(sots_batch_set_survivors(batch_, args_.survivors), "sots_batch_set_survivors");
         checkBatch(sots_batch_set_objective(batch_, args_.objective, args_.objectiveFloor), "sots_batch_set_objective");
+        if (!objectiveWeights_.empty())
+            checkBatch(sots_batch_set_objective_weights(batch_, objectiveWeights_.data(), (uint32_t)objectiveWeights_.size()), "sots_batch_set_objective_weights");
         if (tracking()) checkBatch(sots_batch_track(batch_, trackFlags(), args_.historyEvery, historyCapacity()), "sots_batch_track");
         std::vector<float> mags((size_t)perBatch * half), values((size_t)perBatch * d), fitness(perBatch);
         std::vector<float> nowValues((size_t)perBatch * d), nowFitness(perBatch), everFitness(perBatch);

@@ -12,6 +12,8 @@
 #include <string>
 #include <vector>
 
+#include "Objective_weights.hpp"
+
 // ---------------------------------------------------------------------------------------
 // minimal JSON (objects, arrays, numbers, strings, true/false/null)
 // ---------------------------------------------------------------------------------------
@@ -144,6 +146,40 @@ inline bool readObjectiveKeys(const Json &h, uint32_t &objective, float &floor)
     }
     objective = o;
     floor = f;
+    return true;
+}
+
+// type.HIP.objectiveWeights (sots_set_objective_weights, Objective_weights.hpp): which part of the spectrum counts.
+//   {"bandHz": [lo, hi]}   weight 1 on the bins with lo <= f <= hi, 0 elsewhere (0 <= lo < hi)
+//   "aWeighting"           the A-curve as a power weight
+//   [w_0, ..., w_{N/2-1}]  the table itself
+// Returns whether the key was there.  Throws on another shape, lo >= hi, a negative or non-finite entry, all zeros; what
+// depends on N and the sample rate (a band without a bin, the array's length) is makeObjectiveWeights' to refuse.
+inline bool readObjectiveWeightsKey(const Json &h, Objective_Weights_Spec &spec)
+{
+    if (!h.has("objectiveWeights")) return false;
+    const Json &v = h["objectiveWeights"];
+    const std::string what = "parameters.json: type.HIP.objectiveWeights";
+    Objective_Weights_Spec s;
+    if (v.kind == Json::String) {
+        if (v.str != "aWeighting") throw std::runtime_error(what + " must be \"aWeighting\", {\"bandHz\": [lo, hi]} or an array, not \"" + v.str + "\"");
+        s.kind = Objective_Weights_Spec::AWeighting;
+    } else if (v.kind == Json::Object) {
+        if (!v.has("bandHz") || v.obj.size() != 1 || v["bandHz"].kind != Json::Array || v["bandHz"].arr.size() != 2)
+            throw std::runtime_error(what + ": an object must be {\"bandHz\": [lo, hi]}");
+        s.kind = Objective_Weights_Spec::Band;
+        s.lo = v["bandHz"].arr[0].number();
+        s.hi = v["bandHz"].arr[1].number();
+        if (!(s.lo >= 0.0) || !(s.lo < s.hi) || !std::isfinite(s.hi)) throw std::runtime_error(what + ": bandHz needs 0 <= lo < hi");
+    } else if (v.kind == Json::Array) {
+        s.kind = Objective_Weights_Spec::Table;
+        s.table = v.floats();
+        if (s.table.empty()) throw std::runtime_error(what + ": the array is empty");
+        checkObjectiveWeights(s.table, what);
+    } else {
+        throw std::runtime_error(what + " must be \"aWeighting\", {\"bandHz\": [lo, hi]} or an array");
+    }
+    spec = s;
     return true;
 }
 

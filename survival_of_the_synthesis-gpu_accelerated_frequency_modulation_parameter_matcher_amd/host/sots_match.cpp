@@ -3,7 +3,7 @@
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
 // "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "numDevices", "numElites",
 // "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight", "chunkQueue",
-// "survivors", "objective", "objectiveFloor", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
+// "survivors", "objective", "objectiveFloor", "objectiveWeights", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
 // N-sample chunk with Evolutionary_Strategy_HIP, writes inputGenerated.wav and the
 // outputAudioPath rendering of the best match, and prints the best parameters.
@@ -100,6 +100,8 @@ int main(int argc, char *argv[])
             }
             // the spectral objective: "magnitude" (the reference's, the default) or "logMagnitude" with its floor (Match_JSON.hpp)
             args.objectiveGiven = readObjectiveKeys(h, args.objective, args.objectiveFloor);
+            // per-bin weights of that objective: {"bandHz": [lo, hi]}, "aWeighting" or an array of N/2 numbers (Match_JSON.hpp)
+            (void)readObjectiveWeightsKey(h, args.objectiveWeights);
             // run record (Evolutionary_Strategy_HIP_Arguments): the best individual any generation produced, a history CSV,
             // and stopping a chunk early on a fitness target or a stall
             if (h.has("returnBestEver")) args.returnBestEver = h["returnBestEver"].b;
@@ -148,6 +150,8 @@ int main(int argc, char *argv[])
 
         if (args.objectiveGiven) // (without the keys: not a byte more than before)
             printf("Objective: %s, floor %g\n", args.objective == SOTS_OBJECTIVE_LOG_MAGNITUDE ? "logMagnitude" : "magnitude", (double)args.objectiveFloor);
+        if (args.objectiveWeights.given()) // (likewise)
+            printf("Objective weights: %s, %u of %u bins count\n", args.objectiveWeights.describe().c_str(), hipEs->objectiveWeightBins(), N / 2);
         const auto start = std::chrono::steady_clock::now();
         es->parameterMatchAudio(targetAudio.data(), (uint32_t)targetAudio.size());
         const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
