@@ -257,6 +257,36 @@ int sots_get_objective_weights(const sots_ctx *ctx, float *weights, uint32_t num
 int sots_get_generation(const sots_ctx *ctx, uint32_t *generation);
 int sots_set_generation(sots_ctx *ctx, uint32_t generation);
 
+/* ---- overlap-add rendering of a parameter track (new; the reference writes the last chunk's best row and stops,
+ *      main.cpp:270-275) ----
+ * values is [num_rows][D] unit-range genes, as sots_write_population takes them; row c is the individual that stands for
+ * samples [c hop, c hop + N) of the output.  With a_c row c's audio as sots_stage_synthesise makes it under the context's
+ * voice and sots_set_synth_arithmetic mode, and w the context's fp32 window table (1 - cos, periodic: w[0] = 0, peak 2) or
+ * all ones without SOTS_RENDER_WINDOWED,
+ *   acc[n] = sum w[n - c hop] * a_c[n - c hop]   over the chunks c that cover n, in ASCENDING c,
+ *   den[n] = sum w[n - c hop]                    the same chunks, the same order,
+ *   out[n] = den[n] > 0 ? acc[n] / den[n] : 0    (samples no chunk covers are 0: n >= (num_rows - 1) hop + N)
+ * all in fp32: one multiply and one add per term, uncontracted, and the correctly rounded division - the same inputs give
+ * the same bits on every run (a gather: no atomics), tests/_render_model.py states them in NumPy.  Rectangular with
+ * hop = N the output is the rows' audio end to end.
+ * The work goes in passes: a pass produces the samples of rows_per_pass consecutive chunk starts and synthesises, into
+ * render scratch of the context's own (allocated by the first call, freed with the context), those chunks and the
+ * ceil(N / hop) - 1 chunks in front of them that reach into its range - chunks that straddle a pass boundary are
+ * synthesised again.  The result does not depend on the pass size.  out (host memory) receives out_samples samples:
+ * fewer than the covered range truncates, more gives zeros.
+ * Blocking.  The population, both rotation halves, the audio and spectrum buffers, fitness, generation counter, run
+ * record, splitters and lists are untouched.  SOTS_ERR_INVALID for null or mis-sized args, a hop outside
+ * ceil(N / 64) .. N, unknown flag bits or num_rows == 0; SOTS_ERR_SIZE for values_bytes != num_rows * D * 4. */
+enum sots_render_flags { SOTS_RENDER_WINDOWED = 1 };
+typedef struct sots_render_args {
+    uint32_t struct_size;    /* = sizeof(sots_render_args) */
+    uint32_t hop;            /* samples between chunk starts, ceil(N/64) <= hop <= N, need not divide N */
+    uint32_t flags;          /* enum sots_render_flags */
+    uint32_t rows_per_pass;  /* 0 = the library's choice; else chunk starts per pass, >= 1 */
+} sots_render_args;
+int sots_render_overlap_add(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
+                            const sots_render_args *args, float *out, uint64_t out_samples);
+
 /* ---- per-stage device timing (feeds Benchmarker::addTimer, Benchmarker.hpp:109-130) ---- */
 int sots_timing_enable(sots_ctx *ctx, int enabled);
 int sots_timing_reset(sots_ctx *ctx);
@@ -369,6 +399,10 @@ int sots_batch_synchronize(sots_batch *b);
  * num_chunks * N; num_bins == num_chunks * N/2.  Sets the number of ACTIVE chunks for the calls below. */
 int sots_batch_set_target_audio(sots_batch *b, const float *audio, uint32_t num_samples, uint32_t num_chunks);
 int sots_batch_set_target_spectra(sots_batch *b, const float *magnitudes, uint32_t num_bins, uint32_t num_chunks);
+/* the audio form with chunk k = samples [k hop, k hop + N), 1 <= hop <= N (SOTS_ERR_INVALID otherwise): analysis at a hop.
+ * num_samples >= (num_chunks - 1) hop + N, else SOTS_ERR_SIZE.  sots_batch_set_target_audio is the hop = N case of the
+ * same code. */
+int sots_batch_set_target_audio_hop(sots_batch *b, const float *audio, uint32_t num_samples, uint32_t hop, uint32_t num_chunks);
 /* active chunk c is initialised exactly as sots_init_population(ctx, first_chunk_index + c) would */
 int sots_batch_init_population(sots_batch *b, uint32_t first_chunk_index);
 /* n generations of every active chunk; only enqueues */
@@ -487,6 +521,9 @@ typedef struct sots_queue_stats {
  * num_bins == num_chunks * N/2 and num_samples >= num_chunks * N, else SOTS_ERR_SIZE.  Replaces an earlier queue. */
 int sots_batch_queue_targets_spectra(sots_batch *b, const float *magnitudes, uint64_t num_bins, uint32_t num_chunks);
 int sots_batch_queue_targets_audio(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t num_chunks);
+/* the audio form with chunk k = samples [k hop, k hop + N), 1 <= hop <= N (SOTS_ERR_INVALID otherwise);
+ * num_samples >= (num_chunks - 1) hop + N, else SOTS_ERR_SIZE.  sots_batch_queue_targets_audio is its hop = N case. */
+int sots_batch_queue_targets_audio_hop(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t hop, uint32_t num_chunks);
 /* Runs the stored queue; blocks until the last chunk is retired.  rule NULL: every chunk runs max_generations (>= 1).
  * max_generations need not be a multiple of rule->check_interval: a chunk's last block is the shorter one, as in
  * sots_execute_until.  keep_chunk (SOTS_QUEUE_NO_CHUNK: none; else < num_chunks): that chunk's whole current half, as it

@@ -68,8 +68,10 @@ EXPORTS = [
     "sots_set_objective", "sots_get_objective", "sots_batch_set_objective", "sots_group_set_objective",
     "sots_set_objective_weights", "sots_get_objective_weights", "sots_batch_set_objective_weights",
     "sots_group_set_objective_weights",
+    "sots_render_overlap_add", "sots_batch_set_target_audio_hop", "sots_batch_queue_targets_audio_hop",
 ]
 QUEUE_NO_CHUNK = 0xFFFFFFFF
+RENDER_WINDOWED = 1
 TRACK_BEST_EVER, TRACK_HISTORY = 1, 2
 BATCH_MAX_POPULATION = 1024
 GROUP_OVERLAP, GROUP_FORCE_RCCL, GROUP_UNFUSED, GROUP_EVENT_WAITS = 1, 2, 4, 8
@@ -134,6 +136,11 @@ CHUNK_RESULT_DTYPE = np.dtype([("generations_run", np.uint32), ("best_ever_gener
                                ("best_ever_fitness", np.float32), ("last_fitness", np.float32),
                                ("best_ever_values", np.float32, (MAX_DIMS,)), ("best_ever_steps", np.float32, (MAX_DIMS,)),
                                ("last_values", np.float32, (MAX_DIMS,))])
+
+
+class RenderArgs(C.Structure):
+    """sots_render_args"""
+    _fields_ = [("struct_size", C.c_uint32), ("hop", C.c_uint32), ("flags", C.c_uint32), ("rows_per_pass", C.c_uint32)]
 
 
 class QueueStats(C.Structure):
@@ -265,6 +272,9 @@ def load():
     L.sots_batch_queue_results.argtypes = [vp, vp, u32, C.POINTER(u32)]
     L.sots_batch_queue_read_kept_population.argtypes = [vp, vp, sz, vp, sz, vp, sz]
     L.sots_queue_makespan.argtypes = [C.POINTER(u32), u32, u32, u64p]
+    L.sots_render_overlap_add.argtypes = [vp, vp, sz, u32, C.POINTER(RenderArgs), vp, C.c_uint64]
+    L.sots_batch_set_target_audio_hop.argtypes = [vp, vp, u32, u32, u32]
+    L.sots_batch_queue_targets_audio_hop.argtypes = [vp, vp, C.c_uint64, u32, u32]
     _lib = L
     return L
 
@@ -424,6 +434,18 @@ class HipES:
         t = np.empty(self.N // 2, np.float32)
         self._check(self.L.sots_read_synth(self._h, None, 0, None, 0, _ptr(t), t.nbytes))
         return t
+
+    # -- overlap-add rendering of a parameter track --
+    def render_overlap_add(self, values, hop, windowed=True, rows_per_pass=0, out_samples=None):
+        """values[M][D] unit-range genes, row c standing for samples [c hop, c hop + N): the windowed (or rectangular)
+        overlap-add of the rows' audio, normalised by the summed window.  out_samples None: the covered (M-1) hop + N."""
+        v = _f32(values).reshape(-1, self.D)
+        rows = v.shape[0]
+        n_out = (rows - 1) * hop + self.N if out_samples is None else int(out_samples)
+        out = np.empty(max(n_out, 0), np.float32)
+        args = RenderArgs(C.sizeof(RenderArgs), hop, RENDER_WINDOWED if windowed else 0, rows_per_pass)
+        self._check(self.L.sots_render_overlap_add(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
+        return out
 
     # -- stages --
     def recombine(self):
@@ -662,9 +684,16 @@ class HipBatch:
     def synchronize(self):
         self._check(self.L.sots_batch_synchronize(self._h))
 
-    def set_target_audio(self, audio):
-        """audio[num_chunks][N] (or a flat signal cut into N-sample chunks): one target per chunk"""
+    def set_target_audio(self, audio, hop=None):
+        """audio[num_chunks][N] (or a flat signal cut into N-sample chunks): one target per chunk.  With hop, a flat
+        signal whose chunk k is samples [k hop, k hop + N)."""
         a = _f32(audio)
+        if hop is not None:
+            a = a.reshape(-1)
+            chunks = (a.size - self.N) // hop + 1 if a.size >= self.N and hop > 0 else 0
+            self._check(self.L.sots_batch_set_target_audio_hop(self._h, _ptr(a), a.size, hop, chunks))
+            self.active = chunks
+            return
         chunks = a.shape[0] if a.ndim == 2 else a.size // self.N
         self._check(self.L.sots_batch_set_target_audio(self._h, _ptr(a), a.size, chunks))
         self.active = chunks
@@ -743,9 +772,16 @@ class HipBatch:
         return run.value
 
     # -- chunk queue: any number of chunks through the handle's slots, a slot refilled when its chunk's rule holds --
-    def queue_targets_audio(self, audio):
-        """audio[M][N] (or a flat signal cut into N-sample chunks): the targets of M queued chunks, any M"""
+    def queue_targets_audio(self, audio, hop=None):
+        """audio[M][N] (or a flat signal cut into N-sample chunks): the targets of M queued chunks, any M.  With hop, a
+        flat signal whose chunk k is samples [k hop, k hop + N)."""
         a = _f32(audio)
+        if hop is not None:
+            a = a.reshape(-1)
+            chunks = (a.size - self.N) // hop + 1 if a.size >= self.N and hop > 0 else 0
+            self._check(self.L.sots_batch_queue_targets_audio_hop(self._h, _ptr(a), a.size, hop, chunks))
+            self.queued = chunks
+            return
         chunks = a.shape[0] if a.ndim == 2 else a.size // self.N
         self._check(self.L.sots_batch_queue_targets_audio(self._h, _ptr(a), a.size, chunks))
         self.queued = chunks

@@ -340,21 +340,28 @@ int sots_batch_set_target_spectra(sots_batch *b, const float *magnitudes, uint32
     return SOTS_OK;
 }
 
-int sots_batch_set_target_audio(sots_batch *b, const float *audio, uint32_t num_samples, uint32_t num_chunks)
+int sots_batch_set_target_audio_hop(sots_batch *b, const float *audio, uint32_t num_samples, uint32_t hop, uint32_t num_chunks)
 {
     BATCH_REQUIRE(b);
     if (num_chunks == 0 || num_chunks > b->max_chunks)
         return bfail(b, SOTS_ERR_INVALID, "num_chunks %u outside 1..%u", num_chunks, b->max_chunks);
-    if (!audio || (uint64_t)num_samples < (uint64_t)num_chunks * b->N)
-        return bfail(b, SOTS_ERR_SIZE, "%u chunks of target audio need %llu samples, got %u", num_chunks,
-                     (unsigned long long)num_chunks * b->N, num_samples);
+    if (hop == 0 || hop > b->N) return bfail(b, SOTS_ERR_INVALID, "hop %u outside 1..%u", hop, b->N);
+    const uint64_t need = (uint64_t)(num_chunks - 1u) * hop + b->N; // (hop = N: num_chunks * N)
+    if (!audio || (uint64_t)num_samples < need)
+        return bfail(b, SOTS_ERR_SIZE, "%u chunks of target audio need %llu samples, got %u", num_chunks, (unsigned long long)need, num_samples);
     const uint32_t m = b->N / 2;
     std::vector<float> mag((size_t)num_chunks * m);
     for (uint32_t c = 0; c < num_chunks; ++c) { // the single context's host transform, chunk by chunk
-        const std::vector<float> one = target_spectrum(audio + (size_t)c * b->N, b->N, b->window64, b->window_factor);
+        const std::vector<float> one = target_spectrum(audio + (size_t)c * hop, b->N, b->window64, b->window_factor);
         memcpy(mag.data() + (size_t)c * m, one.data(), (size_t)m * sizeof(float));
     }
     return sots_batch_set_target_spectra(b, mag.data(), (uint32_t)mag.size(), num_chunks);
+}
+
+int sots_batch_set_target_audio(sots_batch *b, const float *audio, uint32_t num_samples, uint32_t num_chunks)
+{
+    BATCH_REQUIRE(b);
+    return sots_batch_set_target_audio_hop(b, audio, num_samples, b->N, num_chunks);
 }
 
 int sots_batch_init_population(sots_batch *b, uint32_t first_chunk_index)
@@ -598,7 +605,7 @@ int sots_batch_queue_targets_spectra(sots_batch *b, const float *magnitudes, uin
     return SOTS_OK;
 }
 
-int sots_batch_queue_targets_audio(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t num_chunks)
+int sots_batch_queue_targets_audio_hop(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t hop, uint32_t num_chunks)
 {
     // (what needs no handle is checked first: a machine without a GPU still tells a bad call from a good one)
     if (num_chunks == 0) return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_targets: num_chunks must be at least 1");
@@ -607,15 +614,25 @@ int sots_batch_queue_targets_audio(sots_batch *b, const float *audio, uint64_t n
     if ((uint64_t)num_chunks * m * sizeof(float) > kQueueMaxTargetBytes)
         return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_targets: %u chunks of %llu bins exceed %llu bytes of stored targets", num_chunks,
                      (unsigned long long)m, (unsigned long long)kQueueMaxTargetBytes);
-    if (!audio || num_samples < (uint64_t)num_chunks * b->N)
+    if (hop == 0 || hop > b->N) return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_targets: hop %u outside 1..%u", hop, b->N);
+    const uint64_t need = (uint64_t)(num_chunks - 1u) * hop + b->N; // (hop = N: num_chunks * N)
+    if (!audio || num_samples < need)
         return bfail(b, SOTS_ERR_SIZE, "%u queued chunks of target audio need %llu samples, got %llu", num_chunks,
-                     (unsigned long long)num_chunks * b->N, (unsigned long long)num_samples);
+                     (unsigned long long)need, (unsigned long long)num_samples);
     std::vector<float> mag((size_t)num_chunks * m);
     for (uint32_t c = 0; c < num_chunks; ++c) { // the host transform of sots_batch_set_target_audio, chunk by chunk
-        const std::vector<float> one = target_spectrum(audio + (size_t)c * b->N, b->N, b->window64, b->window_factor);
+        const std::vector<float> one = target_spectrum(audio + (size_t)c * hop, b->N, b->window64, b->window_factor);
         memcpy(mag.data() + (size_t)c * m, one.data(), (size_t)m * sizeof(float));
     }
     return sots_batch_queue_targets_spectra(b, mag.data(), mag.size(), num_chunks);
+}
+
+int sots_batch_queue_targets_audio(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t num_chunks)
+{
+    // (what needs no handle is checked first: a machine without a GPU still tells a bad call from a good one)
+    if (num_chunks == 0) return bfail(b, SOTS_ERR_INVALID, "sots_batch_queue_targets: num_chunks must be at least 1");
+    BATCH_REQUIRE(b);
+    return sots_batch_queue_targets_audio_hop(b, audio, num_samples, b->N, num_chunks);
 }
 
 int sots_batch_queue_run(sots_batch *b, uint32_t first_chunk_index, uint32_t max_generations, const sots_stop_rule *rule,

@@ -15,6 +15,7 @@
 #include "../../include/sots_hip.h"
 #include "sots_host_math.h"
 #include "sots_kernels.h"
+#include "sots_render.h"
 #include "sots_stop_rule.h"
 #include "sots_track.h"
 
@@ -97,6 +98,8 @@ struct sots_ctx {
     SortExchange next_exchange{};
     bool next_exchange_set = false;
     hipEvent_t next_exchange_gate = nullptr; // the HOST waits for it right before that sort is enqueued
+    // overlap-add rendering (sots_render_overlap_add): scratch of its own, allocated by the first rendering
+    RenderScratch render{};
     // experiment switches; fixed in the shipped library, settable from the environment only in a
     // -DSOTS_EXPERIMENT build (tools/exp_*.sh)
     bool allow_cut = true;
@@ -267,6 +270,7 @@ void free_ctx(sots_ctx *ctx)
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     track_release(ctx->track);
+    render_release(ctx->render);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     (void)hipGetLastError(); // nothing sticky survives a context (the launchers read hipGetLastError after each launch)
     delete ctx;
@@ -1249,6 +1253,65 @@ int sots_set_generation(sots_ctx *ctx, uint32_t generation)
 {
     SOTS_REQUIRE_CTX(ctx);
     ctx->generation = generation;
+    return SOTS_OK;
+}
+
+// ---- overlap-add rendering ----------------------------------------------------
+int sots_render_overlap_add(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows, const sots_render_args *args,
+                            float *out, uint64_t out_samples)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (!args || args->struct_size != sizeof(sots_render_args))
+        return fail(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: null args or sots_render_args.struct_size != %zu", sizeof(sots_render_args));
+    const uint32_t N = ctx->N, hop = args->hop;
+    if (hop < (N + 63u) / 64u || hop > N)
+        return fail(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: hop %u outside %u..%u", hop, (N + 63u) / 64u, N);
+    if (args->flags & ~(uint32_t)SOTS_RENDER_WINDOWED) return fail(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: unknown flags 0x%x", args->flags);
+    if (num_rows == 0) return fail(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: num_rows must be at least 1");
+    if (!values || values_bytes != (size_t)num_rows * ctx->D * sizeof(float))
+        return fail(ctx, SOTS_ERR_SIZE, "sots_render_overlap_add: %u rows need %zu bytes of values, got %zu", num_rows,
+                    (size_t)num_rows * ctx->D * sizeof(float), values_bytes);
+    if (!out && out_samples) return fail(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: null output");
+    if (int rc = bind_device(ctx)) return rc;
+
+    // A pass takes `step` chunk starts of output and holds, besides those chunks, the `reach` chunks in front of them that
+    // extend into its range: synthesised again, so a pass needs nothing of the pass before it.
+    const uint32_t reach = (N + hop - 1u) / hop - 1u, cap = render_max_rows(ctx->pitch);
+    uint32_t step = args->rows_per_pass ? args->rows_per_pass : 4096u;
+    step = step > cap ? cap : step;
+    step = step > num_rows ? num_rows : step;
+    const uint64_t covered = (uint64_t)(num_rows - 1u) * hop + N, want = out_samples < covered ? out_samples : covered;
+    const size_t max_rows = (size_t)step + reach;
+    // (the synthesis kernels store whole tiles of rows where a tile is full: a margin of one tile behind the last row)
+    if (hipError_t e = render_reserve(ctx->render, max_rows * ctx->D, (max_rows + 64u) * ctx->pitch, (size_t)step * hop + N + 4u)) {
+        (void)hipGetLastError();
+        return fail(ctx, SOTS_ERR_HIP, "sots_render_overlap_add: scratch allocation failed: %s", hipGetErrorString(e));
+    }
+    for (uint32_t r0 = 0; r0 < num_rows && (uint64_t)r0 * hop < want; r0 += step) {
+        const uint32_t r1 = num_rows - r0 > step ? r0 + step : num_rows, first = r0 > reach ? r0 - reach : 0u, rows = r1 - first;
+        const uint64_t s0 = (uint64_t)r0 * hop, s1 = r1 == num_rows ? want : (uint64_t)r1 * hop, end = s1 < want ? s1 : want;
+        const uint32_t count = (uint32_t)(end - s0);
+        SOTS_HIP(ctx, hipMemcpyAsync(ctx->render.values, values + (size_t)first * ctx->D, (size_t)rows * ctx->D * sizeof(float),
+                                     hipMemcpyHostToDevice, ctx->stream));
+        if (ctx->synth_arith == SOTS_ARITH_DEVICE_KERNELS)
+            SOTS_HIP(ctx, launch_synth_device_arith(ctx->stream, ctx->cfg.synth_kind, ctx->render.values, ctx->wavetable, ctx->render.audio, ctx->sp,
+                                                    rows, ctx->log2n, ctx->pitch));
+        else
+            SOTS_HIP(ctx, launch_synth(ctx->stream, ctx->cfg.synth_kind, ctx->render.values, ctx->wavetable, ctx->render.audio, ctx->sp, rows,
+                                       ctx->log2n, ctx->pitch, ctx->num_cus, nullptr, ctx->allow_cut));
+        RenderPass ps{};
+        ps.audio = ctx->render.audio;
+        ps.window = (args->flags & SOTS_RENDER_WINDOWED) ? ctx->window : nullptr;
+        ps.out = ctx->render.out;
+        ps.rows = rows, ps.hop = hop, ps.n = N, ps.pitch = ctx->pitch;
+        ps.out_first = (r0 - first) * hop;
+        ps.quads = (count + 3u) / 4u;
+        SOTS_HIP(ctx, launch_overlap_add(ctx->stream, ps));
+        // (stream order keeps the next pass off the scratch until this copy has read it)
+        SOTS_HIP(ctx, hipMemcpyAsync(out + s0, ctx->render.out, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (out_samples > covered) memset(out + covered, 0, (size_t)(out_samples - covered) * sizeof(float));
     return SOTS_OK;
 }
 

@@ -26,6 +26,7 @@
 #include "../../include/sots_hip.h"
 #include "Benchmarker.hpp"
 #include "Evolutionary_Strategy.hpp"
+#include "Match_track.hpp"
 #include "Objective_weights.hpp"
 
 struct Evolutionary_Strategy_HIP_Arguments
@@ -113,6 +114,17 @@ struct Evolutionary_Strategy_HIP_Arguments
     // Applied to the context, to every island of a group and to the chunks in flight (batched and queued alike).
     // sots_match names the weighting in its output (one line) only when parameters.json named it.
     Objective_Weights_Spec objectiveWeights;
+    // Analysis at a hop and the rendering of the whole match (type.HIP.{hopSize,renderMatch,matchPath}).
+    //   hopSize     : samples between chunk starts; 0 (default) = the audio length N, the reference's chunking.  Otherwise
+    //                 ceil(N / 64) <= hopSize <= N, need not divide N; the constructor throws - before any device work - where
+    //                 it is not.  parameterMatchAudio then matches chunk i = samples [i hopSize, i hopSize + N), (L - N) / hopSize
+    //                 + 1 of them, in all its paths (chunk by chunk, in flight, queued).
+    //   renderMatch : sots_match writes the overlap-add rendering of every chunk's match (renderMatch() below) to
+    //                 outputAudioPath instead of 2^14 samples of the last chunk's
+    //   matchPath   : sots_match writes the parameter track there, one CSV row per chunk (Match_track.hpp)
+    uint32_t hopSize = 0;
+    bool renderMatch = false;
+    std::string matchPath = "";
     bool returnBestEver = false;
     uint32_t historyEvery = 0;
     std::string historyPath = "";
@@ -138,6 +150,7 @@ private:
 
     uint32_t numChunks_ = 0;
     uint32_t chunkSize_ = 0;
+    uint32_t hop_ = 0;              // samples between chunk starts: args_.hopSize, or the audio length
     uint32_t targetAudioLength = 0;
     std::vector<float> targetFFT_;
     std::vector<float> objectiveWeights_;       // the table of args_.objectiveWeights for this N; empty: no weights
@@ -268,6 +281,25 @@ public:
     const std::vector<float> &bestFitnessPerChunk() const { return bestFitnessPerChunk_; }
     // generations after which each chunk's result was taken: numGenerations, or where its stop rule first held
     const std::vector<uint32_t> &generationsPerChunk() const { return generationsPerChunk_; }
+    // samples between the chunk starts of parameterMatchAudio, and the chunks its last call matched
+    uint32_t hopSize() const { return hop_; }
+    uint32_t numChunks() const { return numChunks_; }
+    // The whole match as audio: bestParametersPerChunk() through sots_render_overlap_add on this object's context - chunk i's
+    // match stands for samples [i hop, i hop + N); where chunks overlap (hop < N) they are cross-faded with the analysis
+    // window and normalised by its sum, at hop = N they follow each other as they are.  (numChunks - 1) hop + N samples.
+    void renderMatch(std::vector<float> &out)
+    {
+        const uint32_t d = population.numDimensions, chunks = (uint32_t)bestPerChunk_.size();
+        out.assign((size_t)matchCoveredSamples(chunks, objective.audioLength, hop_), 0.0f);
+        if (!chunks) return;
+        std::vector<float> values((size_t)chunks * d);
+        for (uint32_t c = 0; c < chunks; ++c) std::copy(bestPerChunk_[c].begin(), bestPerChunk_[c].begin() + d, values.begin() + (size_t)c * d);
+        sots_render_args ra{};
+        ra.struct_size = sizeof ra;
+        ra.hop = hop_;
+        ra.flags = hop_ < objective.audioLength ? (uint32_t)SOTS_RENDER_WINDOWED : 0u;
+        check(sots_render_overlap_add(ctx_, values.data(), values.size() * sizeof(float), chunks, &ra, out.data(), out.size()), "renderMatch");
+    }
     // generations really run by the last parameterMatchAudio, summed over its chunks (chunks in flight run to their batch's end)
     uint64_t generationsRun() const { return generationsRun_; }
     // bins with a positive weight (all N/2 of them without weights)
@@ -300,6 +332,7 @@ public:
             cfg_.param_min[i] = i < objective.paramMins.size() ? objective.paramMins[i] : 0.0f;
             cfg_.param_max[i] = i < objective.paramMaxs.size() ? objective.paramMaxs[i] : 0.0f;
         }
+        hop_ = matchHop((double)args_.hopSize, objective.audioLength); // (throws before any device work)
         objectiveWeights_ = makeObjectiveWeights(args_.objectiveWeights, objective.audioLength, (double)objective.sampleRate); // (throws before any device work)
         if (args_.numDevices > 1) {
             std::vector<int32_t> devs = args_.devices;
@@ -429,9 +462,10 @@ public:
 
     void parameterMatchAudio(float *aTargetAudio, uint32_t aTargetAudioLength) override
     {
-        // every N-sample chunk is matched from a fresh population (...OpenCL.hpp:572-610)
+        // every N-sample chunk is matched from a fresh population (...OpenCL.hpp:572-610); the chunks start hop_ samples apart
+        // (the reference's N unless type.HIP.hopSize says otherwise)
         chunkSize_ = objective.audioLength;
-        numChunks_ = aTargetAudioLength / chunkSize_;
+        numChunks_ = matchChunkCount(aTargetAudioLength, chunkSize_, hop_); // (hop = N: aTargetAudioLength / N)
         bestPerChunk_.clear();
         bestFitnessPerChunk_.clear();
         generationsPerChunk_.clear();
@@ -460,7 +494,7 @@ public:
             matchChunksInFlight(aTargetAudio);
         } else {
             for (uint32_t i = 0; i < numChunks_; i++) {
-                setTargetAudio(&aTargetAudio[chunkSize_ * i], chunkSize_);
+                setTargetAudio(&aTargetAudio[(size_t)hop_ * i], chunkSize_);
                 initPopulationHIP(i);
                 executeAllGenerations();
                 if (group_) checkGroup(sots_group_synchronize(group_), "synchronize");
@@ -543,7 +577,7 @@ private:
             checkBatch(sots_batch_set_objective_weights(batch_, objectiveWeights_.data(), (uint32_t)objectiveWeights_.size()), "sots_batch_set_objective_weights");
         checkBatch(sots_batch_track(batch_, SOTS_TRACK_BEST_EVER, 0, 0), "sots_batch_track"); // (the queue keeps the best-ever record itself)
         std::vector<float> mags((size_t)numChunks_ * half);
-        for (uint32_t c = 0; c < numChunks_; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)chunkSize_ * c], mags.data() + (size_t)c * half);
+        for (uint32_t c = 0; c < numChunks_; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)hop_ * c], mags.data() + (size_t)c * half);
         checkBatch(sots_batch_queue_targets_spectra(batch_, mags.data(), (uint64_t)mags.size(), numChunks_), "sots_batch_queue_targets_spectra");
         sots_queue_stats stats{};
         stats.struct_size = sizeof stats;
@@ -603,7 +637,7 @@ private:
         uint32_t last = 0;
         for (uint32_t first = 0; first < numChunks_; first += perBatch) {
             const uint32_t n = std::min(perBatch, numChunks_ - first);
-            for (uint32_t c = 0; c < n; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)chunkSize_ * (first + c)], mags.data() + (size_t)c * half);
+            for (uint32_t c = 0; c < n; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)hop_ * (first + c)], mags.data() + (size_t)c * half);
             checkBatch(sots_batch_set_target_spectra(batch_, mags.data(), n * half, n), "sots_batch_set_target_spectra");
             checkBatch(sots_batch_init_population(batch_, first), "sots_batch_init_population");
             uint32_t done = 0;

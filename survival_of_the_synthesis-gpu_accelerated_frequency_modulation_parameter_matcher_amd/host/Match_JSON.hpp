@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "Match_track.hpp"
 #include "Objective_weights.hpp"
 
 // ---------------------------------------------------------------------------------------
@@ -180,6 +181,19 @@ inline bool readObjectiveWeightsKey(const Json &h, Objective_Weights_Spec &spec)
         throw std::runtime_error(what + " must be \"aWeighting\", {\"bandHz\": [lo, hi]} or an array");
     }
     spec = s;
+    return true;
+}
+
+// type.HIP.hopSize (Match_track.hpp): the samples between chunk starts, 0 or absent = the audio length N.  Returns whether the
+// key was there; throws - like the keys above, before any device work - on anything but 0 or a whole number in
+// ceil(N / 64) .. N.
+inline bool readHopSizeKey(const Json &h, uint32_t audioLength, uint32_t &hopSize)
+{
+    if (!h.has("hopSize")) return false;
+    const Json &v = h["hopSize"];
+    if (v.kind != Json::Number) throw std::runtime_error("parameters.json: type.HIP.hopSize must be a number");
+    const uint32_t hop = matchHop(v.num, audioLength);
+    hopSize = v.num == 0.0 ? 0u : hop;
     return true;
 }
 

@@ -3,10 +3,20 @@
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
 // "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "numDevices", "numElites",
 // "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight", "chunkQueue",
-// "survivors", "objective", "objectiveFloor", "objectiveWeights", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
+// "survivors", "objective", "objectiveFloor", "objectiveWeights", "hopSize", "renderMatch", "matchPath", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
 // N-sample chunk with Evolutionary_Strategy_HIP, writes inputGenerated.wav and the
 // outputAudioPath rendering of the best match, and prints the best parameters.
+//   "hopSize"     samples between chunk starts: chunk i is samples [i hopSize, i hopSize + N).  0 or absent: N, the
+//                 reference's chunking; otherwise a whole number in N / 64 (rounded up) .. N, which need not divide N.
+//                 A file of L samples has (L - N) / hopSize + 1 chunks.
+//   "renderMatch" true: outputAudioPath receives the rendering of the WHOLE match, (chunks - 1) hopSize + N samples - every
+//                 chunk's best parameters synthesised and overlap-added on the GPU (sots_render_overlap_add: cross-faded
+//                 with the analysis window where chunks overlap, end to end at hopSize = N) - instead of 2^14 samples of
+//                 the last chunk's.
+//   "matchPath"   a CSV of the parameter track, one row per chunk:
+//                 chunk,start_sample,generations,fitness,u0..u{D-1},p0..p{D-1} - u the unit-range genes (%.9g: the fp32
+//                 bits), p the scaled parameters; with returnBestEver the best-ever individual of each chunk.
 //
 // The JSON reader and the WAV reader/writer are small built-ins: the reference's
 // dependencies (nlohmann json, libsndfile, AudioFile) are not vendored and not needed.
@@ -102,6 +112,10 @@ int main(int argc, char *argv[])
             args.objectiveGiven = readObjectiveKeys(h, args.objective, args.objectiveFloor);
             // per-bin weights of that objective: {"bandHz": [lo, hi]}, "aWeighting" or an array of N/2 numbers (Match_JSON.hpp)
             (void)readObjectiveWeightsKey(h, args.objectiveWeights);
+            // analysis at a hop, the rendering of the whole match and the parameter track (Match_track.hpp; header comment)
+            (void)readHopSizeKey(h, 1u << audioLengthLog2, args.hopSize);
+            if (h.has("renderMatch")) args.renderMatch = h["renderMatch"].b;
+            if (h.has("matchPath")) args.matchPath = h["matchPath"].str;
             // run record (Evolutionary_Strategy_HIP_Arguments): the best individual any generation produced, a history CSV,
             // and stopping a chunk early on a fitness target or a stall
             if (h.has("returnBestEver")) args.returnBestEver = h["returnBestEver"].b;
@@ -159,7 +173,7 @@ int main(int argc, char *argv[])
         const double generations = (double)hipEs->generationsRun(); // over all chunks; fewer than numGenerations each where a stop rule ended them
         const double evaluated = (double)es->population.populationLength * args.numDevices * generations;
         std::cout << "Candidates evaluated per second: " << evaluated / secs << std::endl;
-        std::cout << "Chunks matched per second: " << (double)(targetAudio.size() / N) / secs << std::endl;
+        std::cout << "Chunks matched per second: " << (double)(args.hopSize ? hipEs->numChunks() : targetAudio.size() / N) / secs << std::endl;
 
         const uint32_t P = es->population.populationLength;
         std::vector<float> v(P * D), s(P * D), f(P);
@@ -170,11 +184,28 @@ int main(int argc, char *argv[])
             f[0] = hipEs->bestFitnessPerChunk().back();
         }
 
-        // render 2^14 samples of the best match (main.cpp:270-275)
-        Objective render(P, D, args.es_args.paramMin, args.es_args.paramMax, 14);
-        std::vector<float> audio(1u << 14);
-        synthesise(render, best, audio.data());
-        outputAudioFile(outputAudioPath, audio.data(), 1u << 14);
+        if (!args.matchPath.empty()) { // the parameter track, one row per chunk
+            FILE *track = fopen(args.matchPath.c_str(), "w");
+            if (!track) throw std::runtime_error("cannot write " + args.matchPath);
+            writeMatchTrackHeader(track, D);
+            const auto &rows = hipEs->bestParametersPerChunk();
+            for (uint32_t c = 0; c < rows.size(); ++c)
+                writeMatchTrackRow(track, c, (uint64_t)c * hipEs->hopSize(), hipEs->generationsPerChunk()[c], hipEs->bestFitnessPerChunk()[c], rows[c],
+                                   es->objective.scaleParams(rows[c]));
+            fclose(track);
+        }
+        if (args.renderMatch) { // every chunk's match, overlap-added on the device
+            std::vector<float> whole;
+            hipEs->renderMatch(whole);
+            if (whole.size() > 0xFFFFFFFFull / 3) throw std::runtime_error("renderMatch: the rendering does not fit a WAV file");
+            outputAudioFile(outputAudioPath, whole.data(), (uint32_t)whole.size());
+        } else {
+            // render 2^14 samples of the best match (main.cpp:270-275)
+            Objective render(P, D, args.es_args.paramMin, args.es_args.paramMax, 14);
+            std::vector<float> audio(1u << 14);
+            synthesise(render, best, audio.data());
+            outputAudioFile(outputAudioPath, audio.data(), 1u << 14);
+        }
 
         printf("Overall best parameters found\n Fitness = %g\n", f[0]);
         const std::vector<float> scaled = es->objective.scaleParams(best);
