@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,6 +12,7 @@
 #include <vector>
 
 #include "../../include/sots_hip.h"
+#include "sots_engine.h"
 #include "sots_host_math.h"
 #include "sots_kernels.h"
 #include "sots_render.h"
@@ -38,41 +38,23 @@ thread_local std::string g_create_error;
 
 } // namespace
 
-struct sots_ctx {
-    sots_config cfg{};
-    PopDims pd{};
-    MutateConsts mc{};
-    SynthParams sp{};
-    int device = 0;
-    uint32_t num_cus = 256;
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    uint32_t P = 0, D = 0, N = 0, log2n = 0, n_pad = 0;
-    uint32_t pitch = 0; // floats between audio rows on the device (>= N)
+struct sots_ctx : sots::Engine {
     uint32_t rot = 0, generation = 0;
     bool target_set = false;
     // device buffers
     float *values = nullptr, *steps = nullptr, *fitness = nullptr; // [2][P][D], [2][P][D], [2][P]
-    float *audio = nullptr, *spectrum = nullptr, *target = nullptr;
-    float *wavetable = nullptr, *window = nullptr, *rows = nullptr;
-    float2 *twiddle = nullptr;
+    float *audio = nullptr, *spectrum = nullptr, *target = nullptr, *rows = nullptr;
     uint64_t *keys = nullptr;
     void *sort_scratch = nullptr;
     uint32_t rows_capacity = 0;
-    OccCache occ{};
-    float *x_image = nullptr; // k_fft_x's tables (N >= 2048), rebuilt with every target
-    // the objective (sots_set_objective).  Under LOG_MAGNITUDE the spectral kernels read target_ln = ln(target + floor),
-    // made on the device from `target` (which stays the raw magnitudes) whenever the target or the objective changes;
-    // allocated with the first log objective
-    Objective obj{};
+    // Under SOTS_OBJECTIVE_LOG_MAGNITUDE the spectral kernels read target_ln = ln(target + floor), made on the device from
+    // `target` (which stays the raw magnitudes) whenever the target or the objective changes; allocated with the first
+    // log objective
     float *target_ln = nullptr;
-    // per-bin weights (sots_set_objective_weights): w as passed, u = sqrt(w) on the device as plain bins and as the fused
-    // kernels read it; ctx->obj points at the two while weights are set
-    std::vector<float> weights_w;
-    float *weights_u = nullptr, *weights_image = nullptr;
+    std::vector<float> weights_w; // the per-bin weights as passed (sots_get_objective_weights)
     // selection state: after the fused loop's partial sort only rows [0, tail_first) of the current half
     // are in place; the unsorted half it came from is intact until the next generation starts
     uint32_t sort_mode = SOTS_SORT_LAZY_TAIL;
-    uint32_t synth_arith = SOTS_ARITH_CPU_PATH;
     bool tail_pending = false;
     uint32_t tail_first = 0;
     // the one-launch selection (k_sel_splitters): two slots of splitters, read and written in turn.  spl_valid: the
@@ -105,17 +87,11 @@ struct sots_ctx {
     bool allow_cut = true;
     int skip_stage = 0;
     int fuse_variation = -1; // -1: by population shape, 0 / 1: forced
-    // host tables
-    std::vector<double> window64;
-    float window_factor = 1.0f, inv_n = 0.0f, inv_wf = 1.0f;
     // timing
     bool timing = false;
     std::vector<hipEvent_t> event_pool;
     hipEvent_t chain_tail = nullptr; // fused loop: the event the last stage ended with
     StageClock clocks[SOTS_STAGE_COUNT];
-    mutable std::string err;
-    char arch[32] = {0};
-    char device_name[128] = {0};
 
     float *val(uint32_t half) const { return values + (size_t)half * P * D; }
     float *stp(uint32_t half) const { return steps + (size_t)half * P * D; }
@@ -124,49 +100,12 @@ struct sots_ctx {
 
 namespace {
 
-int fail(const sots_ctx *ctx, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (ctx) ctx->err = buf;
-    else g_create_error = buf;
-    return code;
-}
-
-#define SOTS_HIP(ctx, call)                                                                       \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            (void)hipGetLastError(); /* reported here: do not leave it for a later launch check */ \
-            return fail(ctx, SOTS_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                                      \
-        }                                                                                         \
-    } while (0)
+std::string &err_of(const sots_ctx *ctx) { return ctx ? ctx->err : g_create_error; }
 
 #define SOTS_REQUIRE_CTX(ctx) \
     do {                      \
-        if (!(ctx)) return fail(nullptr, SOTS_ERR_INVALID, "null context"); \
+        if (!(ctx)) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "null context"); \
     } while (0)
-
-uint32_t dims_of(uint32_t kind)
-{
-    switch (kind) {
-    case SOTS_SYNTH_2OP: return 4;
-    case SOTS_SYNTH_3OP_SERIES: return 6;
-    case SOTS_SYNTH_TRIPLE_PAR: return 12;
-    case SOTS_SYNTH_4OP_SERIES: return 8;
-    default: return 0;
-    }
-}
-
-int bind_device(const sots_ctx *ctx)
-{
-    SOTS_HIP(ctx, hipSetDevice(ctx->device));
-    return SOTS_OK;
-}
 
 // ---- stage timing -------------------------------------------------------------------
 hipEvent_t take_event(sots_ctx *c)
@@ -226,7 +165,7 @@ int drain_clocks(sots_ctx *ctx)
             if (rc) continue;
             float ms = 0.0f;
             if (hipEventSynchronize(ev.second) != hipSuccess || hipEventElapsedTime(&ms, ev.first, ev.second) != hipSuccess) {
-                rc = fail(ctx, SOTS_ERR_HIP, "stage timing: %s", hipGetErrorString(hipGetLastError()));
+                rc = SOTS_FAIL(ctx, SOTS_ERR_HIP, "stage timing: %s", hipGetErrorString(hipGetLastError()));
                 continue;
             }
             ck.total_ms += ms;
@@ -264,16 +203,22 @@ void free_ctx(sots_ctx *ctx)
         all.erase(std::unique(all.begin(), all.end()), all.end());
         for (hipEvent_t e : all) (void)hipEventDestroy(e);
     }
-    void *bufs[] = {ctx->values, ctx->steps, ctx->fitness, ctx->audio, ctx->spectrum, ctx->target, ctx->target_ln, ctx->weights_u, ctx->weights_image,
-                    ctx->wavetable, ctx->window, ctx->rows, ctx->twiddle, ctx->keys, ctx->sort_scratch, ctx->x_image, ctx->splitters,
-                    ctx->sel_cnt, ctx->sel_lists};
+    void *bufs[] = {ctx->values, ctx->steps, ctx->fitness, ctx->audio, ctx->spectrum, ctx->target, ctx->target_ln, ctx->rows, ctx->keys,
+                    ctx->sort_scratch, ctx->splitters, ctx->sel_cnt, ctx->sel_lists};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     track_release(ctx->track);
     render_release(ctx->render);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    (void)hipGetLastError(); // nothing sticky survives a context (the launchers read hipGetLastError after each launch)
+    engine_release(*ctx);
     delete ctx;
+}
+
+// a creation that fails: its text outlives the handle in the thread's store
+int abandon(sots_ctx *ctx, int rc)
+{
+    g_create_error = ctx->err;
+    free_ctx(ctx);
+    return rc;
 }
 
 int ensure_rows(sots_ctx *ctx, uint32_t n_rows)
@@ -287,24 +232,9 @@ int ensure_rows(sots_ctx *ctx, uint32_t n_rows)
     return SOTS_OK;
 }
 
-// Rows of the sorted half that the next recombination reads (recombine_source, sots_kernels.hip):
-// whole blocks of parents, floor(numParents / block) of them, at least one.  Immigrants go to the
-// tail of THESE rows: with numParents not a multiple of the block, rows between the last whole
-// block and numParents are never read and immigrants written there would be dead.
-uint32_t breeding_rows(const sots_ctx *ctx)
-{
-    const uint32_t block = ctx->pd.block;
-    uint32_t npb = ctx->cfg.num_parents / block;
-    if (npb == 0) npb = 1;
-    return npb * block;
-}
-
-// rows the selection must deliver in order: what recombination reads, and never fewer than the parents
-uint32_t selected_rows(const sots_ctx *ctx)
-{
-    const uint32_t b = breeding_rows(ctx);
-    return b > ctx->cfg.num_parents ? b : ctx->cfg.num_parents;
-}
+// the rows recombination reads and the rows the selection places (sots_rules.h), of this context
+uint32_t breeding_rows(const sots_ctx *ctx) { return sots::breeding_rows(ctx->cfg.num_parents, ctx->pd.block); }
+uint32_t selected_rows(const sots_ctx *ctx) { return sots::selected_rows(ctx->cfg.num_parents, ctx->pd.block); }
 
 // Produces the rows the selection left out: the full sort of the (still intact) unsorted half, writing
 // only rows >= tail_first of the current half (the rows in front are in place, immigrants included).
@@ -443,7 +373,7 @@ int derive_target(sots_ctx *ctx)
 int require_target(sots_ctx *ctx)
 {
     if (!ctx->target_set)
-        return fail(ctx, SOTS_ERR_STATE, "no target: call sots_set_target_audio or sots_set_target_spectrum first");
+        return SOTS_FAIL(ctx, SOTS_ERR_STATE, "no target: call sots_set_target_audio or sots_set_target_spectrum first");
     return SOTS_OK;
 }
 
@@ -456,12 +386,6 @@ int record_generation(sots_ctx *ctx)
     return SOTS_OK;
 }
 
-int check_stop_rule(const sots_stop_rule *rule)
-{
-    if (!rule || rule->struct_size != sizeof(sots_stop_rule) || rule->check_interval == 0) return SOTS_ERR_INVALID;
-    return SOTS_OK;
-}
-
 } // namespace
 
 // =======================================================================================
@@ -469,91 +393,21 @@ extern "C" {
 
 int sots_create(const sots_config *cfg, sots_ctx **out)
 {
-    if (!cfg || !out) return fail(nullptr, SOTS_ERR_INVALID, "sots_create: null argument");
+    if (!cfg || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_create: null argument");
     *out = nullptr;
-    if (cfg->struct_size != sizeof(sots_config))
-        return fail(nullptr, SOTS_ERR_INVALID, "sots_config.struct_size %u != %zu", cfg->struct_size,
-                    sizeof(sots_config));
-    const uint32_t d = dims_of(cfg->synth_kind);
-    if (d == 0) return fail(nullptr, SOTS_ERR_INVALID, "unknown synth_kind %u", cfg->synth_kind);
-    if (cfg->num_dimensions != d)
-        return fail(nullptr, SOTS_ERR_INVALID, "synth_kind %u needs numDimensions %u, got %u", cfg->synth_kind,
-                    d, cfg->num_dimensions);
-    if (cfg->audio_length_log2 < 8 || cfg->audio_length_log2 > 15)
-        return fail(nullptr, SOTS_ERR_INVALID, "audioLengthLog2 %u outside 8..15", cfg->audio_length_log2);
-    const uint64_t p64 = (uint64_t)cfg->num_parents + cfg->num_offspring;
-    if (cfg->num_parents == 0 || p64 < 2 || p64 > (1ull << 26))
-        return fail(nullptr, SOTS_ERR_INVALID, "population %llu (parents %u) not supported",
-                    (unsigned long long)p64, cfg->num_parents);
-    if (cfg->workgroup_size == 0 || p64 % cfg->workgroup_size != 0)
-        return fail(nullptr, SOTS_ERR_INVALID,
-                    "populationLength %llu must be a multiple of workgroupSize %u (the recombination block)",
-                    (unsigned long long)p64, cfg->workgroup_size);
-
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-        return fail(nullptr, SOTS_ERR_NO_DEVICE, "no HIP device (%s)", hipGetErrorString(e));
-    if (cfg->device < 0 || cfg->device >= ndev)
-        return fail(nullptr, SOTS_ERR_NO_DEVICE, "device %d not in 0..%d", cfg->device, ndev - 1);
+    SOTS_REFUSE(nullptr, config_check(*cfg, 1ull << 26));
 
     sots_ctx *ctx = new sots_ctx();
-    ctx->cfg = *cfg;
-    ctx->device = cfg->device;
-#define CREATE_HIP(call)                                                                          \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            int rc_ = fail(nullptr, SOTS_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
-            free_ctx(ctx);                                                                        \
-            return rc_;                                                                           \
-        }                                                                                         \
-    } while (0)
-    CREATE_HIP(hipSetDevice(ctx->device));
-    hipDeviceProp_t prop;
-    CREATE_HIP(hipGetDeviceProperties(&prop, ctx->device));
-    snprintf(ctx->arch, sizeof ctx->arch, "%s", prop.gcnArchName);
-    snprintf(ctx->device_name, sizeof ctx->device_name, "%s", prop.name);
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        int rc = fail(nullptr, SOTS_ERR_NO_DEVICE, "device %d is %s; libsots_hip carries gfx950 code only",
-                      ctx->device, prop.gcnArchName);
-        free_ctx(ctx);
-        return rc;
-    }
-    ctx->num_cus = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256;
-    CREATE_HIP(hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking));
-    ctx->stream = ctx->own_stream;
-
-    ctx->P = (uint32_t)p64;
-    ctx->D = d;
-    ctx->log2n = cfg->audio_length_log2;
-    ctx->N = 1u << ctx->log2n;
-    ctx->n_pad = next_pow2(ctx->P < 2 ? 2 : ctx->P);
-    {
-        // audio rows are padded off the power-of-two stride (see sots_kernels.h)
-        uint32_t pad = 32;
+    // audio rows are padded off the power-of-two stride (see sots_kernels.h)
+    uint32_t pad = 32;
 #ifdef SOTS_EXPERIMENT
-        if (const char *e = getenv("SOTS_AUDIO_PAD")) pad = (uint32_t)strtoul(e, nullptr, 10) & ~3u; // floats
-        if (const char *e = getenv("SOTS_SYNTH_CUT")) ctx->allow_cut = atoi(e) != 0;                 // 0: never cut the chain
-        if (const char *e = getenv("SOTS_FUSE_VARIATION")) ctx->fuse_variation = atoi(e) != 0 ? 1 : 0;
-        if (const char *e = getenv("SOTS_SKIP_STAGE")) ctx->skip_stage = atoi(e); // 1: no synthesis, 2: no spectral kernel (timing ablations)
+    if (const char *e = getenv("SOTS_AUDIO_PAD")) pad = (uint32_t)strtoul(e, nullptr, 10) & ~3u; // floats
+    if (const char *e = getenv("SOTS_SYNTH_CUT")) ctx->allow_cut = atoi(e) != 0;                 // 0: never cut the chain
+    if (const char *e = getenv("SOTS_FUSE_VARIATION")) ctx->fuse_variation = atoi(e) != 0 ? 1 : 0;
+    if (const char *e = getenv("SOTS_SKIP_STAGE")) ctx->skip_stage = atoi(e); // 1: no synthesis, 2: no spectral kernel (timing ablations)
 #endif
-        ctx->pitch = ctx->N + pad;
-    }
-    ctx->pd = make_pop_dims(ctx->P, ctx->D, cfg->num_parents, cfg->workgroup_size, cfg->gid_base, (uint32_t)cfg->seed,
-                            (uint32_t)(cfg->seed >> 32));
-    // Evolutionary_Strategy.hpp:611-627
-    const float mpi = (float)3.14159265358979323846;
-    ctx->mc.alpha = 1.4f;
-    ctx->mc.one_over_alpha = 1.f / ctx->mc.alpha;
-    ctx->mc.root_two_over_pi = sqrtf(2.f / (float)mpi);
-    ctx->mc.beta_scale = 1.f / (float)ctx->D;
-    const float beta = sqrtf(ctx->mc.beta_scale);
-    ctx->mc.pow_alpha_beta = powf(ctx->mc.alpha, beta);
-    ctx->mc.pow_inv_alpha_beta = powf(ctx->mc.one_over_alpha, beta);
-    memcpy(ctx->sp.pmin, cfg->param_min, sizeof ctx->sp.pmin);
-    memcpy(ctx->sp.pmax, cfg->param_max, sizeof ctx->sp.pmax);
-
+    if (int rc = engine_create(*ctx, *cfg, pad)) return abandon(ctx, rc);
+#define CREATE_HIP(call) SOTS_HIP_OR(ctx, call, return abandon(ctx, rc_))
     const size_t pd_bytes = (size_t)2 * ctx->P * ctx->D * sizeof(float);
     const size_t audio_bytes = (size_t)ctx->P * ctx->pitch * sizeof(float);
     const size_t spec_bytes = (size_t)ctx->P * (ctx->N + 8) * sizeof(float);
@@ -563,11 +417,7 @@ int sots_create(const sots_config *cfg, sots_ctx **out)
     CREATE_HIP(hipMalloc((void **)&ctx->audio, audio_bytes));
     CREATE_HIP(hipMalloc((void **)&ctx->spectrum, spec_bytes));
     CREATE_HIP(hipMalloc((void **)&ctx->target, (size_t)(ctx->N / 2) * sizeof(float)));
-    CREATE_HIP(hipMalloc((void **)&ctx->wavetable, (size_t)SOTS_WAVETABLE_SIZE * sizeof(float)));
-    CREATE_HIP(hipMalloc((void **)&ctx->window, (size_t)ctx->N * sizeof(float)));
-    CREATE_HIP(hipMalloc((void **)&ctx->twiddle, (size_t)ctx->N * sizeof(float2)));
     CREATE_HIP(hipMalloc((void **)&ctx->keys, sort_keys_bytes(ctx->P)));
-    if (ctx->log2n >= 11 && x_table_bytes(ctx->log2n)) CREATE_HIP(hipMalloc((void **)&ctx->x_image, x_table_bytes(ctx->log2n)));
     {
         const size_t a = sort_scratch_bytes(ctx->P), b = select_scratch_bytes(ctx->P);
         CREATE_HIP(hipMalloc(&ctx->sort_scratch, a > b ? a : b));
@@ -589,18 +439,8 @@ int sots_create(const sots_config *cfg, sots_ctx **out)
     CREATE_HIP(hipMemsetAsync(ctx->audio, 0, audio_bytes, ctx->stream));
     CREATE_HIP(hipMemsetAsync(ctx->spectrum, 0, spec_bytes, ctx->stream));
     CREATE_HIP(hipMemsetAsync(ctx->target, 0, (size_t)(ctx->N / 2) * sizeof(float), ctx->stream));
-
-    // host tables the reference also builds on the CPU and uploads (...OpenCL.hpp:315-317)
-    const std::vector<float> table = make_wavetable();
-    ctx->window64 = make_window(ctx->N, &ctx->window_factor);
-    std::vector<float> window32(ctx->N);
-    for (uint32_t i = 0; i < ctx->N; ++i) window32[i] = (float)ctx->window64[i];
-    const std::vector<float> tw = make_twiddles(ctx->N);
-    ctx->inv_n = 1.0f / (float)ctx->N;          // fftOneOverSize
-    ctx->inv_wf = 1.f / ctx->window_factor;     // fftOneOverWindowFactor
-    CREATE_HIP(hipMemcpyAsync(ctx->wavetable, table.data(), table.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    CREATE_HIP(hipMemcpyAsync(ctx->window, window32.data(), window32.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    CREATE_HIP(hipMemcpyAsync(ctx->twiddle, tw.data(), tw.size() * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    TableStaging staging;
+    if (int rc = engine_upload_tables(*ctx, staging)) return abandon(ctx, rc);
     CREATE_HIP(hipStreamSynchronize(ctx->stream));
 #undef CREATE_HIP
     *out = ctx;
@@ -609,12 +449,12 @@ int sots_create(const sots_config *cfg, sots_ctx **out)
 
 void sots_destroy(sots_ctx *ctx) { free_ctx(ctx); }
 
-const char *sots_last_error(const sots_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
+const char *sots_last_error(const sots_ctx *ctx) { return err_of(ctx).c_str(); }
 
 int sots_set_stream(sots_ctx *ctx, void *hip_stream)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->own_stream;
     return SOTS_OK;
@@ -623,7 +463,7 @@ int sots_set_stream(sots_ctx *ctx, void *hip_stream)
 int sots_synchronize(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SOTS_OK;
 }
@@ -633,8 +473,8 @@ int sots_set_target_spectrum(sots_ctx *ctx, const float *magnitudes, uint32_t nu
 {
     SOTS_REQUIRE_CTX(ctx);
     if (!magnitudes || num_bins != ctx->N / 2)
-        return fail(ctx, SOTS_ERR_SIZE, "target spectrum needs %u bins, got %u", ctx->N / 2, num_bins);
-    if (int rc = bind_device(ctx)) return rc;
+        return SOTS_FAIL(ctx, SOTS_ERR_SIZE, "target spectrum needs %u bins, got %u", ctx->N / 2, num_bins);
+    if (int rc = engine_bind(*ctx)) return rc;
     SOTS_HIP(ctx, hipMemcpyAsync(ctx->target, magnitudes, (size_t)num_bins * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     if (int rc = derive_target(ctx)) return rc;
     ctx->target_set = true;
@@ -645,7 +485,7 @@ int sots_set_target_audio(sots_ctx *ctx, const float *audio, uint32_t num_sample
 {
     SOTS_REQUIRE_CTX(ctx);
     if (!audio || num_samples < ctx->N)
-        return fail(ctx, SOTS_ERR_SIZE, "target audio needs %u samples, got %u", ctx->N, num_samples);
+        return SOTS_FAIL(ctx, SOTS_ERR_SIZE, "target audio needs %u samples, got %u", ctx->N, num_samples);
     const std::vector<float> mag = target_spectrum(audio, ctx->N, ctx->window64, ctx->window_factor);
     return sots_set_target_spectrum(ctx, mag.data(), ctx->N / 2);
 }
@@ -654,7 +494,7 @@ int sots_set_target_audio(sots_ctx *ctx, const float *audio, uint32_t num_sample
 int sots_init_population(sots_ctx *ctx, uint32_t chunk_index)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     ctx->rot = 0; // initPopulationCL, ...OpenCL.hpp:371
     ctx->generation = 0;
     // a tail the last run's selection left pending belongs to the OLD population: dropped, never completed into the new one
@@ -674,20 +514,16 @@ int sots_init_population(sots_ctx *ctx, uint32_t chunk_index)
 static int copy_population(sots_ctx *ctx, uint32_t half, bool to_device, void *values, size_t values_bytes,
                            void *steps, size_t steps_bytes, void *fitness, size_t fitness_bytes)
 {
-    const size_t pd_bytes = (size_t)ctx->P * ctx->D * sizeof(float), f_bytes = (size_t)ctx->P * sizeof(float);
-    if ((values && values_bytes != pd_bytes) || (steps && steps_bytes != pd_bytes) ||
-        (fitness && fitness_bytes != f_bytes))
-        return fail(ctx, SOTS_ERR_SIZE, "population byte counts must be %zu (values, steps) and %zu (fitness)",
-                    pd_bytes, f_bytes);
-    if (int rc = bind_device(ctx)) return rc;
+    SOTS_REFUSE(ctx, population_bytes_check(ctx->P, ctx->D, values, values_bytes, steps, steps_bytes, fitness, fitness_bytes));
+    if (int rc = engine_bind(*ctx)) return rc;
     const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
     auto cp = [&](void *host, void *dev, size_t bytes) {
         return to_device ? hipMemcpyAsync(dev, host, bytes, kind, ctx->stream)
                          : hipMemcpyAsync(host, dev, bytes, kind, ctx->stream);
     };
-    if (values) SOTS_HIP(ctx, cp(values, ctx->val(half), pd_bytes));
-    if (steps) SOTS_HIP(ctx, cp(steps, ctx->stp(half), pd_bytes));
-    if (fitness) SOTS_HIP(ctx, cp(fitness, ctx->fit(half), f_bytes));
+    if (values) SOTS_HIP(ctx, cp(values, ctx->val(half), values_bytes));
+    if (steps) SOTS_HIP(ctx, cp(steps, ctx->stp(half), steps_bytes));
+    if (fitness) SOTS_HIP(ctx, cp(fitness, ctx->fit(half), fitness_bytes));
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SOTS_OK;
 }
@@ -723,8 +559,8 @@ int sots_write_synth(sots_ctx *ctx, const float *audio, size_t audio_bytes, cons
     SOTS_REQUIRE_CTX(ctx);
     const size_t a_bytes = (size_t)ctx->P * ctx->N * sizeof(float), s_bytes = (size_t)ctx->P * (ctx->N + 8) * sizeof(float);
     if ((audio && audio_bytes != a_bytes) || (spectrum && spectrum_bytes != s_bytes))
-        return fail(ctx, SOTS_ERR_SIZE, "synth byte counts must be %zu (audio) and %zu (spectrum)", a_bytes, s_bytes);
-    if (int rc = bind_device(ctx)) return rc;
+        return SOTS_FAIL(ctx, SOTS_ERR_SIZE, "synth byte counts must be %zu (audio) and %zu (spectrum)", a_bytes, s_bytes);
+    if (int rc = engine_bind(*ctx)) return rc;
     if (audio)
         SOTS_HIP(ctx, hipMemcpy2DAsync(ctx->audio, (size_t)ctx->pitch * sizeof(float), audio, (size_t)ctx->N * sizeof(float),
                                        (size_t)ctx->N * sizeof(float), ctx->P, hipMemcpyHostToDevice, ctx->stream));
@@ -740,9 +576,9 @@ int sots_read_synth(sots_ctx *ctx, float *audio, size_t audio_bytes, float *spec
     const size_t a_bytes = (size_t)ctx->P * ctx->N * sizeof(float), s_bytes = (size_t)ctx->P * (ctx->N + 8) * sizeof(float);
     const size_t t_bytes = (size_t)(ctx->N / 2) * sizeof(float);
     if ((audio && audio_bytes != a_bytes) || (spectrum && spectrum_bytes != s_bytes) || (target && target_bytes != t_bytes))
-        return fail(ctx, SOTS_ERR_SIZE, "synth byte counts must be %zu (audio), %zu (spectrum), %zu (target)",
+        return SOTS_FAIL(ctx, SOTS_ERR_SIZE, "synth byte counts must be %zu (audio), %zu (spectrum), %zu (target)",
                     a_bytes, s_bytes, t_bytes);
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     if (audio)
         SOTS_HIP(ctx, hipMemcpy2DAsync(audio, (size_t)ctx->N * sizeof(float), ctx->audio, (size_t)ctx->pitch * sizeof(float),
                                        (size_t)ctx->N * sizeof(float), ctx->P, hipMemcpyDeviceToHost, ctx->stream));
@@ -757,7 +593,7 @@ int sots_stage_recombine(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
     if (int rc = settle_tail(ctx)) return rc;
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     const uint32_t src = ctx->rot, dst = ctx->rot ^ 1u;
     {
         StageScope t(ctx, SOTS_STAGE_RECOMBINE);
@@ -771,7 +607,7 @@ int sots_stage_mutate(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
     if (int rc = settle_tail(ctx)) return rc;
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     {
         StageScope t(ctx, SOTS_STAGE_MUTATE);
         SOTS_HIP(ctx, launch_mutate(ctx->stream, ctx->val(ctx->rot), ctx->stp(ctx->rot), ctx->pd, ctx->mc, ctx->generation));
@@ -783,15 +619,10 @@ int sots_stage_synthesise(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
     if (int rc = settle_tail(ctx)) return rc;
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     {
         StageScope t(ctx, SOTS_STAGE_SYNTHESISE);
-        if (ctx->synth_arith == SOTS_ARITH_DEVICE_KERNELS)
-            SOTS_HIP(ctx, launch_synth_device_arith(ctx->stream, ctx->cfg.synth_kind, ctx->val(ctx->rot), ctx->wavetable, ctx->audio,
-                                                    ctx->sp, ctx->P, ctx->log2n, ctx->pitch));
-        else
-        SOTS_HIP(ctx, launch_synth(ctx->stream, ctx->cfg.synth_kind, ctx->val(ctx->rot), ctx->wavetable,
-                                   ctx->audio, ctx->sp, ctx->P, ctx->log2n, ctx->pitch, ctx->num_cus, nullptr, ctx->allow_cut));
+        SOTS_HIP(ctx, engine_synthesise(*ctx, ctx->val(ctx->rot), ctx->audio, ctx->P, nullptr, ctx->allow_cut));
     }
     return maybe_drain(ctx);
 }
@@ -800,7 +631,7 @@ int sots_stage_window(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
     if (int rc = settle_tail(ctx)) return rc;
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     {
         StageScope t(ctx, SOTS_STAGE_WINDOW);
         SOTS_HIP(ctx, launch_window(ctx->stream, ctx->audio, ctx->window, ctx->P, ctx->log2n, ctx->pitch));
@@ -812,7 +643,7 @@ int sots_stage_fft(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
     if (int rc = settle_tail(ctx)) return rc;
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     {
         StageScope t(ctx, SOTS_STAGE_FFT);
         SOTS_HIP(ctx, launch_fft(ctx->stream, ctx->audio, ctx->spectrum, ctx->twiddle, ctx->P, ctx->log2n, ctx->pitch, ctx->num_cus, &ctx->occ));
@@ -825,7 +656,7 @@ int sots_stage_fitness(sots_ctx *ctx)
     SOTS_REQUIRE_CTX(ctx);
     if (int rc = settle_tail(ctx)) return rc;
     if (int rc = require_target(ctx)) return rc;
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     {
         StageScope t(ctx, SOTS_STAGE_FITNESS);
         SOTS_HIP(ctx, launch_fitness(ctx->stream, ctx->spectrum, fitness_target(ctx), ctx->fit(ctx->rot), ctx->P, ctx->log2n,
@@ -838,7 +669,7 @@ int sots_stage_sort(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
     if (int rc = settle_tail(ctx)) return rc;
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     const uint32_t src = ctx->rot, dst = ctx->rot ^ 1u;
     {
         StageScope t(ctx, SOTS_STAGE_SORT);
@@ -853,7 +684,7 @@ int sots_stage_select(sots_ctx *ctx)
     SOTS_REQUIRE_CTX(ctx);
     const bool lists = ctx->lists_ready; // (filed from the half this selection reads: settle_tail writes the other one)
     if (int rc = settle_tail(ctx)) return rc;
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     const uint32_t src = ctx->rot, dst = ctx->rot ^ 1u, need = selected_rows(ctx);
     if (ctx->sort_mode == SOTS_SORT_FULL || !select_applies(ctx->P, need)) return sots_stage_sort(ctx);
     {
@@ -870,8 +701,8 @@ int sots_stage_select(sots_ctx *ctx)
 int sots_stage_bucket_fitness(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!lists_possible(ctx)) return fail(ctx, SOTS_ERR_STATE, "no key lists here: %u splitters per slot, SOTS_SELECT_LISTS=%d", select_splitter_count(ctx->num_cus), (int)ctx->use_lists);
-    if (int rc = bind_device(ctx)) return rc;
+    if (!lists_possible(ctx)) return SOTS_FAIL(ctx, SOTS_ERR_STATE, "no key lists here: %u splitters per slot, SOTS_SELECT_LISTS=%d", select_splitter_count(ctx->num_cus), (int)ctx->use_lists);
+    if (int rc = engine_bind(*ctx)) return rc;
     SelLists sl;
     if (int rc = open_lists(ctx, &sl)) return rc;
     SOTS_HIP(ctx, launch_bucket_fitness(ctx->stream, ctx->fit(ctx->rot), ctx->P, sl));
@@ -882,7 +713,7 @@ int sots_stage_bucket_fitness(sots_ctx *ctx)
 int sots_stage_rotate(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     ctx->lists_ready = false; // (filed from what was the current half)
     // rotationIndex_ flip, ...OpenCL.hpp:486; a kernel argument here, so no transfer
     StageScope t(ctx, SOTS_STAGE_ROTATE);
@@ -916,9 +747,9 @@ int sots_execute_generations(sots_ctx *ctx, uint32_t n)
 {
     SOTS_REQUIRE_CTX(ctx);
     if (int rc = require_target(ctx)) return rc;
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     if (ctx->tail_pending && ctx->tail_first == 0)
-        return fail(ctx, SOTS_ERR_STATE, "sots_stage_select must be followed by sots_stage_rotate");
+        return SOTS_FAIL(ctx, SOTS_ERR_STATE, "sots_stage_select must be followed by sots_stage_rotate");
     const uint32_t need = selected_rows(ctx);
     const bool select = ctx->sort_mode != SOTS_SORT_FULL && select_applies(ctx->P, need);
     // an exchange folded into the last generation's sort (sots_fuse_exchange_next_sort) is used once
@@ -927,7 +758,7 @@ int sots_execute_generations(sots_ctx *ctx, uint32_t n)
     hipEvent_t gate = with_exchange ? ctx->next_exchange_gate : nullptr;
     if (n > 0) ctx->next_exchange_set = false, ctx->next_exchange_gate = nullptr;
     if (with_exchange && select && exchange.sink && exchange.sink_rows > need)
-        return fail(ctx, SOTS_ERR_INVALID, "fused exchange: %u elite rows asked for, sortPopulation places %u per generation here", exchange.sink_rows, need);
+        return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "fused exchange: %u elite rows asked for, sortPopulation places %u per generation here", exchange.sink_rows, need);
     ctx->lists_ready = false;
     for (uint32_t g = 0; g < n; ++g) {
         // the variation below overwrites the unsorted half a pending tail would be completed from; nobody has
@@ -960,13 +791,7 @@ int sots_execute_generations(sots_ctx *ctx, uint32_t n)
             // raw synthesis (the window is applied by the FFT kernel as it loads the row); by default the
             // kernel also makes its individuals: recombination + mutation from the sorted half
             sots::Variation var = {ctx->val(src), ctx->stp(src), ctx->val(dst), ctx->stp(dst), ctx->pd, ctx->mc, ctx->generation};
-            if (device_arith)
-                SOTS_HIP(ctx, launch_synth_device_arith(ctx->stream, ctx->cfg.synth_kind, ctx->val(ctx->rot), ctx->wavetable, ctx->audio,
-                                                        ctx->sp, ctx->P, ctx->log2n, ctx->pitch));
-            else
-            SOTS_HIP(ctx, launch_synth(ctx->stream, ctx->cfg.synth_kind, ctx->val(ctx->rot), ctx->wavetable,
-                                       ctx->audio, ctx->sp, ctx->P, ctx->log2n, ctx->pitch, ctx->num_cus,
-                                       fuse_variation ? &var : nullptr, ctx->allow_cut));
+            SOTS_HIP(ctx, engine_synthesise(*ctx, ctx->val(ctx->rot), ctx->audio, ctx->P, fuse_variation ? &var : nullptr, ctx->allow_cut));
         }
         // Will this generation's selection be the one-launch one, in front of the wide N = 1024 spectral kernel?  Then that
         // kernel files every row's key under its bucket, and the selection reads lists instead of all P fitness values.
@@ -1013,15 +838,8 @@ int sots_execute_generations(sots_ctx *ctx, uint32_t n)
 int sots_track(sots_ctx *ctx, uint32_t flags, uint32_t history_every, uint32_t history_capacity)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (flags & ~(uint32_t)(SOTS_TRACK_BEST_EVER | SOTS_TRACK_HISTORY)) return fail(ctx, SOTS_ERR_INVALID, "unknown track flags %u", flags);
-    if (flags & SOTS_TRACK_HISTORY) {
-        flags |= SOTS_TRACK_BEST_EVER;
-        if (history_every == 0 || history_capacity == 0)
-            return fail(ctx, SOTS_ERR_INVALID, "history needs history_every >= 1 and history_capacity >= 1 (got %u, %u)", history_every, history_capacity);
-        if (history_capacity > kTrackMaxRecords)
-            return fail(ctx, SOTS_ERR_INVALID, "history_capacity %u exceeds %llu records", history_capacity, (unsigned long long)kTrackMaxRecords);
-    }
-    if (int rc = bind_device(ctx)) return rc;
+    SOTS_REFUSE(ctx, track_args_check(&flags, history_every, history_capacity, 0));
+    if (int rc = engine_bind(*ctx)) return rc;
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // a record launch may still be using the old buffers
     SOTS_HIP(ctx, track_setup(ctx->track, flags, history_every, history_capacity, 1, ctx->stream));
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1032,11 +850,11 @@ int sots_read_best_ever(sots_ctx *ctx, float *values, size_t values_bytes, float
                         uint32_t *generation)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!ctx->track.best_ever()) return fail(ctx, SOTS_ERR_STATE, "best-ever tracking is off: call sots_track first");
+    if (!ctx->track.best_ever()) return SOTS_FAIL(ctx, SOTS_ERR_STATE, "best-ever tracking is off: call sots_track first");
     const size_t d_bytes = (size_t)ctx->D * sizeof(float);
     if ((values && values_bytes != d_bytes) || (steps && steps_bytes != d_bytes))
-        return fail(ctx, SOTS_ERR_SIZE, "best-ever byte counts must be %zu (values, steps)", d_bytes);
-    if (int rc = bind_device(ctx)) return rc;
+        return SOTS_FAIL(ctx, SOTS_ERR_SIZE, "best-ever byte counts must be %zu (values, steps)", d_bytes);
+    if (int rc = engine_bind(*ctx)) return rc;
     if (values) SOTS_HIP(ctx, hipMemcpyAsync(values, ctx->track.rows, d_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (steps) SOTS_HIP(ctx, hipMemcpyAsync(steps, ctx->track.rows + SOTS_MAX_DIMS, d_bytes, hipMemcpyDeviceToHost, ctx->stream));
     SOTS_HIP(ctx, track_fetch_meta(ctx->track, ctx->stream, 1));
@@ -1048,9 +866,9 @@ int sots_read_best_ever(sots_ctx *ctx, float *values, size_t values_bytes, float
 int sots_read_history(sots_ctx *ctx, sots_gen_record *out, uint32_t capacity, uint32_t *written, uint64_t *taken)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!ctx->track.history()) return fail(ctx, SOTS_ERR_STATE, "the history is off: call sots_track with SOTS_TRACK_HISTORY first");
-    if (!written || (capacity && !out)) return fail(ctx, SOTS_ERR_INVALID, "read_history: null argument");
-    if (int rc = bind_device(ctx)) return rc;
+    if (!ctx->track.history()) return SOTS_FAIL(ctx, SOTS_ERR_STATE, "the history is off: call sots_track with SOTS_TRACK_HISTORY first");
+    if (!written || (capacity && !out)) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "read_history: null argument");
+    if (int rc = engine_bind(*ctx)) return rc;
     SOTS_HIP(ctx, track_read_history(ctx->track, ctx->stream, 0, out, capacity, written));
     if (taken) *taken = ctx->track.taken;
     return SOTS_OK;
@@ -1058,7 +876,7 @@ int sots_read_history(sots_ctx *ctx, sots_gen_record *out, uint32_t capacity, ui
 
 int sots_stop_rule_holds(const sots_stop_rule *rule, float best_ever_fitness, uint32_t best_ever_generation, uint32_t generation)
 {
-    if (int rc = check_stop_rule(rule)) return rc;
+    if (int rc = stop_rule_check(rule)) return rc;
     // (one copy of the arithmetic for the host and for the chunk queue's turnover kernel: sots_stop_rule.h)
     return stop_rule_holds(rule->target_fitness, rule->stall_generations, best_ever_fitness, best_ever_generation, generation) ? 1 : 0;
 }
@@ -1067,8 +885,8 @@ int sots_execute_until(sots_ctx *ctx, uint32_t max_generations, const sots_stop_
 {
     SOTS_REQUIRE_CTX(ctx);
     if (generations_run) *generations_run = 0;
-    if (check_stop_rule(rule)) return fail(ctx, SOTS_ERR_INVALID, "stop rule: null, wrong struct_size or check_interval 0");
-    if (!ctx->track.best_ever()) return fail(ctx, SOTS_ERR_STATE, "sots_execute_until needs best-ever tracking: call sots_track first");
+    if (stop_rule_check(rule)) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "stop rule: null, wrong struct_size or check_interval 0");
+    if (!ctx->track.best_ever()) return SOTS_FAIL(ctx, SOTS_ERR_STATE, "sots_execute_until needs best-ever tracking: call sots_track first");
     uint32_t done = 0;
     while (done < max_generations) {
         const uint32_t block = std::min(rule->check_interval, max_generations - done);
@@ -1084,7 +902,7 @@ int sots_execute_until(sots_ctx *ctx, uint32_t max_generations, const sots_stop_
 int sots_set_sort_mode(sots_ctx *ctx, uint32_t mode)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (mode > SOTS_SORT_TOP_ONLY) return fail(ctx, SOTS_ERR_INVALID, "unknown sort mode %u", mode);
+    if (mode > SOTS_SORT_TOP_ONLY) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "unknown sort mode %u", mode);
     // the new mode decides what happens to a pending tail: leaving SOTS_SORT_TOP_ONLY completes it (the unsorted half
     // is intact as long as the state is pending, settle_tail), entering it keeps the rows unspecified
     ctx->sort_mode = mode;
@@ -1096,7 +914,7 @@ int sots_set_sort_mode(sots_ctx *ctx, uint32_t mode)
 int sots_set_select_plan(sots_ctx *ctx, uint32_t plan)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (plan > SOTS_SELECT_SPLITTERS) return fail(ctx, SOTS_ERR_INVALID, "unknown select plan %u", plan);
+    if (plan > SOTS_SELECT_SPLITTERS) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "unknown select plan %u", plan);
     ctx->select_plan = plan;
     ctx->lists_ready = false;
     return SOTS_OK;
@@ -1105,7 +923,7 @@ int sots_set_select_plan(sots_ctx *ctx, uint32_t plan)
 int sots_select_splitter_count(const sots_ctx *ctx, uint32_t *count)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!count) return fail(ctx, SOTS_ERR_INVALID, "null count");
+    if (!count) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "null count");
     *count = select_splitter_count(ctx->num_cus);
     return SOTS_OK;
 }
@@ -1114,8 +932,8 @@ int sots_write_select_splitters(sots_ctx *ctx, const uint64_t *keys, uint32_t co
 {
     SOTS_REQUIRE_CTX(ctx);
     const uint32_t b = select_splitter_count(ctx->num_cus);
-    if (!keys || count != b) return fail(ctx, SOTS_ERR_SIZE, "select splitters: %u keys needed, got %u", b, count);
-    if (int rc = bind_device(ctx)) return rc;
+    if (!keys || count != b) return SOTS_FAIL(ctx, SOTS_ERR_SIZE, "select splitters: %u keys needed, got %u", b, count);
+    if (int rc = engine_bind(*ctx)) return rc;
     ctx->lists_ready = false; // (filed between the old splitters)
     SOTS_HIP(ctx, hipMemcpyAsync(splitter_slot(ctx, ctx->spl_cur), keys, (size_t)b * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1126,8 +944,8 @@ int sots_read_select_splitters(sots_ctx *ctx, uint64_t *keys, uint32_t count)
 {
     SOTS_REQUIRE_CTX(ctx);
     const uint32_t b = select_splitter_count(ctx->num_cus);
-    if (!keys || count != b) return fail(ctx, SOTS_ERR_SIZE, "select splitters: %u keys needed, got %u", b, count);
-    if (int rc = bind_device(ctx)) return rc;
+    if (!keys || count != b) return SOTS_FAIL(ctx, SOTS_ERR_SIZE, "select splitters: %u keys needed, got %u", b, count);
+    if (int rc = engine_bind(*ctx)) return rc;
     SOTS_HIP(ctx, hipMemcpyAsync(keys, splitter_slot(ctx, ctx->spl_cur), (size_t)b * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SOTS_OK;
@@ -1136,11 +954,7 @@ int sots_read_select_splitters(sots_ctx *ctx, uint64_t *keys, uint32_t count)
 int sots_set_synth_arithmetic(sots_ctx *ctx, uint32_t arith)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (arith > SOTS_ARITH_DEVICE_KERNELS) return fail(ctx, SOTS_ERR_INVALID, "unknown synthesis arithmetic %u", arith);
-    if (arith == SOTS_ARITH_DEVICE_KERNELS && ctx->cfg.synth_kind == SOTS_SYNTH_4OP_SERIES)
-        return fail(ctx, SOTS_ERR_INVALID, "the reference has no device kernel for the build-defined 4-op voice");
-    ctx->synth_arith = arith;
-    return SOTS_OK;
+    return engine_set_synth_arithmetic(*ctx, arith);
 }
 
 // A setting, like the sort mode: it changes what the NEXT variation computes and nothing now - a pending lazy tail stays
@@ -1148,16 +962,13 @@ int sots_set_synth_arithmetic(sots_ctx *ctx, uint32_t arith)
 int sots_set_survivors(sots_ctx *ctx, uint32_t n)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (n > ctx->cfg.num_parents)
-        return fail(ctx, SOTS_ERR_INVALID, "%u survivors asked for, at most numParents = %u can be kept", n, ctx->cfg.num_parents);
-    ctx->pd.survivors = n;
-    return SOTS_OK;
+    return engine_set_survivors(*ctx, n);
 }
 
 int sots_get_survivors(const sots_ctx *ctx, uint32_t *n)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!n) return fail(ctx, SOTS_ERR_INVALID, "null survivors pointer");
+    if (!n) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "null survivors pointer");
     *n = ctx->pd.survivors;
     return SOTS_OK;
 }
@@ -1167,17 +978,10 @@ int sots_get_survivors(const sots_ctx *ctx, uint32_t *n)
 int sots_set_objective(sots_ctx *ctx, uint32_t objective, float floor)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (objective != SOTS_OBJECTIVE_MAGNITUDE && objective != SOTS_OBJECTIVE_LOG_MAGNITUDE)
-        return fail(ctx, SOTS_ERR_INVALID, "unknown objective %u (0 = magnitude, 1 = log magnitude)", objective);
-    if (objective == SOTS_OBJECTIVE_LOG_MAGNITUDE && !objective_floor_ok(floor))
-        return fail(ctx, SOTS_ERR_INVALID, "log-magnitude floor %g outside 1e-30 .. 1", (double)floor);
-    if (int rc = bind_device(ctx)) return rc;
-    const Objective old = ctx->obj;
-    ctx->obj.kind = objective;
-    ctx->obj.floor = objective == SOTS_OBJECTIVE_LOG_MAGNITUDE ? floor : 0.0f;
-    if (ctx->obj.kind != old.kind) occ_forget(ctx->occ); // (other kernels, other occupancies)
+    Objective old;
+    if (int rc = engine_set_objective(*ctx, objective, floor, &old)) return rc;
     if (int rc = derive_target(ctx)) {
-        ctx->obj = old;
+        engine_restore_objective(*ctx, old);
         return rc;
     }
     return SOTS_OK;
@@ -1187,34 +991,10 @@ int sots_set_objective(sots_ctx *ctx, uint32_t objective, float floor)
 int sots_set_objective_weights(sots_ctx *ctx, const float *weights, uint32_t num_bins)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if ((weights == nullptr) != (num_bins == 0))
-        return fail(ctx, SOTS_ERR_INVALID, "objective weights: a table and its length, or NULL and 0");
-    std::vector<float> u;
-    if (weights) {
-        uint32_t bad = 0;
-        switch (objective_weights_check(weights, num_bins, ctx->N / 2, u, &bad)) {
-        case 1: return fail(ctx, SOTS_ERR_INVALID, "objective weights need %u bins, got %u", ctx->N / 2, num_bins);
-        case 2: return fail(ctx, SOTS_ERR_INVALID, "objective weight %u is %g: every weight must be finite and >= 0", bad, (double)weights[bad]);
-        case 3: return fail(ctx, SOTS_ERR_INVALID, "objective weights are all zero");
-        default: break;
-        }
-    }
-    if (int rc = bind_device(ctx)) return rc;
-    const Objective old = ctx->obj;
-    if (weights) {
-        if (!ctx->weights_u) SOTS_HIP(ctx, hipMalloc((void **)&ctx->weights_u, (size_t)num_bins * sizeof(float)));
-        if (!ctx->weights_image) SOTS_HIP(ctx, hipMalloc((void **)&ctx->weights_image, weight_image_bytes(ctx->log2n)));
-        SOTS_HIP(ctx, hipMemcpyAsync(ctx->weights_u, u.data(), (size_t)num_bins * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        SOTS_HIP(ctx, launch_weight_image(ctx->stream, ctx->weights_image, ctx->weights_u, ctx->log2n));
-        SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (u goes out of scope)
-        ctx->obj.weights = ctx->weights_u;
-        ctx->obj.weights_image = ctx->weights_image;
-    } else {
-        ctx->obj.weights = ctx->obj.weights_image = nullptr;
-    }
-    if ((ctx->obj.weights != nullptr) != (old.weights != nullptr)) occ_forget(ctx->occ); // (other kernels, other occupancies)
+    Objective old;
+    if (int rc = engine_set_objective_weights(*ctx, weights, num_bins, &old)) return rc;
     if (int rc = derive_target(ctx)) {
-        ctx->obj = old;
+        engine_restore_objective(*ctx, old);
         return rc;
     }
     if (weights) ctx->weights_w.assign(weights, weights + num_bins);
@@ -1225,8 +1005,8 @@ int sots_set_objective_weights(sots_ctx *ctx, const float *weights, uint32_t num
 int sots_get_objective_weights(const sots_ctx *ctx, float *weights, uint32_t num_bins, uint32_t *is_set)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!weights && !is_set) return fail(ctx, SOTS_ERR_INVALID, "null weights and is_set pointers");
-    if (weights && num_bins != ctx->N / 2) return fail(ctx, SOTS_ERR_INVALID, "objective weights have %u bins, room for %u", ctx->N / 2, num_bins);
+    if (!weights && !is_set) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "null weights and is_set pointers");
+    if (weights && num_bins != ctx->N / 2) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "objective weights have %u bins, room for %u", ctx->N / 2, num_bins);
     if (is_set) *is_set = ctx->weights_w.empty() ? 0u : 1u;
     if (weights && !ctx->weights_w.empty()) std::copy(ctx->weights_w.begin(), ctx->weights_w.end(), weights);
     return SOTS_OK;
@@ -1235,7 +1015,7 @@ int sots_get_objective_weights(const sots_ctx *ctx, float *weights, uint32_t num
 int sots_get_objective(const sots_ctx *ctx, uint32_t *objective, float *floor)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!objective && !floor) return fail(ctx, SOTS_ERR_INVALID, "null objective and floor pointers");
+    if (!objective && !floor) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "null objective and floor pointers");
     if (objective) *objective = ctx->obj.kind;
     if (floor) *floor = ctx->obj.floor;
     return SOTS_OK;
@@ -1244,7 +1024,7 @@ int sots_get_objective(const sots_ctx *ctx, uint32_t *objective, float *floor)
 int sots_get_generation(const sots_ctx *ctx, uint32_t *generation)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!generation) return fail(ctx, SOTS_ERR_INVALID, "null generation pointer");
+    if (!generation) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "null generation pointer");
     *generation = ctx->generation;
     return SOTS_OK;
 }
@@ -1262,17 +1042,17 @@ int sots_render_overlap_add(sots_ctx *ctx, const float *values, size_t values_by
 {
     SOTS_REQUIRE_CTX(ctx);
     if (!args || args->struct_size != sizeof(sots_render_args))
-        return fail(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: null args or sots_render_args.struct_size != %zu", sizeof(sots_render_args));
+        return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: null args or sots_render_args.struct_size != %zu", sizeof(sots_render_args));
     const uint32_t N = ctx->N, hop = args->hop;
     if (hop < (N + 63u) / 64u || hop > N)
-        return fail(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: hop %u outside %u..%u", hop, (N + 63u) / 64u, N);
-    if (args->flags & ~(uint32_t)SOTS_RENDER_WINDOWED) return fail(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: unknown flags 0x%x", args->flags);
-    if (num_rows == 0) return fail(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: num_rows must be at least 1");
+        return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: hop %u outside %u..%u", hop, (N + 63u) / 64u, N);
+    if (args->flags & ~(uint32_t)SOTS_RENDER_WINDOWED) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: unknown flags 0x%x", args->flags);
+    if (num_rows == 0) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: num_rows must be at least 1");
     if (!values || values_bytes != (size_t)num_rows * ctx->D * sizeof(float))
-        return fail(ctx, SOTS_ERR_SIZE, "sots_render_overlap_add: %u rows need %zu bytes of values, got %zu", num_rows,
+        return SOTS_FAIL(ctx, SOTS_ERR_SIZE, "sots_render_overlap_add: %u rows need %zu bytes of values, got %zu", num_rows,
                     (size_t)num_rows * ctx->D * sizeof(float), values_bytes);
-    if (!out && out_samples) return fail(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: null output");
-    if (int rc = bind_device(ctx)) return rc;
+    if (!out && out_samples) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "sots_render_overlap_add: null output");
+    if (int rc = engine_bind(*ctx)) return rc;
 
     // A pass takes `step` chunk starts of output and holds, besides those chunks, the `reach` chunks in front of them that
     // extend into its range: synthesised again, so a pass needs nothing of the pass before it.
@@ -1285,7 +1065,7 @@ int sots_render_overlap_add(sots_ctx *ctx, const float *values, size_t values_by
     // (the synthesis kernels store whole tiles of rows where a tile is full: a margin of one tile behind the last row)
     if (hipError_t e = render_reserve(ctx->render, max_rows * ctx->D, (max_rows + 64u) * ctx->pitch, (size_t)step * hop + N + 4u)) {
         (void)hipGetLastError();
-        return fail(ctx, SOTS_ERR_HIP, "sots_render_overlap_add: scratch allocation failed: %s", hipGetErrorString(e));
+        return SOTS_FAIL(ctx, SOTS_ERR_HIP, "sots_render_overlap_add: scratch allocation failed: %s", hipGetErrorString(e));
     }
     for (uint32_t r0 = 0; r0 < num_rows && (uint64_t)r0 * hop < want; r0 += step) {
         const uint32_t r1 = num_rows - r0 > step ? r0 + step : num_rows, first = r0 > reach ? r0 - reach : 0u, rows = r1 - first;
@@ -1293,12 +1073,7 @@ int sots_render_overlap_add(sots_ctx *ctx, const float *values, size_t values_by
         const uint32_t count = (uint32_t)(end - s0);
         SOTS_HIP(ctx, hipMemcpyAsync(ctx->render.values, values + (size_t)first * ctx->D, (size_t)rows * ctx->D * sizeof(float),
                                      hipMemcpyHostToDevice, ctx->stream));
-        if (ctx->synth_arith == SOTS_ARITH_DEVICE_KERNELS)
-            SOTS_HIP(ctx, launch_synth_device_arith(ctx->stream, ctx->cfg.synth_kind, ctx->render.values, ctx->wavetable, ctx->render.audio, ctx->sp,
-                                                    rows, ctx->log2n, ctx->pitch));
-        else
-            SOTS_HIP(ctx, launch_synth(ctx->stream, ctx->cfg.synth_kind, ctx->render.values, ctx->wavetable, ctx->render.audio, ctx->sp, rows,
-                                       ctx->log2n, ctx->pitch, ctx->num_cus, nullptr, ctx->allow_cut));
+        SOTS_HIP(ctx, engine_synthesise(*ctx, ctx->render.values, ctx->render.audio, rows, nullptr, ctx->allow_cut));
         RenderPass ps{};
         ps.audio = ctx->render.audio;
         ps.window = (args->flags & SOTS_RENDER_WINDOWED) ? ctx->window : nullptr;
@@ -1326,7 +1101,7 @@ int sots_timing_enable(sots_ctx *ctx, int enabled)
 int sots_timing_reset(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     if (int rc = drain_clocks(ctx)) return rc;
     for (auto &ck : ctx->clocks) {
         ck.total_ms = 0.0;
@@ -1339,8 +1114,8 @@ int sots_timing_reset(sots_ctx *ctx)
 int sots_stage_time_ms(sots_ctx *ctx, int stage, double *total_ms, uint64_t *count)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (stage < 0 || stage >= SOTS_STAGE_COUNT) return fail(ctx, SOTS_ERR_INVALID, "stage %d out of range", stage);
-    if (int rc = bind_device(ctx)) return rc;
+    if (stage < 0 || stage >= SOTS_STAGE_COUNT) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "stage %d out of range", stage);
+    if (int rc = engine_bind(*ctx)) return rc;
     if (int rc = drain_clocks(ctx)) return rc;
     if (total_ms) *total_ms = ctx->clocks[stage].total_ms;
     if (count) *count = ctx->clocks[stage].count;
@@ -1350,9 +1125,9 @@ int sots_stage_time_ms(sots_ctx *ctx, int stage, double *total_ms, uint64_t *cou
 int sots_stage_launch_times_ms(sots_ctx *ctx, int stage, float *out_ms, uint64_t capacity, uint64_t *written)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (stage < 0 || stage >= SOTS_STAGE_COUNT) return fail(ctx, SOTS_ERR_INVALID, "stage %d out of range", stage);
-    if (!written || (capacity && !out_ms)) return fail(ctx, SOTS_ERR_INVALID, "stage_launch_times: null argument");
-    if (int rc = bind_device(ctx)) return rc;
+    if (stage < 0 || stage >= SOTS_STAGE_COUNT) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "stage %d out of range", stage);
+    if (!written || (capacity && !out_ms)) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "stage_launch_times: null argument");
+    if (int rc = engine_bind(*ctx)) return rc;
     if (int rc = drain_clocks(ctx)) return rc;
     const std::vector<float> &v = ctx->clocks[stage].launches_ms;
     const uint64_t n = v.size() < capacity ? v.size() : capacity;
@@ -1365,13 +1140,13 @@ int sots_stage_launch_times_ms(sots_ctx *ctx, int stage, float *out_ms, uint64_t
 int sots_pack_elites_device(sots_ctx *ctx, void *device_rows, uint32_t n_rows)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!device_rows || n_rows > ctx->P) return fail(ctx, SOTS_ERR_INVALID, "pack_elites: bad rows/n_rows %u", n_rows);
+    if (!device_rows || n_rows > ctx->P) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "pack_elites: bad rows/n_rows %u", n_rows);
     if (ctx->tail_pending && n_rows > ctx->tail_first) {
         if (ctx->sort_mode == SOTS_SORT_TOP_ONLY)
-            return fail(ctx, SOTS_ERR_STATE, "pack_elites: %u rows asked for, SOTS_SORT_TOP_ONLY placed %u", n_rows, ctx->tail_first);
+            return SOTS_FAIL(ctx, SOTS_ERR_STATE, "pack_elites: %u rows asked for, SOTS_SORT_TOP_ONLY placed %u", n_rows, ctx->tail_first);
         if (int rc = complete_tail(ctx)) return rc;
     }
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     SOTS_HIP(ctx, launch_pack_rows(ctx->stream, ctx->val(ctx->rot), ctx->stp(ctx->rot), ctx->fit(ctx->rot),
                                    (float *)device_rows, 0, n_rows, ctx->D));
     return SOTS_OK;
@@ -1381,8 +1156,8 @@ int sots_inject_immigrants_device(sots_ctx *ctx, const void *device_rows, uint32
 {
     SOTS_REQUIRE_CTX(ctx);
     if (!device_rows || n_rows > breeding_rows(ctx))
-        return fail(ctx, SOTS_ERR_INVALID, "inject_immigrants: %u rows do not fit the %u parent rows recombination reads", n_rows, breeding_rows(ctx));
-    if (int rc = bind_device(ctx)) return rc;
+        return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "inject_immigrants: %u rows do not fit the %u parent rows recombination reads", n_rows, breeding_rows(ctx));
+    if (int rc = engine_bind(*ctx)) return rc;
     SOTS_HIP(ctx, launch_unpack_rows(ctx->stream, ctx->val(ctx->rot), ctx->stp(ctx->rot), ctx->fit(ctx->rot),
                                      (const float *)device_rows, breeding_rows(ctx) - n_rows, n_rows, ctx->D, 0, 0));
     return SOTS_OK;
@@ -1392,12 +1167,12 @@ int sots_inject_gathered_device(sots_ctx *ctx, const void *gathered_rows, uint32
 {
     SOTS_REQUIRE_CTX(ctx);
     if (!gathered_rows || world == 0 || rank >= world)
-        return fail(ctx, SOTS_ERR_INVALID, "inject_gathered: bad arguments (world %u, rank %u)", world, rank);
+        return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "inject_gathered: bad arguments (world %u, rank %u)", world, rank);
     const uint64_t n_rows = (uint64_t)(world - 1) * elites;
     if (n_rows > breeding_rows(ctx))
-        return fail(ctx, SOTS_ERR_INVALID, "inject_gathered: %llu immigrant rows do not fit the %u parent rows recombination reads",
+        return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "inject_gathered: %llu immigrant rows do not fit the %u parent rows recombination reads",
                     (unsigned long long)n_rows, breeding_rows(ctx));
-    if (int rc = bind_device(ctx)) return rc;
+    if (int rc = engine_bind(*ctx)) return rc;
     SOTS_HIP(ctx, launch_unpack_rows(ctx->stream, ctx->val(ctx->rot), ctx->stp(ctx->rot), ctx->fit(ctx->rot),
                                      (const float *)gathered_rows, breeding_rows(ctx) - (uint32_t)n_rows, (uint32_t)n_rows,
                                      ctx->D, rank * elites, elites));
@@ -1412,15 +1187,15 @@ int sots_fuse_exchange_next_sort(sots_ctx *ctx, void *elite_rows, uint32_t n_eli
     ctx->next_exchange_gate = nullptr;
     SortExchange ex{};
     if (elite_rows) {
-        if (n_elite_rows == 0 || n_elite_rows > ctx->P) return fail(ctx, SOTS_ERR_INVALID, "fused exchange: bad elite row count %u", n_elite_rows);
+        if (n_elite_rows == 0 || n_elite_rows > ctx->P) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "fused exchange: bad elite row count %u", n_elite_rows);
         ex.sink = (float *)elite_rows;
         ex.sink_rows = n_elite_rows;
     }
     if (gathered_rows) {
-        if (world == 0 || rank >= world) return fail(ctx, SOTS_ERR_INVALID, "fused exchange: bad arguments (world %u, rank %u)", world, rank);
+        if (world == 0 || rank >= world) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "fused exchange: bad arguments (world %u, rank %u)", world, rank);
         const uint64_t n_rows = (uint64_t)(world - 1) * elites;
         if (n_rows > breeding_rows(ctx))
-            return fail(ctx, SOTS_ERR_INVALID, "fused exchange: %llu immigrant rows do not fit the %u parent rows recombination reads",
+            return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "fused exchange: %llu immigrant rows do not fit the %u parent rows recombination reads",
                         (unsigned long long)n_rows, breeding_rows(ctx));
         if (n_rows) {
             ex.imm = (const float *)gathered_rows;
@@ -1440,8 +1215,8 @@ int sots_fuse_exchange_next_sort(sots_ctx *ctx, void *elite_rows, uint32_t n_eli
 int sots_pack_elites_host(sots_ctx *ctx, float *rows, uint32_t n_rows)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!rows) return fail(ctx, SOTS_ERR_INVALID, "pack_elites: null rows");
-    if (int rc = bind_device(ctx)) return rc;
+    if (!rows) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "pack_elites: null rows");
+    if (int rc = engine_bind(*ctx)) return rc;
     if (int rc = ensure_rows(ctx, n_rows)) return rc;
     if (int rc = sots_pack_elites_device(ctx, ctx->rows, n_rows)) return rc;
     SOTS_HIP(ctx, hipMemcpyAsync(rows, ctx->rows, (size_t)n_rows * (2 * ctx->D + 1) * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
@@ -1452,8 +1227,8 @@ int sots_pack_elites_host(sots_ctx *ctx, float *rows, uint32_t n_rows)
 int sots_inject_immigrants_host(sots_ctx *ctx, const float *rows, uint32_t n_rows)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!rows) return fail(ctx, SOTS_ERR_INVALID, "inject_immigrants: null rows");
-    if (int rc = bind_device(ctx)) return rc;
+    if (!rows) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "inject_immigrants: null rows");
+    if (int rc = engine_bind(*ctx)) return rc;
     if (int rc = ensure_rows(ctx, n_rows)) return rc;
     SOTS_HIP(ctx, hipMemcpyAsync(ctx->rows, rows, (size_t)n_rows * (2 * ctx->D + 1) * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     if (int rc = sots_inject_immigrants_device(ctx, ctx->rows, n_rows)) return rc;
@@ -1464,7 +1239,7 @@ int sots_inject_immigrants_host(sots_ctx *ctx, const float *rows, uint32_t n_row
 int sots_get_info(const sots_ctx *ctx, sots_info *info)
 {
     SOTS_REQUIRE_CTX(ctx);
-    if (!info) return fail(ctx, SOTS_ERR_INVALID, "null info");
+    if (!info) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "null info");
     memset(info, 0, sizeof *info);
     info->population_length = ctx->P;
     info->num_dimensions = ctx->D;

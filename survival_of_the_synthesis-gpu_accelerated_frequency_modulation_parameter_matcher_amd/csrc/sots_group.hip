@@ -37,6 +37,7 @@
 
 #include "../../include/sots_hip.h"
 #include "sots_host_sync.h"
+#include "sots_rules.h"
 
 using sots_host::JobGate;
 using sots_host::SpinBarrier;
@@ -405,11 +406,10 @@ int sots_group_create(const sots_config *island_cfg, const int32_t *devices, uin
         if (int rc = sots_set_stream(is.ctx, is.stream)) CREATE_FAIL(rc, "island %u: %s", i, sots_last_error(is.ctx));
         // immigrants overwrite the tail of the rows recombination reads: whole parent blocks (sots_inject_gathered_device)
         const uint64_t immigrants = (uint64_t)(num_devices - 1) * g->elites;
-        const uint32_t block = island_cfg->workgroup_size ? island_cfg->workgroup_size : 1u;
-        const uint32_t npb = island_cfg->num_parents / block ? island_cfg->num_parents / block : 1u;
-        if (g->elites > p64 || immigrants > (uint64_t)npb * block)
+        const uint32_t breeding = sots::breeding_rows(island_cfg->num_parents, island_cfg->workgroup_size);
+        if (g->elites > p64 || immigrants > breeding)
             CREATE_FAIL(SOTS_ERR_INVALID, "%u elites from each of %u other islands do not fit the %u parent rows recombination reads",
-                        g->elites, num_devices - 1, npb * block);
+                        g->elites, num_devices - 1, breeding);
         const size_t mine_bytes = (size_t)(g->elites ? g->elites : 1) * g->width * sizeof(float);
         // rows nobody has written yet read as [+inf fitness, +inf ...]: an island that fails before its first exchange
         // still joins the gather, and such rows sort behind everything (0x7F800000 in every float)
@@ -435,15 +435,10 @@ int sots_group_create(const sots_config *island_cfg, const int32_t *devices, uin
     }
 #undef CREATE_HIP
 #undef CREATE_FAIL
-    {
-        // sortPopulation places rows 0..S-1 per generation where the selection applies (enum sots_sort_mode); elites beyond
-        // them need the completed order, i.e. the separate pack launch
-        const uint32_t block = island_cfg->workgroup_size ? island_cfg->workgroup_size : 1u;
-        const uint32_t npb = island_cfg->num_parents / block ? island_cfg->num_parents / block : 1u;
-        const uint32_t placed = npb * block > island_cfg->num_parents ? npb * block : island_cfg->num_parents;
-        g->fused = g->elites <= placed && !(flags & SOTS_GROUP_UNFUSED);
-        g->host_gated = g->fused && (flags & SOTS_GROUP_OVERLAP) && !(flags & SOTS_GROUP_EVENT_WAITS);
-    }
+    // sortPopulation places rows 0..S-1 per generation where the selection applies (enum sots_sort_mode); elites beyond
+    // them need the completed order, i.e. the separate pack launch
+    g->fused = g->elites <= sots::selected_rows(island_cfg->num_parents, island_cfg->workgroup_size) && !(flags & SOTS_GROUP_UNFUSED);
+    g->host_gated = g->fused && (flags & SOTS_GROUP_OVERLAP) && !(flags & SOTS_GROUP_EVENT_WAITS);
     g->rcs.assign(num_devices, SOTS_OK);
     g->barrier = new SpinBarrier(num_devices);
     for (uint32_t i = 1; i < num_devices; ++i) g->workers.emplace_back(worker_main, g, i);

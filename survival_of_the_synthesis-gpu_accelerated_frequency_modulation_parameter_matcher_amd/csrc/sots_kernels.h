@@ -8,19 +8,13 @@
 #include <vector>
 
 #include "../../include/sots_hip.h"
+#include "sots_rules.h" // MutateConsts
 
 namespace sots {
 
 constexpr uint32_t kWavetableSize = SOTS_WAVETABLE_SIZE;
 constexpr uint32_t kTagInit = 0x494e4954u;   // PRNG domain words (4th Philox counter word)
 constexpr uint32_t kTagMutate = 0x4d555441u;
-
-// ES constants, Evolutionary_Strategy.hpp:611-627; the two pow(Ek, beta) values are
-// evaluated once on the host (Ek only ever takes two values, ocl_program.cl:168,185).
-struct MutateConsts {
-    float alpha, one_over_alpha, root_two_over_pi, beta_scale;
-    float pow_alpha_beta, pow_inv_alpha_beta;
-};
 
 struct SynthParams {
     float pmin[SOTS_MAX_DIMS];
@@ -93,25 +87,8 @@ struct Objective {
     const float *weights = nullptr;
     const float *weights_image = nullptr;
 };
-// w[n] as sots_set_objective_weights takes it: n == bins, every entry finite and >= 0, one at least > 0.  0: fine, and
-// u[k] = sqrtf(w[k]) (correctly rounded); 1: wrong length; 2: entry *bad is negative or not finite; 3: all zero
-inline int objective_weights_check(const float *w, uint32_t n, uint32_t bins, std::vector<float> &u, uint32_t *bad)
-{
-    if (n != bins) return 1;
-    bool any = false;
-    for (uint32_t k = 0; k < n; ++k) {
-        if (!(w[k] >= 0.0f) || !std::isfinite(w[k])) return *bad = k, 2;
-        any = any || w[k] > 0.0f;
-    }
-    if (!any) return 3;
-    u.resize(n);
-    for (uint32_t k = 0; k < n; ++k) u[k] = std::sqrt(w[k]);
-    return 0;
-}
 size_t weight_image_bytes(uint32_t log2n);
 hipError_t launch_weight_image(hipStream_t st, float *image, const float *u, uint32_t log2n);
-// 1e-30 <= floor <= 1: m + floor is then a normal fp32 number for every magnitude m >= 0
-inline bool objective_floor_ok(float floor) { return floor >= 1e-30f && floor <= 1.0f; } // (false for NaN)
 // dst[i] = ln(src[i] + floor) with the device routine the fitness epilogues apply to the candidate's bins
 hipError_t launch_objective_map(hipStream_t st, float *dst, const float *src, size_t n, float floor);
 // the cached occupancies belong to the kernels of one objective: forgotten when it changes (the image pointer stays)

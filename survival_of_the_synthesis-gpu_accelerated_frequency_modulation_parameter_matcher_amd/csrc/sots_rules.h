@@ -1,0 +1,187 @@
+// sots_rules.h -- what a context (sots_ctx), a batch (sots_batch) and a group accept, and the numbers that follow from a
+// configuration, stated ONCE: the handles call these and add their own limits.  A refusal is a Fault: the code the entry
+// point returns and the text its last_error gives.  No HIP header: plain C++ compilers build it too (the sanitizer
+// builds of tests/).  Internal to libsots_hip.so.
+#pragma once
+
+#include <stdint.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstddef>
+#include <cstdio>
+#include <vector>
+
+#include "../../include/sots_hip.h"
+
+namespace sots {
+
+struct Fault {
+    int code = SOTS_OK;
+    char text[512] = {0};
+    explicit operator bool() const { return code != SOTS_OK; }
+};
+__attribute__((format(printf, 2, 3))) inline Fault fault(int code, const char *fmt, ...)
+{
+    Fault f;
+    f.code = code;
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(f.text, sizeof f.text, fmt, ap);
+    va_end(ap);
+    return f;
+}
+
+// ---- configuration ----
+// genes of a voice; 0: no such voice
+inline uint32_t dims_of(uint32_t kind)
+{
+    switch (kind) {
+    case SOTS_SYNTH_2OP: return 4;
+    case SOTS_SYNTH_3OP_SERIES: return 6;
+    case SOTS_SYNTH_TRIPLE_PAR: return 12;
+    case SOTS_SYNTH_4OP_SERIES: return 8;
+    default: return 0;
+    }
+}
+
+// Everything a configuration must satisfy whoever takes it; max_population is the caller's own limit on numParents +
+// numOffspring.  Needs no device: a machine without a GPU still tells a bad configuration from a good one.
+constexpr uint64_t kNoPopulationLimit = ~0ull; // (a caller that words its limit itself)
+inline Fault config_check(const sots_config &cfg, uint64_t max_population)
+{
+    if (cfg.struct_size != sizeof(sots_config))
+        return fault(SOTS_ERR_INVALID, "sots_config.struct_size %u != %zu", cfg.struct_size, sizeof(sots_config));
+    const uint32_t d = dims_of(cfg.synth_kind);
+    if (d == 0) return fault(SOTS_ERR_INVALID, "unknown synth_kind %u", cfg.synth_kind);
+    if (cfg.num_dimensions != d)
+        return fault(SOTS_ERR_INVALID, "synth_kind %u needs numDimensions %u, got %u", cfg.synth_kind, d, cfg.num_dimensions);
+    if (cfg.audio_length_log2 < 8 || cfg.audio_length_log2 > 15)
+        return fault(SOTS_ERR_INVALID, "audioLengthLog2 %u outside 8..15", cfg.audio_length_log2);
+    const uint64_t p64 = (uint64_t)cfg.num_parents + cfg.num_offspring;
+    if (cfg.num_parents == 0 || p64 < 2 || p64 > max_population)
+        return fault(SOTS_ERR_INVALID, "population %llu (parents %u) not supported", (unsigned long long)p64, cfg.num_parents);
+    if (cfg.workgroup_size == 0 || p64 % cfg.workgroup_size != 0)
+        return fault(SOTS_ERR_INVALID, "populationLength %llu must be a multiple of workgroupSize %u (the recombination block)",
+                     (unsigned long long)p64, cfg.workgroup_size);
+    return Fault{};
+}
+
+// ES constants, Evolutionary_Strategy.hpp:611-627; the two pow(Ek, beta) values are
+// evaluated once on the host (Ek only ever takes two values, ocl_program.cl:168,185).
+struct MutateConsts {
+    float alpha, one_over_alpha, root_two_over_pi, beta_scale;
+    float pow_alpha_beta, pow_inv_alpha_beta;
+};
+inline MutateConsts mutate_consts(uint32_t num_dimensions)
+{
+    const float mpi = (float)3.14159265358979323846;
+    MutateConsts mc;
+    mc.alpha = 1.4f;
+    mc.one_over_alpha = 1.f / mc.alpha;
+    mc.root_two_over_pi = sqrtf(2.f / (float)mpi);
+    mc.beta_scale = 1.f / (float)num_dimensions;
+    const float beta = sqrtf(mc.beta_scale);
+    mc.pow_alpha_beta = powf(mc.alpha, beta);
+    mc.pow_inv_alpha_beta = powf(mc.one_over_alpha, beta);
+    return mc;
+}
+
+// ---- the rows of a sorted half ----
+// Rows that the next recombination reads (recombine_source, sots_kernels.hip):
+// whole blocks of parents, floor(numParents / block) of them, at least one.  Immigrants go to the
+// tail of THESE rows: with numParents not a multiple of the block, rows between the last whole
+// block and numParents are never read and immigrants written there would be dead.
+inline uint32_t breeding_rows(uint32_t num_parents, uint32_t block)
+{
+    if (block == 0) block = 1;
+    uint32_t npb = num_parents / block;
+    if (npb == 0) npb = 1;
+    return npb * block;
+}
+
+// rows the selection must deliver in order: what recombination reads, and never fewer than the parents
+inline uint32_t selected_rows(uint32_t num_parents, uint32_t block)
+{
+    const uint32_t b = breeding_rows(num_parents, block);
+    return b > num_parents ? b : num_parents;
+}
+
+// one population through the C-ABI: P x D floats of values and of steps, P of fitness; an array that is not passed is not counted
+inline Fault population_bytes_check(uint32_t p, uint32_t d, const void *values, size_t values_bytes, const void *steps, size_t steps_bytes,
+                                    const void *fitness, size_t fitness_bytes)
+{
+    const size_t pd_bytes = (size_t)p * d * sizeof(float), f_bytes = (size_t)p * sizeof(float);
+    if ((values && values_bytes != pd_bytes) || (steps && steps_bytes != pd_bytes) || (fitness && fitness_bytes != f_bytes))
+        return fault(SOTS_ERR_SIZE, "population byte counts must be %zu (values, steps) and %zu (fitness)", pd_bytes, f_bytes);
+    return Fault{};
+}
+
+// ---- objective ----
+// 1e-30 <= floor <= 1: m + floor is then a normal fp32 number for every magnitude m >= 0
+inline bool objective_floor_ok(float floor) { return floor >= 1e-30f && floor <= 1.0f; } // (false for NaN)
+inline Fault objective_check(uint32_t objective, float floor)
+{
+    if (objective != SOTS_OBJECTIVE_MAGNITUDE && objective != SOTS_OBJECTIVE_LOG_MAGNITUDE)
+        return fault(SOTS_ERR_INVALID, "unknown objective %u (0 = magnitude, 1 = log magnitude)", objective);
+    if (objective == SOTS_OBJECTIVE_LOG_MAGNITUDE && !objective_floor_ok(floor))
+        return fault(SOTS_ERR_INVALID, "log-magnitude floor %g outside 1e-30 .. 1", (double)floor);
+    return Fault{};
+}
+
+// w[n] as sots_set_objective_weights takes it: n == bins, every entry finite and >= 0, one at least > 0.  0: fine, and
+// u[k] = sqrtf(w[k]) (correctly rounded); 1: wrong length; 2: entry *bad is negative or not finite; 3: all zero
+inline int objective_weights_check(const float *w, uint32_t n, uint32_t bins, std::vector<float> &u, uint32_t *bad)
+{
+    if (n != bins) return 1;
+    bool any = false;
+    for (uint32_t k = 0; k < n; ++k) {
+        if (!(w[k] >= 0.0f) || !std::isfinite(w[k])) return *bad = k, 2;
+        any = any || w[k] > 0.0f;
+    }
+    if (!any) return 3;
+    u.resize(n);
+    for (uint32_t k = 0; k < n; ++k) u[k] = std::sqrt(w[k]);
+    return 0;
+}
+// ... as a refusal: a table and its length (u as above), or NULL and 0 (no weights, u untouched)
+inline Fault objective_weights_fault(const float *weights, uint32_t num_bins, uint32_t bins, std::vector<float> &u)
+{
+    if ((weights == nullptr) != (num_bins == 0)) return fault(SOTS_ERR_INVALID, "objective weights: a table and its length, or NULL and 0");
+    if (!weights) return Fault{};
+    uint32_t bad = 0;
+    switch (objective_weights_check(weights, num_bins, bins, u, &bad)) {
+    case 1: return fault(SOTS_ERR_INVALID, "objective weights need %u bins, got %u", bins, num_bins);
+    case 2: return fault(SOTS_ERR_INVALID, "objective weight %u is %g: every weight must be finite and >= 0", bad, (double)weights[bad]);
+    case 3: return fault(SOTS_ERR_INVALID, "objective weights are all zero");
+    default: return Fault{};
+    }
+}
+
+// ---- run record, stop rules ----
+constexpr uint64_t kTrackMaxRecords = 1ull << 24; // chunks x history_capacity (1.5 GiB of records)
+// sots_track / sots_batch_track: known flags, a history with a period and room, and no more than kTrackMaxRecords records
+// over the handle's chunks.  *flags comes back normalised (HISTORY implies BEST_EVER).  max_chunks 0: a context, one
+// population whose refusal has no chunk count to name.
+inline Fault track_args_check(uint32_t *flags, uint32_t history_every, uint32_t history_capacity, uint32_t max_chunks)
+{
+    if (*flags & ~(uint32_t)(SOTS_TRACK_BEST_EVER | SOTS_TRACK_HISTORY)) return fault(SOTS_ERR_INVALID, "unknown track flags %u", *flags);
+    if (!(*flags & SOTS_TRACK_HISTORY)) return Fault{};
+    *flags |= SOTS_TRACK_BEST_EVER;
+    if (history_every == 0 || history_capacity == 0)
+        return fault(SOTS_ERR_INVALID, "history needs history_every >= 1 and history_capacity >= 1 (got %u, %u)", history_every, history_capacity);
+    if (max_chunks == 0 && history_capacity > kTrackMaxRecords)
+        return fault(SOTS_ERR_INVALID, "history_capacity %u exceeds %llu records", history_capacity, (unsigned long long)kTrackMaxRecords);
+    if ((uint64_t)history_capacity * max_chunks > kTrackMaxRecords)
+        return fault(SOTS_ERR_INVALID, "history_capacity %u x max_chunks %u exceeds %llu records", history_capacity, max_chunks,
+                     (unsigned long long)kTrackMaxRecords);
+    return Fault{};
+}
+
+inline int stop_rule_check(const sots_stop_rule *rule)
+{
+    if (!rule || rule->struct_size != sizeof(sots_stop_rule) || rule->check_interval == 0) return SOTS_ERR_INVALID;
+    return SOTS_OK;
+}
+
+} // namespace sots

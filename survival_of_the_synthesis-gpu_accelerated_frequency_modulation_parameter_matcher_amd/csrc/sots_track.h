@@ -14,8 +14,6 @@ namespace sots {
 
 static_assert(sizeof(sots_gen_record) == kTrackRecordFloats * sizeof(float), "sots_gen_record is what k_track writes");
 
-constexpr uint64_t kTrackMaxRecords = 1ull << 24; // chunks x history_capacity (1.5 GiB of records)
-
 struct TrackState {
     uint32_t flags = 0;    // enum sots_track_flags; 0: nothing allocated, nothing launched
     uint32_t every = 0;    // history: a record when the generation counter is a multiple of this

@@ -35,6 +35,60 @@ def test_batch_create_rejects_bad_configs(hip, over, max_chunks, needle):
     assert needle in hip.load().sots_batch_last_error(None).decode()
 
 
+# code and full text as the library gave them before the checks moved into csrc/sots_rules.h: one fault per call.
+# SHARED: the faults the rules own, for a context and a batch alike; the rest are the batch's own limits.
+SHARED = [
+    (dict(struct_size=12), "sots_config.struct_size 12 != 176"),
+    (dict(synth_kind=9), "unknown synth_kind 9"),
+    (dict(num_dimensions=6), "synth_kind 0 needs numDimensions 4, got 6"),
+    (dict(synth_kind=1), "synth_kind 1 needs numDimensions 6, got 4"),
+    (dict(audio_length_log2=7), "audioLengthLog2 7 outside 8..15"),
+    (dict(audio_length_log2=16), "audioLengthLog2 16 outside 8..15"),
+    (dict(num_parents=0), "population 16 (parents 0) not supported"),
+    (dict(num_parents=1, num_offspring=0, workgroup_size=1), "population 1 (parents 1) not supported"),
+    (dict(workgroup_size=0), "populationLength 32 must be a multiple of workgroupSize 0 (the recombination block)"),
+    (dict(workgroup_size=24), "populationLength 32 must be a multiple of workgroupSize 24 (the recombination block)"),
+]
+RECORDED_BATCH_CREATE = [(over, 4, text) for over, text in SHARED] + [
+    (dict(), 0, "max_chunks must be at least 1"),
+    (dict(num_parents=512, num_offspring=544), 4,
+     "a batch takes chunk populations of at most 1024, got 1056 (larger ones fill the GPU alone: sots_create)"),
+    (dict(num_parents=1 << 25, num_offspring=(1 << 25) + 32), 4,
+     "a batch takes chunk populations of at most 1024, got 67108896 (larger ones fill the GPU alone: sots_create)"),
+    (dict(num_parents=512, num_offspring=512), (1 << 16) + 1, "max_chunks 65537 x population 1024 exceeds 2^26 rows"),
+]
+
+
+@pytest.mark.parametrize("over,max_chunks,text", RECORDED_BATCH_CREATE)
+def test_batch_create_refusals_keep_their_text(hip, over, max_chunks, text):
+    rc, h = _create(hip, _cfg(hip, **over), max_chunks)
+    assert rc == -1 and not h.value
+    assert hip.load().sots_batch_last_error(None).decode() == text
+
+
+def test_shared_faults_read_the_same_from_both_create_calls(hip):
+    lib = hip.load()
+    for over, text in SHARED:
+        h = C.c_void_p()
+        assert lib.sots_create(C.byref(_cfg(hip, **over)), C.byref(h)) == -1 and not h.value
+        rc, hb = _create(hip, _cfg(hip, **over), 4)
+        assert rc == -1 and not hb.value
+        assert lib.sots_last_error(None).decode() == lib.sots_batch_last_error(None).decode() == text, over
+
+
+@pytest.mark.parametrize("name,args", [
+    ("sots_batch_set_objective", (0, 0.0)),
+    ("sots_batch_set_objective_weights", (None, 0)),
+    ("sots_batch_set_survivors", (0,)),
+    ("sots_batch_track", (0, 0, 0)),
+    ("sots_batch_set_synth_arithmetic", (0,)),
+])
+def test_batch_setters_refuse_a_null_batch(hip, name, args):
+    lib = hip.load()
+    assert getattr(lib, name)(None, *args) == -1
+    assert lib.sots_batch_last_error(None).decode() == "null batch"
+
+
 def test_batch_null_arguments(hip):
     lib = hip.load()
     assert lib.sots_batch_create(None, 4, None) == -1

@@ -61,6 +61,61 @@ def test_create_rejects_bad_configs(hip, over, needle):
     assert needle in lib.sots_last_error(None).decode()
 
 
+# code and full text as the library gave them before the checks moved into csrc/sots_rules.h: one fault per configuration
+RECORDED_CREATE = [
+    (dict(struct_size=12), "sots_config.struct_size 12 != 176"),
+    (dict(synth_kind=9), "unknown synth_kind 9"),
+    (dict(num_dimensions=6), "synth_kind 0 needs numDimensions 4, got 6"),
+    (dict(synth_kind=1), "synth_kind 1 needs numDimensions 6, got 4"),
+    (dict(audio_length_log2=7), "audioLengthLog2 7 outside 8..15"),
+    (dict(audio_length_log2=16), "audioLengthLog2 16 outside 8..15"),
+    (dict(num_parents=0), "population 16 (parents 0) not supported"),
+    (dict(num_parents=1, num_offspring=0, workgroup_size=1), "population 1 (parents 1) not supported"),
+    (dict(workgroup_size=0), "populationLength 32 must be a multiple of workgroupSize 0 (the recombination block)"),
+    (dict(workgroup_size=24), "populationLength 32 must be a multiple of workgroupSize 24 (the recombination block)"),
+    (dict(num_parents=1 << 25, num_offspring=(1 << 25) + 32), "population 67108896 (parents 33554432) not supported"),  # P > 2^26
+]
+
+
+@pytest.mark.parametrize("over,text", RECORDED_CREATE)
+def test_create_refusals_keep_their_text(hip, over, text):
+    lib = hip.load()
+    h = C.c_void_p()
+    rc = lib.sots_create(C.byref(_cfg(hip, **over)), C.byref(h))
+    assert rc == -1 and not h.value
+    assert lib.sots_last_error(None).decode() == text
+
+
+@pytest.mark.parametrize("name,args", [
+    ("sots_set_objective", (0, 0.0)),
+    ("sots_set_objective_weights", (None, 0)),
+    ("sots_set_survivors", (0,)),
+    ("sots_track", (0, 0, 0)),
+    ("sots_set_synth_arithmetic", (0,)),
+])
+def test_setters_refuse_a_null_context(hip, name, args):
+    lib = hip.load()
+    assert getattr(lib, name)(None, *args) == -1
+    assert lib.sots_last_error(None).decode() == "null context"
+
+
+# ---- sanitizers: host code only ---------------------------------------------------------------------------------------------
+SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
+ENV = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+
+
+def test_shared_rules_are_clean_under_asan_and_ubsan(tmp_path):
+    """csrc/sots_rules.h includes no HIP header: a plain g++ program drives every check in it under ASan + UBSan"""
+    import subprocess
+    exe = tmp_path / "rules_san"
+    subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra", *SAN, "-o", str(exe),
+                           os.path.join(ROOT, "tests", "rules_san.cpp")])
+    out = subprocess.run([str(exe)], capture_output=True, text=True, env=ENV, timeout=300)
+    assert out.returncode == 0, (out.stdout + out.stderr)[-4000:]
+    assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
+    assert "shared rules: 73 checks, 0 failures" in out.stdout
+
+
 def test_null_arguments(hip):
     lib = hip.load()
     assert lib.sots_create(None, None) == -1

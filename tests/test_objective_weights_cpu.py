@@ -183,11 +183,19 @@ def test_host_weight_tables_and_json_key(tmp_path):
 
 def test_library_checks_match_the_host_checks():
     """the C-ABI's validity rules are stated once for contexts and batches (objective_weights_check) and refuse what the
-    host's table maker refuses: negative, non-finite, all zero, wrong length"""
-    text = open(os.path.join(PKG_DIR, "csrc", "sots_kernels.h")).read()
-    assert "inline int objective_weights_check(" in text
-    for src in ("sots_capi.hip", "sots_batch.hip"):
-        assert "objective_weights_check(weights, num_bins" in open(os.path.join(PKG_DIR, "csrc", src)).read(), src
+    host's table maker refuses: negative, non-finite, all zero, wrong length.  Once: one definition in one header of
+    csrc/, and one call in all of csrc/*.h and csrc/*.hip, which contexts and batches both reach."""
+    import glob
+    import re
+    csrc = os.path.join(PKG_DIR, "csrc")
+    defined, called = [], []
+    for path in sorted(glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.hip"))):
+        code = re.sub(r"//[^\n]*", "", open(path).read())       # (comments may name it)
+        n_def = code.count("inline int objective_weights_check(")
+        defined += [os.path.basename(path)] * n_def
+        called += [os.path.basename(path)] * (code.count("objective_weights_check(") - n_def)
+    assert len(defined) == 1 and defined[0].endswith(".h"), defined
+    assert len(called) == 1, called
 
 
 def test_sots_match_source_prints_the_weights_only_when_asked():

@@ -4,5 +4,5 @@ cd "$(dirname "$0")/../survival_of_the_synthesis-gpu_accelerated_frequency_modul
 name=$1; shift
 mkdir -p ../variants build
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off "$@" -c -o build/variant_$name.o csrc/sots_kernels.hip
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ../variants/$name.so build/variant_$name.o build/sots_capi.o build/sots_group.o build/sots_host_math.o -ldl -lpthread
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o ../variants/$name.so build/variant_$name.o $(ls build/sots_*.o | grep -v sots_kernels.o) -ldl -lpthread
 echo variants/$name.so
