@@ -287,6 +287,47 @@ typedef struct sots_render_args {
 int sots_render_overlap_add(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
                             const sots_render_args *args, float *out, uint64_t out_samples);
 
+/* ---- phase-continuous rendering of a parameter track (new) ----
+ * The overlap-add rendering starts every row at phase 0, so overlapping rows of one stationary tone are 2 pi f hop / sr out
+ * of phase and their weighted mean is a comb filter in f.  This renders the track as ONE voice whose oscillators never
+ * restart.  Inputs as sots_render_overlap_add: values [num_rows][D] unit-range genes, 1 <= hop <= N, the context's voice,
+ * param_min / param_max and wavetable tab; S = (num_rows - 1) hop + N output samples.
+ * Row position of sample n: row c is anchored at the centre of the samples it analysed, c hop + N/2.  m = n - N/2; for
+ *   m <= 0: k = 0, r = 0; otherwise k = m / hop, r = m % hop; for k >= num_rows - 1: k = num_rows - 1, r = 0.
+ * Genes at n: HOLD (the default) row k + (2 r >= hop ? 1 : 0) as it is.  SOTS_RENDER_GLIDE: for r = 0 row k as it is,
+ *   otherwise t = (float)r / (float)hop (correctly rounded) and g_d = v[k][d] + t * (v[k+1][d] - v[k][d]) in fp32:
+ *   subtract, multiply, add, uncontracted.
+ * Parameters and derived products at n: the fp32 expressions of the reference's CPU path (Evolutionary_Strategy.hpp:368-495),
+ *   per sample: p = min + g (max - min) (the triple voice scales by entries d & 3), m1 = p0 p1, inc1 = c p0 or c p1, ...,
+ *   c = 32768 / 44100.0f.
+ * Phases: unsigned 15.17 fixed point in 32-bit words, so the wrap at W = 32768 is the wrap of the word.
+ *   fix(x): y = x * 131072.0f; rint(y), ties to even, reduced mod 2^32 (a negative increment is its two's complement);
+ *   0 where |y| < 2^62 does not hold.  Every operator: Phi(0) = 0, Phi(n+1) = Phi(n) + fix(inc(n)) mod 2^32, and its table
+ *   read is tab[Phi(n) >> 17]: always in range, no clamp, no wrap tests.  inc(n) of the first operator is the
+ *   constant-frequency increment; of a later one c cur(n) with cur(n) = tab[Phi_prev(n) >> 17] m + off as the reference
+ *   writes it, Phi_prev(n) being the operator before it BEFORE that operator's update.
+ * Output: tab[Phi_last(n) >> 17] amp, the reference's last line per voice; the triple voice: the three chains' products
+ *   added in order and divided by 3 as the synthesis kernels do.  Samples at n >= S are +0; a shorter out_samples truncates.
+ * An operator's phase is thus the exclusive prefix sum of its increments, and integer addition is associative: the bits do
+ * not depend on tiles, grids or passes, and tests/_render_continuous_model.py (NumPy, cumsum in uint32) is exact.  For
+ * one row the output is that row's voice, close to but not bit for bit sots_stage_synthesise's: the phase has 17
+ * fractional bits where fp32 has 8 near W.
+ * The work goes in passes of samples_per_pass output samples; a pass starts from the end phases of the pass before it (one
+ * word per operator: all the state there is).  Render scratch of the context's own as above.  Blocking; population, audio,
+ * spectrum, fitness, generation counter, run record, splitters and lists are untouched.
+ * SOTS_ERR_INVALID for null or mis-sized args, a hop outside 1 .. N, unknown flag bits, num_rows == 0 or S >= 2^31;
+ * SOTS_ERR_SIZE for values_bytes != num_rows * D * 4; SOTS_ERR_STATE under SOTS_ARITH_DEVICE_KERNELS (that mode exists to be
+ * the reference's device kernels bit for bit, and its 3-op voice reads another offset). */
+enum sots_render_continuous_flags { SOTS_RENDER_GLIDE = 1 };
+typedef struct sots_render_continuous_args {
+    uint32_t struct_size;      /* = sizeof(sots_render_continuous_args) */
+    uint32_t hop;              /* samples between row anchors, 1 <= hop <= N */
+    uint32_t flags;            /* enum sots_render_continuous_flags */
+    uint32_t samples_per_pass; /* 0 = the library's choice; else output samples per pass, >= 1 */
+} sots_render_continuous_args;
+int sots_render_continuous(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
+                           const sots_render_continuous_args *args, float *out, uint64_t out_samples);
+
 /* ---- per-stage device timing (feeds Benchmarker::addTimer, Benchmarker.hpp:109-130) ---- */
 int sots_timing_enable(sots_ctx *ctx, int enabled);
 int sots_timing_reset(sots_ctx *ctx);

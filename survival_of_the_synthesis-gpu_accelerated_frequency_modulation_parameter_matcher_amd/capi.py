@@ -69,9 +69,11 @@ EXPORTS = [
     "sots_set_objective_weights", "sots_get_objective_weights", "sots_batch_set_objective_weights",
     "sots_group_set_objective_weights",
     "sots_render_overlap_add", "sots_batch_set_target_audio_hop", "sots_batch_queue_targets_audio_hop",
+    "sots_render_continuous",
 ]
 QUEUE_NO_CHUNK = 0xFFFFFFFF
 RENDER_WINDOWED = 1
+RENDER_GLIDE = 1
 TRACK_BEST_EVER, TRACK_HISTORY = 1, 2
 BATCH_MAX_POPULATION = 1024
 GROUP_OVERLAP, GROUP_FORCE_RCCL, GROUP_UNFUSED, GROUP_EVENT_WAITS = 1, 2, 4, 8
@@ -141,6 +143,11 @@ CHUNK_RESULT_DTYPE = np.dtype([("generations_run", np.uint32), ("best_ever_gener
 class RenderArgs(C.Structure):
     """sots_render_args"""
     _fields_ = [("struct_size", C.c_uint32), ("hop", C.c_uint32), ("flags", C.c_uint32), ("rows_per_pass", C.c_uint32)]
+
+
+class RenderContinuousArgs(C.Structure):
+    """sots_render_continuous_args"""
+    _fields_ = [("struct_size", C.c_uint32), ("hop", C.c_uint32), ("flags", C.c_uint32), ("samples_per_pass", C.c_uint32)]
 
 
 class QueueStats(C.Structure):
@@ -273,6 +280,7 @@ def load():
     L.sots_batch_queue_read_kept_population.argtypes = [vp, vp, sz, vp, sz, vp, sz]
     L.sots_queue_makespan.argtypes = [C.POINTER(u32), u32, u32, u64p]
     L.sots_render_overlap_add.argtypes = [vp, vp, sz, u32, C.POINTER(RenderArgs), vp, C.c_uint64]
+    L.sots_render_continuous.argtypes = [vp, vp, sz, u32, C.POINTER(RenderContinuousArgs), vp, C.c_uint64]
     L.sots_batch_set_target_audio_hop.argtypes = [vp, vp, u32, u32, u32]
     L.sots_batch_queue_targets_audio_hop.argtypes = [vp, vp, C.c_uint64, u32, u32]
     _lib = L
@@ -445,6 +453,19 @@ class HipES:
         out = np.empty(max(n_out, 0), np.float32)
         args = RenderArgs(C.sizeof(RenderArgs), hop, RENDER_WINDOWED if windowed else 0, rows_per_pass)
         self._check(self.L.sots_render_overlap_add(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
+        return out
+
+    # -- phase-continuous rendering of a parameter track --
+    def render_continuous(self, values, hop, glide=False, samples_per_pass=0, out_samples=None):
+        """values[M][D] unit-range genes, row c anchored at sample c hop + N/2: the track as one voice whose oscillators
+        never restart, the genes held from anchor to anchor (switching half way) or, with glide, interpolated between
+        them.  out_samples None: (M-1) hop + N."""
+        v = _f32(values).reshape(-1, self.D)
+        rows = v.shape[0]
+        n_out = (rows - 1) * hop + self.N if out_samples is None else int(out_samples)
+        out = np.empty(max(n_out, 0), np.float32)
+        args = RenderContinuousArgs(C.sizeof(RenderContinuousArgs), hop, RENDER_GLIDE if glide else 0, samples_per_pass)
+        self._check(self.L.sots_render_continuous(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
         return out
 
     # -- stages --

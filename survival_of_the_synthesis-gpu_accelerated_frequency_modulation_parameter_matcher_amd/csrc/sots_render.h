@@ -1,10 +1,13 @@
-// sots_render.h -- overlap-add resynthesis of a parameter track (sots_render.hip).
-// Internal to libsots_hip.so; the public boundary is sots_render_overlap_add in include/sots_hip.h.
+// sots_render.h -- overlap-add resynthesis of a parameter track (sots_render.hip) and its phase-continuous
+// rendering (sots_render_continuous.hip).
+// Internal to libsots_hip.so; the public boundary is sots_render_overlap_add / sots_render_continuous in include/sots_hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+
+#include "sots_kernels.h" // SynthParams
 
 namespace sots {
 
@@ -31,13 +34,74 @@ inline uint32_t render_max_rows(uint32_t pitch)
     return r < 128u ? 128u : r;
 }
 
-// Device memory of the rendering, owned by a context: allocated on first use, grown when a call needs more, freed
-// with the context.  Apart from these three buffers a rendering writes nothing on the device.
+// Device memory of the renderings, owned by a context: allocated on first use, grown when a call needs more, freed
+// with the context.  Apart from these buffers a rendering writes nothing on the device.  The continuous rendering adds
+// `words`: its phase buffers, tile totals and carries in one allocation (ContLayout below says where each lies).
 struct RenderScratch {
     float *values = nullptr, *audio = nullptr, *out = nullptr;
     size_t values_floats = 0, audio_floats = 0, out_floats = 0;
+    uint32_t *words = nullptr;
+    size_t words_count = 0;
 };
 hipError_t render_reserve(RenderScratch &rs, size_t values_floats, size_t audio_floats, size_t out_floats);
+hipError_t render_reserve_words(RenderScratch &rs, size_t words);
 void render_release(RenderScratch &rs);
+
+// ---- phase-continuous rendering ----
+// A pass is `count` consecutive output samples, the first of them sample n0 of the rendering, cut into tiles of
+// kContTile samples counted from the pass's first.  Every operator stage of the voice is three launches in stream order:
+// reduce (a tile's increments summed to one word), scan (one workgroup per chain: the exclusive prefix of the totals on
+// top of the carry the pass before left, and the carry for the pass after), apply (the increments again, scanned inside
+// the tile on top of its base: the stage's phase word of every sample, or - the last stage - the output sample).
+constexpr uint32_t kContTile = 4096;            // samples per tile = kContThreads lanes x 4 samples
+constexpr uint32_t kContMaxPass = 1u << 22;     // samples per pass: 6 phase buffers of 16 MiB at the most (the voice of three chains)
+constexpr uint32_t kContMaxChains = 3, kContMaxStages = 4;
+constexpr size_t kContMaxValueFloats = 1u << 24; // floats of genes a pass may need on the device (64 MiB)
+
+inline uint32_t cont_chains(uint32_t kind) { return kind == SOTS_SYNTH_TRIPLE_PAR ? 3u : 1u; }
+
+// where the words of a rendering lie in RenderScratch::words, for passes of at most pass_samples samples
+struct ContLayout {
+    uint32_t stride, tiles; // words between the chains of a phase buffer (a multiple of 4), tiles of a full pass
+    size_t phi[2], totals, carry, words;
+};
+inline ContLayout cont_layout(uint32_t kind, uint32_t pass_samples)
+{
+    ContLayout l{};
+    const uint32_t chains = cont_chains(kind);
+    l.stride = (pass_samples + 3u) & ~3u;
+    l.tiles = (pass_samples + kContTile - 1u) / kContTile;
+    l.phi[0] = 0;
+    l.phi[1] = (size_t)chains * l.stride;
+    l.totals = 2 * (size_t)chains * l.stride;
+    l.carry = l.totals + (((size_t)chains * l.tiles + 3u) & ~(size_t)3u);
+    l.words = l.carry + kContMaxStages * kContMaxChains;
+    return l;
+}
+
+// Row position of sample n (include/sots_hip.h, sots_render_continuous): row k and the r samples behind its anchor
+// k hop + N/2; the rendering holds row 0 in front of the first anchor and row num_rows - 1 from the last one on.
+__host__ __device__ inline void cont_position(uint32_t n, uint32_t half_n, uint32_t hop, uint32_t num_rows, uint32_t &k, uint32_t &r)
+{
+    k = 0, r = 0;
+    if (n > half_n) {
+        const uint32_t m = n - half_n;
+        k = m / hop, r = m - k * hop;
+        if (k >= num_rows - 1u) k = num_rows - 1u, r = 0;
+    }
+}
+
+struct ContPass {
+    const float *values;    // genes of rows row_base ..., D floats each: every row a sample of the pass looks at
+    const float *wavetable; // kWavetableSize floats
+    uint32_t *words;        // RenderScratch::words
+    float *out;             // count floats (16-byte aligned)
+    ContLayout lay;
+    uint32_t row_base, num_rows, hop, half_n, glide;
+    uint32_t n0, count;
+    SynthParams sp;
+};
+// every stage of one pass; the carries (lay.carry) are the caller's to clear before the first pass
+hipError_t launch_continuous_pass(hipStream_t st, uint32_t kind, const ContPass &pass, uint32_t num_cus);
 
 } // namespace sots

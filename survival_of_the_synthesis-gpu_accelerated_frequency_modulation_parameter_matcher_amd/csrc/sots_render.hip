@@ -115,10 +115,25 @@ hipError_t render_reserve(RenderScratch &rs, size_t values_floats, size_t audio_
     return grow(rs.out, rs.out_floats, out_floats);
 }
 
+hipError_t render_reserve_words(RenderScratch &rs, size_t words)
+{
+    if (words <= rs.words_count) return hipSuccess;
+    if (rs.words) {
+        const hipError_t e = hipFree(rs.words);
+        rs.words = nullptr, rs.words_count = 0;
+        if (e != hipSuccess) return e;
+    }
+    const hipError_t e = hipMalloc((void **)&rs.words, words * sizeof(uint32_t));
+    if (e != hipSuccess) return rs.words = nullptr, e;
+    rs.words_count = words;
+    return hipSuccess;
+}
+
 void render_release(RenderScratch &rs)
 {
     for (float *b : {rs.values, rs.audio, rs.out})
         if (b) (void)hipFree(b);
+    if (rs.words) (void)hipFree(rs.words);
     rs = RenderScratch{};
 }
 

@@ -158,6 +158,31 @@ inline Fault objective_weights_fault(const float *weights, uint32_t num_bins, ui
     }
 }
 
+// ---- phase-continuous rendering ----
+// sots_render_continuous: what it refuses before anything touches the device.  n, d, synth_arith: the context's audio
+// length, genes per row and arithmetic mode.
+inline Fault render_continuous_check(const sots_render_continuous_args *args, uint32_t n, uint32_t d, uint32_t synth_arith, const void *values,
+                                     size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples)
+{
+    if (!args || args->struct_size != sizeof(sots_render_continuous_args))
+        return fault(SOTS_ERR_INVALID, "sots_render_continuous: null args or sots_render_continuous_args.struct_size != %zu",
+                     sizeof(sots_render_continuous_args));
+    if (args->hop < 1u || args->hop > n) return fault(SOTS_ERR_INVALID, "sots_render_continuous: hop %u outside 1..%u", args->hop, n);
+    if (args->flags & ~(uint32_t)SOTS_RENDER_GLIDE) return fault(SOTS_ERR_INVALID, "sots_render_continuous: unknown flags 0x%x", args->flags);
+    if (num_rows == 0) return fault(SOTS_ERR_INVALID, "sots_render_continuous: num_rows must be at least 1");
+    const uint64_t covered = (uint64_t)(num_rows - 1u) * args->hop + n;
+    if (covered >= (1ull << 31))
+        return fault(SOTS_ERR_INVALID, "sots_render_continuous: %u rows at hop %u are %llu samples, 2^31 or more", num_rows, args->hop,
+                     (unsigned long long)covered);
+    if (!values || values_bytes != (size_t)num_rows * d * sizeof(float))
+        return fault(SOTS_ERR_SIZE, "sots_render_continuous: %u rows need %zu bytes of values, got %zu", num_rows, (size_t)num_rows * d * sizeof(float),
+                     values_bytes);
+    if (!out && out_samples) return fault(SOTS_ERR_INVALID, "sots_render_continuous: null output");
+    if (synth_arith == SOTS_ARITH_DEVICE_KERNELS)
+        return fault(SOTS_ERR_STATE, "sots_render_continuous: not under SOTS_ARITH_DEVICE_KERNELS (that mode is the reference's kernels bit for bit)");
+    return Fault{};
+}
+
 // ---- run record, stop rules ----
 constexpr uint64_t kTrackMaxRecords = 1ull << 24; // chunks x history_capacity (1.5 GiB of records)
 // sots_track / sots_batch_track: known flags, a history with a period and room, and no more than kTrackMaxRecords records

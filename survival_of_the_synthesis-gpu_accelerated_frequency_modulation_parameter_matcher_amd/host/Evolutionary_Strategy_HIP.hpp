@@ -121,9 +121,14 @@ struct Evolutionary_Strategy_HIP_Arguments
     //                 + 1 of them, in all its paths (chunk by chunk, in flight, queued).
     //   renderMatch : sots_match writes the overlap-add rendering of every chunk's match (renderMatch() below) to
     //                 outputAudioPath instead of 2^14 samples of the last chunk's
+    //   renderMode  : which renderer renderMatch() uses: 0 = overlap-add (the default), 1 = phase-continuous
+    //                 (sots_render_continuous: one voice whose oscillators never restart, parameters held from chunk centre to
+    //                 chunk centre), 2 = phase-continuous with the parameters interpolated between the centres.  Takes effect
+    //                 only with renderMatch; 1 and 2 are not available with deviceKernelArithmetic.
     //   matchPath   : sots_match writes the parameter track there, one CSV row per chunk (Match_track.hpp)
     uint32_t hopSize = 0;
     bool renderMatch = false;
+    uint32_t renderMode = 0;
     std::string matchPath = "";
     bool returnBestEver = false;
     uint32_t historyEvery = 0;
@@ -287,6 +292,8 @@ public:
     // The whole match as audio: bestParametersPerChunk() through sots_render_overlap_add on this object's context - chunk i's
     // match stands for samples [i hop, i hop + N); where chunks overlap (hop < N) they are cross-faded with the analysis
     // window and normalised by its sum, at hop = N they follow each other as they are.  (numChunks - 1) hop + N samples.
+    // With renderMode 1 or 2 the same track goes through sots_render_continuous instead: the same length, one voice from the
+    // first sample to the last, chunk i's parameters reached at its centre i hop + N/2.
     void renderMatch(std::vector<float> &out)
     {
         const uint32_t d = population.numDimensions, chunks = (uint32_t)bestPerChunk_.size();
@@ -294,6 +301,14 @@ public:
         if (!chunks) return;
         std::vector<float> values((size_t)chunks * d);
         for (uint32_t c = 0; c < chunks; ++c) std::copy(bestPerChunk_[c].begin(), bestPerChunk_[c].begin() + d, values.begin() + (size_t)c * d);
+        if (args_.renderMode != 0u) {
+            sots_render_continuous_args ca{};
+            ca.struct_size = sizeof ca;
+            ca.hop = hop_;
+            ca.flags = args_.renderMode == 2u ? (uint32_t)SOTS_RENDER_GLIDE : 0u;
+            check(sots_render_continuous(ctx_, values.data(), values.size() * sizeof(float), chunks, &ca, out.data(), out.size()), "renderMatch");
+            return;
+        }
         sots_render_args ra{};
         ra.struct_size = sizeof ra;
         ra.hop = hop_;

@@ -197,4 +197,20 @@ inline bool readHopSizeKey(const Json &h, uint32_t audioLength, uint32_t &hopSiz
     return true;
 }
 
+// type.HIP.renderMode: which renderer renderMatch uses.  "overlapAdd" (0, the default: sots_render_overlap_add, every chunk's
+// match from phase 0, cross-faded), "continuous" (1: sots_render_continuous, one voice whose oscillators never restart, the
+// parameters held from chunk centre to chunk centre) or "continuousGlide" (2: the same with the parameters interpolated
+// between the centres).  Returns whether the key was there; throws - before any device work - on anything else.
+inline bool readRenderModeKey(const Json &h, uint32_t &renderMode)
+{
+    if (!h.has("renderMode")) return false;
+    const Json &v = h["renderMode"];
+    const char *names[] = {"overlapAdd", "continuous", "continuousGlide"};
+    if (v.kind == Json::String)
+        for (uint32_t m = 0; m < 3; ++m)
+            if (v.str == names[m]) return renderMode = m, true;
+    throw std::runtime_error("parameters.json: type.HIP.renderMode must be \"overlapAdd\", \"continuous\" or \"continuousGlide\"" +
+                             (v.kind == Json::String ? ", not \"" + v.str + "\"" : std::string()));
+}
+
 #endif

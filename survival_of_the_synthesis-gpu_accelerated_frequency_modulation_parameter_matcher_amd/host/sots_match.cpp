@@ -3,7 +3,7 @@
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
 // "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "numDevices", "numElites",
 // "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight", "chunkQueue",
-// "survivors", "objective", "objectiveFloor", "objectiveWeights", "hopSize", "renderMatch", "matchPath", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
+// "survivors", "objective", "objectiveFloor", "objectiveWeights", "hopSize", "renderMatch", "renderMode", "matchPath", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
 // N-sample chunk with Evolutionary_Strategy_HIP, writes inputGenerated.wav and the
 // outputAudioPath rendering of the best match, and prints the best parameters.
@@ -14,6 +14,11 @@
 //                 chunk's best parameters synthesised and overlap-added on the GPU (sots_render_overlap_add: cross-faded
 //                 with the analysis window where chunks overlap, end to end at hopSize = N) - instead of 2^14 samples of
 //                 the last chunk's.
+//   "renderMode"  which renderer "renderMatch" uses: "overlapAdd" (the default, as above), "continuous" - the parameter track
+//                 as ONE voice whose oscillators never restart (sots_render_continuous): no phase jumps between chunks and
+//                 no comb filter where they overlap; chunk i's parameters hold around its centre i hopSize + N/2 - or
+//                 "continuousGlide", the same with the parameters interpolated from centre to centre.  Same length.
+//                 Ignored without "renderMatch"; not available with "deviceKernelArithmetic".
 //   "matchPath"   a CSV of the parameter track, one row per chunk:
 //                 chunk,start_sample,generations,fitness,u0..u{D-1},p0..p{D-1} - u the unit-range genes (%.9g: the fp32
 //                 bits), p the scaled parameters; with returnBestEver the best-ever individual of each chunk.
@@ -115,6 +120,9 @@ int main(int argc, char *argv[])
             // analysis at a hop, the rendering of the whole match and the parameter track (Match_track.hpp; header comment)
             (void)readHopSizeKey(h, 1u << audioLengthLog2, args.hopSize);
             if (h.has("renderMatch")) args.renderMatch = h["renderMatch"].b;
+            (void)readRenderModeKey(h, args.renderMode);
+            if (args.renderMatch && args.renderMode != 0u && h.has("deviceKernelArithmetic") && h["deviceKernelArithmetic"].b)
+                throw std::runtime_error("parameters.json: type.HIP.renderMode \"continuous\" and \"continuousGlide\" are not available with deviceKernelArithmetic");
             if (h.has("matchPath")) args.matchPath = h["matchPath"].str;
             // run record (Evolutionary_Strategy_HIP_Arguments): the best individual any generation produced, a history CSV,
             // and stopping a chunk early on a fitness target or a stall
@@ -194,7 +202,7 @@ int main(int argc, char *argv[])
                                    es->objective.scaleParams(rows[c]));
             fclose(track);
         }
-        if (args.renderMatch) { // every chunk's match, overlap-added on the device
+        if (args.renderMatch) { // every chunk's match, overlap-added or as one continuous voice (renderMode), on the device
             std::vector<float> whole;
             hipEs->renderMatch(whole);
             if (whole.size() > 0xFFFFFFFFull / 3) throw std::runtime_error("renderMatch: the rendering does not fit a WAV file");
