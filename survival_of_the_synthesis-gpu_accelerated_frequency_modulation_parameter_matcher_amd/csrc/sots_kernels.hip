@@ -4641,51 +4641,39 @@ static uint32_t resident_grid(K kernel, int threads, uint32_t items, uint32_t nu
     return (uint32_t)(items < cap ? items : cap);
 }
 
-// N <= 1024 runs on the wavefront-per-row kernels with LDS exchanges (k_fft, k_fitness), longer rows on the
-// wavefront-per-row kernels with the sub-transforms across lanes (k_fft_x, k_fitness_x)
-#define SOTS_DISPATCH_WAVE(log2n, CALL)   \
-    switch (log2n) {                      \
-    case 9: { CALL(9); break; }           \
-    case 10: { CALL(10); break; }         \
-    default: return hipErrorInvalidValue; \
-    }
+// The occupancy query of resident_grid and the launch: a call site names its instantiation once, as a function pointer
+template <typename... KA, typename... A>
+static hipError_t launch_resident(void (*kernel)(KA...), int threads, uint32_t items, uint32_t num_cus, int *cache, hipStream_t st, A... args)
+{
+    kernel<<<resident_grid(kernel, threads, items, num_cus, cache), threads, 0, st>>>(args...);
+    return hipGetLastError();
+}
+constexpr uint32_t groups_of(uint32_t rows, uint32_t waves) { return (rows + waves - 1) / waves; } // workgroups of `waves` rows
+
+// Which N has which kernel, each list written once (the lists decide what is instantiated): N <= 1024 runs on the
+// wavefront-per-row kernels with LDS exchanges (k_fft, k_fitness), longer rows - and N = 256 (round 4): two complex points
+// per lane, where k_fft's radix-4 / radix-8 passes need four or eight - on the wavefront-per-row kernels with the
+// sub-transforms across lanes (k_fft_x, k_fitness_x; N = 1024 is instantiated for -DSOTS_X_MIN=10), N >= 16384 on the
+// workgroup-per-row kernels (k_fft_big, k_fitness_big)
+template <int... Ls> struct Log2nList {};
+using WaveSizes = Log2nList<9, 10>;
+using XSizes = Log2nList<8, 10, 11, 12, 13>;
+using BigSizes = Log2nList<14, 15>;
+// f(ic<L>{}) for the L of the list that equals log2n; `none` where the list has no such L.  (A left fold: f is instantiated
+// in list order, and the order in which the launchers below first name the kernels is their order in the code object)
+template <int... Ls, typename R, typename F>
+static R for_log2n(Log2nList<Ls...>, uint32_t log2n, R none, F f)
+{
+    (void)(... || (log2n == (uint32_t)Ls && ((void)(none = f(ic<Ls>{})), true)));
+    return none;
+}
+template <typename List> static bool has_log2n(List list, uint32_t log2n) { return for_log2n(list, log2n, false, [](auto) { return true; }); }
 
 #ifndef SOTS_X_MIN
 #define SOTS_X_MIN 11
 #endif
-// ... and N = 256 (round 4): two complex points per lane, the same kernel (k_fft's radix-4 / radix-8 passes need four or eight)
-static bool x_from(uint32_t log2n) { return log2n == 8 || (log2n >= SOTS_X_MIN && log2n <= 13); }
-#define SOTS_DISPATCH_X(log2n, CALL)      \
-    switch (log2n) {                      \
-    case 8: { CALL(8); break; }           \
-    case 10: { CALL(10); break; }         \
-    case 11: { CALL(11); break; }         \
-    case 12: { CALL(12); break; }         \
-    case 13: { CALL(13); break; }         \
-    default: return hipErrorInvalidValue; \
-    }
-static bool big_from(uint32_t log2n) { return log2n == 14 || log2n == 15; }
-// a workgroup per row: as many workgroups as rows, at most four per CU (they loop)
-template <int L, int MODE, bool WIN, bool SEG = false, int OBJ = kObjMagnitude, bool WGT = false, typename... FL>
-static hipError_t launch_fft_big(hipStream_t st, uint32_t p, uint32_t num_cus, const float *audio, float *spectrum, const float *target,
-                                 float *fitness, const float2 *tw, const float *window, float inv_n, float inv_wf, uint32_t pitch, FL... fl)
-{
-    const uint32_t cus = num_cus ? num_cus : 256u, grid = p < 4u * cus ? p : 4u * cus;
-    const size_t lds = ((size_t)(1u << L) / 2u) * sizeof(float2) + 64u;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fft_big<L, MODE, WIN, SEG, OBJ, WGT, FL...>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    k_fft_big<L, MODE, WIN, SEG, OBJ, WGT, FL...><<<grid, kBigThreads, lds, st>>>(audio, spectrum, target, fitness, tw, window, p, inv_n, inv_wf, pitch, fl...);
-    return hipGetLastError();
-}
-template <int L, int OBJ = kObjMagnitude, bool WGT = false, typename... FL>
-static hipError_t launch_fitness_big(hipStream_t st, uint32_t p, uint32_t num_cus, const float *spectrum, const float *target, float *fitness,
-                                     float inv_n, float inv_wf, FL... fl)
-{
-    const uint32_t cus = num_cus ? num_cus : 256u, grid = p < 4u * cus ? p : 4u * cus;
-    k_fitness_big<L, OBJ, WGT, FL...><<<grid, kBigThreads, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...);
-    return hipGetLastError();
-}
-#define SOTS_X_GRID(K, L, MODE) resident_grid(K, x_waves<L, MODE>() * kWave, (p + x_waves<L, MODE>() - 1) / x_waves<L, MODE>(), num_cus, &occ_x[L])
+static bool x_from(uint32_t log2n) { return has_log2n(XSizes{}, log2n) && (log2n == 8 || log2n >= SOTS_X_MIN); }
+static bool big_from(uint32_t log2n) { return has_log2n(BigSizes{}, log2n); }
 
 // N = 1024 from one row per resident wavefront (P >= 12 x CUs): one workgroup of twelve wavefronts per CU, rows dealt as
 // the wavefronts ask (k_fft); 15.7 -> 14.7 us at P = 8192 already, level at 4096
@@ -4700,69 +4688,107 @@ static bool fft_wide(uint32_t p, uint32_t log2n, uint32_t num_cus)
     return log2n == 10 && p >= SOTS_FFT_WIDE_ROWS * fft_wide_waves<10>() * (num_cus ? num_cus : 256u);
 #endif
 }
-#define SOTS_WIDE_GRID(K, slot) resident_grid(K, fft_wide_waves<10>() * kWave, (p + fft_wide_waves<10>() - 1) / fft_wide_waves<10>(), num_cus, &oc->wide[slot])
+
+// The kernel choice of every spectral launcher, plain or segmented, staged or fused.  x_small: a small population, a
+// wavefront per SIMD (k_fft_x with four wavefronts; the fused windowed form only, the others take it as x).  The threshold
+// (fewer 16-row workgroups than CUs) was measured at N = 4096 and 2048, where x_waves is 16; N = 8192 (x_waves 8) follows
+// it unmeasured
+enum class Spectral { none, wave, wide, x, x_small, big };
+static Spectral spectral_choice(uint32_t p, uint32_t log2n, uint32_t num_cus)
+{
+    if (big_from(log2n)) return Spectral::big;
+    if (x_from(log2n)) return groups_of(p, x_waves<12>()) < (num_cus ? num_cus : 256u) ? Spectral::x_small : Spectral::x;
+    if (fft_wide(p, log2n, num_cus)) return Spectral::wide;
+    return has_log2n(WaveSizes{}, log2n) ? Spectral::wave : Spectral::none;
+}
+
+// a workgroup per row: as many workgroups as rows, at most four per CU (they loop)
+static uint32_t big_grid(uint32_t p, uint32_t num_cus)
+{
+    const uint32_t cap = 4u * (num_cus ? num_cus : 256u);
+    return p < cap ? p : cap;
+}
+template <int L, int MODE, bool WIN, bool SEG = false, int OBJ = kObjMagnitude, bool WGT = false, typename... FL>
+static hipError_t launch_fft_big(hipStream_t st, uint32_t p, uint32_t num_cus, const float *audio, float *spectrum, const float *target,
+                                 float *fitness, const float2 *tw, const float *window, float inv_n, float inv_wf, uint32_t pitch, FL... fl)
+{
+    const auto kernel = k_fft_big<L, MODE, WIN, SEG, OBJ, WGT, FL...>;
+    const size_t lds = ((size_t)(1u << L) / 2u) * sizeof(float2) + 64u;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    kernel<<<big_grid(p, num_cus), kBigThreads, lds, st>>>(audio, spectrum, target, fitness, tw, window, p, inv_n, inv_wf, pitch, fl...);
+    return hipGetLastError();
+}
 
 hipError_t launch_fft(hipStream_t st, const float *audio, float *spectrum, const float2 *twiddle,
                       uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus, OccCache *oc)
 {
-    int *occ = oc->fft;
-    if (big_from(log2n)) {
-        if (log2n == 14) return launch_fft_big<14, 0, false>(st, p, num_cus, audio, spectrum, nullptr, nullptr, twiddle, nullptr, 0.f, 0.f, pitch);
-        return launch_fft_big<15, 0, false>(st, p, num_cus, audio, spectrum, nullptr, nullptr, twiddle, nullptr, 0.f, 0.f, pitch);
+    constexpr int W = fft_wide_waves<10>();
+    switch (spectral_choice(p, log2n, num_cus)) {
+    case Spectral::big:
+        return for_log2n(BigSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+            return launch_fft_big<decltype(l)::value, 0, false>(st, p, num_cus, audio, spectrum, nullptr, nullptr, twiddle, nullptr, 0.f, 0.f, pitch);
+        });
+    case Spectral::wide:
+        return launch_resident(k_fft<10, 0, false, W>, W * kWave, groups_of(p, W), num_cus, &oc->wide[0], st, audio, spectrum, nullptr, nullptr, twiddle, nullptr, p, 0.f, 0.f, pitch);
+    case Spectral::x_small: // (no four-wavefront form)
+    case Spectral::x:
+        return for_log2n(XSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+            constexpr int L = decltype(l)::value, WG = x_waves<L, 0>();
+            return launch_resident(k_fft_x<L, 0, false>, WG * kWave, groups_of(p, WG), num_cus, &oc->x_fft[L], st, audio, spectrum, nullptr, nullptr, twiddle, nullptr, p, 0.f, 0.f, pitch, nullptr);
+        });
+    case Spectral::wave:
+        return for_log2n(WaveSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+            constexpr int L = decltype(l)::value;
+            return launch_resident(k_fft<L, 0, false>, kWave, p, num_cus, &oc->fft[L], st, audio, spectrum, nullptr, nullptr, twiddle, nullptr, p, 0.f, 0.f, pitch);
+        });
+    default: return hipErrorInvalidValue;
     }
-    if (fft_wide(p, log2n, num_cus) && !x_from(log2n)) {
-        constexpr int W = fft_wide_waves<10>();
-        k_fft<10, 0, false, W><<<SOTS_WIDE_GRID((k_fft<10, 0, false, W>), 0), W * kWave, 0, st>>>(audio, spectrum, nullptr, nullptr, twiddle, nullptr, p, 0.f, 0.f, pitch);
-        return hipGetLastError();
-    }
-    if (x_from(log2n)) {
-        int *occ_x = oc->x_fft;
-#define CALL(L) k_fft_x<L, 0, false><<<SOTS_X_GRID((k_fft_x<L, 0, false>), L, 0), x_waves<L, 0>() * kWave, 0, st>>>(audio, spectrum, nullptr, nullptr, twiddle, nullptr, p, 0.f, 0.f, pitch, nullptr)
-        SOTS_DISPATCH_X(log2n, CALL)
-#undef CALL
-        return hipGetLastError();
-    }
-#define CALL(L) k_fft<L, 0, false><<<resident_grid(k_fft<L, 0, false>, kWave, p, num_cus, &occ[L]), kWave, 0, st>>>(audio, spectrum, nullptr, nullptr, twiddle, nullptr, p, 0.f, 0.f, pitch)
-    SOTS_DISPATCH_WAVE(log2n, CALL)
-#undef CALL
-    return hipGetLastError();
 }
 
-// OBJ, WGT, FL: the objective and the weights; FL holds the log objective's floor and then the weighted kernels' table
-// (the kernels' last arguments); the unweighted magnitude instantiations are launched exactly as before
-template <int OBJ, bool WGT, typename... FL>
-static hipError_t launch_fitness_o(hipStream_t st, const float *spectrum, const float *target, float *fitness,
-                                   uint32_t p, uint32_t log2n, float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, FL... fl)
+// The objective and the weights of a launch as template arguments: f(ic<OBJ>{}, bool_constant<WGT>{}, fl...), where fl holds
+// the log objective's floor and then the weighted kernels' table u (the kernels' last arguments); the unweighted magnitude
+// instantiations are launched exactly as before there was a choice
+template <typename F>
+static hipError_t with_objective(const Objective &obj, const float *u, F f)
 {
-    int *occ = oc->fitness;
-    if (big_from(log2n)) {
-        if (log2n == 14) return launch_fitness_big<14, OBJ, WGT, FL...>(st, p, num_cus, spectrum, target, fitness, inv_n, inv_wf, fl...);
-        return launch_fitness_big<15, OBJ, WGT, FL...>(st, p, num_cus, spectrum, target, fitness, inv_n, inv_wf, fl...);
+    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE) {
+        if (u) return f(ic<kObjLogMagnitude>{}, std::true_type{}, obj.floor, u);
+        return f(ic<kObjLogMagnitude>{}, std::false_type{}, obj.floor);
     }
-    if (x_from(log2n)) {
-        int *occ_x = oc->x_fitness;
-#define CALL(L) k_fitness_x<L, OBJ, WGT, FL...><<<SOTS_X_GRID((k_fitness_x<L, OBJ, WGT, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...)
-        SOTS_DISPATCH_X(log2n, CALL)
-#undef CALL
-        return hipGetLastError();
-    }
-#define CALL(L) k_fitness<L, OBJ, WGT, FL...><<<resident_grid(k_fitness<L, OBJ, WGT, FL...>, kWave, p, num_cus, &occ[L]), kWave, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...)
-    SOTS_DISPATCH_WAVE(log2n, CALL)
-#undef CALL
-    return hipGetLastError();
+    if (obj.kind != SOTS_OBJECTIVE_MAGNITUDE) return hipErrorInvalidValue;
+    if (u) return f(ic<kObjMagnitude>{}, std::true_type{}, u);
+    return f(ic<kObjMagnitude>{}, std::false_type{});
 }
 
 hipError_t launch_fitness(hipStream_t st, const float *spectrum, const float *target, float *fitness,
                           uint32_t p, uint32_t log2n, float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, const Objective &obj)
 {
-    const float *const u = obj.weights; // (the staged kernels index the plain table by bin)
-    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE) {
-        if (u) return launch_fitness_o<kObjLogMagnitude, true>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc, obj.floor, u);
-        return launch_fitness_o<kObjLogMagnitude, false>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc, obj.floor);
-    }
-    if (obj.kind != SOTS_OBJECTIVE_MAGNITUDE) return hipErrorInvalidValue;
-    if (u) return launch_fitness_o<kObjMagnitude, true>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc, u);
-    return launch_fitness_o<kObjMagnitude, false>(st, spectrum, target, fitness, p, log2n, inv_n, inv_wf, num_cus, oc);
+    // (the staged kernels index the plain weight table by bin)
+    return with_objective(obj, obj.weights, [&](auto o, auto w, auto... fl) {
+        constexpr int OBJ = decltype(o)::value;
+        constexpr bool WGT = decltype(w)::value;
+        switch (spectral_choice(p, log2n, num_cus)) {
+        case Spectral::big:
+            return for_log2n(BigSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+                k_fitness_big<decltype(l)::value, OBJ, WGT, decltype(fl)...><<<big_grid(p, num_cus), kBigThreads, 0, st>>>(spectrum, target, fitness, p, inv_n, inv_wf, fl...);
+                return hipGetLastError();
+            });
+        case Spectral::x_small: // (no four-wavefront form)
+        case Spectral::x:
+            return for_log2n(XSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+                constexpr int L = decltype(l)::value, WG = x_waves<L>();
+                return launch_resident(k_fitness_x<L, OBJ, WGT, decltype(fl)...>, WG * kWave, groups_of(p, WG), num_cus, &oc->x_fitness[L], st, spectrum, target, fitness, p, inv_n, inv_wf, fl...);
+            });
+        case Spectral::wide: // (a wavefront per workgroup at every population)
+        case Spectral::wave:
+            return for_log2n(WaveSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+                constexpr int L = decltype(l)::value;
+                return launch_resident(k_fitness<L, OBJ, WGT, decltype(fl)...>, kWave, p, num_cus, &oc->fitness[L], st, spectrum, target, fitness, p, inv_n, inv_wf, fl...);
+            });
+        default: return hipErrorInvalidValue;
+        }
+    });
 }
 
 hipError_t launch_objective_map(hipStream_t st, float *dst, const float *src, size_t n, float floor)
@@ -4775,107 +4801,113 @@ hipError_t launch_objective_map(hipStream_t st, float *dst, const float *src, si
 // the table image the fused long-row kernel copies in (bytes: x_table_bytes; rebuilt whenever the target changes)
 size_t x_table_bytes(uint32_t log2n)
 {
-    switch (log2n) {
-    case 10: return x_table_floats<10>() * sizeof(float);
-    case 11: return x_table_floats<11>() * sizeof(float);
-    case 12: return x_table_floats<12>() * sizeof(float);
-    case 13: return x_table_floats<13>() * sizeof(float);
-    default: return 0;
-    }
+    return for_log2n(XSizes{}, log2n, (size_t)0, [](auto l) {
+        constexpr int L = decltype(l)::value;
+        return x_applies<L>() ? x_table_floats<L>() * sizeof(float) : (size_t)0; // (N = 256 makes its tables in the workgroup)
+    });
 }
 hipError_t launch_x_tables(hipStream_t st, float *image, const float2 *twiddle, const float *window, const float *target, uint32_t log2n)
 {
     if (!x_from(log2n)) return hipSuccess;
     hipError_t e = hipMemsetAsync(image, 0, x_table_bytes(log2n), st); // (the padding between the lanes' rows)
     if (e != hipSuccess) return e;
-#define CALL(L) k_x_tables<L><<<8, 256, 0, st>>>(image, twiddle, window, target)
-    SOTS_DISPATCH_X(log2n, CALL)
-#undef CALL
-    return hipGetLastError();
+    return for_log2n(XSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+        k_x_tables<decltype(l)::value><<<8, 256, 0, st>>>(image, twiddle, window, target);
+        return hipGetLastError();
+    });
 }
 
-template <int OBJ, bool WGT, typename... FL>
-static hipError_t launch_fft_fitness_o(hipStream_t st, const float *audio, const float *window, const float *target,
-                                       float *fitness, const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch,
-                                       float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, const SelLists *lists, FL... fl)
+// The fused launch, plain (SEG = false: `target` is the one target, or the table image of k_fft_x) or segmented (every row
+// against its chunk's target in the image `target`): one routine, so the same kernel choice for the same row count, and the
+// same OccCache slots.  The forms without a window exist for the plain unweighted magnitude objective only (RAW; the library
+// itself always passes its window; the log N = 4096 form without one would not fit its 128 registers): elsewhere a missing
+// window is an error, not another kernel.  `lists`: the bucketing instantiation (plain only), or nothing - a caller that
+// counts on the lists must not get a launch without them
+template <bool SEG, int OBJ, bool WGT, typename... FL>
+static hipError_t launch_fused(hipStream_t st, const float *audio, const float *window, const float *target, float *fitness,
+                               const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
+                               uint32_t num_cus, OccCache *oc, const SelLists *lists, FL... fl)
 {
-    // The forms without a window exist for the magnitude objective only (the library itself always passes its window; the
-    // log N = 4096 form without one would not fit its 128 registers): elsewhere a missing window is an error, not another kernel
-    constexpr bool RAW = OBJ == kObjMagnitude && !WGT; // (nor for a weighted launch)
+    constexpr bool RAW = !SEG && OBJ == kObjMagnitude && !WGT;
+    constexpr int W = fft_wide_waves<10>();
     if (!RAW && !window) return hipErrorInvalidValue;
-    int *occ_w = oc->fused_win;
-    [[maybe_unused]] int *occ_n = oc->fused_raw;
-    if (lists) { // the bucketing instantiation, or nothing: a caller that counts on the lists must not get a launch without them
-        if (!window || !select_lists_apply(p, log2n, num_cus) || lists->buckets != select_splitter_count(num_cus) || !lists->slot || !lists->cnt || !lists->lists)
-            return hipErrorInvalidValue;
-        constexpr int W = fft_wide_waves<10>();
-        k_fft<10, 1, true, W, false, true, OBJ, WGT, SelLists, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, false, true, OBJ, WGT, SelLists, FL...>), 3), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, *lists, fl...);
-        return hipGetLastError();
-    }
-    if (big_from(log2n)) {
-        if (log2n == 14) {
-            if (window) return launch_fft_big<14, 1, true, false, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
-            if constexpr (RAW) return launch_fft_big<14, 1, false, false, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, nullptr, inv_n, inv_wf, pitch, fl...);
+    if (lists) {
+        if constexpr (SEG) return hipErrorInvalidValue;
+        else {
+            if (!window || !select_lists_apply(p, log2n, num_cus) || lists->buckets != select_splitter_count(num_cus) || !lists->slot || !lists->cnt || !lists->lists)
+                return hipErrorInvalidValue;
+            return launch_resident(k_fft<10, 1, true, W, false, true, OBJ, WGT, SelLists, FL...>, W * kWave, groups_of(p, W), num_cus, &oc->wide[3], st,
+                                   audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, *lists, fl...);
         }
-        if (window) return launch_fft_big<15, 1, true, false, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
-        if constexpr (RAW) return launch_fft_big<15, 1, false, false, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, nullptr, inv_n, inv_wf, pitch, fl...);
     }
-    if (x_from(log2n)) {
-        if (window) {
-            int *occ_x = oc->x_fused_win;
-            // a small population: a wavefront per SIMD.  The threshold (fewer 16-row workgroups than CUs) was measured at
-            // N = 4096 and 2048, where x_waves is 16; N = 8192 (x_waves 8) follows it unmeasured
-            if ((p + x_waves<12>() - 1) / x_waves<12>() < (num_cus ? num_cus : 256u)) {
-                int *occ_s = oc->x_small;
-#define CALL(L) k_fft_x<L, 1, true, 4, false, OBJ, WGT, FL...><<<resident_grid((k_fft_x<L, 1, true, 4, false, OBJ, WGT, FL...>), 4 * kWave, (p + 3) / 4, num_cus, &occ_s[L]), 4 * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
-                SOTS_DISPATCH_X(log2n, CALL)
-#undef CALL
-                return hipGetLastError();
+    // f(bool_constant<WIN>{}): with the window, or without one where that form exists
+    const auto with_window = [&](auto f) {
+        if (window) return f(std::true_type{});
+        if constexpr (RAW) return f(std::false_type{});
+        return hipErrorInvalidValue;
+    };
+    const Spectral choice = spectral_choice(p, log2n, num_cus);
+    switch (choice) {
+    case Spectral::big: // (size outside, window inside: the order of these kernels in the code object)
+        return for_log2n(BigSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+            return with_window([&](auto win) {
+                return launch_fft_big<decltype(l)::value, 1, decltype(win)::value, SEG, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, target, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
+            });
+        });
+    case Spectral::x_small:
+    case Spectral::x:
+        return with_window([&](auto win) {
+            constexpr bool WIN = decltype(win)::value;
+            if constexpr (WIN) { // (no four-wavefront form without a window)
+                if (choice == Spectral::x_small)
+                    return for_log2n(XSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+                        constexpr int L = decltype(l)::value;
+                        return launch_resident(k_fft_x<L, 1, true, 4, SEG, OBJ, WGT, FL...>, 4 * kWave, groups_of(p, 4), num_cus, &oc->x_small[L], st,
+                                               audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...);
+                    });
             }
-#define CALL(L) k_fft_x<L, 1, true, x_waves<L>(), false, OBJ, WGT, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, true, x_waves<L>(), false, OBJ, WGT, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
-            SOTS_DISPATCH_X(log2n, CALL)
-#undef CALL
-        } else if constexpr (RAW) {
-            int *occ_x = oc->x_fused_raw;
-#define CALL(L) k_fft_x<L, 1, false, x_waves<L>(), false, OBJ, WGT, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, false, x_waves<L>(), false, OBJ, WGT, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, nullptr, fl...)
-            SOTS_DISPATCH_X(log2n, CALL)
-#undef CALL
-        }
-        return hipGetLastError();
+            return for_log2n(XSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+                constexpr int L = decltype(l)::value, WG = x_waves<L>();
+                return launch_resident(k_fft_x<L, 1, WIN, WG, SEG, OBJ, WGT, FL...>, WG * kWave, groups_of(p, WG), num_cus, WIN ? &oc->x_fused_win[L] : &oc->x_fused_raw[L], st,
+                                       audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, WIN ? oc->x_image : nullptr, fl...);
+            });
+        });
+    case Spectral::wide:
+        return with_window([&](auto win) {
+            constexpr bool WIN = decltype(win)::value;
+            return launch_resident(k_fft<10, 1, WIN, W, SEG, false, OBJ, WGT, FL...>, W * kWave, groups_of(p, W), num_cus, &oc->wide[WIN ? 1 : 2], st,
+                                   audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...);
+        });
+    case Spectral::wave:
+        return with_window([&](auto win) {
+            constexpr bool WIN = decltype(win)::value;
+            return for_log2n(WaveSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+                constexpr int L = decltype(l)::value;
+                return launch_resident(k_fft<L, 1, WIN, 1, SEG, false, OBJ, WGT, FL...>, kWave, p, num_cus, WIN ? &oc->fused_win[L] : &oc->fused_raw[L], st,
+                                       audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...);
+            });
+        });
+    default: return hipErrorInvalidValue;
     }
-    if (fft_wide(p, log2n, num_cus)) {
-        constexpr int W = fft_wide_waves<10>();
-        if (window) k_fft<10, 1, true, W, false, false, OBJ, WGT, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, false, false, OBJ, WGT, FL...>), 1), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...);
-        else if constexpr (RAW) k_fft<10, 1, false, W, false, false, OBJ, WGT, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, false, W, false, false, OBJ, WGT, FL...>), 2), W * kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, fl...);
-        return hipGetLastError();
-    }
-    if (window) {
-#define CALL(L) k_fft<L, 1, true, 1, false, false, OBJ, WGT, FL...><<<resident_grid((k_fft<L, 1, true, 1, false, false, OBJ, WGT, FL...>), kWave, p, num_cus, &occ_w[L]), kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...)
-        SOTS_DISPATCH_WAVE(log2n, CALL)
-#undef CALL
-        return hipGetLastError();
-    }
-    if constexpr (RAW) {
-#define CALL(L) k_fft<L, 1, false, 1, false, false, OBJ, WGT, FL...><<<resident_grid((k_fft<L, 1, false, 1, false, false, OBJ, WGT, FL...>), kWave, p, num_cus, &occ_n[L]), kWave, 0, st>>>(audio, nullptr, target, fitness, twiddle, nullptr, p, inv_n, inv_wf, pitch, fl...)
-        SOTS_DISPATCH_WAVE(log2n, CALL)
-#undef CALL
-    }
-    return hipGetLastError();
+}
+
+// obj.weights_image holds u in the layout of the kernel's target table (one table for all chunks of a segmented launch)
+template <bool SEG>
+static hipError_t launch_fused_objective(hipStream_t st, const float *audio, const float *window, const float *target, float *fitness,
+                                         const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
+                                         uint32_t num_cus, OccCache *oc, const SelLists *lists, const Objective &obj)
+{
+    if (obj.weights && !obj.weights_image) return hipErrorInvalidValue;
+    return with_objective(obj, obj.weights ? weight_table(obj.weights_image) : nullptr, [&](auto o, auto w, auto... fl) {
+        return launch_fused<SEG, decltype(o)::value, decltype(w)::value>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists, fl...);
+    });
 }
 
 hipError_t launch_fft_fitness(hipStream_t st, const float *audio, const float *window, const float *target,
                               float *fitness, const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch,
                               float inv_n, float inv_wf, uint32_t num_cus, OccCache *oc, const SelLists *lists, const Objective &obj)
 {
-    if (obj.weights && !obj.weights_image) return hipErrorInvalidValue;
-    const float *const u = obj.weights ? weight_table(obj.weights_image) : nullptr; // (in the layout of the kernel's target table)
-    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE) {
-        if (u) return launch_fft_fitness_o<kObjLogMagnitude, true>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists, obj.floor, u);
-        return launch_fft_fitness_o<kObjLogMagnitude, false>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists, obj.floor);
-    }
-    if (obj.kind != SOTS_OBJECTIVE_MAGNITUDE) return hipErrorInvalidValue;
-    if (u) return launch_fft_fitness_o<kObjMagnitude, true>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists, u);
-    return launch_fft_fitness_o<kObjMagnitude, false>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists);
+    return launch_fused_objective<false>(st, audio, window, target, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, lists, obj);
 }
 
 constexpr uint32_t kSortMaxTiles = 256;
@@ -5178,15 +5210,9 @@ hipError_t launch_recombine_mutate_seg(hipStream_t st, const float *vin, const f
 
 size_t seg_target_stride(uint32_t log2n)
 {
-    if (x_from(log2n)) {
-        switch (log2n) {
-        case 8: return x_seg_stride<8>();
-        case 11: return x_seg_stride<11>();
-        case 12: return x_seg_stride<12>();
-        default: return x_seg_stride<13>();
-        }
-    }
-    return (1u << log2n) / 2u;
+    const size_t bins = (1u << log2n) / 2u;
+    if (!x_from(log2n)) return bins;
+    return for_log2n(XSizes{}, log2n, bins, [](auto l) { return (size_t)x_seg_stride<decltype(l)::value>(); });
 }
 
 size_t seg_target_bytes(uint32_t log2n, uint32_t chunks)
@@ -5200,10 +5226,10 @@ hipError_t launch_seg_targets(hipStream_t st, float *image, const float *targets
     if (!x_from(log2n))
         return hipMemcpyAsync(tables, targets, (size_t)chunks * ((1u << log2n) / 2u) * sizeof(float), hipMemcpyDeviceToDevice, st);
     const uint64_t work = (uint64_t)chunks * (1u << log2n) / 2u;
-#define CALL(L) k_x_seg_targets<L><<<grid_for(work, 256), 256, 0, st>>>(tables, targets, chunks)
-    SOTS_DISPATCH_X(log2n, CALL)
-#undef CALL
-    return hipGetLastError();
+    return for_log2n(XSizes{}, log2n, hipErrorInvalidValue, [&](auto l) {
+        k_x_seg_targets<decltype(l)::value><<<grid_for(work, 256), 256, 0, st>>>(tables, targets, chunks);
+        return hipGetLastError();
+    });
 }
 
 // The weight table of the fused kernels: u[N/2] laid out as ONE chunk's target table (plain bins for k_fft and k_fft_big,
@@ -5216,57 +5242,12 @@ hipError_t launch_weight_image(hipStream_t st, float *image, const float *u, uin
     return launch_seg_targets(st, image, u, log2n, 1);
 }
 
-// launch_fft_fitness with a window, every row against its chunk's target: the same kernel choice for the same row
-// count, each kernel's SEG instantiation
-template <int OBJ, bool WGT, typename... FL>
-static hipError_t launch_fft_fitness_seg_o(hipStream_t st, const float *audio, const float *window, const float *seg_image, float *fitness,
-                                           const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
-                                           uint32_t num_cus, OccCache *oc, FL... fl)
-{
-    if (big_from(log2n)) {
-        if (log2n == 14) return launch_fft_big<14, 1, true, true, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
-        return launch_fft_big<15, 1, true, true, OBJ, WGT, FL...>(st, p, num_cus, audio, nullptr, seg_image, fitness, twiddle, window, inv_n, inv_wf, pitch, fl...);
-    }
-    if (x_from(log2n)) {
-        int *occ_x = oc->x_fused_win;
-        if ((p + x_waves<12>() - 1) / x_waves<12>() < (num_cus ? num_cus : 256u)) {
-            int *occ_s = oc->x_small;
-#define CALL(L) k_fft_x<L, 1, true, 4, true, OBJ, WGT, FL...><<<resident_grid((k_fft_x<L, 1, true, 4, true, OBJ, WGT, FL...>), 4 * kWave, (p + 3) / 4, num_cus, &occ_s[L]), 4 * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
-            SOTS_DISPATCH_X(log2n, CALL)
-#undef CALL
-            return hipGetLastError();
-        }
-#define CALL(L) k_fft_x<L, 1, true, x_waves<L>(), true, OBJ, WGT, FL...><<<SOTS_X_GRID((k_fft_x<L, 1, true, x_waves<L>(), true, OBJ, WGT, FL...>), L, 1), x_waves<L>() * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, oc->x_image, fl...)
-        SOTS_DISPATCH_X(log2n, CALL)
-#undef CALL
-        return hipGetLastError();
-    }
-    if (fft_wide(p, log2n, num_cus)) {
-        constexpr int W = fft_wide_waves<10>();
-        k_fft<10, 1, true, W, true, false, OBJ, WGT, FL...><<<SOTS_WIDE_GRID((k_fft<10, 1, true, W, true, false, OBJ, WGT, FL...>), 1), W * kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...);
-        return hipGetLastError();
-    }
-    int *occ_w = oc->fused_win;
-#define CALL(L) k_fft<L, 1, true, 1, true, false, OBJ, WGT, FL...><<<resident_grid((k_fft<L, 1, true, 1, true, false, OBJ, WGT, FL...>), kWave, p, num_cus, &occ_w[L]), kWave, 0, st>>>(audio, nullptr, seg_image, fitness, twiddle, window, p, inv_n, inv_wf, pitch, fl...)
-    SOTS_DISPATCH_WAVE(log2n, CALL)
-#undef CALL
-    return hipGetLastError();
-}
-
+// launch_fft_fitness with a window, every row against its chunk's target: each kernel's SEG instantiation
 hipError_t launch_fft_fitness_seg(hipStream_t st, const float *audio, const float *window, const float *seg_image, float *fitness,
                                   const float2 *twiddle, uint32_t p, uint32_t log2n, uint32_t pitch, float inv_n, float inv_wf,
                                   uint32_t num_cus, OccCache *oc, const Objective &obj)
 {
-    if (obj.weights && !obj.weights_image) return hipErrorInvalidValue;
-    if (obj.weights && !window) return hipErrorInvalidValue;
-    const float *const u = obj.weights ? weight_table(obj.weights_image) : nullptr; // (one table for all chunks)
-    if (obj.kind == SOTS_OBJECTIVE_LOG_MAGNITUDE) {
-        if (u) return launch_fft_fitness_seg_o<kObjLogMagnitude, true>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, obj.floor, u);
-        return launch_fft_fitness_seg_o<kObjLogMagnitude, false>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, obj.floor);
-    }
-    if (obj.kind != SOTS_OBJECTIVE_MAGNITUDE) return hipErrorInvalidValue;
-    if (u) return launch_fft_fitness_seg_o<kObjMagnitude, true>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, u);
-    return launch_fft_fitness_seg_o<kObjMagnitude, false>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc);
+    return launch_fused_objective<true>(st, audio, window, seg_image, fitness, twiddle, p, log2n, pitch, inv_n, inv_wf, num_cus, oc, nullptr, obj);
 }
 
 hipError_t launch_sort_seg(hipStream_t st, const float *vin, const float *sin, const float *fin, float *vout, float *sout,
