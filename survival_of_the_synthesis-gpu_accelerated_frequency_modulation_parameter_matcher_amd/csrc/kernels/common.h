@@ -1,0 +1,67 @@
+// common.h -- what every kernel family uses: the wavefront size, packed-float and compile-time-index types and the
+// cross-lane primitives (wavefront sum, value of lane ^ J).
+#pragma once
+#include "../sots_kernels.h"
+#include <type_traits>
+
+// contraction: off (the translation unit's default; nothing here multiplies and adds)
+#pragma clang fp contract(off)
+namespace sots { namespace {
+
+constexpr int kWave = 64;
+typedef float v2f_t __attribute__((ext_vector_type(2)));
+
+template <int V> using ic = std::integral_constant<int, V>;
+// f(ic<I>{}) for I = FIRST .. LAST-1 with I a compile-time constant inside f (register arrays are indexed with it)
+template <int FIRST, int LAST, typename F>
+__device__ __forceinline__ void static_for(F &&f)
+{
+    if constexpr (FIRST < LAST) {
+        f(ic<FIRST>{});
+        static_for<FIRST + 1, LAST>(f);
+    }
+}
+
+// Wavefront sum without LDS traffic: DPP swaps inside each row of 16 lanes (every lane of a
+// row ends with the row total), then the four row totals are added in row order.
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v)
+{
+    const int m = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false);
+    return v + __int_as_float(m);
+}
+__device__ __forceinline__ float wave_sum(float v)
+{
+    v = dpp_add<0xB1>(v);  // quad_perm [1,0,3,2]
+    v = dpp_add<0x4E>(v);  // quad_perm [2,3,0,1]
+    v = dpp_add<0x141>(v); // row_half_mirror
+    v = dpp_add<0x140>(v); // row_mirror
+    const int iv = __float_as_int(v);
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(iv, 0));
+    const float r1 = __int_as_float(__builtin_amdgcn_readlane(iv, 16));
+    const float r2 = __int_as_float(__builtin_amdgcn_readlane(iv, 32));
+    const float r3 = __int_as_float(__builtin_amdgcn_readlane(iv, 48));
+    return ((r0 + r1) + r2) + r3;
+}
+
+// value of lane (lane ^ J) for J = 1, 2 (DPP quad permutes), 4, 8, 16 (ds_swizzle through the LDS crossbar,
+// no LDS memory), 32 (v_permlane32_swap)
+template <uint32_t J>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t v)
+{
+    if constexpr (J == 1) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, true); // quad_perm [1,0,3,2]
+    else if constexpr (J == 2) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xf, 0xf, true); // quad_perm [2,3,0,1]
+    else if constexpr (J == 32) {
+        const auto sw = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+        return (threadIdx.x & 32u) ? sw[0] : sw[1]; // lanes 32-63 get lane-32's value in [0], lanes 0-31 lane+32's in [1]
+    } else return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (int)((J << 10) | 0x1Fu)); // bit mode: xor J, and 0x1f
+}
+template <uint32_t J> __device__ __forceinline__ float lane_xor_f(float v)
+{
+    if constexpr (J == 8) return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xf, 0xf, true)); // row_ror:8
+    else return __uint_as_float(lane_xor<J>(__float_as_uint(v)));
+}
+
+}} // namespace sots::(anonymous)
+
+#pragma clang fp contract(off)

@@ -12,9 +12,16 @@
 //                                exchange, xor-shuffle reduction of the squared error
 //   * sortPopulation           : bitonic network on (fitness, index) 64-bit keys, LDS tiles
 //
+// Still the one translation unit of the kernels.  The families are moving into csrc/kernels/*.h, each included where
+// its code stood: so far common.h (kWave, v2f_t, ic, static_for, wave_sum, lane_xor), fft.h (complex
+// helpers, Dft<>, Stockham passes, fft_forward, the real-input split) and objective.h (bin_error, bin_error2, trailing
+// kernel arguments, k_objective_map, segmented targets).  Such a file states its contraction mode in its first lines
+// and ends with contract(off), this unit's default.
+//
 // Reference citations are file:line in the reference tree.
 #include "sots_kernels.h"
 #include "sots_stop_rule.h"
+#include "kernels/common.h"
 #include <type_traits>
 
 #include <cstdlib>
@@ -29,8 +36,6 @@ uint32_t next_pow2(uint32_t v)
 }
 
 namespace {
-
-constexpr int kWave = 64;
 
 // ------------------------------------------------------------------------------------
 // Philox4x32-10 (Salmon et al. 2011).  Replaces MWC64X (ocl_program.cl:5-16): the state
@@ -297,7 +302,6 @@ constexpr int kSynthUnroll = SOTS_SYNTH_UNROLL; // samples per pipeline block
 // the block handed over (together about 400 cycles), so longer blocks halve the number of trips
 constexpr int kSynthUnrollCut = SOTS_SYNTH_UNROLL_CUT;
 constexpr float kWf = (float)kWavetableSize;
-typedef float v2f_t __attribute__((ext_vector_type(2)));
 
 // table[clamp((int)pos, 0, W-1)]; CLAMP = false only where the phase is known to be in [0, W)
 template <bool CLAMP = true>
@@ -422,7 +426,6 @@ template <> struct VoiceShape<SOTS_SYNTH_3OP_SERIES> { static constexpr int J = 
 template <> struct VoiceShape<SOTS_SYNTH_4OP_SERIES> { static constexpr int J = 1, OPS = 4, D = 8; };
 template <> struct VoiceShape<SOTS_SYNTH_TRIPLE_PAR> { static constexpr int J = 3, OPS = 2, D = 12; };
 
-template <int V> using ic = std::integral_constant<int, V>;
 
 // SPLIT > 0 (series voices, at most two wavefronts' worth of individuals per CU): the chain is cut in
 // front of operator SPLIT and runs in TWO wavefronts per 64 individuals, so that all four SIMDs of
@@ -775,11 +778,7 @@ __global__ __launch_bounds__((HELP ? (SPLIT ? 8 : 16) : SPLIT3 ? 8 : SPLIT2 ? 6 
                 const uint32_t c0 = (ip >> 2) & (CH - 1);
 #pragma unroll
                 for (int q = 0; q < U / 4; ++q) wr[(c0 + q) ^ l7] = make_float4(y[4 * q], y[4 * q + 1], y[4 * q + 2], y[4 * q + 3]);
-#ifdef SOTS_ABL_NOFLUSH
-                if (false) {
-#else
                 if (c0 == CH - U / 4) { // 4 CH samples parked: flush the tile
-#endif
                     __builtin_amdgcn_wave_barrier();
                     asm volatile("" ::: "memory");
                     const uint32_t i0 = ip + U - 4 * CH;
@@ -843,10 +842,8 @@ __global__ __launch_bounds__((HELP ? (SPLIT ? 8 : 16) : SPLIT3 ? 8 : SPLIT2 ? 6 
                     each_op(op, ic<0>{});
                     each_op(send_handover, ic<1>{});
                     asm volatile("" ::: "memory");
-#ifndef SOTS_ABL_NOBARRIER
                     if constexpr (MY != STAGES - 1) __builtin_amdgcn_s_waitcnt(0xC07F); // lgkmcnt(0): the hand-over is in LDS
                     __builtin_amdgcn_s_barrier();
-#endif
                     asm volatile("" ::: "memory");
                 } else {
                     each_op(op, ic<0>{});
@@ -914,9 +911,6 @@ __global__ __launch_bounds__((HELP ? (SPLIT ? 8 : 16) : SPLIT3 ? 8 : SPLIT2 ? 6 
 // adds only ~30 % (the SIMD issues oldest-first: 54 / 78 in isolation, the kernel ends with the younger), so only the
 // 4-operator voice at 65 ... 128 individuals per CU runs here (launch_synth).
 // ------------------------------------------------------------------------------------
-#ifndef SOTS_OL_ABL
-#define SOTS_OL_ABL 0
-#endif
 template <int OPS> struct OlShape {
     static constexpr int G = OPS == 2 ? 2 : 4; // lanes per individual (3 operators: a fourth lane in front of operator 0 supplies its constant increment)
     static constexpr int R = 16 / G;         // individuals per row of 16 lanes: 8 or 4
@@ -1060,11 +1054,6 @@ __global__ __launch_bounds__(ol_max_waves<VoiceShape<KIND>::OPS>() * kWave) void
             // C: this lane's operator on its block
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-#if SOTS_OL_ABL & 1 // timing ablations (never in the shipped build; the audio is NOT valid): no table reads
-                T[Q][u] = pos * 1e-9f;
-#elif SOTS_OL_ABL & 16 // conflict-free table reads (no index arithmetic either)
-                T[Q][u] = tab[lane + 64 * u];
-#else
                 if constexpr (UNCLAMPED) {
                     T[Q][u] = tab[(uint32_t)pos]; // pos in [0, W]
                 } else {
@@ -1074,12 +1063,9 @@ __global__ __launch_bounds__(ol_max_waves<VoiceShape<KIND>::OPS>() * kWave) void
                     asm("v_cvt_u32_f32 %0, %1" : "=v"(ti) : "v"(pos));
                     T[Q][u] = tab[min(ti, kWavetableSize - 1u)];
                 }
-#endif
                 pos += inc[u];
-#if !(SOTS_OL_ABL & 8) // 8: no wraps
                 const v2f_t bc = v2f_t{pos, pos} + v2f_t{-kWf, wlo};
                 pos = __uint_as_float(min(min(__float_as_uint(bc.x), __float_as_uint(bc.y)), __float_as_uint(pos)));
-#endif
             }
             // (nothing of A may move above this trip's table reads: it would wait for the reads of the trip before with none in
             // flight behind them - the scheduler did, and every trip began with s_waitcnt lgkmcnt(0))
@@ -1092,12 +1078,8 @@ __global__ __launch_bounds__(ol_max_waves<VoiceShape<KIND>::OPS>() * kWave) void
                 const v2f_t o = (m[u / 2] + po) * c;
                 // B: to the operator behind (lanes R ... 15 of every row take from R lanes below; lanes 0 ... R-1 have no source lane
                 // and keep theirs: operator 0's constant)
-#if SOTS_OL_ABL & 2 // no lane shift
-                inc[u] = o.x, inc[u + 1] = o.y;
-#else
                 inc[u] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(inc[u]), __float_as_int(o.x), 0x110 + R, 0xf, 0xf, false));
                 inc[u + 1] = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(inc[u + 1]), __float_as_int(o.y), 0x110 + R, 0xf, 0xf, false));
-#endif
             }
             if constexpr (PHASE == 1) {
                 if (s >= 1 && 2u * (uint32_t)s > k + 1u) { // this operator's first block has not arrived yet
@@ -1106,11 +1088,7 @@ __global__ __launch_bounds__(ol_max_waves<VoiceShape<KIND>::OPS>() * kWave) void
                 }
             }
             // the samples of block k - LAST leave
-#if SOTS_OL_ABL & 4 // no tile, no stores
-            if (pm == 12345.678f && m[0].x == 1.0f && m[1].y == 2.0f && m[2].x == 5.0f && m[3].y == 0.1f) {
-#else
             if (PHASE == 0 || (k >= (uint32_t)LAST && k - (uint32_t)LAST < nb)) {
-#endif
                 const uint32_t ip = (k - (uint32_t)LAST) * U;
                 store_pending(); // the lines read back one trip ago
                 const uint32_t c0 = (ip >> 2) & (CH - 1);
@@ -1194,12 +1172,8 @@ __global__ __launch_bounds__(ol_max_waves<VoiceShape<KIND>::OPS>() * kWave) void
         }
         store_pending();
         };
-#ifdef SOTS_OL_CLAMPED // (experiment: the clamped index for every wavefront)
-        run(std::false_type{});
-#else
         if (unclamped) run(std::true_type{});
         else run(std::false_type{});
-#endif
     }
     if (table_pending) wavetable_ready(); // a workgroup without a tile must not end with copies in flight
 }
@@ -1394,515 +1368,16 @@ __global__ __launch_bounds__(256) void k_window(float *__restrict__ audio, const
     }
 }
 
-// ------------------------------------------------------------------------------------
-// Batched real FFT (replaces clFFT, Evolutionary_Strategy_OpenCL.hpp:156-192,555-561)
-// and fitnessPopulation (ocl_program.cl:594-659 with the CPU bin range k < N/2,
-// Evolutionary_Strategy_CPU.hpp:235).
-//
-// One wavefront transforms one individual: the N real samples are read as M = N/2 complex
-// points, E = M/64 per lane, and go through Stockham autosort passes of radix 8 or 4 (three
-// or two radix-2 butterfly layers done in registers), exchanging through a padded LDS
-// buffer between passes.  A final split step turns Z[k], Z[M-k] into the real-input bins
-// X[k], X[M-k].
-// ------------------------------------------------------------------------------------
-// The transform is not bit-matched to anything (the oracle's FFT is fp64), so fused
-// multiply-adds are allowed here and only here; "on" contracts within one expression, which
-// keeps k_fft<.,1> and k_fitness on identical arithmetic.
-#pragma clang fp contract(on)
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 cmul(float2 a, float2 b)
-{
-    return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
+} // namespace
+} // namespace sots
 
-// ---- complex values as 2-vectors (register pairs): v_pk_add/mul/fma_f32 do a complex add, or half a complex
-// multiply, per instruction, and every wave64 vector instruction holds the SIMD for 4 cycles whatever it does
-__device__ __forceinline__ v2f_t xv(float2 a) { return v2f_t{a.x, a.y}; }
-// a * w: (a.x, a.y) * w.x + (-a.y, a.x) * w.y - a packed multiply and a packed fma (operand selects and negations are
-// instruction modifiers)
-// The packed instructions select the low or high half of each source per result half (op_sel, op_sel_hi) and negate
-// per half (neg_lo, neg_hi); the compiler uses the selects but flips signs of single halves with v_xor and copies, so
-// the few shapes the transform needs are written out.
-#ifndef SOTS_XC_ONE_ASM
-#define SOTS_XC_ONE_ASM 1 // (0: a statement per instruction, rounds 2-3; profiles/r04_experiments.md)
-#endif
-__device__ __forceinline__ v2f_t xc_mul(v2f_t a, v2f_t w)
-{
-#if SOTS_XC_ONE_ASM // both halves in ONE statement: around a statement the compiler pads wait states it cannot rule out (s_nop)
-    v2f_t t;
-    asm("v_pk_mul_f32 %1, %0, %2 op_sel:[0,0] op_sel_hi:[1,0]\n\t"                                              // (a.x w.x, a.y w.x)
-        "v_pk_fma_f32 %0, %0, %2, %1 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]" : "+v"(a), "=&v"(t) : "v"(w)); // (-a.y w.y, a.x w.y) + t
-    return a;
-#else
-    v2f_t t, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,0] op_sel_hi:[1,0]" : "=v"(t) : "v"(a), "v"(w));                       // (a.x w.x, a.y w.x)
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]" : "=v"(r) : "v"(a), "v"(w), "v"(t)); // (-a.y w.y, a.x w.y) + t
-    return r;
-#endif
-}
-__device__ __forceinline__ v2f_t xc_mul_neg_i(v2f_t a) { return v2f_t{a.y, -a.x}; }
-// (-i a) * w = (a.y w.x + a.x w.y, a.y w.y - a.x w.x)
-__device__ __forceinline__ v2f_t xc_mul_negi_w(v2f_t a, v2f_t w)
-{
-#if SOTS_XC_ONE_ASM
-    v2f_t t;
-    asm("v_pk_mul_f32 %1, %0, %2 op_sel:[1,0] op_sel_hi:[0,0] neg_hi:[1,0]\n\t"                                  // (a.y w.x, -a.x w.x)
-        "v_pk_fma_f32 %0, %0, %2, %1 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(a), "=&v"(t) : "v"(w));               // (a.x w.y, a.y w.y) + t
-    return a;
-#else
-    v2f_t t, r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,0] op_sel_hi:[0,0] neg_hi:[1,0]" : "=v"(t) : "v"(a), "v"(w));           // (a.y w.x, -a.x w.x)
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "=v"(r) : "v"(a), "v"(w), "v"(t));        // (a.x w.y, a.y w.y) + t
-    return r;
-#endif
-}
-// a + conj(b), a - conj(b)
-__device__ __forceinline__ v2f_t xc_add_conj(v2f_t a, v2f_t b)
-{
-    v2f_t r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ v2f_t xc_sub_conj(v2f_t a, v2f_t b)
-{
-    v2f_t r;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
+#include "kernels/fft.h"
+#include "kernels/objective.h"
 
+namespace sots {
+namespace {
 
-// a * e^{-i pi/4} and a * e^{-3 i pi/4} for a = (x, y): ((x + y) s, (y - x) s) and ((y - x) s, -(x + y) s), s = sqrt(1/2) -
-// one packed add with swapped and negated halves and one packed multiply each (the same sums and products as the scalar
-// form, so the same bits)
-__device__ __forceinline__ float2 rot_m45(float2 a)
-{
-    const v2f_t av = xv(a);
-    v2f_t t;
-    asm("v_pk_add_f32 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(t) : "v"(av)); // (x + y, y - x)
-    t = t * v2f_t{0.70710678118654752440f, 0.70710678118654752440f};
-    return make_float2(t.x, t.y);
-}
-__device__ __forceinline__ float2 rot_m135(float2 a)
-{
-    const v2f_t av = xv(a);
-    v2f_t t;
-    asm("v_pk_add_f32 %0, %1, %1 op_sel:[1,0] op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[1,1]" : "=v"(t) : "v"(av)); // (y - x, -x - y)
-    t = t * v2f_t{0.70710678118654752440f, 0.70710678118654752440f};
-    return make_float2(t.x, t.y);
-}
-
-// a + (-i) d = (a.x + d.y, a.y - d.x) and a - (-i) d = (a.x - d.y, a.y + d.x) in ONE packed add each (half selects and negations
-// are instruction modifiers): a butterfly's rotation by -i never becomes a register shuffle
-__device__ __forceinline__ float2 add_negi(float2 a, float2 d)
-{
-    v2f_t r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(xv(a)), "v"(xv(d)));
-    return make_float2(r.x, r.y);
-}
-__device__ __forceinline__ float2 sub_negi(float2 a, float2 d)
-{
-    v2f_t r;
-    asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(xv(a)), "v"(xv(d)));
-    return make_float2(r.x, r.y);
-}
-
-template <int R> struct Dft;
-template <> struct Dft<2> {
-    static __device__ __forceinline__ void run(float2 *v)
-    {
-        const float2 a = v[0], b = v[1];
-        v[0] = cadd(a, b);
-        v[1] = csub(a, b);
-    }
-};
-template <> struct Dft<4> {
-    static __device__ __forceinline__ void run(float2 *v)
-    {
-        const float2 t0 = cadd(v[0], v[2]), t1 = csub(v[0], v[2]);
-        const float2 t2 = cadd(v[1], v[3]), d = csub(v[1], v[3]);
-        v[0] = cadd(t0, t2);
-        v[1] = add_negi(t1, d); // t1 + (-i) d
-        v[2] = csub(t0, t2);
-        v[3] = sub_negi(t1, d);
-    }
-};
-template <> struct Dft<8> {
-    static __device__ __forceinline__ void run(float2 *v)
-    {
-        float2 e[4] = {v[0], v[2], v[4], v[6]};
-        float2 o[4] = {v[1], v[3], v[5], v[7]};
-        Dft<4>::run(e);
-        Dft<4>::run(o);
-        // o[k] *= exp(-2 pi i k / 8); k = 2 (a rotation by -i) folded into its butterfly
-        o[1] = rot_m45(o[1]);
-        o[3] = rot_m135(o[3]);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            v[k] = k == 2 ? add_negi(e[k], o[k]) : cadd(e[k], o[k]);
-            v[k + 4] = k == 2 ? sub_negi(e[k], o[k]) : csub(e[k], o[k]);
-        }
-    }
-};
-
-// LDS index padding: one extra complex slot per 8 keeps the stride-8 / stride-64 writes of
-// the first two passes and the unit-stride reads off each other's banks.
-__device__ __forceinline__ int lds_pad(int i) { return i + (i >> 3); }
-
-// One Stockham pass of radix R with NS = product of the radices already applied.
-// Register slot s holds element lane + 64 s of the pass input; butterfly b uses slots
-// b + t*(E/R), t < R.  Output element t of butterfly j goes to (j-k)*R + k + t*NS with
-// k = j mod NS.  The twiddles e^{-2 pi i t k / (NS R)} depend only on the lane, so they are
-// loop-invariant per kernel: twr (when non-null) holds them in registers, B*(R-1) values in
-// (b, t) order; otherwise they come from the N-entry table e^{-2 pi i q / N}, N = 2M.
-template <int M, int R, int NS>
-__device__ __forceinline__ void load_pass_twiddles(float2 *twr, const float2 *__restrict__ tw, int lane)
-{
-    constexpr int E = M / kWave, B = E / R, stride = (2 * M) / (NS * R);
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-        const int k = (lane + kWave * b) & (NS - 1);
-#pragma unroll
-        for (int t = 1; t < R; ++t) twr[b * (R - 1) + t - 1] = tw[t * k * stride];
-    }
-}
-
-// LAST: the pass's outputs stay in registers instead of going to LDS.  For the last pass
-// (NS * R == M, so k == j and j0 == j) output t of butterfly b is element lane + 64 (b + B t): slot
-// b + B t of x, i.e. afterwards x[s] = Z[lane + 64 s].
-template <int M, int R, int NS, bool LAST = false>
-__device__ __forceinline__ void fft_pass(float2 (&x)[M / kWave], float2 *__restrict__ lds,
-                                         const float2 *__restrict__ tw, const float2 *twr, int lane)
-{
-    constexpr int E = M / kWave, B = E / R;
-    static_assert(!LAST || NS * R == M, "only the final pass can stay in registers");
-    float2 out[LAST ? E : 1];
-    static_assert(E % R == 0, "radix must divide the per-lane element count");
-#pragma unroll
-    for (int b = 0; b < B; ++b) {
-        const int j = lane + kWave * b;
-        const int k = j & (NS - 1);
-        float2 v[R];
-#pragma unroll
-        for (int t = 0; t < R; ++t) v[t] = x[b + t * B];
-        if constexpr (NS > 1) {
-            constexpr int stride = (2 * M) / (NS * R);
-#pragma unroll
-            for (int t = 1; t < R; ++t) v[t] = cmul(v[t], twr ? twr[b * (R - 1) + t - 1] : tw[t * k * stride]);
-        }
-        Dft<R>::run(v);
-        if constexpr (LAST) {
-#pragma unroll
-            for (int t = 0; t < R; ++t) out[b + t * B] = v[t];
-        } else {
-            const int j0 = (j - k) * R + k;
-#pragma unroll
-            for (int t = 0; t < R; ++t) lds[lds_pad(j0 + t * NS)] = v[t];
-        }
-    }
-    if constexpr (LAST) {
-#pragma unroll
-        for (int sl = 0; sl < E; ++sl) x[sl] = out[sl];
-    }
-}
-
-template <int M>
-__device__ __forceinline__ void lds_reload(float2 (&x)[M / kWave], const float2 *__restrict__ lds, int lane)
-{
-#pragma unroll
-    for (int s = 0; s < M / kWave; ++s) x[s] = lds[lds_pad(lane + kWave * s)];
-}
-
-// First pass (NS = 1, no twiddles) straight from the 16-byte loads of the row.  Lane l holds
-// the float4 = two complex points at pair index l + 64 h, i.e. complex elements
-// e0 = 2l + 128 h and e0 + 1.  With element e = j + (M/R) t:
-//   B = E/R >= 2: the lane already owns every t of butterflies j = 2l + 64 bb (+1), bb even;
-//   B == 1      : lanes l and l+32 hold the even-t and odd-t halves of butterflies 2l, 2l+1;
-//                 one v_permlane32_swap per register gives lane l all of 2l and lane l+32
-//                 all of 2l+1.
-template <int M, int R>
-__device__ __forceinline__ void fft_first_pass(const float4 (&q)[M / kWave / 2], float2 *__restrict__ lds, int lane)
-{
-    constexpr int E = M / kWave;
-    static_assert(E == R, "one first-pass butterfly per lane (N = 512: radix 4, N = 1024: radix 8)");
-    float2 v[R];
-#pragma unroll
-    for (int h = 0; h < R / 2; ++h) {
-        const auto sx = __builtin_amdgcn_permlane32_swap(__float_as_uint(q[h].x), __float_as_uint(q[h].z), false, false);
-        const auto sy = __builtin_amdgcn_permlane32_swap(__float_as_uint(q[h].y), __float_as_uint(q[h].w), false, false);
-        v[2 * h] = make_float2(__uint_as_float(sx[0]), __uint_as_float(sy[0]));
-        v[2 * h + 1] = make_float2(__uint_as_float(sx[1]), __uint_as_float(sy[1]));
-    }
-    Dft<R>::run(v);
-    const int j = 2 * (lane & 31) + (lane >> 5);
-#pragma unroll
-    for (int t = 0; t < R; ++t) lds[lds_pad(j * R + t)] = v[t];
-}
-
-// All passes for M complex points (N = 512: 4.4.4.4, N = 1024: 8.8.8), starting from the row as
-// loaded; the last pass stays in registers: x[s] = Z[lane + 64 s].  The per-lane pass twiddles
-// (all passes after the first) are loop-invariant and live in registers.
-template <int M> constexpr int tw_count() { return M == 256 ? 9 : 14; }
-
-template <int M>
-__device__ __forceinline__ void preload_twiddles(float2 (&twr)[tw_count<M>()], const float2 *__restrict__ tw, int lane)
-{
-    static_assert(M == 256 || M == 512, "wavefront-per-row FFT is for N <= 1024");
-    if constexpr (M == 256) {
-        load_pass_twiddles<M, 4, 4>(&twr[0], tw, lane);
-        load_pass_twiddles<M, 4, 16>(&twr[3], tw, lane);
-        load_pass_twiddles<M, 4, 64>(&twr[6], tw, lane);
-    } else {
-        load_pass_twiddles<M, 8, 8>(&twr[0], tw, lane);
-        load_pass_twiddles<M, 8, 64>(&twr[7], tw, lane);
-    }
-}
-
-// Between the passes of ONE wavefront's transform.  A workgroup of one wavefront: __syncthreads(), of which the compiler
-// drops the s_barrier and keeps the fence (s_waitcnt lgkmcnt(0)).  A workgroup of several wavefronts, each with its own
-// piece of LDS (W > 1 below): the fence written out - a barrier would tie the wavefronts together for nothing.  (The LDS
-// executes a wavefront's instructions in order; ordering them by a compiler barrier alone measures the same,
-// profiles/r03_experiments.md.)
-template <bool ALONE>
-__device__ __forceinline__ void wave_lds_sync()
-{
-    if constexpr (ALONE) __syncthreads();
-    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
-template <int M, bool ALONE = true>
-__device__ __forceinline__ void fft_forward(const float4 (&q)[M / kWave / 2], float2 *__restrict__ lds,
-                                            const float2 *__restrict__ tw, const float2 (&twr)[tw_count<M>()], int lane,
-                                            float2 (&x)[M / kWave])
-{
-#define SOTS_SYNC() wave_lds_sync<ALONE>()
-#define SOTS_FIRST(R)                        \
-    fft_first_pass<M, R>(q, lds, lane);      \
-    SOTS_SYNC();
-#define SOTS_PASS(R, NS, OFF)                             \
-    fft_pass<M, R, NS>(x, lds, tw, &twr[OFF], lane);      \
-    SOTS_SYNC();
-#define SOTS_NEXT()                          \
-    lds_reload<M>(x, lds, lane);             \
-    SOTS_SYNC();
-#define SOTS_LAST(R, NS, OFF) fft_pass<M, R, NS, true>(x, lds, tw, &twr[OFF], lane);
-    if constexpr (M == 256) {
-        SOTS_FIRST(4) SOTS_NEXT() SOTS_PASS(4, 4, 0) SOTS_NEXT() SOTS_PASS(4, 16, 3) SOTS_NEXT() SOTS_LAST(4, 64, 6)
-    } else {
-        SOTS_FIRST(8) SOTS_NEXT() SOTS_PASS(8, 8, 0) SOTS_NEXT() SOTS_LAST(8, 64, 7)
-    }
-#undef SOTS_SYNC
-#undef SOTS_FIRST
-#undef SOTS_PASS
-#undef SOTS_NEXT
-#undef SOTS_LAST
-}
-
-// Real-input split for the pair (k, M-k), 0 <= k < M/2:
-//   Ee = (Z[k] + conj Z[M-k]) / 2,  Oo = -i (Z[k] - conj Z[M-k]) / 2,  T = e^{-2 pi i k/N} Oo
-//   X[k] = Ee + T,  X[M-k] = conj(Ee - T)
-// With Z[M] read as Z[0] the same formula gives X[0] = Re Z0 + Im Z0 and the Nyquist bin
-// X[M] = Re Z0 - Im Z0 for k = 0, so no lane takes a different path.  Bin M/2, which no pair
-// covers, is X[M/2] = conj Z[M/2].
-// After the last pass lane l holds z[s] = Z[l + 64 s].  For k = l + 64 q the partner
-// Z[M-k] = Z[(64-l) + 64 (E-1-q)] is slot E-1-q of lane 64-l: one ds_bpermute per dword through
-// the LDS crossbar, no LDS memory and no bank conflicts (this replaces a write of the whole
-// transform to LDS and two reads of it).  Lane 0 pairs with itself one slot further:
-// Z[M - 64 q] = its own slot E-q, and Z[M] = Z[0] for q = 0.
-template <int M>
-__device__ __forceinline__ float2 split_partner(const float2 (&z)[M / kWave], int q, int lane, int partner_addr)
-{
-    constexpr int E = M / kWave;
-    const float2 mine = z[q == 0 ? 0 : E - q];                    // what lane 0 needs
-    const float2 send = z[E - 1 - q];                             // what lane 64-l needs from this lane
-    const float px = __int_as_float(__builtin_amdgcn_ds_bpermute(partner_addr, __float_as_int(send.x)));
-    const float py = __int_as_float(__builtin_amdgcn_ds_bpermute(partner_addr, __float_as_int(send.y)));
-    return lane == 0 ? mine : make_float2(px, py);
-}
-
-// In packed form, without the two 1/2 factors: 2 X[k] and 2 conj X[M-k] (a factor of two is exact in fp32; the fitness
-// folds it into its magnitude scale and takes magnitudes, the spectrum writer halves and conjugates as it stores) - six
-// packed instructions for two bins
-__device__ __forceinline__ void split_pair_2x(float2 a, float2 bz, float2 w, v2f_t &xa2, v2f_t &xbc2)
-{
-    const v2f_t av = xv(a), bv = xv(bz);
-    const v2f_t ee = xc_add_conj(av, bv), dd = xc_sub_conj(av, bv);
-    const v2f_t t = xc_mul_negi_w(dd, xv(w));
-    xa2 = ee + t;
-    xbc2 = ee - t;
-}
-
-// (|X| * scale - target)^2 with scale = 1 / N / windowFactor, Evolutionary_Strategy.hpp:517-519 /
-// ocl_program.cl:608-611 (one combined factor: 1/N is a power of two and the window factor is 1 to an ulp).
-// v_sqrt_f32 (1 ulp) instead of the correctly rounded sequence: the transform feeding it is
-// fp32 against the oracle's fp64 anyway.  The fused kernels pass 2 X and scale / 2: the same value bit for bit.
-__device__ __forceinline__ float bin_error(float2 x, float target, float scale)
-{
-    const float raw = __builtin_amdgcn_sqrtf(x.x * x.x + x.y * x.y);
-    const float e = raw * scale - target;
-    return e * e;
-}
-
-// Two bins at once, each with its own running sum: the magnitudes come out of v_sqrt_f32 one by one, the scale, the
-// subtraction and the squared accumulation are packed (acc2 = (sum over the bins k, sum over the bins M - k); k_fft<., 1> and
-// k_fitness add the two halves in the same order, so both paths still give the same fp32 sum)
-__device__ __forceinline__ void bin_error2(v2f_t &acc2, float2 xa, float2 xb, float ta, float tb, float scale)
-{
-    const v2f_t raw = v2f_t{__builtin_amdgcn_sqrtf(xa.x * xa.x + xa.y * xa.y), __builtin_amdgcn_sqrtf(xb.x * xb.x + xb.y * xb.y)};
-    const v2f_t e = raw * v2f_t{scale, scale} - v2f_t{ta, tb};
-    acc2 = acc2 + e * e;
-}
-// The weighted forms (bin_error_w / bin_error2_w below): the same signed error e, times u = sqrt(w) of the
-// bin - one product, rounded once - and the squared accumulation as it stands above.  u = 1 gives the unweighted bits,
-// u = 0 makes a finite bin contribute exactly 0.
-__device__ __forceinline__ float bin_error_wt(float2 x, float target, float scale, float u)
-{
-    const float raw = __builtin_amdgcn_sqrtf(x.x * x.x + x.y * x.y);
-    const float e = (raw * scale - target) * u;
-    return e * e;
-}
-__device__ __forceinline__ void bin_error2_wt(v2f_t &acc2, float2 xa, float2 xb, float ta, float tb, float scale, float ua, float ub)
-{
-    const v2f_t raw = v2f_t{__builtin_amdgcn_sqrtf(xa.x * xa.x + xa.y * xa.y), __builtin_amdgcn_sqrtf(xb.x * xb.x + xb.y * xb.y)};
-    const v2f_t e = (raw * v2f_t{scale, scale} - v2f_t{ta, tb}) * v2f_t{ua, ub};
-    acc2 = acc2 + e * e;
-}
-
-// ---- the selectable objective (sots_set_objective) ----
-// OBJ is a template parameter of every kernel that turns bins into fitness.  kObjMagnitude is the reference's sum above,
-// and its instantiations are the kernels as they were: no extra argument, no extra instruction.  kObjLogMagnitude:
-// sum_k (ln(m_k + floor) - ln(t_k + floor))^2 with m_k = |X_k| scale.  The kernels read a target table that already holds
-// ln(t_k + floor), in whatever layout they read the magnitudes in (k_objective_map below made it with obj_ln_floor, the
-// routine of the epilogues: a bin whose magnitude equals the target's contributes exactly 0, and nobody's log but
-// v_log_f32's is involved).  The floor is one more kernel argument of the log instantiations only, behind all others.
-constexpr int kObjMagnitude = SOTS_OBJECTIVE_MAGNITUDE, kObjLogMagnitude = SOTS_OBJECTIVE_LOG_MAGNITUDE;
-// (host side: the table inside a weight image, launch_weight_image)
-static inline const float *weight_table(const float *image) { return image + kSegTargetHeadFloats; }
-#pragma clang fp contract(off) // (m + floor and log2 x ln 2 round one by one, here and in the table's kernel)
-// ln(m + floor): v_log_f32 (log2, 1 ulp) times ln 2.  m >= 0 and 1e-30 <= floor <= 1 keep the argument a normal number,
-// which is all that instruction handles; NaN and +inf pass through.
-__device__ __forceinline__ float obj_ln_floor(float m, float floor)
-{
-    return __builtin_amdgcn_logf(m + floor) * 0.693147180559945f;
-}
-__device__ __forceinline__ float bin_error_log(float raw, float target_ln, float scale, float floor)
-{
-    const float e = obj_ln_floor(raw * scale, floor) - target_ln;
-    return e * e;
-}
-// (the packed form, as bin_error2: scale, floor, ln 2, the subtraction and the squared accumulation are packed; lane by
-// lane the operations and their order are obj_ln_floor's)
-__device__ __forceinline__ void bin_error2_log(v2f_t &acc2, v2f_t raw, float ta, float tb, float scale, float floor)
-{
-    const v2f_t a = raw * v2f_t{scale, scale} + v2f_t{floor, floor};
-    const v2f_t l = v2f_t{__builtin_amdgcn_logf(a.x), __builtin_amdgcn_logf(a.y)} * v2f_t{0.693147180559945f, 0.693147180559945f};
-    const v2f_t e = l - v2f_t{ta, tb};
-    acc2 = acc2 + e * e;
-}
-// (weighted: bin_error_wt's note)
-__device__ __forceinline__ float bin_error_log_wt(float raw, float target_ln, float scale, float floor, float u)
-{
-    const float e = (obj_ln_floor(raw * scale, floor) - target_ln) * u;
-    return e * e;
-}
-__device__ __forceinline__ void bin_error2_log_wt(v2f_t &acc2, v2f_t raw, float ta, float tb, float scale, float floor, float ua, float ub)
-{
-    const v2f_t a = raw * v2f_t{scale, scale} + v2f_t{floor, floor};
-    const v2f_t l = v2f_t{__builtin_amdgcn_logf(a.x), __builtin_amdgcn_logf(a.y)} * v2f_t{0.693147180559945f, 0.693147180559945f};
-    const v2f_t e = (l - v2f_t{ta, tb}) * v2f_t{ua, ub};
-    acc2 = acc2 + e * e;
-}
-#pragma clang fp contract(on)
-template <int OBJ>
-__device__ __forceinline__ float bin_error_o(float2 x, float target, float scale, [[maybe_unused]] float floor)
-{
-    if constexpr (OBJ == kObjLogMagnitude) return bin_error_log(__builtin_amdgcn_sqrtf(x.x * x.x + x.y * x.y), target, scale, floor);
-    else return bin_error(x, target, scale);
-}
-template <int OBJ>
-__device__ __forceinline__ void bin_error2_o(v2f_t &acc2, float2 xa, float2 xb, float ta, float tb, float scale, [[maybe_unused]] float floor)
-{
-    if constexpr (OBJ == kObjLogMagnitude)
-        bin_error2_log(acc2, v2f_t{__builtin_amdgcn_sqrtf(xa.x * xa.x + xa.y * xa.y), __builtin_amdgcn_sqrtf(xb.x * xb.x + xb.y * xb.y)}, ta, tb, scale, floor);
-    else bin_error2(acc2, xa, xb, ta, tb, scale);
-}
-// ---- per-bin weights (sots_set_objective_weights) ----
-// WGT is the second template parameter of those kernels: F = sum_k (u_k e_k)^2 with e_k the signed error of the objective
-// and u_k = sqrt(w_k), a table made once on the host.  The weighted instantiations take the table as one more trailing
-// argument, behind the floor; the others are the kernels as they were.  This pair is the one statement of it: every fused
-// and staged kernel calls it, so fused fitness equals staged fitness bit for bit.
-template <int OBJ, bool WGT>
-__device__ __forceinline__ float bin_error_w(float2 x, float target, float scale, [[maybe_unused]] float floor, [[maybe_unused]] float u)
-{
-    if constexpr (!WGT) return bin_error_o<OBJ>(x, target, scale, floor);
-    else if constexpr (OBJ == kObjLogMagnitude) return bin_error_log_wt(__builtin_amdgcn_sqrtf(x.x * x.x + x.y * x.y), target, scale, floor, u);
-    else return bin_error_wt(x, target, scale, u);
-}
-template <int OBJ, bool WGT>
-__device__ __forceinline__ void bin_error2_w(v2f_t &acc2, float2 xa, float2 xb, float ta, float tb, float scale, [[maybe_unused]] float floor,
-                                             [[maybe_unused]] float ua, [[maybe_unused]] float ub)
-{
-    if constexpr (!WGT) bin_error2_o<OBJ>(acc2, xa, xb, ta, tb, scale, floor);
-    else if constexpr (OBJ == kObjLogMagnitude)
-        bin_error2_log_wt(acc2, v2f_t{__builtin_amdgcn_sqrtf(xa.x * xa.x + xa.y * xa.y), __builtin_amdgcn_sqrtf(xb.x * xb.x + xb.y * xb.y)}, ta, tb, scale, floor, ua, ub);
-    else bin_error2_wt(acc2, xa, xb, ta, tb, scale, ua, ub);
-}
-// the floor out of a kernel's trailing arguments: (), (lists) - magnitude - or (floor), (lists, floor); a weighted
-// instantiation's table stands behind them
-__device__ __forceinline__ float obj_floor() { return 0.0f; }
-__device__ __forceinline__ float obj_floor(float floor) { return floor; }
-__device__ __forceinline__ float obj_floor(const SelLists &) { return 0.0f; }
-__device__ __forceinline__ float obj_floor(const SelLists &, float floor) { return floor; }
-__device__ __forceinline__ float obj_floor(const float *) { return 0.0f; }
-__device__ __forceinline__ float obj_floor(float floor, const float *) { return floor; }
-__device__ __forceinline__ float obj_floor(const SelLists &, const float *) { return 0.0f; }
-__device__ __forceinline__ float obj_floor(const SelLists &, float floor, const float *) { return floor; }
-// the weight table out of them: the last argument where it is a pointer
-__device__ __forceinline__ const float *obj_weights() { return nullptr; }
-__device__ __forceinline__ const float *obj_weights(const float *u) { return u; }
-template <typename T, typename... R>
-__device__ __forceinline__ const float *obj_weights(const T &, R... r) { return obj_weights(r...); }
-// target[i] -> ln(target[i] + floor): the derived table of the log objective, plain bins (every other layout is copied from it)
-__global__ __launch_bounds__(256) void k_objective_map(float *__restrict__ dst, const float *__restrict__ src, size_t n, float floor)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = obj_ln_floor(src[i], floor);
-}
-
-// Wavefront sum without LDS traffic: DPP swaps inside each row of 16 lanes (every lane of a
-// row ends with the row total), then the four row totals are added in row order.
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v)
-{
-    const int m = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false);
-    return v + __int_as_float(m);
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-    v = dpp_add<0xB1>(v);  // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);  // quad_perm [2,3,0,1]
-    v = dpp_add<0x141>(v); // row_half_mirror
-    v = dpp_add<0x140>(v); // row_mirror
-    const int iv = __float_as_int(v);
-    const float r0 = __int_as_float(__builtin_amdgcn_readlane(iv, 0));
-    const float r1 = __int_as_float(__builtin_amdgcn_readlane(iv, 16));
-    const float r2 = __int_as_float(__builtin_amdgcn_readlane(iv, 32));
-    const float r3 = __int_as_float(__builtin_amdgcn_readlane(iv, 48));
-    return ((r0 + r1) + r2) + r3;
-}
-
-// Segmented target image (chunks in flight): word 0 holds the rows per chunk, the chunks' tables follow from float
-// kSegHead on, `stride` floats each - the N/2 bins for k_fft and k_fft_big, k_fft_x's per-(lane, register) target
-// table for k_fft_x (x_seg_stride).  Row r reads the table of chunk r / rows.
-constexpr uint32_t kSegHead = kSegTargetHeadFloats; // (256 bytes: the tables start aligned)
-__device__ __forceinline__ uint32_t seg_target_rows(const float *image)
-{
-    return __builtin_amdgcn_readfirstlane(reinterpret_cast<const uint32_t *>(image)[0]);
-}
-__device__ __forceinline__ const float *seg_target_chunk(const float *image, uint32_t chunk, uint32_t stride)
-{
-    return image + kSegHead + (size_t)chunk * stride;
-}
-
+#pragma clang fp contract(on) // (the transform's mode, kernels/fft.h: k_fft<., 1> and k_fitness share their arithmetic with the helpers they call)
 // ------------------------------------------------------------------------------------
 // Selection keys, and the bucket of a key between the splitters of a slot (list mode).  They stand in
 // front of the spectral kernel because k_fft<.., BUCKET = true> files every row's key under its bucket as soon as it
@@ -2024,22 +1499,14 @@ __device__ __forceinline__ void bkt_visit(const SelLists &bk, const uint32_t *__
 // `target` is then a segmented target image (seg_target_rows / seg_target_chunk above) and every row reads its chunk's bins
 // from it in global memory (L2) instead of the workgroup's one target in LDS.  Same arithmetic, same order.
 template <int LOG2N> constexpr int fft_wide_waves() { return LOG2N == 10 ? 12 : 16; }
-// The lists are one more kernel argument of the BUCKET instantiation ONLY (LISTS = SelLists): the others keep their
-// argument list, and with it their code, to the byte (an argument in front of the hidden ones moves those).
+// The lists are one more kernel argument of the BUCKET instantiation ONLY (the first of the trailing arguments, kernels/objective.h):
+// the others keep their argument list, and with it their code, to the byte (an argument in front of the hidden ones moves those).
 struct BktNoLists {};
-__device__ __forceinline__ BktNoLists bkt_lists() { return {}; }
-__device__ __forceinline__ BktNoLists bkt_lists(float) { return {}; }
-__device__ __forceinline__ const SelLists &bkt_lists(const SelLists &l) { return l; }
-__device__ __forceinline__ const SelLists &bkt_lists(const SelLists &l, float) { return l; }
-__device__ __forceinline__ BktNoLists bkt_lists(const float *) { return {}; }
-__device__ __forceinline__ BktNoLists bkt_lists(float, const float *) { return {}; }
-__device__ __forceinline__ const SelLists &bkt_lists(const SelLists &l, const float *) { return l; }
-__device__ __forceinline__ const SelLists &bkt_lists(const SelLists &l, float, const float *) { return l; }
 // BUCKET (the wide fitness kernel in front of a one-launch selection, list mode): every row's key goes into the list of
 // its bucket between the splitters of bk.slot (bkt_visit above) - the slot was written a generation ago, the row's
 // fitness is in a register here, and the selection's 256 workgroups no longer ask all P rows each.
-// OBJ (MODE 1): the objective; the log instantiations take the floor as their last argument (bin_error_o above)
-// WGT (MODE 1): per-bin weights; the table u[N/2] is then the very last argument (bin_error_w above).  Without SEG it sits
+// OBJ (MODE 1): the objective; the log instantiations take the floor as their last argument (bin_error, kernels/objective.h)
+// WGT (MODE 1): per-bin weights; the table u[N/2] is then the very last argument (bin_error2, kernels/objective.h).  Without SEG it sits
 // in LDS beside the target, one float2 {target, u} per bin; with SEG the chunk's target is read from global memory as
 // ever and u - one table for all chunks - sits in LDS on its own (read from global memory beside the target, the
 // one-wavefront form needed 188 registers and lost its third wavefront per SIMD).
@@ -2052,9 +1519,9 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
     static_assert(sizeof...(LISTS) == (BUCKET ? 1 : 0) + (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the BUCKET instantiation takes the lists, the log ones the floor, the weighted ones their table, the others nothing");
     static_assert((OBJ == kObjMagnitude && !WGT) || MODE == 1, "the objective belongs to the fitness epilogue");
     static_assert(!WGT || WIN, "the weighted forms exist with a window only");
-    [[maybe_unused]] const auto bk = bkt_lists(lists...);
-    [[maybe_unused]] const float floor_eps = obj_floor(lists...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(lists...);
+    [[maybe_unused]] const auto bk = trailing<SelLists>(BktNoLists{}, lists...);
+    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, lists...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, lists...);
     constexpr int N = 1 << LOG2N, M = N / 2, E = M / kWave, H = E / 2;
     static_assert(LOG2N == 9 || LOG2N == 10, "wavefront-per-row FFT is for N <= 1024");
     static_assert(!BUCKET || (MODE == 1 && W > 1 && !SEG), "keys are filed by the wide fitness kernel only");
@@ -2110,11 +1577,7 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
     // transformed - a row's transform is shorter than the loaded memory latency, and the registers
     // are there (168 = three wavefronts per SIMD).
     auto request = [&](float4 (&dst)[Q], uint32_t r) { // rows past the end re-read the current one
-#ifdef SOTS_ABL_FFT_CACHED_ROWS
-        const float4 *__restrict__ in = reinterpret_cast<const float4 *>(audio + (size_t)((r < p_len ? r : ind) & 511u) * pitch); // timing ablation: rows from L2
-#else
         const float4 *__restrict__ in = reinterpret_cast<const float4 *>(audio + (size_t)(r < p_len ? r : ind) * pitch);
-#endif
 #pragma unroll
         for (int h = 0; h < Q; ++h) dst[h] = SOTS_ROW_LOAD(in + lane + kWave * h);
     };
@@ -2194,16 +1657,16 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
                 if constexpr (WGT) {
                     const int k2 = k == 0 ? M / 2 : M - k;
                     if constexpr (SEG) {
-                        bin_error2_w<OBJ, true>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tg[k], tg[k2], half_scale, floor_eps, u_s[k], u_s[k2]);
+                        bin_error2<OBJ, true>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tg[k], tg[k2], half_scale, floor_eps, u_s[k], u_s[k2]);
                         if constexpr (W == 1) __builtin_amdgcn_sched_barrier(0); // (the one-wavefront form: read ahead, the weights cost the third wavefront per SIMD)
                     }
                     else {
                         const float2 ta = tu_s[k], tb = tu_s[k2];
-                        bin_error2_w<OBJ, true>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), ta.x, tb.x, half_scale, floor_eps, ta.y, tb.y);
+                        bin_error2<OBJ, true>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), ta.x, tb.x, half_scale, floor_eps, ta.y, tb.y);
                     }
                 } else
-                if constexpr (SEG) bin_error2_o<OBJ>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tg[k], tg[k == 0 ? M / 2 : M - k], half_scale, floor_eps);
-                else bin_error2_o<OBJ>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tgt_s[k], tgt_s[k == 0 ? M / 2 : M - k], half_scale, floor_eps);
+                if constexpr (SEG) bin_error2<OBJ, false>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tg[k], tg[k == 0 ? M / 2 : M - k], half_scale, floor_eps, 0.0f, 0.0f);
+                else bin_error2<OBJ, false>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tgt_s[k], tgt_s[k == 0 ? M / 2 : M - k], half_scale, floor_eps, 0.0f, 0.0f);
             }
             float acc = wave_sum(acc2.x + acc2.y);
             if (lane == 0) fitness[ind] = acc;
@@ -2263,8 +1726,8 @@ __global__ __launch_bounds__(kWave) void k_fitness(const float *__restrict__ spe
                                                    float inv_wf, FLOOR... floor)
 {
     static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the log instantiation takes the floor, the weighted one its table");
-    [[maybe_unused]] const float floor_eps = obj_floor(floor...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(floor...);
+    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, floor...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, floor...);
     constexpr int N = 1 << LOG2N, M = N / 2, E = M / kWave;
     const int lane = threadIdx.x;
     for (uint32_t ind = blockIdx.x; ind < p_len; ind += gridDim.x) {
@@ -2274,7 +1737,7 @@ __global__ __launch_bounds__(kWave) void k_fitness(const float *__restrict__ spe
         for (int q = 0; q < E / 2; ++q) {
             const int k = lane + kWave * q;
             const int kb = k == 0 ? M / 2 : M - k;
-            bin_error2_w<OBJ, WGT>(acc2, row[k], row[kb], target[k], target[kb], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f, WGT ? wgt_u[kb] : 0.0f);
+            bin_error2<OBJ, WGT>(acc2, row[k], row[kb], target[k], target[kb], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f, WGT ? wgt_u[kb] : 0.0f);
         }
         float acc = wave_sum(acc2.x + acc2.y);
         if (lane == 0) fitness[ind] = acc;
@@ -2637,18 +2100,6 @@ constexpr uint32_t kSelSkew = 4;                    // consecutive tiles start 4
 // beats the two-level full sort (237 against 244 us per generation), at 262144 it loses (496 against 482), so it stops at 128 tiles
 constexpr uint32_t kSelMinTiles = 16, kSelMaxTiles = 128, kSelMaxOwn = 512; // kSelMaxTiles: tiles the rank kernel handles (of either size)
 
-// value of lane (lane ^ J) for J = 1, 2 (DPP quad permutes), 4, 8, 16 (ds_swizzle through the LDS crossbar,
-// no LDS memory), 32 (v_permlane32_swap)
-template <uint32_t J>
-__device__ __forceinline__ uint32_t lane_xor(uint32_t v)
-{
-    if constexpr (J == 1) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xf, 0xf, true); // quad_perm [1,0,3,2]
-    else if constexpr (J == 2) return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xf, 0xf, true); // quad_perm [2,3,0,1]
-    else if constexpr (J == 32) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-        return (threadIdx.x & 32u) ? sw[0] : sw[1]; // lanes 32-63 get lane-32's value in [0], lanes 0-31 lane+32's in [1]
-    } else return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, (int)((J << 10) | 0x1Fu)); // bit mode: xor J, and 0x1f
-}
 
 template <uint32_t K, uint32_t J>
 __device__ __forceinline__ void bitonic_step(uint32_t &b, uint32_t &i, uint32_t lane)
@@ -3656,54 +3107,28 @@ template <int LOG2N> constexpr int x_points() { return (1 << LOG2N) / 2 / kWave;
 #ifndef SOTS_X_WAVES12
 #define SOTS_X_WAVES12 16
 #endif
-#ifndef SOTS_X_SADDR
-#define SOTS_X_SADDR 1
-#endif
-#ifndef SOTS_X_PAIR_SPLIT
-#define SOTS_X_PAIR_SPLIT 1 // both bins of a pair (k, M - k) in one lane (0: every lane its own E bins, rounds 2-3)
-#endif
 // wavefronts (independent rows) per workgroup: what the registers allow (MODE 0, the spectrum writer of the stage-separated
 // path, needs a few more than the fused kernel)
 template <int LOG2N, int MODE = 1> constexpr int x_waves() { return LOG2N >= 13 ? 8 : LOG2N == 12 ? (MODE == 0 ? 12 : SOTS_X_WAVES12) : 16; }
 template <int LOG2N> constexpr bool x_applies() { return LOG2N >= 10 && LOG2N <= 13; }
 
-// target bin of entry (lane l, register r) of k_fft_x's target table.  With SOTS_X_PAIR_SPLIT a lane turns out its own bin
+// target bin of entry (lane l, register r) of k_fft_x's target table.  A lane turns out its own bin
 // for the first register of a pair (RR, R2 = bitrev(E - bitrev(RR))) and its PARTNER lane's bin M - k for the second, so the
 // second register's entry holds that bin's target: the partner is lane l ^ 63 (p' = 63 - p), its bin at r is q + E (63 - p).
 template <int E, int EB>
 __device__ __forceinline__ uint32_t x_target_bin(uint32_t l, uint32_t r)
 {
     const uint32_t q = __brev(r) >> (32 - EB), pp = __brev(l) >> 26;
-#if SOTS_X_PAIR_SPLIT
     const uint32_t r2 = q == 0 ? 0u : __brev((uint32_t)E - q) >> (32 - EB);
     return r2 < r ? q + E * (63u - pp) : q + E * pp;
-#else
-    return q + E * pp;
-#endif
-}
-// f(ic<I>{}) for I = FIRST .. LAST-1 with I a compile-time constant inside f (register arrays are indexed with it)
-template <int FIRST, int LAST, typename F>
-__device__ __forceinline__ void static_for(F &&f)
-{
-    if constexpr (FIRST < LAST) {
-        f(ic<FIRST>{});
-        static_for<FIRST + 1, LAST>(f);
-    }
 }
 
 // Complex values are 2-vectors here (register pairs): the transform is VALU-bound (85 % busy at 2400 one-float
 // instructions per row in its first form), and v_pk_add/mul/fma_f32 do a complex add, or half a complex multiply, per
 // instruction.
-#ifndef SOTS_X_NT
-#define SOTS_X_NT 1
-#endif
 __device__ __forceinline__ v2f_t x_row_load(const float2 *p)
 {
-#if SOTS_X_NT
     return __builtin_nontemporal_load(reinterpret_cast<const v2f_t *>(p)); // rows are read once
-#else
-    return *reinterpret_cast<const v2f_t *>(p);
-#endif
 }
 // one radix-2 DIF stage of the E-point transform over the registers: pairs (a, a + H) inside groups of 2 H
 template <int H, int E, int N>
@@ -3721,11 +3146,6 @@ __device__ __forceinline__ void x_reg_stage(v2f_t (&x)[E], const float2 *__restr
     if constexpr (H > 1) x_reg_stage<H / 2, E, N>(x, tw);
 }
 
-template <uint32_t J> __device__ __forceinline__ float lane_xor_f(float v)
-{
-    if constexpr (J == 8) return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xf, 0xf, true)); // row_ror:8
-    else return __uint_as_float(lane_xor<J>(__float_as_uint(v)));
-}
 
 // one radix-2 DIF stage over the lanes, partner l ^ H, on every register: own * (+-1) + partner, times the lane's
 // constant (1 where bit H is clear)
@@ -3735,7 +3155,6 @@ __device__ __forceinline__ void x_lane_stage(v2f_t (&x)[E], float sgn, v2f_t wl)
 #pragma unroll
     for (int r = 0; r < E; ++r) {
         const v2f_t p = v2f_t{lane_xor_f<H>(x[r].x), lane_xor_f<H>(x[r].y)};
-#if SOTS_XC_ONE_ASM
         if constexpr (H != 1) { // the butterfly and its twiddle as one statement (see xc_mul)
             v2f_t t, u = x[r];
             asm("v_pk_fma_f32 %0, %0, %2, %3\n\t"
@@ -3743,11 +3162,8 @@ __device__ __forceinline__ void x_lane_stage(v2f_t (&x)[E], float sgn, v2f_t wl)
                 "v_pk_fma_f32 %0, %0, %4, %1 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]"
                 : "+v"(u), "=&v"(t) : "v"(v2f_t{sgn, sgn}), "v"(p), "v"(wl));
             x[r] = u;
-        } else
-#endif
-        {
-        const v2f_t t = x[r] * v2f_t{sgn, sgn} + p;
-        x[r] = H == 1 ? t : xc_mul(t, wl);
+        } else {
+            x[r] = x[r] * v2f_t{sgn, sgn} + p; // (the last stage's twiddle is 1)
         }
         if (r % 4 == 3) __builtin_amdgcn_sched_barrier(0); // (four registers' partner fetches in flight at a time)
     }
@@ -3810,8 +3226,8 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
 {
     static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0) && ((OBJ == kObjMagnitude && !WGT) || MODE == 1), "the log instantiation (fitness epilogue only) takes the floor, the weighted one its table");
     static_assert(!WGT || WIN, "the weighted forms exist with a window only");
-    [[maybe_unused]] const float floor_eps = obj_floor(floor...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(floor...);
+    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, floor...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, floor...);
     constexpr int N = 1 << LOG2N, M = N / 2, E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), W = WG;
     constexpr int S2 = E + 2, S1 = E + 4; // lane strides of the float2 / float tables (16-byte reads, spread over the banks)
     __shared__ __attribute__((aligned(16))) float xt_s[x_table_floats<LOG2N>()]; // (the variants without window or target leave theirs unused)
@@ -3922,10 +3338,6 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
         const unsigned long long xs_t2 = __builtin_amdgcn_s_memtime();
 #endif
         float acc = 0.0f;
-#if !SOTS_X_PAIR_SPLIT
-        v2f_t out_even = v2f_t{0.f, 0.f}; // MODE 0: bins leave two at a time, in bin order
-        float2 *__restrict__ dst = MODE == 0 ? reinterpret_cast<float2 *>(spectrum + (size_t)row * (N + 8)) + E * pp : nullptr;
-#endif
         // one bin: register RR of this lane with its partner Z[M - k]
         auto bin2x = [&](auto r_tag) -> v2f_t {
             constexpr int RR = decltype(r_tag)::value, Q = x_bitrev(RR, EB), R2 = Q == 0 ? 0 : x_bitrev(E - Q, EB);
@@ -3936,7 +3348,6 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
             const v2f_t ee = xc_add_conj(x[RR], zm), dd = xc_sub_conj(x[RR], zm);
             return ee + xc_mul_negi_w(dd, w); // 2 X[k] = (Z[k] + conj Z[M-k]) + W_N^k (-i) (Z[k] - conj Z[M-k])
         };
-#if SOTS_X_PAIR_SPLIT
         // BOTH bins of the pair (k, M - k) from this lane's Z[k] (register RR) and the partner lane's Z[M - k] (its register
         // R2): ee and t = W_N^k (-i) dd once, 2 X[k] = ee + t and 2 conj X[M - k] = ee - t.  The partner lane does the same with
         // ITS register RR and this lane's R2, so every lane still turns out E bins - half of them its partner's - with half
@@ -3950,7 +3361,6 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
             const v2f_t ee = xc_add_conj(x[RR], zm), t = xc_mul_negi_w(xc_sub_conj(x[RR], zm), w);
             xa = ee + t, xb = ee - t;
         };
-#endif
         if constexpr (MODE == 1) {
             // target entry (this lane, register RR): the workgroup's table in LDS, or (SEG) the row's chunk's in global memory
             const float *__restrict__ tg = SEG ? seg_target_chunk(target, row / seg_rows, x_seg_stride<LOG2N>()) + lane * S1 : nullptr;
@@ -3969,7 +3379,6 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
             // its way without a second set of registers.
             // (a wavefront's last row has no successor: it re-reads row 0, which every wavefront of the launch then finds in
             // L2 - loads under `if (more)` cost the compiler its register allocation)
-#if SOTS_X_SADDR
             // the next row's address as a uniform base (scalar registers: audio + row offset) plus the lane's byte offset, instead
             // of the loop-invariant 64-bit pointer audio + lane offset plus a uniform row offset: with the pair split that pointer
             // was the one value too many for the 128 registers (an 8-byte spill, reloaded once per row; 130 against 127 us)
@@ -3981,49 +3390,26 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
             typedef const __attribute__((address_space(1))) char *x_gptr_t; // global, not generic: global_load, not flat_load
             const x_gptr_t in_next_base = (x_gptr_t)(((uint64_t)in_next_hi << 32) | (uint64_t)in_next_lo);
             const uint32_t lane_bytes = lane * 8u;
-#else
-            const float2 *__restrict__ in_next = reinterpret_cast<const float2 *>(audio + (size_t)(more ? nxt : 0u) * pitch);
-#endif
             static_for<0, E>([&](auto r_tag) {
                 constexpr int RR = decltype(r_tag)::value, Q = x_bitrev(RR, EB), R2 = Q == 0 ? 0 : x_bitrev(E - Q, EB);
                 if constexpr (R2 >= RR) {
-#if SOTS_X_PAIR_SPLIT
                     if constexpr (R2 != RR) {
                         v2f_t xa, xb;
                         pair2x(ic<RR>{}, xa, xb);
-                        acc += bin_error_w<OBJ, WGT>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps, u_at(RR));
-                        acc += bin_error_w<OBJ, WGT>(make_float2(xb.x, xb.y), tgt_at(R2), half_scale, floor_eps, u_at(R2)); // the partner lane's bin M - k: x_target_bin
+                        acc += bin_error<OBJ, WGT>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps, u_at(RR));
+                        acc += bin_error<OBJ, WGT>(make_float2(xb.x, xb.y), tgt_at(R2), half_scale, floor_eps, u_at(R2)); // the partner lane's bin M - k: x_target_bin
                     } else {
                         const v2f_t xa = bin2x(ic<RR>{});
-                        acc += bin_error_w<OBJ, WGT>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps, u_at(RR));
+                        acc += bin_error<OBJ, WGT>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps, u_at(RR));
                     }
-#else
-                    const v2f_t xa = bin2x(ic<RR>{});
-                    acc += bin_error_w<OBJ, WGT>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps, u_at(RR));
-                    if constexpr (R2 != RR) {
-                        const v2f_t xb = bin2x(ic<R2>{});
-                        acc += bin_error_w<OBJ, WGT>(make_float2(xb.x, xb.y), tgt_at(R2), half_scale, floor_eps, u_at(R2));
-                    }
-#endif
-#ifndef SOTS_X_RECYCLE
-#define SOTS_X_RECYCLE 1
-#endif
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (SOTS_X_RECYCLE != 0) {
-#if SOTS_X_SADDR
-                        typedef const __attribute__((address_space(1))) v2f_t *x_gv2_t;
-                        x[RR] = __builtin_nontemporal_load((x_gv2_t)(in_next_base + (lane_bytes + 8u * kWave * RR)));
-                        if constexpr (R2 != RR) x[R2] = __builtin_nontemporal_load((x_gv2_t)(in_next_base + (lane_bytes + 8u * kWave * R2)));
-#else
-                        x[RR] = x_row_load(in_next + lane + kWave * RR);
-                        if constexpr (R2 != RR) x[R2] = x_row_load(in_next + lane + kWave * R2);
-#endif
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
+                    typedef const __attribute__((address_space(1))) v2f_t *x_gv2_t;
+                    x[RR] = __builtin_nontemporal_load((x_gv2_t)(in_next_base + (lane_bytes + 8u * kWave * RR)));
+                    if constexpr (R2 != RR) x[R2] = __builtin_nontemporal_load((x_gv2_t)(in_next_base + (lane_bytes + 8u * kWave * R2)));
+                    __builtin_amdgcn_sched_barrier(0);
                 }
             });
         } else
-#if SOTS_X_PAIR_SPLIT
         static_for<0, E>([&](auto r_tag) { // MODE 0, the fused kernel's pairs: the same values, written where they belong
             constexpr int RR = decltype(r_tag)::value, Q = x_bitrev(RR, EB), R2 = Q == 0 ? 0 : x_bitrev(E - Q, EB);
             if constexpr (R2 >= RR) {
@@ -4041,27 +3427,6 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
             }
             if constexpr (RR % 4 == 3) __builtin_amdgcn_sched_barrier(0);
         });
-#else
-        static_for<0, E>([&](auto i_tag) {
-            // MODE 0 walks the bins in order
-            constexpr int I = decltype(i_tag)::value, RR = MODE == 0 ? x_bitrev(I, EB) : I;
-            constexpr int Q = x_bitrev(RR, EB), R2 = Q == 0 ? 0 : x_bitrev(E - Q, EB);
-            const int addr = Q == 0 ? addr_zero : addr_flip;
-            const v2f_t zm = v2f_t{__int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(x[R2].x))),
-                                   __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(x[R2].y)))};
-            const v2f_t w = xv(tws_s[lane * S2 + RR]);
-            // 2 X[k] = (Z[k] + conj Z[M-k]) + W_N^k (-i) (Z[k] - conj Z[M-k])
-            const v2f_t ee = xc_add_conj(x[RR], zm), dd = xc_sub_conj(x[RR], zm);
-            const v2f_t x2 = ee + xc_mul_negi_w(dd, w);
-            if constexpr (MODE == 0) {
-                if constexpr (Q % 2 == 0) out_even = x2 * v2f_t{0.5f, 0.5f};
-                else *reinterpret_cast<float4 *>(dst + Q - 1) = make_float4(out_even.x, out_even.y, 0.5f * x2.x, 0.5f * x2.y);
-            } else {
-                acc += bin_error_w<OBJ, WGT>(make_float2(x2.x, x2.y), tgt_s[lane * S1 + RR], half_scale, floor_eps, WGT ? wgt_u[lane * S1 + RR] : 0.0f);
-            }
-            if constexpr (I % 4 == 3) __builtin_amdgcn_sched_barrier(0);
-        });
-#endif
         if constexpr (MODE == 0) {
             // the Nyquist bin X[M] = Re Z0 - Im Z0, from Z0 itself: lane 0 still holds it in register 0
             if (lane == 0) reinterpret_cast<float2 *>(spectrum + (size_t)row * (N + 8))[M] = make_float2(x[0].x - x[0].y, 0.0f);
@@ -4078,7 +3443,7 @@ __global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MI
         }
 #endif
         if (!more) break;
-        if constexpr (MODE == 0 || SOTS_X_RECYCLE == 0) { // (MODE 1 has asked for the row already, pair by pair)
+        if constexpr (MODE == 0) { // (MODE 1 has asked for the row already, pair by pair)
             const float2 *__restrict__ in = reinterpret_cast<const float2 *>(audio + (size_t)nxt * pitch);
             static_for<0, E>([&](auto j_tag) { x[decltype(j_tag)::value] = x_row_load(in + lane + kWave * decltype(j_tag)::value); });
         }
@@ -4120,8 +3485,8 @@ __global__ __launch_bounds__(kBigThreads) void k_fft_big(const float *__restrict
 {
     static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0) && ((OBJ == kObjMagnitude && !WGT) || MODE == 1), "the log instantiation (fitness epilogue only) takes the floor, the weighted one its table");
     static_assert(!WGT || WIN, "the weighted forms exist with a window only");
-    [[maybe_unused]] const float floor_eps = obj_floor(floor...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(floor...);
+    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, floor...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, floor...);
     constexpr uint32_t N = 1u << LOG2N, M = N / 2, LM = LOG2N - 1, T = kBigThreads;
     extern __shared__ float2 big_z[]; // M complex points (the launch asks for M * 8 + 64 bytes)
     float *__restrict__ red = reinterpret_cast<float *>(big_z + M);
@@ -4165,7 +3530,7 @@ __global__ __launch_bounds__(kBigThreads) void k_fft_big(const float *__restrict
         } else {
             float acc = 0.0f;
             const float *__restrict__ tg = SEG ? seg_target_chunk(target, row / seg_target_rows(target), M) : target;
-            for (uint32_t k = t; k < M; k += T) acc += bin_error_w<OBJ, WGT>(bin(k), tg[k], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f);
+            for (uint32_t k = t; k < M; k += T) acc += bin_error<OBJ, WGT>(bin(k), tg[k], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f);
             const float total = big_block_sum(acc, red);
             if (t == 0) fitness[row] = total;
         }
@@ -4178,14 +3543,14 @@ __global__ __launch_bounds__(kBigThreads) void k_fitness_big(const float *__rest
                                                              float *__restrict__ fitness, uint32_t p_len, float inv_n, float inv_wf, FLOOR... floor)
 {
     static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the log instantiation takes the floor, the weighted one its table");
-    [[maybe_unused]] const float floor_eps = obj_floor(floor...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(floor...);
+    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, floor...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, floor...);
     constexpr uint32_t N = 1u << LOG2N, M = N / 2, T = kBigThreads;
     __shared__ float red[kBigThreads / kWave];
     for (uint32_t row = blockIdx.x; row < p_len; row += gridDim.x) {
         const float2 *__restrict__ src = reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8));
         float acc = 0.0f;
-        for (uint32_t k = threadIdx.x; k < M; k += T) acc += bin_error_w<OBJ, WGT>(src[k], target[k], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f);
+        for (uint32_t k = threadIdx.x; k < M; k += T) acc += bin_error<OBJ, WGT>(src[k], target[k], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f);
         const float total = big_block_sum(acc, red);
         if (threadIdx.x == 0) fitness[row] = total;
         __syncthreads();
@@ -4198,8 +3563,8 @@ __global__ __launch_bounds__(x_waves<LOG2N>() * kWave) void k_fitness_x(const fl
                                                                        float *__restrict__ fitness, uint32_t p_len, float inv_n, float inv_wf, FLOOR... floor)
 {
     static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the log instantiation takes the floor, the weighted one its table");
-    [[maybe_unused]] const float floor_eps = obj_floor(floor...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = obj_weights(floor...);
+    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, floor...);
+    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, floor...);
     constexpr int N = 1 << LOG2N, E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), W = x_waves<LOG2N>();
     const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const uint32_t pp = __brev(lane) >> 26;
@@ -4215,28 +3580,20 @@ __global__ __launch_bounds__(x_waves<LOG2N>() * kWave) void k_fitness_x(const fl
                 const int q = x_bitrev(rr, EB), r2 = q == 0 ? 0 : x_bitrev(E - q, EB);
                 if (r2 < rr) continue;
                 const int k = E * pp + q;
-                acc += bin_error_w<OBJ, true>(bins[k], target[k], inv_n * inv_wf, floor_eps, wgt_u[k]);
+                acc += bin_error<OBJ, true>(bins[k], target[k], inv_n * inv_wf, floor_eps, wgt_u[k]);
                 if (r2 != rr) {
-#if SOTS_X_PAIR_SPLIT
                     const int k2 = N / 2 - k;
-#else
-                    const int k2 = E * pp + x_bitrev(r2, EB);
-#endif
-                    acc += bin_error_w<OBJ, true>(bins[k2], target[k2], inv_n * inv_wf, floor_eps, wgt_u[k2]);
+                    acc += bin_error<OBJ, true>(bins[k2], target[k2], inv_n * inv_wf, floor_eps, wgt_u[k2]);
                 }
             }
         } else
         static_for<0, E>([&](auto r_tag) { // k_fft_x's order: register pairs (RR, R2 = bitrev(E - bitrev(RR)))
             constexpr int RR = decltype(r_tag)::value, Q = x_bitrev(RR, EB), R2 = Q == 0 ? 0 : x_bitrev(E - Q, EB);
             if constexpr (R2 >= RR) {
-                acc += bin_error_w<OBJ, WGT>(src[Q], target[E * pp + Q], inv_n * inv_wf, floor_eps, WGT ? wgt_u[E * pp + Q] : 0.0f);
-#if SOTS_X_PAIR_SPLIT
+                acc += bin_error<OBJ, WGT>(src[Q], target[E * pp + Q], inv_n * inv_wf, floor_eps, WGT ? wgt_u[E * pp + Q] : 0.0f);
                 // the pair's second bin is the PARTNER lane's: M - k (k_fft_x's pair2x)
                 if constexpr (R2 != RR)
-                    acc += bin_error_w<OBJ, WGT>(reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8))[N / 2 - (E * pp + Q)], target[N / 2 - (E * pp + Q)], inv_n * inv_wf, floor_eps, WGT ? wgt_u[N / 2 - (E * pp + Q)] : 0.0f);
-#else
-                if constexpr (R2 != RR) acc += bin_error_w<OBJ, WGT>(src[x_bitrev(R2, EB)], target[E * pp + x_bitrev(R2, EB)], inv_n * inv_wf, floor_eps, WGT ? wgt_u[E * pp + x_bitrev(R2, EB)] : 0.0f);
-#endif
+                    acc += bin_error<OBJ, WGT>(reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8))[N / 2 - (E * pp + Q)], target[N / 2 - (E * pp + Q)], inv_n * inv_wf, floor_eps, WGT ? wgt_u[N / 2 - (E * pp + Q)] : 0.0f);
             }
         });
         acc = wave_sum(acc);

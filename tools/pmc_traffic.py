@@ -1,6 +1,7 @@
 """profiles/pmc_traffic.json (HBM bytes per launch of each fused-loop kernel, keyed by workload) from a
 pmc_summary.json of tools/pmc_collect.sh:
     python tools/pmc_traffic.py <pmc_summary.json> <workload key, e.g. P65536_N1024_2op> [round tag]"""
+import glob
 import hashlib
 import json
 import os
@@ -25,8 +26,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "survival_of_the_synthesis-gpu_accelerated_frequency_modulation_parameter_matcher_amd"
 # bench.py reports these figures only while the kernel source is the one they were collected on
 sha16 = hashlib.sha256(open(os.path.join(ROOT, PKG, "csrc", "sots_kernels.hip"), "rb").read()).hexdigest()[:16]
+# ... but kernel families are moving into csrc/kernels/*.h, which that hash does not see.  One hash over all of them, the
+# translation unit first and the family files by name (what a staleness guard should compare; bench.py still reads the key above)
+tree = hashlib.sha256()
+for src in [os.path.join(ROOT, PKG, "csrc", "sots_kernels.hip")] + sorted(glob.glob(os.path.join(ROOT, PKG, "csrc", "kernels", "*.h"))):
+    tree.update(open(src, "rb").read())
 entry = {"_round": tag,
          "kernels_sha16": sha16,
+         "kernel_tree_sha16": tree.hexdigest()[:16],
          "synthesise": round(nbytes(pick("k_synth"))),
          "window+FFT+fitness": round(nbytes(pick("k_fft"))),
          "recombine+mutate": round(nbytes("k_recombine_mutate")) if "k_recombine_mutate" in d else None,

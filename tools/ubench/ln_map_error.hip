@@ -1,5 +1,5 @@
 // Diagnostic measurement (not part of the product): the absolute error of the log objective's map ln(m + floor) as the
-// spectral kernels compute it (obj_ln_floor, csrc/sots_kernels.hip: v_log_f32 of the fp32 sum, times ln 2 in fp32)
+// spectral kernels compute it (obj_ln_floor, csrc/kernels/objective.h: v_log_f32 of the fp32 sum, times ln 2 in fp32)
 // against libm's fp64 log of the exact sum, for magnitudes m in [0, 2 - floor] - arguments in [floor, 2].  The expression
 // below is that routine's, compiled with the library's -ffp-contract=off.  Every `stride`-th fp32 value of the range is
 // visited; the maximum is reported per floor, with the argument it occurred at.  DESIGN.md 4.6 quotes the result.
