@@ -1537,6 +1537,30 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
     const uint32_t grid = gridDim.x;
     uint32_t ind = blockIdx.x + wave * grid;
     if (W == 1 && ind >= p_len) return;
+    // Three row buffers rotate (no copies): two rows are in flight beside the one being
+    // transformed - a row's transform is shorter than the loaded memory latency, and the registers
+    // are there (168 = three wavefronts per SIMD).
+    constexpr int Q = E / 2; // rows are read 16 bytes per lane: pair index lane + 64 h holds complex points 2(lane+64h), +1
+    auto request = [&](float4 (&dst)[Q], uint32_t r) { // rows past the end re-read the current one
+        const float4 *__restrict__ in = reinterpret_cast<const float4 *>(audio + (size_t)(r < p_len ? r : ind) * pitch);
+#pragma unroll
+        for (int h = 0; h < Q; ++h) dst[h] = SOTS_ROW_LOAD(in + lane + kWave * h);
+    };
+    // The first two rows are asked for BEFORE the tables below: they need nothing but ind, p_len and pitch, and the
+    // memory side then moves rows while the tables arrive.  What this buys is limited: loads return in order, so the
+    // wait of the target's copy into LDS in front of the barrier (vmcnt(0)) now also waits for both rows - the barrier
+    // stands behind the row latency instead of the row requests behind the barrier - and window and twiddles are still a
+    // round trip of their own behind it.  Every table load stands behind the requests in the queue and is used before
+    // the first row is, so the loop's waits still count row loads only.  A wavefront whose first row lies past the end
+    // returns behind the barrier with two requests in flight: harmless, they read the workgroup's own first row
+    // (blockIdx.x < p_len: no more workgroups than rows).
+    float4 b0[Q], b1[Q], b2[Q];
+    uint32_t r0 = ind, r1 = blockIdx.x + (W + wave) * grid, r2; // the rows in the three buffers
+    const uint32_t first = ind < p_len ? ind : blockIdx.x;
+    request(b0, first);
+    asm volatile("" ::: "memory"); // keep the two requests in this order (the loop's waits count on it)
+    request(b1, r1 < p_len ? r1 : first);
+    asm volatile("" ::: "memory"); // ... and the tables behind them
     if (threadIdx.x == 0) next_s = 2 * W;
 
     // per-lane constants of the split / fitness step, loaded once (nothing but the audio
@@ -1564,8 +1588,6 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
     if constexpr (MODE == 1 || W > 1) __syncthreads(); // (the only workgroup barrier: target, row counter and bounds are there)
     if (ind >= p_len) return;
 
-    // rows are read 16 bytes per lane: pair index lane + 64 h holds complex points 2(lane+64h), +1
-    constexpr int Q = E / 2;
     float4 wv[WIN ? Q : 1];
     if constexpr (WIN) {
 #pragma unroll
@@ -1573,14 +1595,6 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
     }
     float2 twr[tw_count<M>()];
     preload_twiddles<M>(twr, tw, lane);
-    // Three row buffers rotate (no copies): two rows are in flight beside the one being
-    // transformed - a row's transform is shorter than the loaded memory latency, and the registers
-    // are there (168 = three wavefronts per SIMD).
-    auto request = [&](float4 (&dst)[Q], uint32_t r) { // rows past the end re-read the current one
-        const float4 *__restrict__ in = reinterpret_cast<const float4 *>(audio + (size_t)(r < p_len ? r : ind) * pitch);
-#pragma unroll
-        for (int h = 0; h < Q; ++h) dst[h] = SOTS_ROW_LOAD(in + lane + kWave * h);
-    };
     // transforms the row in `cur` (individual `ind`) after requesting row ind + 2 grid into `fill`
 #ifdef SOTS_STAMP
     unsigned long long st_wait = 0, st_fft = 0, st_tail = 0, st_rows = 0;
@@ -1695,11 +1709,6 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
 #endif
         return filled;
     };
-    float4 b0[Q], b1[Q], b2[Q];
-    uint32_t r0 = ind, r1 = blockIdx.x + (W + wave) * grid, r2; // the rows in the three buffers
-    request(b0, r0);
-    asm volatile("" ::: "memory"); // keep the two requests in this order (the loop's waits count on it)
-    request(b1, r1);
     while (true) { // (takes only grow: a wavefront whose next row is past the end has no later one either)
         ind = r0, r2 = process(b0, b2);
         if (r1 >= p_len) break;
