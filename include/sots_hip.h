@@ -551,7 +551,7 @@ typedef struct sots_chunk_result {            /* 208 bytes */
 } sots_chunk_result;
 typedef struct sots_queue_stats {
     uint32_t struct_size;                     /* = sizeof(sots_queue_stats), set by the caller */
-    uint32_t slots;                           /* min(max_chunks, num_chunks) */
+    uint32_t slots;                           /* min(max_chunks, num_chunks); with carried rows min(max_chunks, segments) */
     uint64_t global_generations;              /* generations the batch loop ran until the last chunk retired */
     uint64_t chunk_generations;               /* sum of generations_run */
 } sots_queue_stats;
@@ -575,6 +575,33 @@ int sots_batch_queue_targets_audio_hop(sots_batch *b, const float *audio, uint64
  * can be run again.  stats may be NULL. */
 int sots_batch_queue_run(sots_batch *b, uint32_t first_chunk_index, uint32_t max_generations, const sots_stop_rule *rule,
                          uint32_t keep_chunk, sots_queue_stats *stats);
+/* Carried rows (new): a setting {carry_rows R, segment_chunks L} of the batch that sots_batch_queue_run
+ * alone reads.  The M queued chunks are cut into segments of L consecutive chunks, segment g = chunks [g L, min((g+1) L, M)).
+ * Chunk k with k % L != 0 is a SUCCESSOR: it starts in the slot in which chunk k-1 has just been retired, in the same
+ * launch, from this population:
+ *   row 0          values and steps of chunk k-1's best-ever record, as its result holds them;
+ *   rows 1..R-1    values and steps of rows 1..R-1 of chunk k-1's current (sorted) half as it was when retired;
+ *   rows R..P-1    exactly what sots_init_population(first_chunk_index + k) draws for those rows;
+ *   every fitness 0, the record cleared, the counter 0, the target chunk k's - all as without carrying.
+ * A segment's first chunk (k % L == 0) starts exactly as without carrying.  A free slot draws the next unstarted SEGMENT;
+ * S = min(max_chunks, ceil(M / L)) slots run, slot c starting with chunk c L, and sots_queue_stats.slots reports that S.
+ * Chunk k's result depends on its predecessors in its segment only - not on the slot, on max_chunks or on when the
+ * segment started.  It is bit for bit what a tracked sots_ctx with the same survivors setting reports from
+ *     if (k % L) { (pv, ps) = sots_read_population; (bv, bs) = sots_read_best_ever; }          state left by chunk k-1
+ *     sots_set_target_spectrum(target k); sots_init_population(first_chunk_index + k);
+ *     if (k % L) { (v, s) = sots_read_population; v[0..R-1] = pv[0..R-1]; s[0..R-1] = ps[0..R-1]; v[0] = bv; s[0] = bs;
+ *                  sots_write_population(v, s, no fitness); }
+ *     sots_execute_until(max_generations, rule)
+ * carry_rows 0 (the default) turns it off: segment_chunks is ignored and reported as 0, and a run enqueues the launches
+ * and computes the bits it always did.  Otherwise 1 <= carry_rows <= numParents (recombination reads parent rows only: R
+ * chooses how many of the first generation's parents are carried and how many are fresh) and segment_chunks >= 1 (1: no
+ * chunk is a successor; larger than M: one segment); anything else is SOTS_ERR_INVALID and the old setting stays.
+ * Without survivors the carried rows are only ingredients of the first recombination: use it with
+ * sots_batch_set_survivors >= 1.  Targets, objective, weights, survivors and runs keep the setting;
+ * sots_batch_execute_* ignores it.  With it the loop generations are bounded by segments of min(L, M) chunks:
+ * ((ceil(M / L) - 1) / S + 2) L max_generations with a rule, ceil(ceil(M / L) / S) L max_generations without. */
+int sots_batch_queue_set_carry(sots_batch *b, uint32_t carry_rows, uint32_t segment_chunks);
+int sots_batch_queue_get_carry(const sots_batch *b, uint32_t *carry_rows, uint32_t *segment_chunks);
 /* the results of the last run, chunk 0 first: *written = min(num_chunks, capacity).  SOTS_ERR_STATE before a run.  Blocking. */
 int sots_batch_queue_results(sots_batch *b, sots_chunk_result *out, uint32_t capacity, uint32_t *written);
 /* the kept chunk's population; pointers and byte counts as sots_read_population.  SOTS_ERR_STATE when the last run kept none. */

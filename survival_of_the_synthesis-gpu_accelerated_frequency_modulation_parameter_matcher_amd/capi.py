@@ -70,6 +70,7 @@ EXPORTS = [
     "sots_group_set_objective_weights",
     "sots_render_overlap_add", "sots_batch_set_target_audio_hop", "sots_batch_queue_targets_audio_hop",
     "sots_render_continuous",
+    "sots_batch_queue_set_carry", "sots_batch_queue_get_carry",
 ]
 QUEUE_NO_CHUNK = 0xFFFFFFFF
 RENDER_WINDOWED = 1
@@ -283,6 +284,8 @@ def load():
     L.sots_render_continuous.argtypes = [vp, vp, sz, u32, C.POINTER(RenderContinuousArgs), vp, C.c_uint64]
     L.sots_batch_set_target_audio_hop.argtypes = [vp, vp, u32, u32, u32]
     L.sots_batch_queue_targets_audio_hop.argtypes = [vp, vp, C.c_uint64, u32, u32]
+    L.sots_batch_queue_set_carry.argtypes = [vp, u32, u32]
+    L.sots_batch_queue_get_carry.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
     _lib = L
     return L
 
@@ -830,6 +833,18 @@ class HipBatch:
         self._check(self.L.sots_batch_queue_results(self._h, _ptr(out), out.size, C.byref(n)))
         return out[:n.value], {"slots": stats.slots, "global_generations": stats.global_generations,
                                "chunk_generations": stats.chunk_generations}
+
+    def queue_set_carry(self, carry_rows, segment_chunks=0):
+        """queue_run only: the queued chunks are cut into segments of segment_chunks, and inside a segment a chunk starts
+        from its predecessor's best-ever record (row 0) and rows 1..carry_rows-1, beside fresh rows.  carry_rows 0: off.
+        Use it with set_survivors(>= 1)."""
+        self._check(self.L.sots_batch_queue_set_carry(self._h, carry_rows, segment_chunks))
+
+    def queue_carry(self):
+        """(carry_rows, segment_chunks); (0, 0) when off"""
+        r, l = C.c_uint32(), C.c_uint32()
+        self._check(self.L.sots_batch_queue_get_carry(self._h, C.byref(r), C.byref(l)))
+        return r.value, l.value
 
     def queue_kept_population(self):
         v = np.empty((self.P, self.D), np.float32)

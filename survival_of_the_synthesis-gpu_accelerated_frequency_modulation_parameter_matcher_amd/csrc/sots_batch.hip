@@ -52,6 +52,8 @@ struct sots_batch : sots::Engine {
     uint32_t *q_state = nullptr;     // {head, retired, last retirement, 0} and the slot table [max_chunks][2] behind them
     uint32_t *q_pinned = nullptr;    // host uint32[2][4]: the loop's look at q_state, one per block in flight
     hipEvent_t q_event[2] = {nullptr, nullptr};
+    // carried rows (sots_batch_queue_set_carry): a setting of the handle, kept over targets and runs.  0, 0: off
+    uint32_t q_carry_rows = 0, q_segment_chunks = 0;
 
     size_t rows() const { return (size_t)max_chunks * P; }
     float *val(uint32_t half) const { return values + (size_t)half * rows() * D; }
@@ -491,30 +493,46 @@ int sots_batch_queue_run(sots_batch *b, uint32_t first_chunk_index, uint32_t max
     if (b->track.history())
         return SOTS_FAIL(b, SOTS_ERR_STATE, "sots_batch_queue_run keeps no per-slot history: call sots_batch_track without SOTS_TRACK_HISTORY");
     if (b->q_chunks == 0) return SOTS_FAIL(b, SOTS_ERR_STATE, "no queue: call sots_batch_queue_targets_audio or sots_batch_queue_targets_spectra first");
-    const uint32_t chunks = b->q_chunks, slots = chunks < b->max_chunks ? chunks : b->max_chunks;
+    // carry off: every chunk a segment of its own, and everything below is what it always was
+    const QueuePlan plan = queue_plan(b->q_chunks, b->max_chunks, b->q_carry_rows, b->q_segment_chunks);
+    const bool carry = b->q_carry_rows != 0;
+    const uint32_t chunks = b->q_chunks, slots = plan.slots;
     if (keep_chunk != SOTS_QUEUE_NO_CHUNK && keep_chunk >= chunks)
         return SOTS_FAIL(b, SOTS_ERR_INVALID, "sots_batch_queue_run: keep_chunk %u not in 0..%u", keep_chunk, chunks - 1);
-    // No chunk runs longer than max_generations, so the last one retires within `bound` loop generations: without a rule
-    // every slot turns over together and the loop below enqueues exactly that many.
-    const uint64_t waves = ((uint64_t)chunks + slots - 1) / slots;
-    const uint64_t bound = rule ? ((uint64_t)(chunks - 1) / slots + 2) * max_generations : waves * max_generations;
+    // No chunk runs longer than max_generations, so the last one retires within `bound` loop generations (queue_loop_bound):
+    // without a rule every slot turns over together and the loop below enqueues exactly that many.
+    const uint64_t bound = queue_loop_bound(plan, max_generations, rule != nullptr);
     if (bound > 0xFFFFFFFFull) // (the loop generation is a 32-bit kernel argument)
         return SOTS_FAIL(b, SOTS_ERR_INVALID, "sots_batch_queue_run: %u chunks of up to %u generations in %u slots exceed 2^32 loop generations", chunks,
                      max_generations, slots);
     if (int rc = engine_bind(*b)) return rc;
 
     // the slots start with chunks 0..slots-1, exactly as sots_batch_set_target_spectra + sots_batch_init_population start them
+    // (a carry run: slot c with chunk c * segment, the first of segment c; the head then counts segments)
     b->active = 0; // whatever happens from here on, the ordinary calls need their targets again
     b->q_ran = b->q_kept = false;
     std::vector<uint32_t> start(4 + 2 * (size_t)slots, 0u);
     start[0] = slots;
-    for (uint32_t c = 0; c < slots; ++c) start[4 + 2 * c] = c;
+    for (uint32_t c = 0; c < slots; ++c) start[4 + 2 * c] = c * plan.segment;
     SOTS_HIP(b, hipMemcpyAsync(b->q_state, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, b->stream));
-    SOTS_HIP(b, launch_seg_targets(b->stream, b->seg_image, queue_targets(b), b->log2n, slots));
+    if (!carry) {
+        SOTS_HIP(b, launch_seg_targets(b->stream, b->seg_image, queue_targets(b), b->log2n, slots));
+    } else { // one slot per launch: slot c's table from chunk c * segment's target (outside the loop: its cost does not matter)
+        const size_t stride = seg_target_stride(b->log2n), half = b->N / 2;
+        for (uint32_t c = 0; c < slots; ++c)
+            SOTS_HIP(b, launch_seg_targets(b->stream, b->seg_image + (size_t)c * stride, queue_targets(b) + (size_t)c * plan.segment * half, b->log2n, 1));
+    }
     SOTS_HIP(b, track_clear(b->track, b->stream));
     b->rot = 0;
     b->generation = 0;
-    SOTS_HIP(b, launch_init_population_seg(b->stream, b->val(0), b->stp(0), b->fit(0), b->pd, first_chunk_index, slots));
+    if (!carry) {
+        SOTS_HIP(b, launch_init_population_seg(b->stream, b->val(0), b->stp(0), b->fit(0), b->pd, first_chunk_index, slots));
+    } else {
+        const size_t pop = (size_t)b->P * b->D;
+        for (uint32_t c = 0; c < slots; ++c)
+            SOTS_HIP(b, launch_init_population_seg(b->stream, b->val(0) + c * pop, b->stp(0) + c * pop, b->fit(0) + (size_t)c * b->P, b->pd,
+                                                   first_chunk_index + c * plan.segment, 1));
+    }
     SOTS_HIP(b, hipStreamSynchronize(b->stream)); // `start` leaves scope; the loop below starts from an empty stream
 
     QueueArgs q{};
@@ -535,6 +553,9 @@ int sots_batch_queue_run(sots_batch *b, uint32_t first_chunk_index, uint32_t max
     q.stall_generations = rule ? rule->stall_generations : 0u;
     q.x_log2n = queue_x_log2n(b->log2n);
     q.half_bins = b->N / 2;
+    q.carry_rows = b->q_carry_rows;
+    q.segment_chunks = carry ? plan.segment : 0u;
+    q.num_segments = carry ? plan.segments : 0u;
 
     // Blocks of check_interval generations; after each the queue's counters come back through a small asynchronous copy
     // to pinned memory.  The host waits for the copy of the block BEFORE the one it has just enqueued, so the device never
@@ -581,6 +602,24 @@ int sots_batch_queue_run(sots_batch *b, uint32_t first_chunk_index, uint32_t max
         stats->global_generations = seen[2];
         for (uint32_t r : run) stats->chunk_generations += r;
     }
+    return SOTS_OK;
+}
+
+int sots_batch_queue_set_carry(sots_batch *b, uint32_t carry_rows, uint32_t segment_chunks)
+{
+    BATCH_REQUIRE(b);
+    SOTS_REFUSE(b, queue_carry_check(carry_rows, segment_chunks, b->cfg.num_parents));
+    b->q_carry_rows = carry_rows;
+    b->q_segment_chunks = carry_rows ? segment_chunks : 0u;
+    return SOTS_OK;
+}
+
+int sots_batch_queue_get_carry(const sots_batch *b, uint32_t *carry_rows, uint32_t *segment_chunks)
+{
+    BATCH_REQUIRE(b);
+    if (!carry_rows || !segment_chunks) return SOTS_FAIL(b, SOTS_ERR_INVALID, "sots_batch_queue_get_carry: null pointer");
+    *carry_rows = b->q_carry_rows;
+    *segment_chunks = b->q_segment_chunks;
     return SOTS_OK;
 }
 

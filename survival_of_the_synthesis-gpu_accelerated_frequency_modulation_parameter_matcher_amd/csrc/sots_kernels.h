@@ -275,13 +275,18 @@ struct QueueArgs {
     uint32_t stall_generations;
     uint32_t x_log2n;   // queue_x_log2n(): log2 N where the image holds k_fft_x's tables, 0 where it holds the N/2 bins
     uint32_t half_bins; // N/2
+    // carry (sots_batch_queue_set_carry): carry_rows 0 = off, and the two words behind it are not read.  Otherwise 1 <=
+    // carry_rows <= numParents, segment_chunks >= 1, num_segments = ceil(num_chunks / segment_chunks), and state[0] counts
+    // segments: the next unstarted one
+    uint32_t carry_rows, segment_chunks, num_segments;
 };
 uint32_t queue_x_log2n(uint32_t log2n);
 // k_recombine_mutate_seg with the generation of row r's slot read from slot_table
 hipError_t launch_recombine_mutate_queue(hipStream_t st, const float *vin, const float *sin, float *vout, float *sout, const PopDims &pd,
                                          const MutateConsts &mc, const uint32_t *slot_table, uint32_t slots);
 // after a generation's sort, on the half it wrote: the best-ever record of every busy slot (meta, rows: as launch_track) and
-// the turnover of those whose chunk ends here; global_generation = generations the queue loop has run, this one included
+// the turnover of those whose chunk ends here; global_generation = generations the queue loop has run, this one included.
+// q.carry_rows chooses the kernel: 0, the turnover as it always was; otherwise its carry form
 hipError_t launch_queue_turnover(hipStream_t st, float *values, float *steps, float *fitness, const PopDims &pd, uint32_t *meta,
                                  float *rows, const QueueArgs &q, uint32_t global_generation, uint32_t slots);
 

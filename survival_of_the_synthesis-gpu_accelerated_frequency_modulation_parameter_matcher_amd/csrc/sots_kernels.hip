@@ -4808,6 +4808,11 @@ __global__ __launch_bounds__(256) void k_track_clear(uint32_t *__restrict__ meta
 // record cleared, counter zeroed, target table rewritten from the stored targets.  With the queue empty the slot goes idle.
 // values / steps / fitness: the half the sort has just written (the turnover writes the new chunk's rows there: it is the
 // half the next generation's variation reads).
+// CARRY (sots_batch_queue_set_carry): the chunks are cut into segments of q.segment_chunks; the head counts
+// SEGMENTS, and inside a segment the slot takes chunk + 1 without touching it.  Such a successor keeps the retired
+// chunk's rows where they lie: row 0 becomes the best-ever record (the `rec` words threads 0..31 hold), rows 1..R-1 stay
+// as the sort left them, and the refill draws rows R..P-1 only - by local row index, so they are a fresh start's rows.
+// Without CARRY the body is the kernel's as it was before carrying existed.
 // ------------------------------------------------------------------------------------
 template <int LOG2N>
 __device__ __forceinline__ void queue_fill_x_table(float *__restrict__ image, const float *__restrict__ target, uint32_t slot,
@@ -4817,6 +4822,7 @@ __device__ __forceinline__ void queue_fill_x_table(float *__restrict__ image, co
     for (uint32_t le = t; le < (uint32_t)(kWave * x_points<LOG2N>()); le += threads) x_seg_target_entry<LOG2N>(table, target, le);
 }
 
+template <bool CARRY>
 __global__ __launch_bounds__(256) void k_queue_turnover(float *__restrict__ values, float *__restrict__ steps, float *__restrict__ fitness,
                                                         PopDims pd, uint32_t *__restrict__ meta, float *__restrict__ rows, QueueArgs q,
                                                         uint32_t global_generation)
@@ -4873,10 +4879,19 @@ __global__ __launch_bounds__(256) void k_queue_turnover(float *__restrict__ valu
         }
         for (uint32_t e = t; e < p; e += threads) q.kept_fitness[e] = f[e];
     }
+    // a successor: the next chunk of this chunk's segment
+    const bool successor = CARRY && queue_has_successor(chunk, q.segment_chunks, q.num_chunks);
     if (t == 0) {
         atomicAdd(&q.state[1], 1u);                    // retired
         atomicMax(&q.state[2], global_generation);     // the loop generation of the last retirement
-        next_s = atomicAdd(&q.state[0], 1u);           // the queue head: the next unstarted chunk
+        if (!CARRY) {
+            next_s = atomicAdd(&q.state[0], 1u);       // the queue head: the next unstarted chunk
+        } else if (successor) {
+            next_s = chunk + 1u;                       // inside a segment the head is not touched
+        } else {
+            const uint32_t seg = atomicAdd(&q.state[0], 1u); // the queue head: the next unstarted SEGMENT
+            next_s = queue_segment_start(seg, q.segment_chunks, q.num_segments, kQueueNoChunk);
+        }
     }
     __syncthreads(); // the draw is in LDS, and the old rows have been read
     const uint32_t next = next_s;
@@ -4886,7 +4901,16 @@ __global__ __launch_bounds__(256) void k_queue_turnover(float *__restrict__ valu
     }
 
     // ---- refill: k_init_population_seg's draws for chunk first_chunk + next, a cleared record, the target table ----
-    for (uint32_t e = t; e < p * d; e += threads) {
+    uint32_t fresh = 0u; // the first element drawn: a successor's rows 0..R-1 are carried (R <= numParents <= p)
+    if (CARRY && successor) {
+        fresh = q.carry_rows * d;
+        if (t < kTrackRowFloats) { // row 0: the retired chunk's best-ever record
+            const uint32_t j = t % SOTS_MAX_DIMS;
+            if (j < d) (t < SOTS_MAX_DIMS ? v : s)[j] = rec;
+        }
+        for (uint32_t i = t; i < q.carry_rows; i += threads) f[i] = 0.0f;
+    }
+    for (uint32_t e = fresh + t; e < p * d; e += threads) {
         const uint32_t i = e / d, gene = e - i * d;
         const U4 rn = philox4x32_10(pd.gid_base + i, q.first_chunk + next, gene >> 2, kTagInit, pd.seed_lo, pd.seed_hi);
         const float u = draw_unit(u4_at(rn, gene & 3u));
@@ -4929,7 +4953,13 @@ hipError_t launch_queue_turnover(hipStream_t st, float *values, float *steps, fl
                                  float *rows, const QueueArgs &q, uint32_t global_generation, uint32_t slots)
 {
     if (slots == 0 || pd.d == 0 || pd.d > SOTS_MAX_DIMS || q.num_chunks == 0 || q.max_generations == 0) return hipErrorInvalidValue;
-    k_queue_turnover<<<slots, 256, 0, st>>>(values, steps, fitness, pd, meta, rows, q, global_generation);
+    if (q.carry_rows) {
+        // (the kernel trusts these: rows 0..R-1 lie inside the slot's population, and the segment arithmetic neither divides by 0 nor wraps)
+        if (q.carry_rows > pd.p || q.segment_chunks == 0 || q.num_segments != (q.num_chunks - 1u) / q.segment_chunks + 1u) return hipErrorInvalidValue;
+        k_queue_turnover<true><<<slots, 256, 0, st>>>(values, steps, fitness, pd, meta, rows, q, global_generation);
+    } else {
+        k_queue_turnover<false><<<slots, 256, 0, st>>>(values, steps, fitness, pd, meta, rows, q, global_generation);
+    }
     return hipGetLastError();
 }
 

@@ -209,4 +209,43 @@ inline int stop_rule_check(const sots_stop_rule *rule)
     return SOTS_OK;
 }
 
+// ---- chunk queue: carried rows (sots_batch_queue_set_carry) ----
+// rows 0 turns carrying off (the segment length is then ignored); otherwise 1 <= rows <= numParents - recombination reads
+// parent rows only - and segments of at least one chunk
+inline Fault queue_carry_check(uint32_t rows, uint32_t segment, uint32_t num_parents)
+{
+    if (rows == 0) return Fault{};
+    if (rows > num_parents)
+        return fault(SOTS_ERR_INVALID, "sots_batch_queue_set_carry: %u carried rows asked for, at most numParents = %u can be carried", rows, num_parents);
+    if (segment == 0) return fault(SOTS_ERR_INVALID, "sots_batch_queue_set_carry: segment_chunks must be at least 1 with carry_rows %u", rows);
+    return Fault{};
+}
+
+// How a run of `chunks` (>= 1) queued chunks is laid out over a handle of max_chunks (>= 1) slots.  Without carrying
+// (rows 0) every chunk is a segment of its own: segment 1, segments = chunks.  With it a segment never holds more than
+// the whole queue, so the length counts as min(segment, chunks).  Slot c starts with chunk c * segment.
+struct QueuePlan {
+    uint32_t segment, segments, slots;
+};
+inline QueuePlan queue_plan(uint32_t chunks, uint32_t max_chunks, uint32_t carry_rows, uint32_t segment_chunks)
+{
+    QueuePlan p;
+    p.segment = carry_rows == 0 ? 1u : (segment_chunks < chunks ? segment_chunks : chunks);
+    p.segments = (chunks - 1u) / p.segment + 1u;
+    p.slots = p.segments < max_chunks ? p.segments : max_chunks;
+    return p;
+}
+
+// Loop generations within which the last chunk retires.  No chunk runs longer than max_generations, so no segment runs
+// longer than segment * max_generations.  Without a rule every segment but the last takes exactly that and the slots turn
+// over together: ceil(segments / slots) rounds.  With a rule a slot draws its last segment no later than
+// (segments - 1) / slots + 1 full rounds after the start and needs one more to end it.  Saturates at UINT64_MAX.
+inline uint64_t queue_loop_bound(const QueuePlan &p, uint32_t max_generations, bool with_rule)
+{
+    const uint64_t rounds = with_rule ? (uint64_t)(p.segments - 1u) / p.slots + 2u : ((uint64_t)p.segments + p.slots - 1u) / p.slots;
+    const uint64_t per_round = (uint64_t)p.segment * max_generations; // < 2^64
+    if (per_round != 0 && rounds > ~0ull / per_round) return ~0ull;
+    return rounds * per_round;
+}
+
 } // namespace sots

@@ -1,6 +1,6 @@
 // sots_stop_rule.h -- the arithmetic of the stop rules (sots_stop_rule, include/sots_hip.h) in ONE copy for the host
 // (sots_stop_rule_holds, the block loops of sots_execute_until) and for the device (the chunk queue's turnover,
-// k_queue_turnover), and the queue's makespan model.  No HIP header: plain C++ compilers build it too (the sanitizer
+// k_queue_turnover), the turnover's segment arithmetic likewise, and the queue's makespan model.  No HIP header: plain C++ compilers build it too (the sanitizer
 // builds of tests/).  Internal to libsots_hip.so.
 #pragma once
 
@@ -30,6 +30,19 @@ SOTS_HOST_DEVICE inline bool stop_rule_holds(float target_fitness, uint32_t stal
         if (since >= stall_generations) return true;
     }
     return false;
+}
+
+// Carried rows (sots_batch_queue_set_carry): the queue's chunks in segments of `segment` (>= 1) consecutive chunks, the
+// turnover's arithmetic.  Does the slot that retires `chunk` (< num_chunks) go on with chunk + 1, the next of its segment?
+SOTS_HOST_DEVICE inline bool queue_has_successor(uint32_t chunk, uint32_t segment, uint32_t num_chunks)
+{
+    return (chunk + 1u) % segment != 0u && chunk + 1u < num_chunks; // (chunk + 1 <= num_chunks: no wrap)
+}
+// the first chunk of the segment a free slot drew from the head, or `none` where the head has passed the last segment
+// (num_segments = ceil(num_chunks / segment), so seg * segment <= num_chunks - 1: no wrap)
+SOTS_HOST_DEVICE inline uint32_t queue_segment_start(uint32_t seg, uint32_t segment, uint32_t num_segments, uint32_t none)
+{
+    return seg < num_segments ? seg * segment : none;
 }
 
 // The global generations an in-order refill of `slots` slots takes: every slot is free at generation 0, chunk k starts

@@ -93,6 +93,14 @@ struct Evolutionary_Strategy_HIP_Arguments
     // chunk of its batch is done.  Same per-chunk results, same lines printed.  With a historyPath (the slots keep no history
     // rings) today's batch-by-batch path runs.  Off by default: nothing changes.
     bool chunkQueue = false;
+    // Carried rows (type.HIP.{carryRows,segmentChunks}; sots_batch_queue_set_carry), chunk queue only: the
+    // chunks are cut into segments of segmentChunks consecutive chunks, and inside a segment a chunk starts from its
+    // predecessor's best-ever individual (row 0) and rows 1..carryRows-1 beside fresh rows, so that neighbouring rows of the
+    // parameter track describe one voice.  carryRows 0 (default): off, nothing changes.  segmentChunks 0: ceil(chunks /
+    // chunksInFlight), one segment per slot.  Meant for survivors >= 1.  Where the queue does not run (chunksInFlight 1,
+    // numDevices > 1, populationLength > 1024) parameterMatchAudio throws rather than match without carrying.
+    uint32_t carryRows = 0;
+    uint32_t segmentChunks = 0;
     // Elitist survival (type.HIP.survivors; sots_set_survivors): rows 0..survivors-1 of the sorted population pass through
     // recombination and mutation unchanged and are evaluated again with the offspring.  0 (default) is the reference's
     // strategy; at most numParents, above that the constructor / parameterMatchAudio throws with the library's text.
@@ -503,6 +511,9 @@ public:
         const bool queued = batched && args_.chunkQueue && !historyFile_ && numGenerations > 0 && numChunks_ > 0;
         if (batched && args_.chunkQueue && historyFile_ && args_.verbose)
             printf("chunkQueue: a history file is written, matching batch by batch\n");
+        if (args_.carryRows && !queued)
+            throw std::runtime_error("Evolutionary_Strategy_HIP: carryRows needs the chunk queue (chunkQueue, chunksInFlight > 1, one device, "
+                                     "populationLength <= 1024, no history file)");
         if (queued) {
             matchChunkQueue(aTargetAudio);
         } else if (batched) {
@@ -591,6 +602,9 @@ private:
         if (!objectiveWeights_.empty())
             checkBatch(sots_batch_set_objective_weights(batch_, objectiveWeights_.data(), (uint32_t)objectiveWeights_.size()), "sots_batch_set_objective_weights");
         checkBatch(sots_batch_track(batch_, SOTS_TRACK_BEST_EVER, 0, 0), "sots_batch_track"); // (the queue keeps the best-ever record itself)
+        const uint32_t segment = !args_.carryRows ? 0u : args_.segmentChunks ? args_.segmentChunks : (numChunks_ + args_.chunksInFlight - 1u) / args_.chunksInFlight;
+        checkBatch(sots_batch_queue_set_carry(batch_, args_.carryRows, segment), "sots_batch_queue_set_carry");
+        if (args_.carryRows && args_.verbose) printf("Carried rows: %u, in segments of %u chunks\n", args_.carryRows, segment);
         std::vector<float> mags((size_t)numChunks_ * half);
         for (uint32_t c = 0; c < numChunks_; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)hop_ * c], mags.data() + (size_t)c * half);
         checkBatch(sots_batch_queue_targets_spectra(batch_, mags.data(), (uint64_t)mags.size(), numChunks_), "sots_batch_queue_targets_spectra");

@@ -213,4 +213,37 @@ inline bool readRenderModeKey(const Json &h, uint32_t &renderMode)
                              (v.kind == Json::String ? ", not \"" + v.str + "\"" : std::string()));
 }
 
+// type.HIP.carryRows / type.HIP.segmentChunks (sots_batch_queue_set_carry): inside a segment of
+// segmentChunks consecutive chunks a chunk starts from its predecessor's best-ever individual and rows 1..carryRows-1, beside
+// fresh rows.  carryRows absent or 0: off, and segmentChunks is not looked at.  segmentChunks absent (left 0 here): the
+// matcher takes ceil(chunks / chunksInFlight), one segment per slot.  Returns whether carrying is on; throws - like the keys
+// above, before any device work - on carryRows that is no whole number or exceeds numParents, on segmentChunks that is no
+// whole number >= 1, on carryRows without chunkQueue (only the queue carries) and on carryRows with a historyPath (that
+// path matches batch by batch).
+inline bool readCarryKeys(const Json &h, uint32_t numParents, uint32_t &carryRows, uint32_t &segmentChunks)
+{
+    if (!h.has("carryRows")) return false;
+    const Json &v = h["carryRows"];
+    if (v.kind != Json::Number || !(v.num >= 0.0) || v.num != std::floor(v.num))
+        throw std::runtime_error("parameters.json: type.HIP.carryRows must be a whole number, 0 or more");
+    if (v.num == 0.0) return false;
+    if (v.num > (double)numParents)
+        throw std::runtime_error("parameters.json: type.HIP.carryRows " + std::to_string((unsigned long long)std::fmin(v.num, 1.8e19)) +
+                                 " exceeds evolutionary.numParents " + std::to_string(numParents) + ": only parent rows can be carried");
+    if (!h.has("chunkQueue") || !h["chunkQueue"].b)
+        throw std::runtime_error("parameters.json: type.HIP.carryRows needs type.HIP.chunkQueue: only the chunk queue carries rows");
+    if (h.has("historyPath") && !h["historyPath"].str.empty())
+        throw std::runtime_error("parameters.json: type.HIP.carryRows cannot be combined with type.HIP.historyPath: a history file is matched batch by batch");
+    uint32_t segment = 0;
+    if (h.has("segmentChunks")) {
+        const Json &l = h["segmentChunks"];
+        if (l.kind != Json::Number || !(l.num >= 1.0) || l.num != std::floor(l.num))
+            throw std::runtime_error("parameters.json: type.HIP.segmentChunks must be a whole number, 1 or more");
+        segment = l.num >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)l.num;
+    }
+    carryRows = (uint32_t)v.num;
+    segmentChunks = segment;
+    return true;
+}
+
 #endif

@@ -3,7 +3,7 @@
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
 // "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "numDevices", "numElites",
 // "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight", "chunkQueue",
-// "survivors", "objective", "objectiveFloor", "objectiveWeights", "hopSize", "renderMatch", "renderMode", "matchPath", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
+// "carryRows", "segmentChunks", "survivors", "objective", "objectiveFloor", "objectiveWeights", "hopSize", "renderMatch", "renderMode", "matchPath", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
 // N-sample chunk with Evolutionary_Strategy_HIP, writes inputGenerated.wav and the
 // outputAudioPath rendering of the best match, and prints the best parameters.
@@ -106,6 +106,8 @@ int main(int argc, char *argv[])
             if (h.has("chunksInFlight")) args.chunksInFlight = (uint32_t)h["chunksInFlight"].number();
             // ... through one queue: a slot takes the next chunk as soon as its chunk's stop rule holds
             if (h.has("chunkQueue")) args.chunkQueue = h["chunkQueue"].b;
+            // ... whose chunks, in segments of segmentChunks, start from their predecessor's best rows (Match_JSON.hpp)
+            (void)readCarryKeys(h, args.es_args.pop.numParents, args.carryRows, args.segmentChunks);
             // elitist survival: the best `survivors` rows are carried unchanged into each generation (0: the reference's strategy)
             if (h.has("survivors")) {
                 // a value above every population goes to the library as the largest count, which refuses it with its own text
