@@ -74,6 +74,9 @@ def lib():
     L.sots_or_draw_unit.argtypes = [C.c_uint32]
     L.sots_or_draw_unit.restype = C.c_float
     L.sots_or_mutate_gene.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32, u32p]
+    L.sots_or_draw_word.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.sots_or_draw_word.restype = C.c_uint32
+    L.sots_or_mutate_words.argtypes = [u32p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32]
     L.sots_or_es_create.argtypes = [C.POINTER(Config)]
     L.sots_or_es_create.restype = C.c_void_p
     L.sots_or_es_destroy.argtypes = [C.c_void_p]
@@ -190,6 +193,19 @@ def mutate(v, s, seed, gid_base, generation):
 
 def draw_unit(word):
     return np.float32(lib().sots_or_draw_unit(int(word) & 0xFFFFFFFF))
+
+
+def draw_word(seed, gid, epoch, index, tag=TAG_MUTATE):
+    """random word `index` of (gid, epoch) in domain `tag`; the counters are taken modulo 2^32, as the device's wrap"""
+    m = 0xFFFFFFFF
+    return int(lib().sots_or_draw_word(seed, gid & m, epoch & m, index & m, tag))
+
+
+def mutate_words(p, d, seed, gid_base, generation):
+    """words[p][d][13]: what mutate() hands to mutate_gene for every gene (gid_base + i wraps modulo 2^32)"""
+    w = np.zeros((p, d, 13), np.uint32)
+    lib().sots_or_mutate_words(w, p, d, seed, gid_base & 0xFFFFFFFF, generation & 0xFFFFFFFF)
+    return w
 
 
 def mutate_gene(value, step, d, words):

@@ -531,6 +531,19 @@ void sots_or_mutate(float *values, float *steps, uint32_t p, uint32_t d,
         }
 }
 
+uint32_t sots_or_draw_word(uint64_t seed, uint32_t gid, uint32_t epoch, uint32_t index, uint32_t tag)
+{
+    return draw_word(seed, gid, epoch, index, tag);
+}
+
+void sots_or_mutate_words(uint32_t *words, uint32_t p, uint32_t d, uint64_t seed, uint32_t gid_base, uint32_t generation)
+{
+    for (uint32_t i = 0; i < p; ++i)
+        for (uint32_t j = 0; j < d; ++j)
+            for (uint32_t t = 0; t < 13; ++t)
+                words[((size_t)i * d + j) * 13u + t] = draw_word(seed, gid_base + i, generation, j * 16u + t, SOTS_OR_TAG_MUTATE);
+}
+
 static int fit_less(float a, float b)
 {
     if (isnan(a)) return 0;

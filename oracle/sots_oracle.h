@@ -84,6 +84,10 @@ void sots_or_mutate_gene(float *value, float *step, uint32_t d, const uint32_t w
 /* ocl_program.cl:155-190, in place */
 void sots_or_mutate(float *values, float *steps, uint32_t p, uint32_t d,
                     uint64_t seed, uint32_t gid_base, uint32_t generation);
+/* the random words themselves: word `index` of (gid, epoch) in domain `tag`, and the 13 words of every gene that
+ * sots_or_mutate hands to sots_or_mutate_gene, words[p][d][13] (for models that restate the rule from the words) */
+uint32_t sots_or_draw_word(uint64_t seed, uint32_t gid, uint32_t epoch, uint32_t index, uint32_t tag);
+void sots_or_mutate_words(uint32_t *words, uint32_t p, uint32_t d, uint64_t seed, uint32_t gid_base, uint32_t generation);
 /* ascending by fitness, stable (Evolutionary_Strategy.hpp:108-124), NaN last. perm[r] = source row */
 void sots_or_sort_perm(const float *fitness, uint32_t p, uint32_t *perm);
 
