@@ -613,6 +613,40 @@ int sots_batch_queue_read_kept_population(sots_batch *b, float *values, size_t v
  * device, no handle. */
 int sots_queue_makespan(const uint32_t *generations_run, uint32_t num_chunks, uint32_t slots, uint64_t *global_generations);
 
+/* ---- analysis on the device (new; the reference transforms every chunk on the host, Objective::calculateFFT,
+ * Evolutionary_Strategy.hpp:524-542) ----
+ * Frame f of a signal is its samples [f hop, f hop + N), 1 <= hop <= N.  The device analysis uploads the signal ONCE and
+ * transforms every frame where it lies: the batch's fp32 window table, a real-input FFT in fp32, and for k < N/2
+ * m_k = |X_k / N / windowFactor| - the magnitudes sots_batch_set_target_spectra and sots_batch_queue_targets_spectra take.
+ * A frame's bits depend on its N samples only (not on hop, the frame count or its neighbours); a non-finite sample makes
+ * the magnitudes of the frames that contain it non-finite, and of no other frame.
+ *
+ * THE DEVICE'S MAGNITUDES ARE NOT THE HOST'S BITS.  The host transform is fp64 rounded to fp32 at the end, the device's
+ * is fp32 throughout: they agree to about 3e-6 of a frame's largest bin, and a population matched against one does not
+ * repeat, bit for bit, a run against the other.  Hence a setting, off by default. */
+enum sots_analysis { SOTS_ANALYSIS_HOST = 0, SOTS_ANALYSIS_DEVICE = 1 };
+/* How the four audio target calls of the batch (sots_batch_set_target_audio[_hop], sots_batch_queue_targets_audio[_hop])
+ * make their spectra.  HOST (the default): chunk by chunk on the host, every copy, launch and bit as before.  DEVICE: the
+ * (num_chunks - 1) hop + N samples go up once, the device analysis writes the stored targets, and the call continues as its
+ * spectra form does; then the samples are bounded as below (SOTS_ERR_INVALID beyond 2^28).  An unknown mode is
+ * SOTS_ERR_INVALID and the old setting stays.  Targets already stored are not touched. */
+int sots_batch_set_analysis(sots_batch *b, uint32_t mode);
+int sots_batch_get_analysis(const sots_batch *b, uint32_t *mode);
+/* The device analysis of num_frames frames, whatever the mode: magnitudes[num_frames][N/2] come back to the host,
+ * num_bins == num_frames * N/2.  Blocking.  Population, targets, queue, run record and counters stay as they are; the
+ * scratch is the batch's own and is freed with it.
+ * SOTS_ERR_INVALID: a null pointer, hop outside 1..N, num_frames 0, (num_frames - 1) hop + N > 2^28 samples or
+ * num_frames * N/2 * 4 > 2^30 bytes.  SOTS_ERR_SIZE: num_samples < (num_frames - 1) hop + N, or a wrong num_bins. */
+int sots_batch_analyse_audio_hop(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t hop, uint32_t num_frames,
+                                 float *magnitudes, uint64_t num_bins);
+/* Frame k of `audio` scored against STORED QUEUE TARGET k under the batch's objective, floor and weights:
+ * fitness[k] = sum_j (u_j e_j)^2 with e_j the objective's signed error of bin j, summed in a fixed order (the same inputs
+ * give the same bits run to run; they need not be the bits a spectral kernel gives a synthesised row).  A signal scored
+ * against device-made targets of the same samples gives exactly 0.  Needs a stored queue (SOTS_ERR_STATE) of num_chunks
+ * chunks (SOTS_ERR_SIZE); the other limits are those of sots_batch_analyse_audio_hop.  Blocking; changes nothing. */
+int sots_batch_queue_score_audio_hop(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t hop, float *fitness,
+                                     uint32_t num_chunks);
+
 /* ---- introspection ---- */
 typedef struct sots_info {
     uint32_t population_length, num_dimensions, audio_length, spectrum_row_floats;

@@ -71,7 +71,9 @@ EXPORTS = [
     "sots_render_overlap_add", "sots_batch_set_target_audio_hop", "sots_batch_queue_targets_audio_hop",
     "sots_render_continuous",
     "sots_batch_queue_set_carry", "sots_batch_queue_get_carry",
+    "sots_batch_set_analysis", "sots_batch_get_analysis", "sots_batch_analyse_audio_hop", "sots_batch_queue_score_audio_hop",
 ]
+ANALYSIS_HOST, ANALYSIS_DEVICE = 0, 1  # enum sots_analysis
 QUEUE_NO_CHUNK = 0xFFFFFFFF
 RENDER_WINDOWED = 1
 RENDER_GLIDE = 1
@@ -286,6 +288,10 @@ def load():
     L.sots_batch_queue_targets_audio_hop.argtypes = [vp, vp, C.c_uint64, u32, u32]
     L.sots_batch_queue_set_carry.argtypes = [vp, u32, u32]
     L.sots_batch_queue_get_carry.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    L.sots_batch_set_analysis.argtypes = [vp, u32]
+    L.sots_batch_get_analysis.argtypes = [vp, C.POINTER(u32)]
+    L.sots_batch_analyse_audio_hop.argtypes = [vp, vp, C.c_uint64, u32, u32, vp, C.c_uint64]
+    L.sots_batch_queue_score_audio_hop.argtypes = [vp, vp, C.c_uint64, u32, vp, u32]
     _lib = L
     return L
 
@@ -845,6 +851,39 @@ class HipBatch:
         r, l = C.c_uint32(), C.c_uint32()
         self._check(self.L.sots_batch_queue_get_carry(self._h, C.byref(r), C.byref(l)))
         return r.value, l.value
+
+    # -- analysis on the device --
+    def set_analysis(self, mode):
+        """ANALYSIS_HOST (the default) or ANALYSIS_DEVICE: how set_target_audio / queue_targets_audio make their spectra.
+        The device's fp32 magnitudes are not the host's fp64 bits: a run against one does not repeat a run against the other."""
+        self._check(self.L.sots_batch_set_analysis(self._h, mode))
+
+    def get_analysis(self):
+        m = C.c_uint32()
+        self._check(self.L.sots_batch_get_analysis(self._h, C.byref(m)))
+        return m.value
+
+    def _frames(self, a, hop, frames):
+        if frames is not None:
+            return frames
+        return (a.size - self.N) // hop + 1 if a.size >= self.N and hop > 0 else 0
+
+    def analyse_audio_hop(self, audio, hop, frames=None):
+        """magnitudes[frames][N/2] of a flat signal's frames [k hop, k hop + N), made on the device whatever the mode;
+        frames None: as many as the signal holds"""
+        a = _f32(audio).reshape(-1)
+        frames = self._frames(a, hop, frames)
+        out = np.empty((frames, self.N // 2), np.float32)
+        self._check(self.L.sots_batch_analyse_audio_hop(self._h, _ptr(a), a.size, hop, frames, _ptr(out), out.size))
+        return out
+
+    def queue_score_audio_hop(self, audio, hop, chunks=None):
+        """fitness[chunks]: frame k of a flat signal against stored queue target k under the batch's objective and weights"""
+        a = _f32(audio).reshape(-1)
+        chunks = self._frames(a, hop, chunks)
+        out = np.empty(chunks, np.float32)
+        self._check(self.L.sots_batch_queue_score_audio_hop(self._h, _ptr(a), a.size, hop, _ptr(out), chunks))
+        return out
 
     def queue_kept_population(self):
         v = np.empty((self.P, self.D), np.float32)

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/sots_hip.h"
+#include "sots_analyse.h"
 #include "sots_engine.h"
 #include "sots_host_math.h"
 #include "sots_kernels.h"
@@ -54,6 +55,10 @@ struct sots_batch : sots::Engine {
     hipEvent_t q_event[2] = {nullptr, nullptr};
     // carried rows (sots_batch_queue_set_carry): a setting of the handle, kept over targets and runs.  0, 0: off
     uint32_t q_carry_rows = 0, q_segment_chunks = 0;
+    // analysis on the device (sots_batch_set_analysis): how the audio target calls make their spectra, and the scratch of
+    // every device analysis (the uploaded signal, what sots_batch_analyse_audio_hop / _queue_score_audio_hop read back)
+    uint32_t analysis = SOTS_ANALYSIS_HOST;
+    AnalyseScratch an{};
 
     size_t rows() const { return (size_t)max_chunks * P; }
     float *val(uint32_t half) const { return values + (size_t)half * rows() * D; }
@@ -93,6 +98,7 @@ void free_batch(sots_batch *b)
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     track_release(b->track);
+    analyse_release(b->an);
     queue_release(b);
     engine_release(*b);
     delete b;
@@ -156,6 +162,27 @@ std::vector<float> spectra_at_hop(const sots_batch *b, const float *audio, uint3
     return mag;
 }
 
+// The device analysis, enqueued: the samples of `frames` frames at a hop go up into the batch's scratch, once, and their
+// magnitudes (bins: the scaled bins, for launch_score_frames) are written to dst, device memory.  The caller has checked
+// the counts (analysis_frames_check) and synchronises before `audio` may go away.
+int analyse_to(sots_batch *b, const float *audio, uint32_t hop, uint32_t frames, float *dst, bool bins)
+{
+    const size_t need = (size_t)analysis_samples(frames, hop, b->N);
+    SOTS_HIP(b, analyse_reserve(b->an, need, 0, 0));
+    SOTS_HIP(b, hipMemcpyAsync(b->an.signal, audio, need * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    SOTS_HIP(b, launch_analyse(b->stream, b->an.signal, b->window, b->twiddle, dst, bins, b->log2n, hop, frames, b->inv_n, b->inv_wf));
+    return SOTS_OK;
+}
+bool device_analysis(const sots_batch *b) { return b->analysis == SOTS_ANALYSIS_DEVICE; }
+// the audio target calls under SOTS_ANALYSIS_DEVICE: one upload holds at most kAnalysisMaxSamples
+int device_samples_check(const sots_batch *b, uint64_t need)
+{
+    if (need > kAnalysisMaxSamples)
+        return SOTS_FAIL(b, SOTS_ERR_INVALID, "device analysis: %llu samples of target audio, more than %llu", (unsigned long long)need,
+                         (unsigned long long)kAnalysisMaxSamples);
+    return SOTS_OK;
+}
+
 // One generation of `chunks` chunk populations, enqueued: variation | synthesis | window + FFT + fitness | sort, each
 // over every chunk's rows, and the rotation index back where the sorted rows are.  vary(src, dst) launches the
 // variation, the caller's own: by the batch's generation counter, or by the queue's slot table.
@@ -176,6 +203,37 @@ template <class Vary> int enqueue_generation(sots_batch *b, uint32_t chunks, Var
     SOTS_HIP(b, launch_sort_seg(b->stream, b->val(src), b->stp(src), b->fit(src), b->val(dst), b->stp(dst), b->fit(dst), b->P,
                                 b->D, chunks));
     b->rot = dst;
+    return SOTS_OK;
+}
+
+// A new stored queue of num_chunks chunks (the caller has checked the count against kQueueMaxTargetBytes): an earlier
+// queue is released, the buffers are allocated, fill() enqueues what writes b->q_targets - the copy of uploaded
+// magnitudes, or the device analysis - and the targets' derived table follows.
+template <class Fill> int queue_store(sots_batch *b, uint32_t num_chunks, Fill fill)
+{
+    const uint64_t need = (uint64_t)num_chunks * (b->N / 2);
+    if (int rc = engine_bind(*b)) return rc;
+    SOTS_HIP(b, hipStreamSynchronize(b->stream));
+    queue_release(b);
+    const size_t pd_floats = (size_t)b->P * b->D;
+#define QUEUE_HIP(call) SOTS_HIP_OR(b, call, queue_release(b); return rc_)
+    QUEUE_HIP(hipMalloc((void **)&b->q_targets, need * sizeof(float)));
+    QUEUE_HIP(hipMalloc((void **)&b->q_results, (size_t)num_chunks * sizeof(sots_chunk_result)));
+    QUEUE_HIP(hipMalloc((void **)&b->q_kept_rows, (2 * pd_floats + b->P) * sizeof(float)));
+    QUEUE_HIP(hipMalloc((void **)&b->q_state, (4 + 2 * (size_t)b->max_chunks) * sizeof(uint32_t)));
+    QUEUE_HIP(hipHostMalloc((void **)&b->q_pinned, 2 * 4 * sizeof(uint32_t), hipHostMallocDefault));
+    for (hipEvent_t &e : b->q_event) QUEUE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (int rc = fill()) {
+        queue_release(b);
+        return rc;
+    }
+    QUEUE_HIP(hipStreamSynchronize(b->stream));
+#undef QUEUE_HIP
+    b->q_chunks = num_chunks;
+    if (int rc = queue_derive(b)) {
+        queue_release(b);
+        return rc;
+    }
     return SOTS_OK;
 }
 
@@ -268,6 +326,14 @@ int sots_batch_set_target_audio_hop(sots_batch *b, const float *audio, uint32_t 
     const uint64_t need = (uint64_t)(num_chunks - 1u) * hop + b->N; // (hop = N: num_chunks * N)
     if (!audio || (uint64_t)num_samples < need)
         return SOTS_FAIL(b, SOTS_ERR_SIZE, "%u chunks of target audio need %llu samples, got %u", num_chunks, (unsigned long long)need, num_samples);
+    if (device_analysis(b)) { // one upload, the spectra made where they are stored, then as sots_batch_set_target_spectra goes on
+        if (int rc = device_samples_check(b, need)) return rc;
+        if (int rc = engine_bind(*b)) return rc;
+        if (int rc = analyse_to(b, audio, hop, num_chunks, b->targets, false)) return rc;
+        if (int rc = batch_derive(b, num_chunks)) return rc; // (new targets: every chunk's record starts over)
+        b->active = num_chunks;
+        return SOTS_OK;
+    }
     const std::vector<float> mag = spectra_at_hop(b, audio, hop, num_chunks);
     return sots_batch_set_target_spectra(b, mag.data(), (uint32_t)mag.size(), num_chunks);
 }
@@ -427,26 +493,10 @@ int sots_batch_queue_targets_spectra(sots_batch *b, const float *magnitudes, uin
     if (!magnitudes || num_bins != need)
         return SOTS_FAIL(b, SOTS_ERR_SIZE, "%u queued target spectra need %llu bins, got %llu", num_chunks, (unsigned long long)need,
                      (unsigned long long)num_bins);
-    if (int rc = engine_bind(*b)) return rc;
-    SOTS_HIP(b, hipStreamSynchronize(b->stream));
-    queue_release(b);
-    const size_t pd_floats = (size_t)b->P * b->D;
-#define QUEUE_HIP(call) SOTS_HIP_OR(b, call, queue_release(b); return rc_)
-    QUEUE_HIP(hipMalloc((void **)&b->q_targets, need * sizeof(float)));
-    QUEUE_HIP(hipMalloc((void **)&b->q_results, (size_t)num_chunks * sizeof(sots_chunk_result)));
-    QUEUE_HIP(hipMalloc((void **)&b->q_kept_rows, (2 * pd_floats + b->P) * sizeof(float)));
-    QUEUE_HIP(hipMalloc((void **)&b->q_state, (4 + 2 * (size_t)b->max_chunks) * sizeof(uint32_t)));
-    QUEUE_HIP(hipHostMalloc((void **)&b->q_pinned, 2 * 4 * sizeof(uint32_t), hipHostMallocDefault));
-    for (hipEvent_t &e : b->q_event) QUEUE_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    QUEUE_HIP(hipMemcpyAsync(b->q_targets, magnitudes, need * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    QUEUE_HIP(hipStreamSynchronize(b->stream));
-#undef QUEUE_HIP
-    b->q_chunks = num_chunks;
-    if (int rc = queue_derive(b)) {
-        queue_release(b);
-        return rc;
-    }
-    return SOTS_OK;
+    return queue_store(b, num_chunks, [&]() -> int {
+        SOTS_HIP(b, hipMemcpyAsync(b->q_targets, magnitudes, need * sizeof(float), hipMemcpyHostToDevice, b->stream));
+        return SOTS_OK;
+    });
 }
 
 int sots_batch_queue_targets_audio_hop(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t hop, uint32_t num_chunks)
@@ -463,6 +513,10 @@ int sots_batch_queue_targets_audio_hop(sots_batch *b, const float *audio, uint64
     if (!audio || num_samples < need)
         return SOTS_FAIL(b, SOTS_ERR_SIZE, "%u queued chunks of target audio need %llu samples, got %llu", num_chunks,
                      (unsigned long long)need, (unsigned long long)num_samples);
+    if (device_analysis(b)) { // one upload, the spectra made where they are stored, then as sots_batch_queue_targets_spectra goes on
+        if (int rc = device_samples_check(b, need)) return rc;
+        return queue_store(b, num_chunks, [&]() -> int { return analyse_to(b, audio, hop, num_chunks, b->q_targets, false); });
+    }
     const std::vector<float> mag = spectra_at_hop(b, audio, hop, num_chunks);
     return sots_batch_queue_targets_spectra(b, mag.data(), mag.size(), num_chunks);
 }
@@ -473,6 +527,59 @@ int sots_batch_queue_targets_audio(sots_batch *b, const float *audio, uint64_t n
     if (num_chunks == 0) return SOTS_FAIL(b, SOTS_ERR_INVALID, "sots_batch_queue_targets: num_chunks must be at least 1");
     BATCH_REQUIRE(b);
     return sots_batch_queue_targets_audio_hop(b, audio, num_samples, b->N, num_chunks);
+}
+
+// ---- analysis on the device ----
+int sots_batch_set_analysis(sots_batch *b, uint32_t mode)
+{
+    BATCH_REQUIRE(b);
+    SOTS_REFUSE(b, analysis_mode_check(mode));
+    b->analysis = mode;
+    return SOTS_OK;
+}
+
+int sots_batch_get_analysis(const sots_batch *b, uint32_t *mode)
+{
+    BATCH_REQUIRE(b);
+    if (!mode) return SOTS_FAIL(b, SOTS_ERR_INVALID, "sots_batch_get_analysis: null pointer");
+    *mode = b->analysis;
+    return SOTS_OK;
+}
+
+int sots_batch_analyse_audio_hop(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t hop, uint32_t num_frames, float *magnitudes,
+                                 uint64_t num_bins)
+{
+    BATCH_REQUIRE(b);
+    SOTS_REFUSE(b, analysis_frames_check("sots_batch_analyse_audio_hop", audio, num_samples, hop, num_frames, magnitudes, b->N));
+    const uint64_t bins = (uint64_t)num_frames * (b->N / 2);
+    if (num_bins != bins)
+        return SOTS_FAIL(b, SOTS_ERR_SIZE, "sots_batch_analyse_audio_hop: %u frames give %llu bins, got room for %llu", num_frames,
+                         (unsigned long long)bins, (unsigned long long)num_bins);
+    if (int rc = engine_bind(*b)) return rc;
+    SOTS_HIP(b, analyse_reserve(b->an, 0, (size_t)bins, 0));
+    if (int rc = analyse_to(b, audio, hop, num_frames, b->an.out, false)) return rc;
+    SOTS_HIP(b, hipMemcpyAsync(magnitudes, b->an.out, (size_t)bins * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    SOTS_HIP(b, hipStreamSynchronize(b->stream));
+    return SOTS_OK;
+}
+
+int sots_batch_queue_score_audio_hop(sots_batch *b, const float *audio, uint64_t num_samples, uint32_t hop, float *fitness, uint32_t num_chunks)
+{
+    BATCH_REQUIRE(b);
+    SOTS_REFUSE(b, analysis_frames_check("sots_batch_queue_score_audio_hop", audio, num_samples, hop, num_chunks, fitness, b->N));
+    if (b->q_chunks == 0)
+        return SOTS_FAIL(b, SOTS_ERR_STATE, "no queue: call sots_batch_queue_targets_audio or sots_batch_queue_targets_spectra first");
+    if (num_chunks != b->q_chunks)
+        return SOTS_FAIL(b, SOTS_ERR_SIZE, "sots_batch_queue_score_audio_hop: the queue holds %u chunks, got %u", b->q_chunks, num_chunks);
+    if (int rc = engine_bind(*b)) return rc;
+    // the scaled bins of every frame (two floats a bin), then one wavefront per frame against the stored target of its index
+    SOTS_HIP(b, analyse_reserve(b->an, 0, (size_t)num_chunks * b->N, num_chunks));
+    if (int rc = analyse_to(b, audio, hop, num_chunks, b->an.out, true)) return rc;
+    SOTS_HIP(b, launch_score_frames(b->stream, reinterpret_cast<const float2 *>(b->an.out), queue_targets(b), b->an.fitness, b->log2n, num_chunks,
+                                    b->obj));
+    SOTS_HIP(b, hipMemcpyAsync(fitness, b->an.fitness, (size_t)num_chunks * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    SOTS_HIP(b, hipStreamSynchronize(b->stream));
+    return SOTS_OK;
 }
 
 int sots_batch_queue_run(sots_batch *b, uint32_t first_chunk_index, uint32_t max_generations, const sots_stop_rule *rule,

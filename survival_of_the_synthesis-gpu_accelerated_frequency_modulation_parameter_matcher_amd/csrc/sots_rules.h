@@ -158,6 +158,37 @@ inline Fault objective_weights_fault(const float *weights, uint32_t num_bins, ui
     }
 }
 
+// ---- analysis on the device (sots_batch_set_analysis, sots_batch_analyse_audio_hop) ----
+inline Fault analysis_mode_check(uint32_t mode)
+{
+    if (mode != SOTS_ANALYSIS_HOST && mode != SOTS_ANALYSIS_DEVICE)
+        return fault(SOTS_ERR_INVALID, "unknown analysis mode %u (0 = host, 1 = device)", mode);
+    return Fault{};
+}
+constexpr uint64_t kAnalysisMaxSamples = 1ull << 28;     // one upload
+constexpr uint64_t kAnalysisMaxSpectrumBytes = 1ull << 30; // frames x N/2 magnitudes: the bound of the queue's stored targets
+// samples that `frames` (>= 1) frames of n at a hop cover; 64-bit throughout: frames up to 2^32 - 1, hop up to 2^15
+inline uint64_t analysis_samples(uint32_t frames, uint32_t hop, uint32_t n) { return (uint64_t)(frames - 1u) * hop + n; }
+// What the device analysis refuses before anything touches the device: frames of n samples at a hop out of num_samples
+// of audio, one result per frame (or frames x n/2, the caller's own check) into out.  who: the entry point, for the text.
+inline Fault analysis_frames_check(const char *who, const void *audio, uint64_t num_samples, uint32_t hop, uint32_t frames, const void *out, uint32_t n)
+{
+    if (!audio || !out) return fault(SOTS_ERR_INVALID, "%s: null pointer", who);
+    if (hop == 0 || hop > n) return fault(SOTS_ERR_INVALID, "%s: hop %u outside 1..%u", who, hop, n);
+    if (frames == 0) return fault(SOTS_ERR_INVALID, "%s: the frame count must be at least 1", who);
+    const uint64_t need = analysis_samples(frames, hop, n), bytes = (uint64_t)frames * (n / 2u) * sizeof(float);
+    if (need > kAnalysisMaxSamples)
+        return fault(SOTS_ERR_INVALID, "%s: %u frames at hop %u cover %llu samples, more than %llu", who, frames, hop, (unsigned long long)need,
+                     (unsigned long long)kAnalysisMaxSamples);
+    if (bytes > kAnalysisMaxSpectrumBytes)
+        return fault(SOTS_ERR_INVALID, "%s: %u frames of %u bins exceed %llu bytes of spectra", who, frames, n / 2u,
+                     (unsigned long long)kAnalysisMaxSpectrumBytes);
+    if (num_samples < need)
+        return fault(SOTS_ERR_SIZE, "%s: %u frames at hop %u need %llu samples, got %llu", who, frames, hop, (unsigned long long)need,
+                     (unsigned long long)num_samples);
+    return Fault{};
+}
+
 // ---- phase-continuous rendering ----
 // sots_render_continuous: what it refuses before anything touches the device.  n, d, synth_arith: the context's audio
 // length, genes per row and arithmetic mode.

@@ -101,6 +101,17 @@ struct Evolutionary_Strategy_HIP_Arguments
     // numDevices > 1, populationLength > 1024) parameterMatchAudio throws rather than match without carrying.
     uint32_t carryRows = 0;
     uint32_t segmentChunks = 0;
+    // Analysis on the device (type.HIP.{deviceAnalysis,matchReport}; sots_batch_set_analysis).
+    //   deviceAnalysis : the chunks in flight (batched and queued alike) get their target spectra from ONE upload of the audio
+    //                    per batch - the library's fp32 transform on the device - instead of Objective::calculateFFT chunk by
+    //                    chunk on the host.  The targets are then not the host's bits (fp32 against fp64), so neither are the
+    //                    matches: off by default.  Where matching would go chunk by chunk (chunksInFlight <= 1, numDevices > 1,
+    //                    populationLength > 1024) the constructor throws - before any device work - rather than fall back.
+    //   matchReport    : sots_match scores the rendered match against the stored targets, chunk by chunk (scoreAgainstTargets()
+    //                    below), and writes chunk,fitness,rendered_fitness there.  Needs renderMatch and the chunk queue (it
+    //                    keeps the targets); otherwise the constructor throws the same way.
+    bool deviceAnalysis = false;
+    std::string matchReport = "";
     // Elitist survival (type.HIP.survivors; sots_set_survivors): rows 0..survivors-1 of the sorted population pass through
     // recombination and mutation unchanged and are evaluated again with the offspring.  0 (default) is the reference's
     // strategy; at most numParents, above that the constructor / parameterMatchAudio throws with the library's text.
@@ -323,6 +334,17 @@ public:
         ra.flags = hop_ < objective.audioLength ? (uint32_t)SOTS_RENDER_WINDOWED : 0u;
         check(sots_render_overlap_add(ctx_, values.data(), values.size() * sizeof(float), chunks, &ra, out.data(), out.size()), "renderMatch");
     }
+    // Frame k of `signal` (samples [k hop, k hop + N), the hop of the match) scored against the stored target of chunk k under
+    // the objective, floor and weights of the match: what a listener of `signal` gets where bestFitnessPerChunk() is what the
+    // search saw (a chunk's row synthesised from phase 0).  After a parameterMatchAudio through the chunk queue only: the queue
+    // keeps the targets.  signal: at least (numChunks - 1) hop + N samples, e.g. renderMatch()'s.
+    void scoreAgainstTargets(const std::vector<float> &signal, std::vector<float> &fitness)
+    {
+        if (!batch_) throw std::runtime_error("Evolutionary_Strategy_HIP: scoreAgainstTargets needs a match through the chunk queue");
+        fitness.assign(numChunks_, 0.0f);
+        if (sots_batch_queue_score_audio_hop(batch_, signal.data(), (uint64_t)signal.size(), hop_, fitness.data(), numChunks_) != SOTS_OK)
+            throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_batch_queue_score_audio_hop: ") + sots_batch_last_error(batch_));
+    }
     // generations really run by the last parameterMatchAudio, summed over its chunks (chunks in flight run to their batch's end)
     uint64_t generationsRun() const { return generationsRun_; }
     // bins with a positive weight (all N/2 of them without weights)
@@ -357,6 +379,14 @@ public:
         }
         hop_ = matchHop((double)args_.hopSize, objective.audioLength); // (throws before any device work)
         objectiveWeights_ = makeObjectiveWeights(args_.objectiveWeights, objective.audioLength, (double)objective.sampleRate); // (throws before any device work)
+        // (likewise: no silent fall-back to the host analysis, which would change the result's bits behind the user's back)
+        const bool inFlight = args_.chunksInFlight > 1 && args_.numDevices <= 1 && population.populationLength <= 1024u;
+        if (args_.deviceAnalysis && !inFlight)
+            throw std::runtime_error("Evolutionary_Strategy_HIP: deviceAnalysis needs the chunks in flight (chunksInFlight > 1, one device, "
+                                     "populationLength <= 1024)");
+        if (!args_.matchReport.empty() && !(args_.renderMatch && inFlight && args_.chunkQueue && (args_.historyEvery == 0 || args_.historyPath.empty())))
+            throw std::runtime_error("Evolutionary_Strategy_HIP: matchReport needs renderMatch and the chunk queue (chunkQueue, chunksInFlight > 1, "
+                                     "one device, populationLength <= 1024, no history file)");
         if (args_.numDevices > 1) {
             std::vector<int32_t> devs = args_.devices;
             if (devs.empty())
@@ -605,9 +635,15 @@ private:
         const uint32_t segment = !args_.carryRows ? 0u : args_.segmentChunks ? args_.segmentChunks : (numChunks_ + args_.chunksInFlight - 1u) / args_.chunksInFlight;
         checkBatch(sots_batch_queue_set_carry(batch_, args_.carryRows, segment), "sots_batch_queue_set_carry");
         if (args_.carryRows && args_.verbose) printf("Carried rows: %u, in segments of %u chunks\n", args_.carryRows, segment);
-        std::vector<float> mags((size_t)numChunks_ * half);
-        for (uint32_t c = 0; c < numChunks_; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)hop_ * c], mags.data() + (size_t)c * half);
-        checkBatch(sots_batch_queue_targets_spectra(batch_, mags.data(), (uint64_t)mags.size(), numChunks_), "sots_batch_queue_targets_spectra");
+        if (args_.deviceAnalysis) { // the samples the chunks cover go up once; the device makes the spectra where the queue stores them
+            checkBatch(sots_batch_set_analysis(batch_, SOTS_ANALYSIS_DEVICE), "sots_batch_set_analysis");
+            checkBatch(sots_batch_queue_targets_audio_hop(batch_, aTargetAudio, matchCoveredSamples(numChunks_, objective.audioLength, hop_), hop_, numChunks_),
+                       "sots_batch_queue_targets_audio_hop");
+        } else {
+            std::vector<float> mags((size_t)numChunks_ * half);
+            for (uint32_t c = 0; c < numChunks_; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)hop_ * c], mags.data() + (size_t)c * half);
+            checkBatch(sots_batch_queue_targets_spectra(batch_, mags.data(), (uint64_t)mags.size(), numChunks_), "sots_batch_queue_targets_spectra");
+        }
         sots_queue_stats stats{};
         stats.struct_size = sizeof stats;
         checkBatch(sots_batch_queue_run(batch_, 0, numGenerations, stopRuleSet() ? &rule_ : nullptr, numChunks_ - 1, &stats), "sots_batch_queue_run");
@@ -651,6 +687,7 @@ private:
         if (!objectiveWeights_.empty())
             checkBatch(sots_batch_set_objective_weights(batch_, objectiveWeights_.data(), (uint32_t)objectiveWeights_.size()), "sots_batch_set_objective_weights");
         if (tracking()) checkBatch(sots_batch_track(batch_, trackFlags(), args_.historyEvery, historyCapacity()), "sots_batch_track");
+        if (args_.deviceAnalysis) checkBatch(sots_batch_set_analysis(batch_, SOTS_ANALYSIS_DEVICE), "sots_batch_set_analysis");
         std::vector<float> mags((size_t)perBatch * half), values((size_t)perBatch * d), fitness(perBatch);
         std::vector<float> nowValues((size_t)perBatch * d), nowFitness(perBatch), everFitness(perBatch);
         std::vector<uint32_t> nowGeneration(perBatch), stoppedAt(perBatch);
@@ -666,8 +703,14 @@ private:
         uint32_t last = 0;
         for (uint32_t first = 0; first < numChunks_; first += perBatch) {
             const uint32_t n = std::min(perBatch, numChunks_ - first);
-            for (uint32_t c = 0; c < n; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)hop_ * (first + c)], mags.data() + (size_t)c * half);
-            checkBatch(sots_batch_set_target_spectra(batch_, mags.data(), n * half, n), "sots_batch_set_target_spectra");
+            if (args_.deviceAnalysis) { // the batch's samples, from its first chunk's start on, in one upload
+                checkBatch(sots_batch_set_target_audio_hop(batch_, aTargetAudio + (size_t)hop_ * first,
+                                                           (uint32_t)matchCoveredSamples(n, objective.audioLength, hop_), hop_, n),
+                           "sots_batch_set_target_audio_hop");
+            } else {
+                for (uint32_t c = 0; c < n; ++c) objective.calculateFFT((float *)&aTargetAudio[(size_t)hop_ * (first + c)], mags.data() + (size_t)c * half);
+                checkBatch(sots_batch_set_target_spectra(batch_, mags.data(), n * half, n), "sots_batch_set_target_spectra");
+            }
             checkBatch(sots_batch_init_population(batch_, first), "sots_batch_init_population");
             uint32_t done = 0;
             if (stopRuleSet()) {

@@ -246,4 +246,35 @@ inline bool readCarryKeys(const Json &h, uint32_t numParents, uint32_t &carryRow
     return true;
 }
 
+// type.HIP.deviceAnalysis / type.HIP.matchReport (sots_batch_set_analysis, sots_batch_queue_score_audio_hop).
+//   deviceAnalysis  true: the chunks' target spectra are made on the device from one upload of the audio instead of chunk by
+//                   chunk on the host - fp32 against fp64, so the match is not the host analysis's bit for bit.  Only the
+//                   chunks in flight analyse on the device: it needs chunksInFlight > 1, one device and a population of at most
+//                   1024; otherwise this throws rather than analyse on the host behind the user's back.
+//   matchReport     a path: after rendering, the rendered signal is scored chunk by chunk against the stored targets and a CSV
+//                   chunk,fitness,rendered_fitness is written there.  Needs renderMatch and the chunk queue (chunkQueue,
+//                   chunksInFlight > 1, no historyPath: the queue keeps the targets the score reads).
+// Returns whether either is on; throws - like the keys above, before any device work - where a prerequisite is missing.
+inline bool readAnalysisKeys(const Json &h, uint64_t populationLength, bool &deviceAnalysis, std::string &matchReport)
+{
+    const bool device = h.has("deviceAnalysis") && h["deviceAnalysis"].b;
+    const std::string report = h.has("matchReport") ? h["matchReport"].str : std::string();
+    const bool inFlight = h.has("chunksInFlight") && h["chunksInFlight"].number() > 1.0;
+    const bool oneDevice = !h.has("numDevices") || h["numDevices"].number() <= 1.0;
+    if (device && !(inFlight && oneDevice && populationLength <= 1024u))
+        throw std::runtime_error("parameters.json: type.HIP.deviceAnalysis needs the chunks in flight (type.HIP.chunksInFlight > 1, one device, "
+                                 "a population of at most 1024): chunk by chunk the analysis stays on the host");
+    if (!report.empty()) {
+        if (!h.has("renderMatch") || !h["renderMatch"].b)
+            throw std::runtime_error("parameters.json: type.HIP.matchReport needs type.HIP.renderMatch: it scores the rendered match");
+        const bool queue = h.has("chunkQueue") && h["chunkQueue"].b && inFlight && oneDevice && populationLength <= 1024u;
+        if (!queue || (h.has("historyPath") && !h["historyPath"].str.empty()))
+            throw std::runtime_error("parameters.json: type.HIP.matchReport needs the chunk queue (type.HIP.chunkQueue, chunksInFlight > 1, one device, "
+                                     "a population of at most 1024, no historyPath): the queue keeps the targets the score reads");
+    }
+    deviceAnalysis = device;
+    matchReport = report;
+    return device || !report.empty();
+}
+
 #endif

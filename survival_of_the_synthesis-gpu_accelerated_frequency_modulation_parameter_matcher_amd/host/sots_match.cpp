@@ -3,7 +3,7 @@
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
 // "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "numDevices", "numElites",
 // "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight", "chunkQueue",
-// "carryRows", "segmentChunks", "survivors", "objective", "objectiveFloor", "objectiveWeights", "hopSize", "renderMatch", "renderMode", "matchPath", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
+// "carryRows", "segmentChunks", "survivors", "objective", "objectiveFloor", "objectiveWeights", "hopSize", "renderMatch", "renderMode", "matchPath", "deviceAnalysis", "matchReport", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
 // N-sample chunk with Evolutionary_Strategy_HIP, writes inputGenerated.wav and the
 // outputAudioPath rendering of the best match, and prints the best parameters.
@@ -22,6 +22,12 @@
 //   "matchPath"   a CSV of the parameter track, one row per chunk:
 //                 chunk,start_sample,generations,fitness,u0..u{D-1},p0..p{D-1} - u the unit-range genes (%.9g: the fp32
 //                 bits), p the scaled parameters; with returnBestEver the best-ever individual of each chunk.
+//   "deviceAnalysis" true: the chunks' target spectra come from one upload of the audio and an fp32 transform on the GPU
+//                 instead of the host's fp64 one, chunk by chunk.  Not the same bits, so not the same match: off by default.
+//                 Needs "chunksInFlight" > 1 (one device, a population of at most 1024).
+//   "matchReport" a CSV chunk,fitness,rendered_fitness (%.9g), one row per chunk: the fitness the search reported for the
+//                 chunk, and that of the RENDERED signal's frame at the chunk's place against the same target.  Needs
+//                 "renderMatch" and "chunkQueue".
 //
 // The JSON reader and the WAV reader/writer are small built-ins: the reference's
 // dependencies (nlohmann json, libsndfile, AudioFile) are not vendored and not needed.
@@ -126,6 +132,8 @@ int main(int argc, char *argv[])
             if (args.renderMatch && args.renderMode != 0u && h.has("deviceKernelArithmetic") && h["deviceKernelArithmetic"].b)
                 throw std::runtime_error("parameters.json: type.HIP.renderMode \"continuous\" and \"continuousGlide\" are not available with deviceKernelArithmetic");
             if (h.has("matchPath")) args.matchPath = h["matchPath"].str;
+            // the targets analysed on the device, and the report that scores the rendered match against them (Match_JSON.hpp)
+            (void)readAnalysisKeys(h, (uint64_t)args.es_args.pop.numParents + args.es_args.pop.numOffspring, args.deviceAnalysis, args.matchReport);
             // run record (Evolutionary_Strategy_HIP_Arguments): the best individual any generation produced, a history CSV,
             // and stopping a chunk early on a fitness target or a stall
             if (h.has("returnBestEver")) args.returnBestEver = h["returnBestEver"].b;
@@ -209,6 +217,15 @@ int main(int argc, char *argv[])
             hipEs->renderMatch(whole);
             if (whole.size() > 0xFFFFFFFFull / 3) throw std::runtime_error("renderMatch: the rendering does not fit a WAV file");
             outputAudioFile(outputAudioPath, whole.data(), (uint32_t)whole.size());
+            if (!args.matchReport.empty()) { // what was rendered against what was asked for, chunk by chunk, beside what the search reported
+                std::vector<float> rendered;
+                hipEs->scoreAgainstTargets(whole, rendered);
+                FILE *report = fopen(args.matchReport.c_str(), "w");
+                if (!report) throw std::runtime_error("cannot write " + args.matchReport);
+                fprintf(report, "chunk,fitness,rendered_fitness\n");
+                for (uint32_t c = 0; c < rendered.size(); ++c) fprintf(report, "%u,%.9g,%.9g\n", c, hipEs->bestFitnessPerChunk()[c], rendered[c]);
+                fclose(report);
+            }
         } else {
             // render 2^14 samples of the best match (main.cpp:270-275)
             Objective render(P, D, args.es_args.paramMin, args.es_args.paramMax, 14);
