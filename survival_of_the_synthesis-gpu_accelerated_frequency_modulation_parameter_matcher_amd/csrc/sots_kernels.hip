@@ -13,15 +13,18 @@
 //   * sortPopulation           : bitonic network on (fitness, index) 64-bit keys, LDS tiles
 //
 // Still the one translation unit of the kernels.  The families are moving into csrc/kernels/*.h, each included where
-// its code stood: so far common.h (kWave, v2f_t, ic, static_for, wave_sum, lane_xor), fft.h (complex
-// helpers, Dft<>, Stockham passes, fft_forward, the real-input split) and objective.h (bin_error, bin_error2, trailing
-// kernel arguments, k_objective_map, segmented targets).  Such a file states its contraction mode in its first lines
-// and ends with contract(off), this unit's default.
+// its code stood.  Out: common.h, stamps.h, fft.h, objective.h and every family compiled with contraction
+// on or standing between two of them - sel_keys.h, spectral_wave.h (k_fft), sort.h, select_tiles.h, select_splitters.h,
+// spectral_x.h (k_fft_x), spectral_big.h (k_fft_big).  Such a file states its contraction mode in its first lines and
+// ends with contract(off), this unit's default, so no contraction pragma is left in this file.  Still here, all in the
+// default mode: variation, synthesis, k_window, the island exchange, and behind the first launchers k_synth_dev,
+// k_bucket_fitness and the run record / chunk queue.
 //
 // Reference citations are file:line in the reference tree.
 #include "sots_kernels.h"
 #include "sots_stop_rule.h"
 #include "kernels/common.h"
+#include "kernels/stamps.h"
 #include <type_traits>
 
 #include <cstdlib>
@@ -262,15 +265,6 @@ __global__ __launch_bounds__(256) void k_recombine_mutate_queue(const float *__r
     }
 }
 
-// Audio rows are read exactly once per generation: non-temporal loads keep them from
-// displacing other data in L2 / Infinity Cache (P = 131072: 151 -> 132 us; neutral at 65536).
-typedef float v4f_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 nt_load4(const float4 *p)
-{
-    const v4f_t v = __builtin_nontemporal_load(reinterpret_cast<const v4f_t *>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-#define SOTS_ROW_LOAD(p) nt_load4(p)
 // ------------------------------------------------------------------------------------
 // synthesisePopulation{,DoubleSeries,TripleParallel}, ocl_program.cl:280-443 /
 // Objective::synthesiseAudio*, Evolutionary_Strategy.hpp:368-495.
@@ -359,56 +353,6 @@ __device__ __forceinline__ void wavetable_ready()
     __builtin_amdgcn_s_waitcnt(0); // vmcnt(0): the copies have landed
     __syncthreads();
 }
-
-#if defined(SOTS_STAMP) || defined(SOTS_STAMP_ENDS)
-// Diagnostic builds only (never the shipped library): per-wavefront shader cycles and 100 MHz
-// ticks, read back with sots_debug_stamps().
-__device__ unsigned long long g_stamps[2 * 16384];
-#endif
-#ifdef SOTS_STAMP
-struct StampScope {
-    unsigned long long t0, r0;
-    uint32_t slot;
-    __device__ StampScope(uint32_t s) : slot(s)
-    {
-        t0 = __builtin_amdgcn_s_memtime();
-        r0 = __builtin_amdgcn_s_memrealtime();
-    }
-    __device__ ~StampScope()
-    {
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        if ((threadIdx.x & 63) == 0 && slot < 16384) {
-            g_stamps[2 * slot] = t1 - t0;
-            g_stamps[2 * slot + 1] = r1 - r0;
-        }
-    }
-};
-#define SOTS_STAMP_SCOPE(slot) StampScope stamp_scope_(slot)
-// phase stamps of the selection kernels: shader cycles since the workgroup started, 16 phases per workgroup,
-// kept behind the synthesis stamps (slots 8192..)
-#define SOTS_PHASE_BEGIN() const unsigned long long phase_t0_ = __builtin_amdgcn_s_memtime()
-#define SOTS_PHASE(n)                                                                                              \
-    do {                                                                                                           \
-        if (threadIdx.x == 0 && blockIdx.x < 512)                                                                  \
-            g_stamps[2 * 8192 + blockIdx.x * 16 + (n)] = __builtin_amdgcn_s_memtime() - phase_t0_;                 \
-    } while (0)
-// absolute clock of any one lane (diagnostics of wavefront start skew inside a workgroup)
-// the chip-wide 100 MHz clock of one lane (when workgroups start and end relative to each other)
-#define SOTS_PHASE_REAL(n)                                                                                         \
-    do {                                                                                                           \
-        if (threadIdx.x == 0 && blockIdx.x < 512) g_stamps[2 * 8192 + blockIdx.x * 16 + (n)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#define SOTS_PHASE_ABS(n, cond)                                                                                   \
-    do {                                                                                                           \
-        if ((cond) && blockIdx.x < 512) g_stamps[2 * 8192 + blockIdx.x * 16 + (n)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#else
-#define SOTS_STAMP_SCOPE(slot)
-#define SOTS_PHASE_BEGIN()
-#define SOTS_PHASE(n)
-#define SOTS_PHASE_REAL(n)
-#define SOTS_PHASE_ABS(n, cond)
-#endif
 
 // ---- every voice, one lane per individual, whole-line stores through LDS -------------------
 // Each wavefront owns an 8 KiB tile [64 rows][8 chunks of 16 B], XOR-swizzled by row so that
@@ -1373,2282 +1317,16 @@ __global__ __launch_bounds__(256) void k_window(float *__restrict__ audio, const
 
 #include "kernels/fft.h"
 #include "kernels/objective.h"
+#include "kernels/sel_keys.h"
+#include "kernels/spectral_wave.h"
+#include "kernels/sort.h"
+#include "kernels/select_tiles.h"
+#include "kernels/select_splitters.h"
+#include "kernels/spectral_x.h"
+#include "kernels/spectral_big.h"
 
 namespace sots {
 namespace {
-
-#pragma clang fp contract(on) // (the transform's mode, kernels/fft.h: k_fft<., 1> and k_fitness share their arithmetic with the helpers they call)
-// ------------------------------------------------------------------------------------
-// Selection keys, and the bucket of a key between the splitters of a slot (list mode).  They stand in
-// front of the spectral kernel because k_fft<.., BUCKET = true> files every row's key under its bucket as soon as it
-// has the row's fitness: the selection then reads its bucket's keys from a list instead of streaming all P.
-// ------------------------------------------------------------------------------------
-// order-preserving bits of a fitness: every number (at most 0xFF800000, +inf) below NaN (0xFFFFFFFD), NaN
-// below the padding key (0xFFFFFFFE); 0xFFFFFFFF stays free so that "bits + 1" never wraps
-constexpr uint32_t kSelPadBits = 0xFFFFFFFEu;
-__device__ __forceinline__ uint32_t order_bits(float f)
-{
-    if (f != f) return 0xFFFFFFFDu;
-    const uint32_t u = __float_as_uint(f == 0.0f ? 0.0f : f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-constexpr uint32_t kSplBitsNegInf = 0x007FFFFFu, kSplBitsPosInf = 0xFF800000u; // order_bits(-inf), order_bits(+inf)
-
-__device__ __forceinline__ uint64_t sel_key(float f, uint32_t idx) { return ((uint64_t)order_bits(f) << 32) | idx; }
-
-// the least key that is >= t and that compares like t against every key that exists: bits below -inf's hold no key, and
-// neither does 0x7FFFFFFF (-0 is keyed as +0)
-__device__ __forceinline__ uint64_t spl_normalise(uint64_t t)
-{
-    const uint32_t b = (uint32_t)(t >> 32);
-    if (b < kSplBitsNegInf) return (uint64_t)kSplBitsNegInf << 32;
-    if (b == 0x7FFFFFFFu) return (uint64_t)0x80000000u << 32;
-    return t;
-}
-
-constexpr uint32_t kBktMaxBuckets = kSelListMaxBuckets; // bounds a bucketing workgroup keeps in LDS (2 KiB)
-static_assert(kBktMaxBuckets % kWave == 0, "a lane looks at kBktMaxBuckets / 64 bounds");
-
-// The slot made non-decreasing exactly as k_sel_splitters makes it (t_0 = 0, running maximum, spl_normalise), into
-// bnd: ONE wavefront, in front of a workgroup barrier.  Bound q's fitness bits lie at bnd[q], its row index at
-// bnd[kBktMaxBuckets + q].  Bound 0 and those from B on are ~0, a bound no key reaches: the bucket of a key is then the
-// number of bounds t_q <= key.
-__device__ __forceinline__ void bkt_bounds(const uint64_t *__restrict__ slot, uint32_t B, uint32_t *__restrict__ bnd, uint32_t lane)
-{
-    constexpr uint32_t C = kBktMaxBuckets / kWave;
-    unsigned long long v[C], carry = 0;
-#pragma unroll
-    for (uint32_t c = 0; c < C; ++c) {
-        const uint32_t q = c * kWave + lane;
-        v[c] = q && q < B ? slot[q] : 0ull;
-    }
-#pragma unroll
-    for (uint32_t c = 0; c < C; ++c) {
-        unsigned long long x = v[c];
-#pragma unroll
-        for (uint32_t m = 1; m < kWave; m <<= 1) {
-            const unsigned long long y = __shfl_up(x, m);
-            if (lane >= m && y > x) x = y;
-        }
-        x = x > carry ? x : carry;
-        carry = __shfl(x, kWave - 1);
-        const uint32_t q = c * kWave + lane;
-        const uint64_t t = q && q < B ? spl_normalise(x) : ~0ull;
-        bnd[q] = (uint32_t)(t >> 32);
-        bnd[kBktMaxBuckets + q] = (uint32_t)t;
-    }
-}
-
-// a key on its way into its bucket's list: key and segment (bucket * kSelListShards + shard) wavefront-uniform, pos lane
-// 0's (the counter's answer)
-struct BktPend {
-    uint64_t key;
-    uint32_t seg, pos;
-};
-constexpr uint32_t kBktNone = 0xFFFFFFFFu; // BktPend::seg: nothing on its way
-
-// the store that a visit left behind: the counter has answered by now
-__device__ __forceinline__ void bkt_flush(const SelLists &bk, const BktPend &pd, uint32_t lane)
-{
-    if (pd.seg != kBktNone && lane == 0 && pd.pos < kSelListSeg) bk.lists[(size_t)pd.seg * kSelListSeg + pd.pos] = pd.key;
-}
-// One wavefront-uniform key: the full 64-bit compare against every bound (in a tie population the row index decides),
-// a lane taking kBktMaxBuckets / 64 of them; the ballots' population counts add up to the bucket.  The fitness bits are
-// compared first, and the row indices only where a bound has the key's fitness bits (wavefront-uniform).  A CLOSED bucket
-// (j < B - 1) counts the key in the caller's shard - every key, also beyond the segment's capacity - and the key is stored
-// at the counter's answer by the NEXT visit (or bkt_flush): the answer then never stalls the caller's loop.  The open
-// last bucket does nothing: it is P minus the closed ones, and while a run improves it is a third of the population.
-// The count is an atomicInc that never wraps, not an atomicAdd: the compiler aggregates additions of a uniform value over
-// the wavefront and WAITS for the answer on the spot (s_waitcnt vmcnt(0): the caller's rows in flight with it).
-__device__ __forceinline__ void bkt_visit(const SelLists &bk, const uint32_t *__restrict__ bnd, uint64_t key, uint32_t shard, uint32_t lane,
-                                          BktPend &pd)
-{
-    bkt_flush(bk, pd, lane);
-    const uint32_t kb = (uint32_t)(key >> 32), ki = (uint32_t)key;
-    uint32_t j = 0;
-    uint64_t ties[kBktMaxBuckets / kWave], any = 0;
-#pragma unroll
-    for (uint32_t c = 0; c < kBktMaxBuckets / kWave; ++c) {
-        const uint32_t hi = bnd[c * kWave + lane];
-        j += (uint32_t)__popcll(__ballot(hi < kb));
-        ties[c] = __ballot(hi == kb);
-        any |= ties[c];
-    }
-    if (any) {
-#pragma unroll
-        for (uint32_t c = 0; c < kBktMaxBuckets / kWave; ++c)
-            j += (uint32_t)__popcll(ties[c] & __ballot(bnd[kBktMaxBuckets + c * kWave + lane] <= ki));
-    }
-    pd.key = key;
-    pd.seg = j < bk.buckets - 1 ? j * kSelListShards + shard : kBktNone; // (buckets >= 2)
-    if (pd.seg != kBktNone && lane == 0) pd.pos = atomicInc(&bk.cnt[pd.seg], 0xFFFFFFFFu);
-}
-
-// MODE 0: write spectrum rows; MODE 1: accumulate the fitness directly
-// WIN: multiply by the fp32 window while loading (the generation loop then skips the window
-// pass; the product is the same single fp32 rounding either way).
-// Rows of N <= 1024 only (longer rows: k_fft_x).
-// W: wavefronts per workgroup, each transforming rows of its own.  W = 1: workgroup b takes rows b, b + grid, ... - small
-// populations, a wavefront wherever there is room.  W = 12 (N = 1024: what the registers let a CU hold, ONE workgroup per
-// CU): the workgroup's rows b + t grid are dealt to its wavefronts as they ask (an LDS counter; every grid-th row, so that
-// the whole GPU reads one moving window of the audio: a contiguous block of rows per workgroup is 8 % slower).  The SIMD issues for its
-// oldest wavefront first: with a fixed deal the three wavefronts of a SIMD finish their equal shares one after the
-// other and the last one runs alone, far below the issue rate (k_fft_x below has the numbers).
-// SEG (chunks in flight, sots_batch): the rows belong to consecutive chunks of equal size, each with a target of its own;
-// `target` is then a segmented target image (seg_target_rows / seg_target_chunk above) and every row reads its chunk's bins
-// from it in global memory (L2) instead of the workgroup's one target in LDS.  Same arithmetic, same order.
-template <int LOG2N> constexpr int fft_wide_waves() { return LOG2N == 10 ? 12 : 16; }
-// The lists are one more kernel argument of the BUCKET instantiation ONLY (the first of the trailing arguments, kernels/objective.h):
-// the others keep their argument list, and with it their code, to the byte (an argument in front of the hidden ones moves those).
-struct BktNoLists {};
-// BUCKET (the wide fitness kernel in front of a one-launch selection, list mode): every row's key goes into the list of
-// its bucket between the splitters of bk.slot (bkt_visit above) - the slot was written a generation ago, the row's
-// fitness is in a register here, and the selection's 256 workgroups no longer ask all P rows each.
-// OBJ (MODE 1): the objective; the log instantiations take the floor as their last argument (bin_error, kernels/objective.h)
-// WGT (MODE 1): per-bin weights; the table u[N/2] is then the very last argument (bin_error2, kernels/objective.h).  Without SEG it sits
-// in LDS beside the target, one float2 {target, u} per bin; with SEG the chunk's target is read from global memory as
-// ever and u - one table for all chunks - sits in LDS on its own (read from global memory beside the target, the
-// one-wavefront form needed 188 registers and lost its third wavefront per SIMD).
-template <int LOG2N, int MODE, bool WIN, int W = 1, bool SEG = false, bool BUCKET = false, int OBJ = kObjMagnitude, bool WGT = false, typename... LISTS>
-__global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audio, float *__restrict__ spectrum,
-                                                   const float *__restrict__ target, float *__restrict__ fitness,
-                                                   const float2 *__restrict__ tw, const float *__restrict__ window,
-                                                   uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch, LISTS... lists)
-{
-    static_assert(sizeof...(LISTS) == (BUCKET ? 1 : 0) + (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the BUCKET instantiation takes the lists, the log ones the floor, the weighted ones their table, the others nothing");
-    static_assert((OBJ == kObjMagnitude && !WGT) || MODE == 1, "the objective belongs to the fitness epilogue");
-    static_assert(!WGT || WIN, "the weighted forms exist with a window only");
-    [[maybe_unused]] const auto bk = trailing<SelLists>(BktNoLists{}, lists...);
-    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, lists...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, lists...);
-    constexpr int N = 1 << LOG2N, M = N / 2, E = M / kWave, H = E / 2;
-    static_assert(LOG2N == 9 || LOG2N == 10, "wavefront-per-row FFT is for N <= 1024");
-    static_assert(!BUCKET || (MODE == 1 && W > 1 && !SEG), "keys are filed by the wide fitness kernel only");
-    __shared__ uint32_t bnd_s[BUCKET ? 2 * kBktMaxBuckets : 1];
-    __shared__ float2 lds_all[W][M + M / 8 + 1];
-    __shared__ uint32_t next_s;
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-    float2 *const lds = lds_all[wave];
-    const float half_scale = 0.5f * (inv_n * inv_wf); // the split below leaves a factor of two in
-    const int partner_addr = ((kWave - lane) & (kWave - 1)) * 4; // ds_bpermute byte address of lane 64-l
-    // buffer b0 starts with take `wave`, b1 with take W + wave; take t is row blockIdx.x + t grid
-    const uint32_t grid = gridDim.x;
-    uint32_t ind = blockIdx.x + wave * grid;
-    if (W == 1 && ind >= p_len) return;
-    // Three row buffers rotate (no copies): two rows are in flight beside the one being
-    // transformed - a row's transform is shorter than the loaded memory latency, and the registers
-    // are there (168 = three wavefronts per SIMD).
-    constexpr int Q = E / 2; // rows are read 16 bytes per lane: pair index lane + 64 h holds complex points 2(lane+64h), +1
-    auto request = [&](float4 (&dst)[Q], uint32_t r) { // rows past the end re-read the current one
-        const float4 *__restrict__ in = reinterpret_cast<const float4 *>(audio + (size_t)(r < p_len ? r : ind) * pitch);
-#pragma unroll
-        for (int h = 0; h < Q; ++h) dst[h] = SOTS_ROW_LOAD(in + lane + kWave * h);
-    };
-    // The first two rows are asked for BEFORE the tables below: they need nothing but ind, p_len and pitch, and the
-    // memory side then moves rows while the tables arrive.  What this buys is limited: loads return in order, so the
-    // wait of the target's copy into LDS in front of the barrier (vmcnt(0)) now also waits for both rows - the barrier
-    // stands behind the row latency instead of the row requests behind the barrier - and window and twiddles are still a
-    // round trip of their own behind it.  Every table load stands behind the requests in the queue and is used before
-    // the first row is, so the loop's waits still count row loads only.  A wavefront whose first row lies past the end
-    // returns behind the barrier with two requests in flight: harmless, they read the workgroup's own first row
-    // (blockIdx.x < p_len: no more workgroups than rows).
-    float4 b0[Q], b1[Q], b2[Q];
-    uint32_t r0 = ind, r1 = blockIdx.x + (W + wave) * grid, r2; // the rows in the three buffers
-    const uint32_t first = ind < p_len ? ind : blockIdx.x;
-    request(b0, first);
-    asm volatile("" ::: "memory"); // keep the two requests in this order (the loop's waits count on it)
-    request(b1, r1 < p_len ? r1 : first);
-    asm volatile("" ::: "memory"); // ... and the tables behind them
-    if (threadIdx.x == 0) next_s = 2 * W;
-
-    // per-lane constants of the split / fitness step, loaded once (nothing but the audio
-    // prefetch is in flight inside the loop, so its waits never drain the prefetch)
-    float2 w_split[H];
-#pragma unroll
-    for (int q = 0; q < H; ++q) w_split[q] = tw[lane + kWave * q];
-    // the target spectrum sits in LDS (2N bytes): eight registers fewer than holding this lane's
-    // bins, which is what keeps N = 1024 at three wavefronts per SIMD with two rows in flight
-    __shared__ float tgt_s[MODE == 1 && !SEG && !WGT ? M + 1 : 1];
-    __shared__ float2 tu_s[MODE == 1 && !SEG && WGT ? M + 1 : 1]; // (weighted: {target, u} of a bin in one 8-byte read)
-    __shared__ float u_s[MODE == 1 && SEG && WGT ? M + 1 : 1];
-    if constexpr (MODE == 1 && SEG && WGT) {
-        for (int k = threadIdx.x; k < M; k += W * kWave) u_s[k] = wgt_u[k];
-    }
-    if constexpr (MODE == 1 && !SEG && WGT) {
-        for (int k = threadIdx.x; k < M; k += W * kWave) tu_s[k] = make_float2(target[k], wgt_u[k]);
-    } else if constexpr (MODE == 1 && !SEG) {
-        for (int k = threadIdx.x; k < M; k += W * kWave) tgt_s[k] = target[k];
-    }
-    const uint32_t seg_rows = SEG ? seg_target_rows(target) : 1u;
-    if constexpr (BUCKET) {
-        if (wave == W - 1) bkt_bounds(bk.slot, bk.buckets, bnd_s, lane); // (a wavefront of the workgroup's last rows)
-    }
-    if constexpr (MODE == 1 || W > 1) __syncthreads(); // (the only workgroup barrier: target, row counter and bounds are there)
-    if (ind >= p_len) return;
-
-    float4 wv[WIN ? Q : 1];
-    if constexpr (WIN) {
-#pragma unroll
-        for (int h = 0; h < Q; ++h) wv[h] = reinterpret_cast<const float4 *>(window)[lane + kWave * h];
-    }
-    float2 twr[tw_count<M>()];
-    preload_twiddles<M>(twr, tw, lane);
-    // transforms the row in `cur` (individual `ind`) after requesting row ind + 2 grid into `fill`
-#ifdef SOTS_STAMP
-    unsigned long long st_wait = 0, st_fft = 0, st_tail = 0, st_rows = 0;
-    const uint32_t st_slot = blockIdx.x * W + wave;
-    const unsigned long long st_begin = __builtin_amdgcn_s_memrealtime(); // 100 MHz, common to the whole chip
-    const unsigned long long st_begin_clk = __builtin_amdgcn_s_memtime();
-#define SOTS_FFT_T(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
-#else
-#define SOTS_FFT_T(var)
-#endif
-#ifdef SOTS_STAMP_ENDS
-    // light stamps (no per-phase timers: the register allocation stays the product's): when every wavefront starts its
-    // first row and ends, and how many rows it took (tools/fft_ends_probe.py)
-    const unsigned long long se_begin = __builtin_amdgcn_s_memrealtime();
-    uint32_t se_rows = 0;
-#endif
-    uint32_t pend = 0, dealt = 2; // the take on its way (lane 0) / W = 1: takes so far
-    auto next_take = [&]() {
-        if constexpr (W == 1) return dealt++;
-        else {
-            const uint32_t t = __builtin_amdgcn_readfirstlane(pend);
-            if (lane == 0) pend = atomicAdd(&next_s, 1u); // answered during this row's transform
-            return t;
-        }
-    };
-    if constexpr (W > 1) {
-        if (lane == 0) pend = atomicAdd(&next_s, 1u);
-    }
-    BktPend bkt = {0ull, kBktNone, 0u}; // the key whose place in its list is on its way (BUCKET)
-    // transforms the row in `cur` (row `ind`) after requesting this wavefront's next take into `fill`; returns that row
-    auto process = [&](float4 (&cur)[Q], float4 (&fill)[Q]) -> uint32_t {
-        SOTS_FFT_T(t0);
-#ifdef SOTS_STAMP
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Q) : "memory"); // the row in `cur` has landed (the newer request may still fly)
-#endif
-        SOTS_FFT_T(t1);
-        if constexpr (WIN) {
-#pragma unroll
-            for (int h = 0; h < Q; ++h) { // two packed multiplies per 16 bytes
-                const v2f_t lo = v2f_t{cur[h].x, cur[h].y} * v2f_t{wv[h].x, wv[h].y}, hi = v2f_t{cur[h].z, cur[h].w} * v2f_t{wv[h].z, wv[h].w};
-                cur[h] = make_float4(lo.x, lo.y, hi.x, hi.y);
-            }
-        }
-        const uint32_t filled = blockIdx.x + next_take() * grid;
-        request(fill, filled);
-#ifdef SOTS_STAMP_ENDS
-        ++se_rows;
-#endif
-        float2 z[E]; // z[s] = Z[lane + 64 s]
-        fft_forward<M, W == 1>(cur, lds, tw, twr, lane, z);
-        SOTS_FFT_T(t2);
-        // bin M/2 = conj Z[M/2]; Z[M/2] = Z[0 + 64 (E/2)] is lane 0's slot E/2, and only lane 0 (k = 0) uses it
-        const float2 x_half = make_float2(z[E / 2].x, -z[E / 2].y);
-        if constexpr (MODE == 0) {
-            float2 *__restrict__ row = reinterpret_cast<float2 *>(spectrum + (size_t)ind * (N + 8));
-#pragma unroll
-            for (int q = 0; q < H; ++q) {
-                const int k = lane + kWave * q;
-                v2f_t xa2, xbc2;
-                split_pair_2x(z[q], split_partner<M>(z, q, lane, partner_addr), w_split[q], xa2, xbc2);
-                row[k] = make_float2(0.5f * xa2.x, 0.5f * xa2.y);
-                row[M - k] = make_float2(0.5f * xbc2.x, -0.5f * xbc2.y); // k = 0 lands on the Nyquist bin M
-            }
-            if (lane == 0) row[M / 2] = x_half;
-        } else {
-            v2f_t acc2 = v2f_t{0.0f, 0.0f};
-            const float *__restrict__ tg = SEG ? seg_target_chunk(target, ind / seg_rows, M) : nullptr;
-#pragma unroll
-            for (int q = 0; q < H; ++q) {
-                const int k = lane + kWave * q;
-                v2f_t xa2, xbc2;
-                split_pair_2x(z[q], split_partner<M>(z, q, lane, partner_addr), w_split[q], xa2, xbc2); // 2 X[k], 2 conj X[M-k]
-                if (k == 0) xbc2 = v2f_t{2.0f * x_half.x, 2.0f * x_half.y}; // the fitness skips the Nyquist bin and needs bin M/2
-                if constexpr (WGT) {
-                    const int k2 = k == 0 ? M / 2 : M - k;
-                    if constexpr (SEG) {
-                        bin_error2<OBJ, true>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tg[k], tg[k2], half_scale, floor_eps, u_s[k], u_s[k2]);
-                        if constexpr (W == 1) __builtin_amdgcn_sched_barrier(0); // (the one-wavefront form: read ahead, the weights cost the third wavefront per SIMD)
-                    }
-                    else {
-                        const float2 ta = tu_s[k], tb = tu_s[k2];
-                        bin_error2<OBJ, true>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), ta.x, tb.x, half_scale, floor_eps, ta.y, tb.y);
-                    }
-                } else
-                if constexpr (SEG) bin_error2<OBJ, false>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tg[k], tg[k == 0 ? M / 2 : M - k], half_scale, floor_eps, 0.0f, 0.0f);
-                else bin_error2<OBJ, false>(acc2, make_float2(xa2.x, xa2.y), make_float2(xbc2.x, xbc2.y), tgt_s[k], tgt_s[k == 0 ? M / 2 : M - k], half_scale, floor_eps, 0.0f, 0.0f);
-            }
-            float acc = wave_sum(acc2.x + acc2.y);
-            if (lane == 0) fitness[ind] = acc;
-            if constexpr (BUCKET) {
-                // (uniform by construction; said to the compiler so that key and bucket stay in scalar registers)
-                const uint32_t kb = __builtin_amdgcn_readfirstlane(order_bits(acc));
-                bkt_visit(bk, bnd_s, ((uint64_t)kb << 32) | ind, blockIdx.x % kSelListShards, lane, bkt);
-            }
-        }
-        wave_lds_sync<W == 1>(); // orders this row's LDS reads before the next row's writes
-#ifdef SOTS_STAMP
-        {
-            const unsigned long long t3 = __builtin_amdgcn_s_memtime();
-            if (st_rows == 0 && lane == 0 && st_slot < 512) g_stamps[3 * 8192 + st_slot * 16 + 7] = t0 - st_begin_clk; // prologue
-            st_wait += t1 - t0, st_fft += t2 - t1, st_tail += t3 - t2, st_rows += 1;
-            if (lane == 0 && st_slot < 512) {
-                g_stamps[3 * 8192 + st_slot * 16 + 0] = st_wait;
-                g_stamps[3 * 8192 + st_slot * 16 + 1] = st_fft;
-                g_stamps[3 * 8192 + st_slot * 16 + 2] = st_tail;
-                g_stamps[3 * 8192 + st_slot * 16 + 3] = st_rows;
-                g_stamps[3 * 8192 + st_slot * 16 + 4] = st_begin;
-                g_stamps[3 * 8192 + st_slot * 16 + 5] = __builtin_amdgcn_s_memrealtime();
-                g_stamps[3 * 8192 + st_slot * 16 + 6] = __builtin_amdgcn_s_memtime() - st_begin_clk;
-            }
-        }
-#endif
-        return filled;
-    };
-    while (true) { // (takes only grow: a wavefront whose next row is past the end has no later one either)
-        ind = r0, r2 = process(b0, b2);
-        if (r1 >= p_len) break;
-        ind = r1, r0 = process(b1, b0);
-        if (r2 >= p_len) break;
-        ind = r2, r1 = process(b2, b1);
-        if (r0 >= p_len) break;
-    }
-    if constexpr (BUCKET) bkt_flush(bk, bkt, lane);
-#ifdef SOTS_STAMP_ENDS
-    if (lane == 0 && blockIdx.x * W + wave < 4096) {
-        unsigned long long *o = g_stamps + (blockIdx.x * W + wave) * 4;
-        o[0] = se_begin, o[1] = __builtin_amdgcn_s_memrealtime(), o[2] = se_rows, o[3] = __builtin_amdgcn_s_getreg(4 | (0 << 6) | ((16 - 1) << 11)); // HW_ID: wave, SIMD, CU, SH, SE
-    }
-#endif
-}
-
-// fitnessPopulation on materialised spectrum rows; same bin -> lane assignment and
-// summation order as k_fft<.., 1>, so both paths give the same fp32 sum.
-template <int LOG2N, int OBJ = kObjMagnitude, bool WGT = false, typename... FLOOR>
-__global__ __launch_bounds__(kWave) void k_fitness(const float *__restrict__ spectrum,
-                                                   const float *__restrict__ target,
-                                                   float *__restrict__ fitness, uint32_t p_len, float inv_n,
-                                                   float inv_wf, FLOOR... floor)
-{
-    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the log instantiation takes the floor, the weighted one its table");
-    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, floor...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, floor...);
-    constexpr int N = 1 << LOG2N, M = N / 2, E = M / kWave;
-    const int lane = threadIdx.x;
-    for (uint32_t ind = blockIdx.x; ind < p_len; ind += gridDim.x) {
-        const float2 *__restrict__ row = reinterpret_cast<const float2 *>(spectrum + (size_t)ind * (N + 8));
-        v2f_t acc2 = v2f_t{0.0f, 0.0f};
-#pragma unroll
-        for (int q = 0; q < E / 2; ++q) {
-            const int k = lane + kWave * q;
-            const int kb = k == 0 ? M / 2 : M - k;
-            bin_error2<OBJ, WGT>(acc2, row[k], row[kb], target[k], target[kb], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f, WGT ? wgt_u[kb] : 0.0f);
-        }
-        float acc = wave_sum(acc2.x + acc2.y);
-        if (lane == 0) fitness[ind] = acc;
-    }
-}
-
-#pragma clang fp contract(off)
-
-// ------------------------------------------------------------------------------------
-// sortPopulation, ocl_program.cl:664-711 (rank sort) / Population::bubbleSortPopulation,
-// Evolutionary_Strategy.hpp:108-124.  Ascending by fitness, equal fitness keeps the lower
-// original index first (the CPU's stable order), NaN after every number.  Implemented as a
-// bitonic network over unique 64-bit keys (order-preserving fitness bits << 32 | index).
-// ------------------------------------------------------------------------------------
-// ---- island exchange inside the kernels that move the sorted rows (SortExchange, sots_kernels.h) -------------
-// a destination row that belongs to an immigrant: the local row that sorted there is NOT written
-__device__ __forceinline__ bool ex_immigrant_row(const SortExchange &ex, uint32_t dst)
-{
-    return ex.imm != nullptr && dst - ex.imm_first < ex.imm_rows;
-}
-// element `c` (0..d-1 values, d..2d-1 steps, 2d fitness) of destination row dst also goes to the packed elite rows
-__device__ __forceinline__ void ex_sink(const SortExchange &ex, uint32_t dst, uint32_t c, uint32_t d, float v)
-{
-    if (dst < ex.sink_rows) ex.sink[(size_t)dst * (2 * d + 1) + (c == 2 * d ? 0u : c + 1u)] = v;
-}
-// the immigrant rows themselves (k_unpack_rows' copy), by the threads of ONE workgroup
-__device__ __forceinline__ void ex_unpack(const SortExchange &ex, float *__restrict__ vout, float *__restrict__ sout,
-                                          float *__restrict__ fout, uint32_t d, uint32_t tid, uint32_t threads)
-{
-    if (ex.imm == nullptr) return;
-    const uint32_t w = 2 * d + 1, total = ex.imm_rows * w;
-    for (uint32_t e = tid; e < total; e += threads) {
-        const uint32_t r = e / w, c = e - r * w, dst = ex.imm_first + r;
-        const uint32_t sr = r < ex.skip_first ? r : r + ex.skip_count;
-        const float v = ex.imm[(size_t)sr * w + c]; // packed rows: [fitness, values.., steps..]
-        if (c == 0) fout[dst] = v;
-        else if (c <= d) vout[(size_t)dst * d + (c - 1)] = v;
-        else sout[(size_t)dst * d + (c - 1 - d)] = v;
-        if (dst < ex.sink_rows) ex.sink[(size_t)dst * w + c] = v;
-    }
-}
-
-constexpr int kSortThreads = 1024;
-constexpr uint32_t kSortTile = 4096; // keys per LDS tile (32 KiB)
-constexpr uint32_t kSortSmall = 1024; // populations sorted by one workgroup in one launch (k_sort_small)
-
-__device__ __forceinline__ uint64_t make_key(float f, uint32_t idx)
-{
-    uint32_t u;
-    if (f != f) {
-        u = 0xFFFFFFFFu;
-    } else {
-        u = __float_as_uint(f == 0.0f ? 0.0f : f);
-        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    return ((uint64_t)u << 32) | idx;
-}
-
-// Padding slot g >= P of the power-of-two key array: after every real key (NaN included) and
-// unique, which the counting merges rely on.
-__device__ __forceinline__ uint64_t pad_key(uint32_t g) { return 0xFFFFFFFF00000000ull | g; }
-
-__device__ __forceinline__ void cmp_swap(uint64_t &a, uint64_t &b, bool ascending)
-{
-    if ((a > b) == ascending) {
-        const uint64_t t = a;
-        a = b;
-        b = t;
-    }
-}
-
-// Builds the keys of one tile and sorts it completely (all steps with k <= tile).
-__global__ __launch_bounds__(kSortThreads) void k_sort_tiles(const float *__restrict__ fitness,
-                                                             uint64_t *__restrict__ keys, uint32_t p_len,
-                                                             uint32_t tile, uint32_t alternate)
-{
-    __shared__ uint64_t s[kSortTile];
-    const uint32_t base = blockIdx.x * tile;
-    // alternate != 0: odd tiles end up descending, ready for further global bitonic merges;
-    // alternate == 0: every tile ascending (rank merge)
-    const uint32_t dir_base = alternate ? base : 0u;
-    for (uint32_t i = threadIdx.x; i < tile; i += blockDim.x) {
-        const uint32_t g = base + i;
-        s[i] = g < p_len ? make_key(fitness[g], g) : pad_key(g);
-    }
-    __syncthreads();
-    for (uint32_t k = 2; k <= tile; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            for (uint32_t t = threadIdx.x; t < tile / 2; t += blockDim.x) {
-                const uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const uint32_t hi = lo | j;
-                const bool asc = (((dir_base + lo) & k) == 0);
-                uint64_t a = s[lo], b = s[hi];
-                cmp_swap(a, b, asc);
-                s[lo] = a;
-                s[hi] = b;
-            }
-            __syncthreads();
-        }
-    }
-    for (uint32_t i = threadIdx.x; i < tile; i += blockDim.x) keys[base + i] = s[i];
-}
-
-// 1024-key tile for the rank merge, without workgroup barriers in the sorting network: each
-// of the four wavefronts bitonic-sorts its own run of 256 keys in its private quarter of the
-// LDS buffer (the LDS operations of one wavefront execute in order, so the 36 steps need no
-// s_barrier), then every key's place in the tile is its index in its own run plus its lower
-// bound in the other three runs (24 LDS reads), the same counting argument as the tile merge.
-constexpr uint32_t kRunKeys = 256;
-
-__global__ __launch_bounds__(256) void k_sort_tiles_1k(const float *__restrict__ fitness,
-                                                       uint64_t *__restrict__ keys, uint32_t p_len)
-{
-    __shared__ uint64_t runs[4 * kRunKeys];
-    __shared__ uint64_t merged[4 * kRunKeys];
-    const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const uint32_t base = blockIdx.x * 4 * kRunKeys + wave * kRunKeys;
-    uint64_t *__restrict__ run = runs + wave * kRunKeys;
-#pragma unroll
-    for (uint32_t r = 0; r < kRunKeys / kWave; ++r) {
-        const uint32_t i = lane + kWave * r, g = base + i;
-        run[i] = g < p_len ? make_key(fitness[g], g) : pad_key(g);
-    }
-    for (uint32_t k = 2; k <= kRunKeys; k <<= 1) {
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            __builtin_amdgcn_wave_barrier();
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (uint32_t r = 0; r < kRunKeys / 2 / kWave; ++r) {
-                const uint32_t t = lane + kWave * r;
-                const uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-                const uint32_t hi = lo | j;
-                uint64_t a = run[lo], b = run[hi];
-                cmp_swap(a, b, (lo & k) == 0);
-                run[lo] = a;
-                run[hi] = b;
-            }
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (uint32_t r = 0; r < kRunKeys / kWave; ++r) {
-        const uint32_t i = lane + kWave * r;
-        const uint64_t x = run[i];
-        uint32_t rank = i;
-#pragma unroll
-        for (uint32_t o = 1; o < 4; ++o) {
-            const uint64_t *__restrict__ other = runs + ((wave + o) & 3u) * kRunKeys;
-            uint32_t pos = 0;
-#pragma unroll
-            for (uint32_t step = kRunKeys >> 1; step >= 1; step >>= 1) pos += (other[pos + step - 1] < x) ? step : 0u;
-            rank += pos + ((other[pos] < x) ? 1u : 0u);
-        }
-        merged[rank] = x;
-    }
-    __syncthreads();
-    uint64_t *__restrict__ out = keys + (size_t)blockIdx.x * 4 * kRunKeys;
-    for (uint32_t i = threadIdx.x; i < 4 * kRunKeys; i += 256) out[i] = merged[i];
-}
-
-// One compare-exchange step (k, j) with j >= tile, over the whole padded array.
-__global__ __launch_bounds__(256) void k_sort_global_step(uint64_t *__restrict__ keys, uint32_t n_pad,
-                                                          uint32_t k, uint32_t j)
-{
-    for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n_pad / 2; t += gridDim.x * blockDim.x) {
-        const uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const uint32_t hi = lo | j;
-        const bool asc = ((lo & k) == 0);
-        uint64_t a = keys[lo], b = keys[hi];
-        cmp_swap(a, b, asc);
-        keys[lo] = a;
-        keys[hi] = b;
-    }
-}
-
-// The remaining steps j = tile/2 .. 1 of merge size k, tile-local.
-__global__ __launch_bounds__(kSortThreads) void k_sort_tile_merge(uint64_t *__restrict__ keys, uint32_t k,
-                                                                  uint32_t tile)
-{
-    __shared__ uint64_t s[kSortTile];
-    const uint32_t base = blockIdx.x * tile;
-    for (uint32_t i = threadIdx.x; i < tile; i += blockDim.x) s[i] = keys[base + i];
-    __syncthreads();
-    const bool asc = ((base & k) == 0); // k > tile: the direction is uniform over the tile
-    for (uint32_t j = tile >> 1; j > 0; j >>= 1) {
-        for (uint32_t t = threadIdx.x; t < tile / 2; t += blockDim.x) {
-            const uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-            const uint32_t hi = lo | j;
-            uint64_t a = s[lo], b = s[hi];
-            cmp_swap(a, b, asc);
-            s[lo] = a;
-            s[hi] = b;
-        }
-        __syncthreads();
-    }
-    for (uint32_t i = threadIdx.x; i < tile; i += blockDim.x) keys[base + i] = s[i];
-}
-
-// ---- rank merge of sorted tiles ------------------------------------------------------
-// With T sorted tiles of unique keys, the final position of a key is the number of keys
-// below it = its index in its own tile + sum over the other tiles of lower_bound(tile, key).
-// Workgroup (a, b) stages tile b in LDS and binary-searches every key of tile a in it;
-// the T partial counts per key are then summed by the scatter kernel, which moves the
-// (2D+1)-float row straight to its final place.  Two launches instead of the ~15 of the
-// global bitonic steps, and every CU is busy.
-constexpr int kRankThreads = 256;
-constexpr uint32_t kRankGroup = 8;      // tiles staged in LDS per workgroup (tile = 1024: 64 KiB)
-constexpr uint32_t kRankLdsKeys = 8192; // LDS capacity in keys
-
-// Workgroup (a, g): keys of tile a against tiles [g*GROUP, (g+1)*GROUP); writes one partial
-// count per key of a.  Keys are unique, so against its own tile a key's lower bound is its
-// sorted index and no tile needs a special case.  The tiles are staged by LDS-DMA (all pieces
-// in flight at once) and the GROUP x 4 binary searches of a thread advance together, one level
-// per trip, so a trip has GROUP x 4 independent LDS reads in flight instead of 4.
-// MERGE (large populations, first of two levels): the grid has one workgroup per tile, which ranks its
-// keys inside its OWN group of GROUP tiles only and writes them to their place in the group's
-// sorted run of GROUP * tile keys (merged[]); the second level then ranks runs instead of tiles.
-template <uint32_t GROUP, bool MERGE = false>
-__global__ __launch_bounds__(kRankThreads) void k_sort_rank_pairs(const uint64_t *__restrict__ keys,
-                                                                  uint16_t *__restrict__ partial,
-                                                                  uint32_t n_pad, uint32_t tile,
-                                                                  uint64_t *__restrict__ merged = nullptr)
-{
-    __shared__ uint64_t s[kRankLdsKeys];
-    const uint32_t a = blockIdx.x, g = MERGE ? blockIdx.x / GROUP : blockIdx.y;
-    const uint64_t *__restrict__ kb = keys + (size_t)g * GROUP * tile;
-    {
-        typedef __attribute__((address_space(3))) void *lds_ptr_t;
-        const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave), lane = threadIdx.x & (kWave - 1);
-        constexpr uint32_t kChunk = kWave * 2; // keys per wavefront instruction (16 B per lane)
-        for (uint32_t ch = wave; ch < GROUP * tile / kChunk; ch += kRankThreads / kWave)
-            __builtin_amdgcn_global_load_lds(kb + ch * kChunk + lane * 2u, (lds_ptr_t)(s + ch * kChunk), 16, 0, 0);
-        __builtin_amdgcn_s_waitcnt(0); // the copies have landed
-    }
-    __syncthreads();
-    const uint64_t *__restrict__ ka = keys + (size_t)a * tile;
-    uint16_t *__restrict__ out = partial + (size_t)g * n_pad + (size_t)a * tile;
-    for (uint32_t i0 = threadIdx.x; i0 < tile; i0 += 4 * kRankThreads) {
-        uint64_t x[4];
-        uint32_t pos[GROUP][4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t i = i0 + q * kRankThreads;
-            x[q] = i < tile ? ka[i] : 0ull;
-#pragma unroll
-            for (uint32_t bb = 0; bb < GROUP; ++bb) pos[bb][q] = 0;
-        }
-        for (uint32_t step = tile >> 1; step >= 1; step >>= 1) {
-#pragma unroll
-            for (uint32_t bb = 0; bb < GROUP; ++bb)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) pos[bb][q] += (s[bb * tile + pos[bb][q] + step - 1] < x[q]) ? step : 0u;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            uint32_t total = 0;
-#pragma unroll
-            for (uint32_t bb = 0; bb < GROUP; ++bb) total += pos[bb][q] + ((s[bb * tile + pos[bb][q]] < x[q]) ? 1u : 0u);
-            const uint32_t i = i0 + q * kRankThreads;
-            if constexpr (MERGE) {
-                if (i < tile) merged[(size_t)g * GROUP * tile + total] = x[q];
-            } else {
-                if (i < tile) out[i] = (uint16_t)total;
-            }
-        }
-    }
-}
-
-// 64 consecutive slots of the tile-sorted key array per workgroup: four quarter-sums of the
-// partial counts per slot (all 256 lanes load), then the rows move to their final places.
-__global__ __launch_bounds__(kRankThreads) void k_sort_rank_scatter(const uint64_t *__restrict__ keys,
-                                                                    const uint16_t *__restrict__ partial,
-                                                                    const float *__restrict__ vin,
-                                                                    const float *__restrict__ sin,
-                                                                    const float *__restrict__ fin,
-                                                                    float *__restrict__ vout, float *__restrict__ sout,
-                                                                    float *__restrict__ fout, uint32_t n_pad,
-                                                                    uint32_t groups, uint32_t p_len, uint32_t d,
-                                                                    uint32_t first_row, SortExchange ex)
-{
-    constexpr uint32_t kSlots = 64;
-    if (blockIdx.x == 0) ex_unpack(ex, vout, sout, fout, d, threadIdx.x, kRankThreads);
-    __shared__ uint32_t part[4][kSlots];
-    __shared__ uint32_t src_row[kSlots];
-    const uint32_t j = threadIdx.x & (kSlots - 1), quarter = threadIdx.x / kSlots;
-    const uint32_t e = blockIdx.x * kSlots + j;
-    uint32_t sum = 0;
-    for (uint32_t g = quarter; g < groups; g += 4) sum += partial[(size_t)g * n_pad + e];
-    part[quarter][j] = sum;
-    if (quarter == 0) src_row[j] = (uint32_t)keys[e]; // >= P for padding keys
-    __syncthreads();
-    const uint32_t w = 2 * d + 1;
-    for (uint32_t t = threadIdx.x; t < kSlots * w; t += kRankThreads) {
-        const uint32_t jj = t / w, c = t - jj * w;
-        const uint32_t src = src_row[jj];
-        if (src >= p_len) continue;
-        const uint32_t dst = part[0][jj] + part[1][jj] + part[2][jj] + part[3][jj];
-        if (dst < first_row) continue; // rows the selection kernels have already placed
-        if (ex_immigrant_row(ex, dst)) continue;
-        const float v = c < d ? vin[(size_t)src * d + c] : c < 2 * d ? sin[(size_t)src * d + (c - d)] : fin[src];
-        if (c < d) vout[(size_t)dst * d + c] = v;
-        else if (c < 2 * d) sout[(size_t)dst * d + (c - d)] = v;
-        else fout[dst] = v;
-        ex_sink(ex, dst, c, d, v);
-    }
-}
-
-// Row r of the new half <- row (keys[r] & 0xffffffff) of the old half.
-__global__ __launch_bounds__(256) void k_sort_gather(const uint64_t *__restrict__ keys,
-                                                     const float *__restrict__ vin,
-                                                     const float *__restrict__ sin,
-                                                     const float *__restrict__ fin, float *__restrict__ vout,
-                                                     float *__restrict__ sout, float *__restrict__ fout,
-                                                     uint32_t p_len, uint32_t d, uint32_t first_row, SortExchange ex)
-{
-    const uint32_t w = 2 * d + 1;
-    const uint32_t total = p_len * w;
-    if (blockIdx.x == 0) ex_unpack(ex, vout, sout, fout, d, threadIdx.x, blockDim.x);
-    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x + first_row * w; e < total; e += gridDim.x * blockDim.x) {
-        const uint32_t r = e / w, c = e - r * w;
-        if (ex_immigrant_row(ex, r)) continue;
-        const uint32_t src = (uint32_t)keys[r];
-        const float v = c < d ? vin[(size_t)src * d + c] : c < 2 * d ? sin[(size_t)src * d + (c - d)] : fin[src];
-        if (c < d) vout[(size_t)r * d + c] = v;
-        else if (c < 2 * d) sout[(size_t)r * d + (c - d)] = v;
-        else fout[r] = v;
-        ex_sink(ex, r, c, d, v);
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// Selection for the fused generation loop: the best `need` rows IN ORDER and nothing else.
-// The next recombination reads whole parent blocks only (recombine_source above,
-// ocl_program.cl:99-112), so inside sots_execute_generations the order of the other rows is
-// never looked at; the full order is produced (by launch_sort, from the untouched unsorted half)
-// when somebody reads the population.  Rows 0..need-1 are bit-identical to the full sort's.
-//
-// Two launches.  k_sel_tiles sorts tiles of 1024 (fitness bits, index) keys: one key per lane,
-// 16 wavefronts sort 64 keys each in registers (bitonic network over lane exchanges, no LDS
-// traffic, no barrier), then every key's place in the tile is its lane plus its lower bound in
-// the other 15 runs.  It writes the sorted fitness bits and indices as two u32 arrays and, per
-// tile, the four keys at positions 255, 511, 767, 1023 ("samples").
-// k_sel_rank_scatter (one workgroup per CU) finds v* = the ceil(need/256)-th smallest sample:
-// at least need keys are <= v*, and every key <= v* lies in its tile's first
-// 256 * (samples_t <= v*) + 256 positions.  Only those prefixes (need + 256 * tiles keys when
-// there are no ties: 128 KiB at P = 65536) are staged in LDS as 4-byte fitness bits; a staged key's
-// rank is the sum of its lower bounds in every staged prefix, and keys whose rank is below `need`
-// move their rows.  Tiles are contiguous index ranges, so "equal fitness, lower index first" needs
-// no index in LDS: against an EARLIER tile an equal key counts (<=), against a LATER one it does
-// not (<).  Keys above v* get ranks >= need (every key <= v* is staged and there are >= need of
-// them), so no check can fail and there is no fallback path; prefixes that exceed the LDS are staged
-// in several passes.
-// ------------------------------------------------------------------------------------
-constexpr uint32_t kSelTile = 1024, kSelSamples = 4, kSelQuantum = kSelTile / kSelSamples;
-constexpr uint32_t kSelThreads = 1024, kSelLanesPerKey = 8, kSelKeysPerRound = kSelThreads / kSelLanesPerKey;
-constexpr uint32_t kSelCap = 35328;                 // staged keys per pass: 138 KiB of LDS
-constexpr uint32_t kSelSkew = 4;                    // consecutive tiles start 4 more words (16 B) off the 1 KiB grid, see below
-// the rank kernel handles 16..64 tiles of 1024 keys (P <= 65536) and, for P = 131072, 32 tiles of 4096 keys merged four by
-// four (k_sel_merge4).  Same-box A/B of the un-instrumented loop (profiles/r03_experiments.md): at P = 131072 the selection
-// beats the two-level full sort (237 against 244 us per generation), at 262144 it loses (496 against 482), so it stops at 128 tiles
-constexpr uint32_t kSelMinTiles = 16, kSelMaxTiles = 128, kSelMaxOwn = 512; // kSelMaxTiles: tiles the rank kernel handles (of either size)
-
-
-template <uint32_t K, uint32_t J>
-__device__ __forceinline__ void bitonic_step(uint32_t &b, uint32_t &i, uint32_t lane)
-{
-    const uint32_t pb = lane_xor<J>(b), pi = lane_xor<J>(i);
-    const bool keep_min = ((lane & J) == 0) == ((lane & K) == 0);
-    const bool mine_less = b < pb || (b == pb && i < pi);
-    if (keep_min != mine_less) {
-        b = pb;
-        i = pi;
-    }
-}
-template <uint32_t K, uint32_t J>
-__device__ __forceinline__ void bitonic_merge(uint32_t &b, uint32_t &i, uint32_t lane)
-{
-    bitonic_step<K, J>(b, i, lane);
-    if constexpr (J > 1) bitonic_merge<K, J / 2>(b, i, lane);
-}
-
-// SPLIT workgroups per tile (blockIdx = tile + part * tiles): a tile is 16 wavefronts on ONE CU, and with the 64 tiles of
-// P = 65536 three quarters of the GPU idle while each of those CUs answers 1440 wavefront-wide LDS reads of the searches.
-// Every workgroup of a tile sorts all 16 runs (the searches need them; the register network is cheap), then only the
-// wavefronts of ITS runs - a quarter, one per SIMD - search and write.
-#ifndef SOTS_SEL_SPLIT
-#define SOTS_SEL_SPLIT 4
-#endif
-template <uint32_t SPLIT>
-__global__ __launch_bounds__(kSelTile) void k_sel_tiles(const float *__restrict__ fitness, uint32_t *__restrict__ kbits,
-                                                         uint32_t *__restrict__ kidx, uint32_t *__restrict__ samples,
-                                                         uint32_t p_len, uint32_t tiles)
-{
-    constexpr uint32_t kRuns = kSelTile / kWave;
-    __shared__ uint32_t runs[kSelTile];
-    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-    const uint32_t tile = SPLIT == 1 ? blockIdx.x : blockIdx.x % tiles, part = SPLIT == 1 ? 0u : blockIdx.x / tiles;
-    const uint32_t g = tile * kSelTile + tid;
-    SOTS_PHASE_BEGIN();
-    uint32_t b = g < p_len ? order_bits(fitness[g]) : kSelPadBits, i = g; // padding keys sort last, by index
-#ifdef SOTS_STAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the stamp below then includes the fitness load
-#endif
-    SOTS_PHASE(8);
-    bitonic_merge<2, 1>(b, i, lane);
-    bitonic_merge<4, 2>(b, i, lane);
-    bitonic_merge<8, 4>(b, i, lane);
-    bitonic_merge<16, 8>(b, i, lane);
-    bitonic_merge<32, 16>(b, i, lane);
-    bitonic_merge<64, 32>(b, i, lane);
-    runs[tid] = b;
-    __syncthreads();
-    SOTS_PHASE(9);
-    if (SPLIT > 1 && wave / (kRuns / SPLIT) != part) return;
-    // place in the tile = lane + lower bounds in the other 15 runs, all 15 searches advanced level by level so
-    // that the LDS reads of a level are in flight together.  A run of an earlier wavefront holds lower indices,
-    // so its equal keys come first (count <=, i.e. < b + 1), a later run's do not (<).
-    uint32_t pos[kRuns], thr[kRuns]; // absolute positions in runs[]; "entries below thr" is what is counted
-#pragma unroll
-    for (uint32_t w = 0; w < kRuns; ++w) {
-        pos[w] = w * kWave;
-        thr[w] = w == wave ? 0u : b + (w < wave ? 1u : 0u); // own run: nothing counts (the lane is added below)
-    }
-#pragma unroll
-    for (uint32_t step = kWave / 2; step >= 1; step >>= 1) {
-#pragma unroll
-        for (uint32_t w = 0; w < kRuns; ++w) pos[w] += runs[pos[w] + step - 1] < thr[w] ? step : 0u;
-    }
-    uint32_t rank = lane;
-#pragma unroll
-    for (uint32_t w = 0; w < kRuns; ++w) rank += pos[w] - w * kWave + (runs[pos[w]] < thr[w] ? 1u : 0u);
-    SOTS_PHASE(10);
-    const size_t o = (size_t)tile * kSelTile + rank;
-    kbits[o] = b;
-    kidx[o] = i;
-    if ((rank & (kSelQuantum - 1)) == kSelQuantum - 1) {
-        samples[tile * kSelSamples + rank / kSelQuantum] = b;
-        samples[tiles * kSelSamples + tile * kSelSamples + rank / kSelQuantum] = i; // indices behind all the bits
-    }
-    SOTS_PHASE(11);
-}
-
-// A whole population of at most 1024 rows in ONE launch and one workgroup (the reference's default sizes are this
-// small, and there a launch costs as much as the sort): k_sel_tiles' network - one key per lane, 64-key runs sorted in
-// registers, a key's place = its lane + its lower bounds in the other runs - and then the workgroup moves the rows,
-// a lane per output element.  Same order as the full sort: fitness, equal fitness by index, NaN last.
-// SEG (chunks in flight): workgroup b sorts the b-th block of p_len rows, the grid one workgroup per chunk.
-template <uint32_t RUNS, bool SEG = false>
-__global__ __launch_bounds__(RUNS *kWave) void k_sort_small(const float *__restrict__ vin, const float *__restrict__ sin,
-                                                            const float *__restrict__ fin, float *__restrict__ vout,
-                                                            float *__restrict__ sout, float *__restrict__ fout,
-                                                            uint32_t p_len, uint32_t d, uint32_t first_row, SortExchange ex)
-{
-    if constexpr (SEG) {
-        const size_t rows = (size_t)blockIdx.x * p_len;
-        vin += rows * d, sin += rows * d, fin += rows;
-        vout += rows * d, sout += rows * d, fout += rows;
-    }
-    __shared__ uint32_t runs[RUNS * kWave], from[RUNS * kWave];
-    ex_unpack(ex, vout, sout, fout, d, threadIdx.x, RUNS * kWave);
-    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-    uint32_t b = tid < p_len ? order_bits(fin[tid]) : kSelPadBits, i = tid;
-    bitonic_merge<2, 1>(b, i, lane);
-    bitonic_merge<4, 2>(b, i, lane);
-    bitonic_merge<8, 4>(b, i, lane);
-    bitonic_merge<16, 8>(b, i, lane);
-    bitonic_merge<32, 16>(b, i, lane);
-    bitonic_merge<64, 32>(b, i, lane);
-    uint32_t rank = lane;
-    if constexpr (RUNS > 1) {
-        runs[tid] = b;
-        __syncthreads();
-        uint32_t pos[RUNS], thr[RUNS];
-#pragma unroll
-        for (uint32_t w = 0; w < RUNS; ++w) {
-            pos[w] = w * kWave;
-            thr[w] = w == wave ? 0u : b + (w < wave ? 1u : 0u);
-        }
-#pragma unroll
-        for (uint32_t step = kWave / 2; step >= 1; step >>= 1) {
-#pragma unroll
-            for (uint32_t w = 0; w < RUNS; ++w) pos[w] += runs[pos[w] + step - 1] < thr[w] ? step : 0u;
-        }
-#pragma unroll
-        for (uint32_t w = 0; w < RUNS; ++w) rank += pos[w] - w * kWave + (runs[pos[w]] < thr[w] ? 1u : 0u);
-    }
-    // from[place] = the row that sorted there (padding keys sort behind every row).  The rows then move with lane =
-    // OUTPUT element: a wavefront's stores are consecutive addresses and its loads runs of d consecutive floats - one
-    // workgroup is one CU's address path, and a lane-per-row move (64 cache lines per instruction, 2 d + 1
-    // instructions each way) took twice as long as the sort itself at d = 12.
-    from[rank] = i;
-    __syncthreads();
-    constexpr uint32_t T = RUNS * kWave;
-    if (tid < p_len && tid >= first_row && !ex_immigrant_row(ex, tid)) {
-        const float f = fin[from[tid]];
-        fout[tid] = f;
-        ex_sink(ex, tid, 2 * d, d, f);
-    }
-    const uint32_t qd = T / d, rd = T - qd * d; // uniform: one scalar division per launch
-    uint32_t r = tid / d, c = tid - r * d;
-    while (r < p_len) { // four elements per trip, their loads in flight together
-        uint32_t dst[4], row[4];
-        float v[4], s[4];
-        bool ok[4];
-#pragma unroll
-        for (uint32_t q = 0; q < 4; ++q) {
-            row[q] = r, dst[q] = r * d + c;
-            ok[q] = r < p_len && r >= first_row && !ex_immigrant_row(ex, r);
-            if (ok[q]) {
-                const uint32_t src = from[r] * d + c;
-                v[q] = vin[src], s[q] = sin[src];
-            }
-            r += qd, c += rd;
-            if (c >= d) c -= d, ++r;
-        }
-#pragma unroll
-        for (uint32_t q = 0; q < 4; ++q)
-            if (ok[q]) {
-                const uint32_t cq = dst[q] - row[q] * d;
-                vout[dst[q]] = v[q], sout[dst[q]] = s[q];
-                ex_sink(ex, row[q], cq, d, v[q]), ex_sink(ex, row[q], d + cq, d, s[q]);
-            }
-    }
-}
-
-// Four neighbouring sorted tiles of 1024 keys -> one sorted tile of 4096 with a sample every 512 keys.  For
-// populations of 128 k and more the rank kernel's work (staged keys x tiles x search depth) is quartered by
-// having a quarter of the tiles.  One workgroup per group of four: the 4096 fitness-bit words sit in LDS, a key's
-// place = its position in its own tile + its lower bounds in the three siblings (earlier tile: <=, later: <).
-constexpr uint32_t kSelBigTile = 4 * kSelTile, kSelBigQuantum = 512, kSelBigSamples = kSelBigTile / kSelBigQuantum;
-
-__global__ __launch_bounds__(kSelTile) void k_sel_merge4(const uint32_t *__restrict__ kbits, const uint32_t *__restrict__ kidx,
-                                                          uint32_t *__restrict__ obits, uint32_t *__restrict__ oidx,
-                                                          uint32_t *__restrict__ samples)
-{
-    __shared__ uint32_t s[kSelBigTile];
-    const uint32_t tid = threadIdx.x;
-    const size_t base = (size_t)blockIdx.x * kSelBigTile;
-    uint32_t b[4], i[4];
-#pragma unroll
-    for (uint32_t t = 0; t < 4; ++t) { // thread `tid` holds position `tid` of each of the four tiles
-        b[t] = kbits[base + t * kSelTile + tid];
-        i[t] = kidx[base + t * kSelTile + tid];
-        s[t * kSelTile + tid] = b[t];
-    }
-    __syncthreads();
-    uint32_t pos[4][4], thr[4][4]; // [own tile][sibling]: absolute search positions in s[]
-#pragma unroll
-    for (uint32_t t = 0; t < 4; ++t)
-#pragma unroll
-        for (uint32_t u = 0; u < 4; ++u) {
-            pos[t][u] = u * kSelTile;
-            thr[t][u] = u == t ? 0u : b[t] + (u < t ? 1u : 0u); // bits <= 0xFFFFFFFE: no wrap
-        }
-#pragma unroll
-    for (uint32_t step = kSelTile / 2; step >= 1; step >>= 1) {
-#pragma unroll
-        for (uint32_t t = 0; t < 4; ++t)
-#pragma unroll
-            for (uint32_t u = 0; u < 4; ++u)
-                if (u != t) pos[t][u] += s[pos[t][u] + step - 1] < thr[t][u] ? step : 0u;
-    }
-    const uint32_t ns = gridDim.x * kSelBigSamples;
-#pragma unroll
-    for (uint32_t t = 0; t < 4; ++t) {
-        uint32_t rank = tid;
-#pragma unroll
-        for (uint32_t u = 0; u < 4; ++u)
-            if (u != t) rank += pos[t][u] - u * kSelTile + (s[pos[t][u]] < thr[t][u] ? 1u : 0u);
-        obits[base + rank] = b[t];
-        oidx[base + rank] = i[t];
-        if ((rank & (kSelBigQuantum - 1)) == kSelBigQuantum - 1) {
-            samples[blockIdx.x * kSelBigSamples + rank / kSelBigQuantum] = b[t];
-            samples[ns + blockIdx.x * kSelBigSamples + rank / kSelBigQuantum] = i[t];
-        }
-    }
-}
-
-constexpr uint32_t kSelChains = 8; // tiles searched together by one lane (independent LDS reads in flight)
-
-// TILE keys per sorted tile, a sample every QUANT keys (1024 / 256 straight from k_sel_tiles; 4096 / 512 after
-// k_sel_merge4 for populations whose 1024-key tiles would be too many); R samples per lane = tiles * (TILE / QUANT) / 64
-// LPK lanes share a key's searches, each kSelChains tiles at a time: 8 for the 64 tiles of the 1024-key layout, 4 for
-// the <= 20 big tiles a pass stages (with 8, three quarters of the search chains would run empty)
-template <uint32_t R, uint32_t TILE, uint32_t QUANT, uint32_t LPK>
-__global__ __launch_bounds__(kSelThreads) void k_sel_rank_scatter(const uint32_t *__restrict__ kbits,
-                                                                  const uint32_t *__restrict__ kidx,
-                                                                  const uint32_t *__restrict__ samples,
-                                                                  const float *__restrict__ vin,
-                                                                  const float *__restrict__ sin,
-                                                                  const float *__restrict__ fin,
-                                                                  float *__restrict__ vout, float *__restrict__ sout,
-                                                                  float *__restrict__ fout, uint32_t tiles, uint32_t need,
-                                                                  uint32_t p_len, uint32_t d, SortExchange ex, uint32_t whole_tiles)
-{
-    constexpr uint32_t kWaves = kSelThreads / kWave;
-    if (blockIdx.x == 0) ex_unpack(ex, vout, sout, fout, d, threadIdx.x, kSelThreads);
-    // the names of the 1024 / 256 layout, shadowed by this instantiation's values
-    constexpr uint32_t kSelTile = TILE, kSelQuantum = QUANT, kSelSamples = TILE / QUANT;
-    // a tile whose prefix STARTS inside the window fits whole, skew included (at most window / QUANT tiles per pass)
-    constexpr uint32_t kSelWindow = TILE == 1024 ? 33536 : 30720;
-    static_assert(kSelWindow + kSelTile + kSelSkew * (kSelWindow / kSelQuantum) <= kSelCap, "staging buffer too small");
-    static_assert(R * kWave <= kSelMaxTiles * sots::kSelSamples, "sample store too small");
-    __shared__ __attribute__((aligned(16))) uint32_t staged[kSelCap];
-    __shared__ __attribute__((aligned(16))) uint32_t smp[kSelMaxTiles * sots::kSelSamples], smi[kSelMaxTiles * sots::kSelSamples];
-    __shared__ uint32_t off[kSelMaxTiles + 1]; // first staged position of each tile, all passes concatenated
-    __shared__ uint16_t chunk_tile[kSelMaxTiles * sots::kSelSamples]; // tile of every QUANT staged positions
-    // LDS place of tile t's prefix in its pass: off[t] - w0 + kSelSkew * (t - ta).  Prefix lengths are multiples
-    // of 256 words, so without the skew every prefix would start on bank 0 and the first binary-search levels
-    // (positions 511, 255, 127, 63, 31 of eight different tiles in one instruction) would all hit bank 31.
-    __shared__ uint32_t own_bits[kSelMaxOwn], own_tile[kSelMaxOwn], own_pos[kSelMaxOwn], own_rank[kSelMaxOwn], own_src[kSelMaxOwn];
-    __shared__ uint32_t wave_tot[kWaves];
-    __shared__ unsigned long long vstar_s;
-    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-    const uint32_t ns = tiles * kSelSamples;
-    SOTS_PHASE_BEGIN();
-
-    // ---- v* = the k-th smallest sample, k = ceil(need / 256), in (fitness bits, index) order: with the
-    // index in the comparison, equal fitness values (a converged population is full of them) cannot
-    // inflate the staged prefixes.  Every lane holds R = ns / 64 samples in registers; wavefront w ranks the
-    // samples held by lanes 4w .. 4w+3: one sample at a time is broadcast as a SCALAR and compared with all
-    // ns samples by R 64-bit vector compares whose lane masks are counted by s_bcnt1 - 64 comparisons per
-    // vector instruction and no per-lane counters (a lane-per-pair count costs several times the vector work).
-    // whole_tiles > 0 (a population of at most 8 real tiles, padded to 16): the real tiles are staged whole and the tiles of
-    // padding not at all - no samples to fetch, no v* to rank (2.6 us in front of the copies), and every key's rank is exact
-    if (whole_tiles == 0)
-        for (uint32_t e = tid; e < ns; e += kSelThreads) {
-            smp[e] = samples[e];
-            smi[e] = samples[ns + e];
-        }
-    const uint32_t kth = (need + kSelQuantum - 1) / kSelQuantum;
-    if (whole_tiles != 0) {
-        if (tid == 0) vstar_s = ~0ull;
-    } else if (kth > ns) {
-        if (tid == 0) vstar_s = ~0ull; // more rows wanted than the samples can vouch for: stage everything
-    } else {
-        unsigned long long key[R]; // (bits << 32) | index: unique, so the ranks are a permutation
-#pragma unroll
-        for (uint32_t r = 0; r < R; ++r)
-            key[r] = ((unsigned long long)samples[lane + kWave * r] << 32) | samples[ns + lane + kWave * r];
-#pragma unroll
-        for (uint32_t r = 0; r < R; ++r) {
-#pragma unroll
-            for (uint32_t l = 0; l < 4; ++l) {
-                const uint32_t src_lane = 4u * wave + l;
-                const unsigned long long v = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(key[r] >> 32), (int)src_lane) << 32) |
-                                             (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)key[r], (int)src_lane);
-                uint32_t below = 0;
-#pragma unroll
-                for (uint32_t r2 = 0; r2 < R; ++r2) below += (uint32_t)__popcll(__ballot(key[r2] < v));
-                if (below == kth - 1 && lane == 0) vstar_s = v; // exactly one sample has this rank
-            }
-        }
-    }
-    __syncthreads();
-    SOTS_PHASE(1);
-    const uint32_t vstar_b = (uint32_t)(vstar_s >> 32), vstar_i = (uint32_t)vstar_s;
-
-    // ---- staged prefix of every tile (256, 512, 768 or 1024 keys), exclusive scan -> off[] ---------
-    {
-        uint32_t quanta = 0; // prefix length / 256
-        if (whole_tiles != 0) {
-            quanta = tid < whole_tiles ? kSelSamples : 0u;
-        } else if (tid < tiles) {
-            uint32_t m = 0;
-#pragma unroll
-            for (uint32_t j = 0; j < kSelSamples; ++j) {
-                const uint32_t sb = smp[tid * kSelSamples + j], si = smi[tid * kSelSamples + j];
-                m += (sb < vstar_b || (sb == vstar_b && si <= vstar_i)) ? 1u : 0u;
-            }
-            quanta = m >= kSelSamples ? kSelSamples : m + 1u;
-        }
-        // prefix sum inside the wavefront from four ballots (quanta is 0..4), across wavefronts through LDS
-        uint32_t before_lane = 0, wave_sum = 0;
-#pragma unroll
-        for (uint32_t q = 1; q <= kSelSamples; ++q) {
-            const uint64_t mask = __ballot(quanta >= q);
-            before_lane += __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-            wave_sum += (uint32_t)__popcll(mask);
-        }
-        if (lane == 0) wave_tot[wave] = wave_sum;
-        __syncthreads();
-        uint32_t before = before_lane;
-        for (uint32_t w = 0; w < wave; ++w) before += wave_tot[w];
-        if (tid < tiles) {
-            off[tid + 1] = (before + quanta) * kSelQuantum;
-            for (uint32_t q = 0; q < quanta; ++q) chunk_tile[before + q] = (uint16_t)tid;
-        }
-        if (tid == 0) off[0] = 0;
-    }
-    __syncthreads();
-    SOTS_PHASE(2);
-    const uint32_t total = off[tiles];
-
-    // ---- this workgroup's keys: an equal share of the staged positions.  Their fitness bits and row
-    // indices are requested now and land while the prefixes are staged -------------------------------
-    const uint32_t share = (total + gridDim.x - 1) / gridDim.x; // <= kSelMaxOwn by the launcher's grid
-    uint32_t my_tile = 0xFFFFFFFFu, my_pos = 0, my_bits = 0xFFFFFFFFu, my_src = 0; // slot `tid`
-    {
-        const uint32_t g = blockIdx.x * share + tid;
-        if (tid < share && g < total) {
-            my_tile = chunk_tile[g / kSelQuantum];
-            my_pos = g - off[my_tile];
-            my_bits = kbits[(size_t)my_tile * kSelTile + my_pos];
-            my_src = kidx[(size_t)my_tile * kSelTile + my_pos];
-        }
-    }
-    SOTS_PHASE(3);
-
-    // ---- passes over the staged prefixes ---------------------------------------------------------
-    typedef __attribute__((address_space(3))) void *lds_ptr_t;
-    const uint32_t sub = tid & (kSelLanesPerKey - 1);
-    constexpr uint32_t kRowRounds = kSelMaxOwn / kSelKeysPerRound, kColsPerLane = (2 * SOTS_MAX_DIMS + 1 + kSelLanesPerKey - 1) / kSelLanesPerKey;
-    float val[kRowRounds][kColsPerLane];
-    const uint32_t passes = off[tiles - 1] / kSelWindow + 1;
-    uint32_t ta = 0;
-    for (uint32_t pass = 0; pass < passes; ++pass) {
-        const uint32_t w0 = pass * kSelWindow;
-        // first tile that starts at or beyond the end of this window: tiles [ta, tb) are staged
-        uint32_t tb = tiles;
-        if (w0 + kSelWindow < total) {
-            const uint32_t t = chunk_tile[(w0 + kSelWindow) / kSelQuantum]; // the tile that owns that position
-            tb = off[t] == w0 + kSelWindow ? t : t + 1;
-        }
-        if (pass) __syncthreads(); // the previous pass's searches are done with the staging buffer
-        // wavefront w copies tiles ta + w, ta + w + 16, ...: lane m fetches the bounds of the m-th of them, then
-        // the copies are issued back to back with wavefront-uniform (readlane) arguments
-        {
-            const uint32_t mine = ta + wave + lane * kWaves;
-            const uint32_t b0 = mine < tb ? off[mine] : 0u, b1 = mine < tb ? off[mine + 1] : 0u;
-            uint32_t m = 0;
-            for (uint32_t tt = ta + wave; tt < tb; tt += kWaves, ++m) {
-                const uint32_t o0 = (uint32_t)__builtin_amdgcn_readlane((int)b0, (int)m), o1 = (uint32_t)__builtin_amdgcn_readlane((int)b1, (int)m);
-                const uint32_t *__restrict__ src = kbits + (size_t)tt * kSelTile;
-                for (uint32_t e = 0; e < o1 - o0; e += 4 * kWave) // a multiple of 256: whole wavefront instructions
-                    __builtin_amdgcn_global_load_lds(src + e + 4 * lane, (lds_ptr_t)(staged + (o0 - w0) + kSelSkew * (tt - ta) + e), 16, 0, 0);
-            }
-        }
-        if (pass == 0) { // the own-key loads were issued before the copies, so they have landed too
-            const bool live = my_tile != 0xFFFFFFFFu && my_bits != kSelPadBits; // padding keys move nothing
-            if (tid < kSelMaxOwn) {
-                own_tile[tid] = live ? my_tile : 0xFFFFFFFFu;
-                own_pos[tid] = my_pos;
-                own_bits[tid] = my_bits;
-                own_src[tid] = my_src;
-                own_rank[tid] = 0;
-            }
-        }
-        SOTS_PHASE(4);
-        __builtin_amdgcn_s_waitcnt(0); // vmcnt(0): this wavefront's copies have landed
-        __syncthreads();
-        SOTS_PHASE(5);
-        if (pass == 0) {
-            // the rows of this workgroup's keys are requested now, before it is known which of them made it (about
-            // half do): the loads fly while the ranks are computed, eight lanes per key, lane `sub` holding row
-            // elements sub, sub + 8, ...
-#pragma unroll
-            for (uint32_t r = 0; r < kRowRounds; ++r) {
-                const uint32_t slot = r * kSelKeysPerRound + tid / kSelLanesPerKey;
-                if (slot >= share || own_tile[slot] == 0xFFFFFFFFu) continue;
-                const uint32_t src = own_src[slot];
-#pragma unroll
-                for (uint32_t q = 0; q < kColsPerLane; ++q) {
-                    const uint32_t c = sub + q * kSelLanesPerKey;
-                    if (c < d) val[r][q] = vin[(size_t)src * d + c];
-                    else if (c < 2 * d) val[r][q] = sin[(size_t)src * d + (c - d)];
-                    else if (c < 2 * d + 1) val[r][q] = fin[src];
-                }
-            }
-        }
-        for (uint32_t r0 = 0; r0 < share; r0 += kSelThreads / LPK) {
-            const uint32_t slot = r0 + tid / LPK, ssub = tid % LPK;
-            const uint32_t t_own = slot < share ? own_tile[slot] : 0xFFFFFFFFu;
-            const bool live = t_own != 0xFFFFFFFFu;
-            const uint32_t xb = live ? own_bits[slot] : 0u, pos_own = live ? own_pos[slot] : 0u;
-            uint32_t count = 0;
-            // kSelChains tiles per lane at a time, their binary searches advanced level by level.  A search keeps
-            // the ABSOLUTE position in staged[] (one add less per step).
-            for (uint32_t t0 = ta + ssub; t0 < tb; t0 += LPK * kSelChains) {
-                uint32_t base[kSelChains], n[kSelChains], thr[kSelChains], p[kSelChains];
-#pragma unroll
-                for (uint32_t m = 0; m < kSelChains; ++m) {
-                    const uint32_t tt = t0 + m * LPK;
-                    const bool in = tt < tb && live;
-                    const uint32_t o0 = in ? off[tt] : w0, o1 = in ? off[tt + 1] : w0;
-                    base[m] = o0 - w0 + (in ? kSelSkew * (tt - ta) : 0u);
-                    n[m] = o1 - o0;
-                    thr[m] = in ? xb + (tt < t_own ? 1u : 0u) : 0u; // xb <= 0xFFFFFFFD for a live key: no wrap; never 0
-                    p[m] = base[m];
-                }
-                // levels of a quantum or more: only while the step stays inside the prefix (prefix lengths are
-                // multiples of the quantum, not powers of two)
-#pragma unroll
-                for (uint32_t step = kSelTile / 2; step >= kSelQuantum; step >>= 1) {
-#pragma unroll
-                    for (uint32_t m = 0; m < kSelChains; ++m)
-                        p[m] += (p[m] + step <= base[m] + n[m] && staged[p[m] + step - 1] < thr[m]) ? step : 0u;
-                }
-                // a search that has reached the end of its prefix stops (threshold 0: nothing compares below it)
-#pragma unroll
-                for (uint32_t m = 0; m < kSelChains; ++m) thr[m] = p[m] - base[m] >= n[m] ? 0u : thr[m];
-#pragma unroll
-                for (uint32_t step = kSelQuantum / 2; step >= 1; step >>= 1) {
-#pragma unroll
-                    for (uint32_t m = 0; m < kSelChains; ++m) p[m] += staged[p[m] + step - 1] < thr[m] ? step : 0u;
-                }
-#pragma unroll
-                for (uint32_t m = 0; m < kSelChains; ++m) {
-                    const uint32_t tt = t0 + m * LPK;
-                    const uint32_t lb = p[m] - base[m] + (staged[p[m]] < thr[m] ? 1u : 0u);
-                    count += (tt == t_own && tt < tb) ? pos_own : lb; // the own tile counts in the pass that stages it
-                }
-            }
-            count += lane_xor<1>(count);
-            if constexpr (LPK >= 4) count += lane_xor<2>(count);
-            if constexpr (LPK == 8) count += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)count, 0x141, 0xf, 0xf, false); // row_half_mirror
-            static_assert(LPK == 2 || LPK == 4 || LPK == 8, "the partial counts are added over 2, 4 or 8 neighbouring lanes");
-            if (ssub == 0 && live) own_rank[slot] += count; // one writer per slot
-        }
-        ta = tb;
-    }
-    __syncthreads();
-    SOTS_PHASE(6);
-
-    // ---- rows of the keys that made it (requested above) -------------------------------------------
-    const uint32_t width = 2 * d + 1;
-#pragma unroll
-    for (uint32_t r = 0; r < kRowRounds; ++r) {
-        const uint32_t slot = r * kSelKeysPerRound + tid / kSelLanesPerKey;
-        if (slot >= share || own_tile[slot] == 0xFFFFFFFFu) continue;
-        const uint32_t dst = own_rank[slot];
-        if (dst >= need || ex_immigrant_row(ex, dst)) continue;
-#pragma unroll
-        for (uint32_t q = 0; q < kColsPerLane; ++q) {
-            const uint32_t c = sub + q * kSelLanesPerKey;
-            if (c < d) vout[(size_t)dst * d + c] = val[r][q];
-            else if (c < 2 * d) sout[(size_t)dst * d + (c - d)] = val[r][q];
-            else if (c < width) fout[dst] = val[r][q];
-            if (c < width) ex_sink(ex, dst, c, d, val[r][q]);
-        }
-    }
-    SOTS_PHASE(7);
-}
-
-// ------------------------------------------------------------------------------------
-// The selection in ONE launch, ranked between stored splitters.
-//
-// Keys are (order_bits(fitness) << 32) | row index: unique, ties by index, NaN last.  The slot holds B = gridDim.x
-// 64-bit splitters; every workgroup makes them non-decreasing the same way (t_0 = 0, running maximum), so the buckets
-// [t_j, t_{j+1}) - the last one open - are disjoint and cover every key WHATEVER the slot holds.  Workgroup j streams
-// all P fitness values once, counts the keys below t_j (c_j) and collects the keys of its bucket in LDS, sorts that
-// list (bitonic network in LDS) and has every key's final position: c_j + its place in the list.  Rows with a position
-// below `need` move; the keys at positions q * step become the next launch's splitters, written to the OTHER slot.
-// Good splitters (the previous generation's, a generation moves the distribution little) make small buckets; bad ones
-// only cost time: a bucket that outgrows the LDS list is collected again into keys_scratch[c_j ...] (the buckets'
-// places in the final order, so disjoint) and sorted there by its workgroup alone.  No workgroup waits for another.
-//
-// The stream compares in the float domain where both bounds are the bits of numbers: f < bound is order_bits(f) <
-// bits(bound), NaN compares false as its key lies above every number, and -0 = +0 both ways; the row index decides only
-// where a fitness EQUALS a bound (one wavefront-uniform branch).  Bounds above +inf (NaN keys, 0xFFFF...) take the
-// 64-bit compare.
-// ------------------------------------------------------------------------------------
-constexpr uint32_t kSplThreads = 1024;
-constexpr uint32_t kSplCap = 8192;       // keys of the LDS list (64 KiB)
-constexpr uint32_t kSplMaxBuckets = 1024; // splitters per slot (the grid is one workgroup per CU)
-constexpr uint32_t kSplAhead = 16;        // 16-byte loads per lane requested up front (64 registers)
-__device__ __forceinline__ float spl_bound_float(uint64_t t) // of a normalised bound with numeric bits
-{
-    const uint32_t b = (uint32_t)(t >> 32);
-    return __uint_as_float((b & 0x80000000u) ? b ^ 0x80000000u : ~b);
-}
-
-struct SplScan {
-    uint64_t lo, hi;
-    float lo_f, hi_f;
-    bool last; // the open bucket: no upper bound
-};
-
-// one key per lane: counts the keys below lo, appends the bucket's keys (LDS list while it has room; to `spill`, the
-// second time round, all of them)
-template <bool FLOATS>
-__device__ __forceinline__ void spl_visit(const SplScan &s, float f, uint32_t idx, bool valid, uint32_t &below,
-                                          uint32_t *__restrict__ n_s, uint64_t *__restrict__ list, uint64_t *__restrict__ spill)
-{
-    uint64_t b_lo, b_hi;
-    if constexpr (FLOATS) {
-        b_lo = __ballot(f < s.lo_f);
-        b_hi = s.last ? ~0ull : __ballot(f < s.hi_f);
-        const uint64_t eq_lo = __ballot(f == s.lo_f), eq_hi = s.last ? 0ull : __ballot(f == s.hi_f);
-        if (eq_lo | eq_hi) { // wavefront-uniform: somebody's fitness equals a bound, the index decides
-            b_lo |= eq_lo & __ballot(idx < (uint32_t)s.lo);
-            b_hi |= eq_hi & __ballot(idx < (uint32_t)s.hi);
-        }
-    } else {
-        const uint64_t key = sel_key(f, idx);
-        b_lo = __ballot(valid && key < s.lo);
-        b_hi = __ballot(valid && (s.last || key < s.hi));
-    }
-    below += (uint32_t)__popcll(b_lo);
-    const uint64_t in = b_hi & ~b_lo;
-    if (in) {
-        const uint32_t lane = threadIdx.x & (kWave - 1);
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(n_s, (uint32_t)__popcll(in));
-        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(in >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)in, 0u));
-        if ((in >> lane) & 1ull) {
-            const uint64_t key = sel_key(f, idx);
-            if (spill) spill[slot] = key;
-            else if (slot < kSplCap) list[slot] = key;
-        }
-    }
-}
-
-// all P keys past one workgroup; returns the wavefront's count of keys below lo
-template <bool FLOATS>
-__device__ __forceinline__ uint32_t spl_stream(const SplScan &s, const float *__restrict__ fin, uint32_t p_len, bool vec, uint32_t first,
-                                               uint32_t *__restrict__ n_s, uint64_t *__restrict__ list, uint64_t *__restrict__ spill)
-{
-    constexpr uint32_t kPerIter = 4 * kSplThreads, kBatch = 4;
-    const uint32_t tid = threadIdx.x;
-    uint32_t below = 0, done = first; // keys in front of `first` are done (vec: first == 0)
-    if (vec) { // whole iterations of 16 bytes per lane, four loads in flight
-        const uint32_t full = p_len / kPerIter;
-        uint32_t it = 0;
-        for (; it + kBatch <= full; it += kBatch) {
-            float4 q[kBatch];
-#pragma unroll
-            for (uint32_t u = 0; u < kBatch; ++u) q[u] = *reinterpret_cast<const float4 *>(fin + (size_t)(it + u) * kPerIter + 4 * tid);
-#pragma unroll
-            for (uint32_t u = 0; u < kBatch; ++u) {
-                const uint32_t i0 = (it + u) * kPerIter + 4 * tid;
-                spl_visit<FLOATS>(s, q[u].x, i0, true, below, n_s, list, spill);
-                spl_visit<FLOATS>(s, q[u].y, i0 + 1, true, below, n_s, list, spill);
-                spl_visit<FLOATS>(s, q[u].z, i0 + 2, true, below, n_s, list, spill);
-                spl_visit<FLOATS>(s, q[u].w, i0 + 3, true, below, n_s, list, spill);
-            }
-        }
-        for (; it < full; ++it) {
-            const uint32_t i0 = it * kPerIter + 4 * tid;
-            const float4 q = *reinterpret_cast<const float4 *>(fin + i0);
-            spl_visit<FLOATS>(s, q.x, i0, true, below, n_s, list, spill);
-            spl_visit<FLOATS>(s, q.y, i0 + 1, true, below, n_s, list, spill);
-            spl_visit<FLOATS>(s, q.z, i0 + 2, true, below, n_s, list, spill);
-            spl_visit<FLOATS>(s, q.w, i0 + 3, true, below, n_s, list, spill);
-        }
-        done = full * kPerIter;
-    }
-    // the rest one key per lane, with the 64-bit compare (it takes the lanes beyond the end as well)
-    for (uint32_t i0 = done; i0 < p_len; i0 += kSplThreads) { // workgroup-uniform trip count
-        const uint32_t idx = i0 + tid;
-        const bool valid = idx < p_len;
-        const float f = valid ? fin[idx] : 0.0f;
-        spl_visit<false>(s, f, idx, valid, below, n_s, list, spill);
-    }
-    return below;
-}
-
-// ---- the stream where both bounds are numbers: per key one compare and a per-lane count for "below lo", one compare
-// for "not above hi"; the keys that pass both - the bucket's, and the ties with either bound - are then decided by
-// their 64-bit keys.
-// a lane whose key passed both float compares (lo_f <= f <= hi_f): the bucket's, or a tie with one of the bounds, where
-// the row index decides - key < lo only if f == lo_f and the index is below lo's, key < hi unless f == hi_f and the index
-// is not below hi's.  A converged population ties by the thousand: every lane comes through here then.
-__device__ __forceinline__ void spl_candidate(const SplScan &s, float f, uint32_t idx, uint32_t &cnt, uint32_t *__restrict__ n_s,
-                                              uint64_t *__restrict__ list)
-{
-    const bool below = f == s.lo_f && idx < (uint32_t)s.lo;
-    cnt += below ? 1u : 0u;
-    if (!below && (f < s.hi_f || idx < (uint32_t)s.hi)) {
-        const uint32_t slot = atomicAdd(n_s, 1u);
-        if (slot < kSplCap) list[slot] = sel_key(f, idx);
-    }
-}
-template <bool COUNT_ONLY>
-__device__ __forceinline__ void spl_fast4(const SplScan &s, const float4 q, uint32_t i0, uint32_t &cnt, uint32_t *__restrict__ n_s,
-                                          uint64_t *__restrict__ list)
-{
-    const bool l0 = q.x < s.lo_f, l1 = q.y < s.lo_f, l2 = q.z < s.lo_f, l3 = q.w < s.lo_f;
-    cnt += (l0 ? 1u : 0u) + (l1 ? 1u : 0u) + (l2 ? 1u : 0u) + (l3 ? 1u : 0u);
-    if constexpr (COUNT_ONLY) { // the ties with lo that lie below it: by the row index
-        const uint32_t li = (uint32_t)s.lo;
-        const bool e0 = q.x == s.lo_f, e1 = q.y == s.lo_f, e2 = q.z == s.lo_f, e3 = q.w == s.lo_f;
-        if (e0 | e1 | e2 | e3)
-            cnt += (e0 && i0 < li ? 1u : 0u) + (e1 && i0 + 1 < li ? 1u : 0u) + (e2 && i0 + 2 < li ? 1u : 0u) + (e3 && i0 + 3 < li ? 1u : 0u);
-    } else {
-        // per lane, no ballots: a few lanes of a few wavefront instructions have a candidate while the splitters are good
-        const bool c0 = !l0 && q.x <= s.hi_f, c1 = !l1 && q.y <= s.hi_f, c2 = !l2 && q.z <= s.hi_f, c3 = !l3 && q.w <= s.hi_f;
-        if (c0 | c1 | c2 | c3) {
-            if (c0) spl_candidate(s, q.x, i0, cnt, n_s, list);
-            if (c1) spl_candidate(s, q.y, i0 + 1, cnt, n_s, list);
-            if (c2) spl_candidate(s, q.z, i0 + 2, cnt, n_s, list);
-            if (c3) spl_candidate(s, q.w, i0 + 3, cnt, n_s, list);
-        }
-    }
-}
-// the whole iterations of 16 bytes per lane (`full` of them).  The first kSplAhead were requested by the caller, all at
-// once, before it did anything else: with one or two kilobytes in flight per wavefront the stream ran at the latency of
-// four dependent batches, four times the time the data takes to arrive.  A population of 65 536 is exactly kSplAhead.
-template <bool COUNT_ONLY>
-__device__ __forceinline__ uint32_t spl_stream_fast(const SplScan &s, const float *__restrict__ fin, uint32_t full, const float4 (&pre)[kSplAhead],
-                                                    uint32_t &cnt, uint32_t *__restrict__ n_s, uint64_t *__restrict__ list)
-{
-    constexpr uint32_t kPerIter = 4 * kSplThreads;
-    const uint32_t tid = threadIdx.x;
-#pragma unroll
-    for (uint32_t u = 0; u < kSplAhead; ++u)
-        if (u < full) spl_fast4<COUNT_ONLY>(s, pre[u], u * kPerIter + 4 * tid, cnt, n_s, list);
-    for (uint32_t it = kSplAhead; it < full; ++it) {
-        const uint32_t i0 = it * kPerIter + 4 * tid;
-        spl_fast4<COUNT_ONLY>(s, *reinterpret_cast<const float4 *>(fin + i0), i0, cnt, n_s, list);
-    }
-    return full * kPerIter;
-}
-
-// ---- ordering up to 1024 keys, one per lane: the distances below 64 are lane exchanges in registers (k_sel_tiles'
-// network with the direction as an argument), the others go through LDS, written to one of two buffers in turn so
-// that a step needs one barrier
-template <uint32_t J>
-__device__ __forceinline__ void spl_reg_merge(uint32_t &b, uint32_t &i, uint32_t lane, bool asc)
-{
-    const uint32_t pb = lane_xor<J>(b), pi = lane_xor<J>(i);
-    const bool keep_min = ((lane & J) == 0) == asc;
-    const bool mine_less = b < pb || (b == pb && i < pi);
-    if (keep_min != mine_less) {
-        b = pb;
-        i = pi;
-    }
-    if constexpr (J > 1) spl_reg_merge<J / 2>(b, i, lane, asc);
-}
-
-__device__ __forceinline__ void spl_cmp_swap(uint64_t *__restrict__ a, uint32_t i, uint32_t l, bool ascending)
-{
-    const uint64_t x = a[i], y = a[l];
-    if ((x > y) == ascending) {
-        a[i] = y;
-        a[l] = x;
-    }
-}
-
-__global__ __launch_bounds__(kSplThreads) void k_sel_splitters(const float *__restrict__ vin, const float *__restrict__ sin,
-                                                                const float *__restrict__ fin, float *__restrict__ vout,
-                                                                float *__restrict__ sout, float *__restrict__ fout,
-                                                                const uint64_t *__restrict__ spl_in, uint64_t *__restrict__ spl_out,
-                                                                uint64_t *__restrict__ keys_scratch, uint32_t p_len, uint32_t need,
-                                                                uint32_t step, uint32_t d, SortExchange ex, uint32_t vec, SelLists bk)
-{
-    __shared__ __attribute__((aligned(16))) uint64_t list[kSplCap];
-    __shared__ unsigned long long bound_s[2];
-    __shared__ uint32_t n_s, c_s;
-    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
-    const uint32_t B = gridDim.x, j = blockIdx.x;
-    if (j == 0) ex_unpack(ex, vout, sout, fout, d, tid, kSplThreads);
-    SOTS_PHASE_BEGIN();
-    // the slot, then the stream, are requested before anything else (loads return in order: the bounds are made while the
-    // keys arrive)
-    const unsigned long long my_spl = tid && tid <= j + 1 && tid < B ? spl_in[tid] : 0ull; // B <= kSplThreads
-    // LIST MODE (bk.cnt): the kernel that made the fitness has filed every key under its bucket between these same
-    // splitters.  Instead of the stream: the closed buckets' counters - c is the sum of those in front, n the own one, the
-    // open bucket's the rest of P - and the own list, asked for at its full capacity before n is known (what lies
-    // beyond n is an older generation's and is never looked at).  The set the NEXT generation counts into is cleared here.
-    const bool by_list = bk.cnt != nullptr;
-    constexpr uint32_t kShardWords = kSelListShards / 4; // a bucket's counters, 16 bytes at a time
-    uint4 cnt_q[kShardWords], own_q[kShardWords];        // bucket tid's / this workgroup's own
-#pragma unroll
-    for (uint32_t w = 0; w < kShardWords; ++w) {
-        cnt_q[w] = by_list && tid + 1 < B ? reinterpret_cast<const uint4 *>(bk.cnt)[tid * kShardWords + w] : uint4{0u, 0u, 0u, 0u};
-        own_q[w] = by_list ? reinterpret_cast<const uint4 *>(bk.cnt)[j * kShardWords + w] : uint4{0u, 0u, 0u, 0u};
-    }
-    uint64_t pre_list[kSelListCap / kSplThreads];
-#pragma unroll
-    for (uint32_t u = 0; u < kSelListCap / kSplThreads; ++u) pre_list[u] = by_list ? bk.lists[(size_t)j * kSelListCap + u * kSplThreads + tid] : 0ull;
-    if (by_list && tid < kSelListShards) bk.cnt_other[j * kSelListShards + tid] = 0u;
-    uint32_t my_cnt = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kShardWords; ++w) my_cnt += cnt_q[w].x + cnt_q[w].y + cnt_q[w].z + cnt_q[w].w;
-    const uint32_t full = (vec & 1u) ? p_len / (4 * kSplThreads) : 0u, ahead = by_list ? 0u : full;
-    float4 pre[kSplAhead];
-#pragma unroll
-    for (uint32_t u = 0; u < kSplAhead; ++u) pre[u] = u < ahead ? *reinterpret_cast<const float4 *>(fin + (size_t)u * 4 * kSplThreads + 4 * tid) : float4{0.f, 0.f, 0.f, 0.f};
-
-    // ---- this workgroup's bounds: the running maximum of the slot up to j and up to j + 1, t_0 = 0 --------------
-    if (tid < 2) bound_s[tid] = 0;
-    if (tid == 0) n_s = 0, c_s = 0;
-    __syncthreads();
-    {
-        unsigned long long lo = tid <= j ? my_spl : 0ull, hi = my_spl;
-#pragma unroll
-        for (int m = kWave / 2; m >= 1; m >>= 1) {
-            const unsigned long long l2 = __shfl_xor(lo, m), h2 = __shfl_xor(hi, m);
-            lo = l2 > lo ? l2 : lo;
-            hi = h2 > hi ? h2 : hi;
-        }
-        if (lane == 0 && hi != 0) { // (a wavefront with nothing to add holds zeros)
-            atomicMax(&bound_s[0], lo);
-            atomicMax(&bound_s[1], hi);
-        }
-    }
-    if (by_list) {
-        uint32_t in_front = tid < j ? my_cnt : 0u;
-#pragma unroll
-        for (int m = kWave / 2; m >= 1; m >>= 1) in_front += __shfl_xor(in_front, m);
-        if (lane == 0 && in_front) atomicAdd(&c_s, in_front);
-        if (tid == j) n_s = my_cnt; // (the open bucket: 0 here, P - c below)
-        static_assert(kSelListSeg * kSelListShards == kSelListCap && kSelListShards % 4 == 0 && kSplThreads % kSelListSeg == 0, "segments");
-    }
-    __syncthreads();
-    SplScan s;
-    s.last = j + 1 == B;
-    s.lo = spl_normalise(bound_s[0]);
-    s.hi = spl_normalise(bound_s[1]);
-    const bool floats = (uint32_t)(s.lo >> 32) <= kSplBitsPosInf && (s.last || (uint32_t)(s.hi >> 32) <= kSplBitsPosInf);
-    s.lo_f = floats ? spl_bound_float(s.lo) : 0.0f;
-    s.hi_f = floats && !s.last ? spl_bound_float(s.hi) : 0.0f;
-    SOTS_PHASE(1);
-
-    // ---- the stream ---------------------------------------------------------------------------------------------
-    // The open bucket (the last workgroup) only counts on its way through: it holds whatever lies beyond the last
-    // splitter - most of the population when the splitters are good - and is looked at only if positions below `reach`
-    // fall into it.
-    const bool count_only = !by_list && floats && s.last;
-    const uint32_t reach = (B - 1) * step + 1 > need ? (B - 1) * step + 1 : need;
-    bool stream = !by_list;
-    if (by_list) {
-        // The list serves unless it overflowed, or the bucket is the open one and has rows to place (nobody files the open
-        // bucket).  Then this workgroup alone streams as without lists - counting and collecting by the 64-bit keys, into
-        // the LDS list while it has room - which is exact for every slot; the counters are a promise of speed only.
-        const uint32_t c0 = c_s, n0 = s.last ? p_len - c0 : n_s;
-        const bool owes = n0 != 0 && c0 < reach && !(s.last && c0 >= need);
-        // the segments one behind the other: place `at` of segment g goes to (keys of the segments in front) + at
-        const uint32_t own[kSelListShards] = {own_q[0].x, own_q[0].y, own_q[0].z, own_q[0].w, own_q[1].x, own_q[1].y, own_q[1].z, own_q[1].w,
-                                              own_q[2].x, own_q[2].y, own_q[2].z, own_q[2].w, own_q[3].x, own_q[3].y, own_q[3].z, own_q[3].w};
-        static_assert(kSelListShards == 16, "own[] spells the sixteen counters out");
-        bool overflow = false;
-#pragma unroll
-        for (uint32_t g = 0; g < kSelListShards; ++g) overflow |= own[g] > kSelListSeg;
-        stream = owes && (s.last || overflow);
-        if (owes && !stream) {
-#pragma unroll
-            for (uint32_t u = 0; u < kSelListCap / kSplThreads; ++u) {
-                const uint32_t g0 = (u * kSplThreads + tid) / kSelListSeg, at = tid % kSelListSeg; // (kSplThreads is a multiple of the segment)
-                uint32_t front = 0, mine = 0;
-#pragma unroll
-                for (uint32_t g = 0; g < kSelListShards; ++g) {
-                    front += g < g0 ? own[g] : 0u;
-                    mine = g == g0 ? own[g] : mine;
-                }
-                if (at < mine) list[front + at] = pre_list[u];
-            }
-        }
-        __syncthreads(); // (everybody has read c_s and n_s)
-        if (stream && tid == 0) n_s = 0, c_s = 0;
-        if (stream) __syncthreads();
-    }
-    if (stream) {
-        uint32_t cnt = 0, done = 0;
-        if (!by_list && floats && (vec & 1u)) { // (list mode has not asked for `pre`)
-            done = count_only ? spl_stream_fast<true>(s, fin, full, pre, cnt, &n_s, list)
-                              : spl_stream_fast<false>(s, fin, full, pre, cnt, &n_s, list);
-#pragma unroll
-            for (int m = kWave / 2; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m);
-        }
-        if (done < p_len || !floats) cnt += spl_stream<false>(s, fin, p_len, (vec & 1u) != 0 && done == 0, done, &n_s, list, nullptr);
-        if (lane == 0 && cnt) atomicAdd(&c_s, cnt);
-    }
-    __syncthreads();
-    SOTS_PHASE(2);
-    const uint32_t c = c_s, n = count_only || (by_list && !stream && s.last) ? p_len - c : n_s;
-    // positions [c, c + n) are this workgroup's: rows to move below `need`, splitters to write at q * step, q < B
-    if (j == 0 && tid == 0) spl_out[0] = 0;
-    if (n == 0 || c >= reach) return;
-    if (s.last && c >= need) {
-        // The open bucket moves no row and only owes the splitters whose positions fall into it.  It keeps its own lower
-        // bound for them instead of ordering what may be most of the population: a splitter may be ANY key, and this one
-        // stays the last while the cut stays in front of it (a converged population whose keys all tie puts exactly as many
-        // keys below it every generation: position (B - 1) * step is then always the open bucket's first)
-        for (uint32_t q = (c + step - 1) / step + tid; q < B; q += kSplThreads)
-            if (q) spl_out[q] = s.lo;
-        return;
-    }
-    if (count_only || n > kSplCap) {
-        // the bucket (again): into the LDS list if it fits, else - the slow path - into its place in the scratch keys
-        __syncthreads();
-        if (tid == 0) n_s = 0;
-        __syncthreads();
-        (void)spl_stream<false>(s, fin, p_len, (vec & 1u) != 0, 0, &n_s, list, n > kSplCap ? keys_scratch + c : nullptr);
-        __syncthreads();
-    }
-
-    const uint64_t *sorted = list;
-    uint32_t my_src = 0; // one key per lane: the row of the key at place tid
-    if (n <= kSplThreads) {
-        // ---- one key per lane (the usual case)
-        uint32_t kb = 0xFFFFFFFFu, ki = 0xFFFFFFFFu; // beyond n: above every key
-        if (tid < n) {
-            const uint64_t key = list[tid];
-            kb = (uint32_t)(key >> 32);
-            ki = (uint32_t)key;
-        }
-        __syncthreads(); // the list is in registers: its first 2048 places are the two exchange buffers now
-        uint32_t n_pad = kWave, buf = 0;
-        while (n_pad < n) n_pad <<= 1;
-        const bool busy = tid < n_pad; // wavefront-uniform: the others hold nothing but padding and only keep the barriers
-        if (busy) {
-            spl_reg_merge<1>(kb, ki, lane, (tid & 2u) == 0);
-            spl_reg_merge<2>(kb, ki, lane, (tid & 4u) == 0);
-            spl_reg_merge<4>(kb, ki, lane, (tid & 8u) == 0);
-            spl_reg_merge<8>(kb, ki, lane, (tid & 16u) == 0);
-            spl_reg_merge<16>(kb, ki, lane, (tid & 32u) == 0);
-            spl_reg_merge<32>(kb, ki, lane, (tid & 64u) == 0);
-        }
-        for (uint32_t k = 2 * kWave; k <= n_pad; k <<= 1) {
-            const bool asc = (tid & k) == 0;
-            for (uint32_t jj = k >> 1; jj >= kWave; jj >>= 1) {
-                list[buf * kSplThreads + tid] = ((uint64_t)kb << 32) | ki;
-                __syncthreads();
-                const uint64_t other = list[buf * kSplThreads + (tid ^ jj)];
-                buf ^= 1u; // the next step writes the other buffer: nobody waits for this step's readers
-                const uint64_t mine = ((uint64_t)kb << 32) | ki;
-                if ((((tid & jj) == 0) == asc) != (mine < other)) {
-                    kb = (uint32_t)(other >> 32);
-                    ki = (uint32_t)other;
-                }
-            }
-            if (busy) spl_reg_merge<32>(kb, ki, lane, asc);
-        }
-        list[buf * kSplThreads + tid] = ((uint64_t)kb << 32) | ki;
-        my_src = ki;
-        __syncthreads();
-        sorted = list + buf * kSplThreads;
-    } else if (n <= kSplCap) {
-        // ---- bitonic network over the LDS list, padded with keys above every key.  A step whose distance stays inside
-        // 64 pairs touches only the 128 keys its wavefront touched in the step before: no workgroup barrier between two
-        // such steps
-        uint32_t n_pad = 2;
-        while (n_pad < n) n_pad <<= 1;
-        for (uint32_t i = n + tid; i < n_pad; i += kSplThreads) list[i] = ~0ull;
-        bool prev_local = false;
-        for (uint32_t k = 2; k <= n_pad; k <<= 1) {
-            for (uint32_t jj = k >> 1; jj > 0; jj >>= 1) {
-                const bool local = jj <= kWave / 2;
-                if (prev_local && local) {
-                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                } else {
-                    __syncthreads();
-                }
-                prev_local = local;
-                for (uint32_t pr = tid; pr < n_pad / 2; pr += kSplThreads) {
-                    const uint32_t i = ((pr & ~(jj - 1)) << 1) | (pr & (jj - 1));
-                    spl_cmp_swap(list, i, i + jj, (i & k) == 0);
-                }
-            }
-        }
-        __syncthreads();
-    } else {
-        // ---- the slow path: the bucket in its place in the scratch keys, ordered there by an ascending
-        // network whose missing upper end counts as keys above every key (pairs that reach beyond n are no-ops)
-        uint64_t *g = keys_scratch + c; // (collected above)
-        uint32_t n_pad = 2, log2k = 1;
-        while (n_pad < n) n_pad <<= 1;
-        for (uint32_t k = 2; k <= n_pad; k <<= 1, ++log2k) {
-            __syncthreads();
-            for (uint32_t pr = tid; pr < n_pad / 2; pr += kSplThreads) { // first step of a merge: i against its mirror in the block
-                const uint32_t blk = pr >> (log2k - 1), x = pr & ((k >> 1) - 1);
-                const uint32_t i = blk * k + x, l = blk * k + (k - 1 - x);
-                if (l < n) spl_cmp_swap(g, i, l, true);
-            }
-            for (uint32_t jj = k >> 2; jj > 0; jj >>= 1) {
-                __syncthreads();
-                for (uint32_t pr = tid; pr < n_pad / 2; pr += kSplThreads) {
-                    const uint32_t i = ((pr & ~(jj - 1)) << 1) | (pr & (jj - 1));
-                    if (i + jj < n) spl_cmp_swap(g, i, i + jj, true);
-                }
-            }
-        }
-        __syncthreads();
-        sorted = g;
-    }
-    SOTS_PHASE(3);
-
-    // ---- next launch's splitters: the keys at positions q * step, 1 <= q < B -----------------------------------------
-    {
-        const uint32_t q0 = c == 0 ? 1u : (c + step - 1) / step;
-        for (uint32_t q = q0 + tid; q < B && (uint64_t)q * step < (uint64_t)c + n; q += kSplThreads) spl_out[q] = sorted[q * step - c];
-    }
-    // ---- rows ----------------------------------------------------------------------------------------------------
-    if (c >= need) return;
-    const uint32_t rows = need - c < n ? need - c : n, width = 2 * d + 1;
-    if (n <= kSplThreads && d == 4 && (vec & 2u)) {
-        // a lane per row, its key still in registers: all of a row's loads are in flight together (16-byte rows)
-        const uint32_t dst = c + tid;
-        if (tid < rows && !ex_immigrant_row(ex, dst)) {
-            const float4 v = reinterpret_cast<const float4 *>(vin)[my_src], t = reinterpret_cast<const float4 *>(sin)[my_src];
-            const float f = fin[my_src];
-            reinterpret_cast<float4 *>(vout)[dst] = v;
-            reinterpret_cast<float4 *>(sout)[dst] = t;
-            fout[dst] = f;
-            if (dst < ex.sink_rows) {
-                const float row[9] = {v.x, v.y, v.z, v.w, t.x, t.y, t.z, t.w, f};
-#pragma unroll
-                for (uint32_t col = 0; col < 9; ++col) ex_sink(ex, dst, col, d, row[col]);
-            }
-        }
-        SOTS_PHASE(4);
-        return;
-    }
-    for (uint32_t e = tid; e < rows * width; e += kSplThreads) {
-        const uint32_t r = e / width, col = e - r * width, dst = c + r;
-        if (ex_immigrant_row(ex, dst)) continue;
-        const uint32_t src = (uint32_t)sorted[r];
-        float v;
-        if (col < d) v = vin[(size_t)src * d + col];
-        else if (col < 2 * d) v = sin[(size_t)src * d + (col - d)];
-        else v = fin[src];
-        if (col < d) vout[(size_t)dst * d + col] = v;
-        else if (col < 2 * d) sout[(size_t)dst * d + (col - d)] = v;
-        else fout[dst] = v;
-        ex_sink(ex, dst, col, d, v);
-    }
-    SOTS_PHASE(4);
-}
-
-// the splitter slot after the two-launch selection: the sorted fitness it wrote, at the same rank step (a splitter
-// needs no index: any value does, the order of the slot is what makes the buckets small)
-__global__ __launch_bounds__(kSplMaxBuckets) void k_sel_seed(const float *__restrict__ fsorted, uint64_t *__restrict__ spl_out,
-                                                             uint32_t need, uint32_t step, uint32_t buckets)
-{
-    const uint32_t q = threadIdx.x;
-    if (q >= buckets) return;
-    const uint32_t pos = q * step < need ? q * step : need - 1;
-    spl_out[q] = q ? (uint64_t)order_bits(fsorted[pos]) << 32 : 0ull;
-}
-
-// ------------------------------------------------------------------------------------
-// Batched real FFT + fitness for N = 4096 (and 2048) WITHOUT LDS exchanges: one wavefront per row,
-// E = N/128 complex points per lane in registers, the 64-point sub-transforms ACROSS lanes.
-//
-// The workgroup-per-row kernel above makes four dependent LDS round trips per row behind workgroup
-// barriers, with 8 wavefronts per CU (0.40 of the HBM roofline at N = 4096).  Here a row never leaves
-// the registers of its wavefront.  With M = 64 E complex points z[n], n = l + 64 j (lane l, register j):
-//   Z[q + E p] = sum_l W_64^{l p} ( W_M^{l q} sum_j z[l + 64 j] W_E^{j q} )
-//   1. an E-point DFT over j inside every lane (radix-2 DIF in registers; register r ends with q = bitrev(r));
-//   2. the twiddle W_M^{l q};
-//   3. for every register a 64-point DFT over the LANES: six radix-2 DIF stages whose partner lane is l ^ h,
-//      h = 32, 16, 8, 4, 2, 1 - v_permlane32_swap, ds_swizzle (LDS crossbar, no LDS memory), DPP row rotate,
-//      DPP quad permutes - a lane with bit h clear keeps a + b, the other one (a - b) W_2h^{l mod h}
-//      (both as fma(own, +-1, partner) times a per-lane constant).  Lane l ends with p = bitrev6(l).
-// So lane l, register r holds Z[k], k = bitrev(r) + E bitrev6(l): E consecutive bins per lane.  The real-input
-// split needs Z[M - k]: register bitrev(E - q) of lane l ^ 63 (q >= 1) - one ds_bpermute per dword - and every
-// lane turns E bins into squared errors: for half of its registers BOTH bins of the pair (k, M - k), its own and its
-// partner lane's (round 4, pair2x: the pair's sum and twiddled difference are worked out once, not once in each of the two
-// lanes).  Window, step-2 twiddles, split twiddles and target are laid out per (lane, register) in LDS once per workgroup
-// (61 KiB, read as 16-byte words).
-// ------------------------------------------------------------------------------------
-#pragma clang fp contract(on)
-constexpr int x_bitrev(int v, int bits)
-{
-    int r = 0;
-    for (int i = 0; i < bits; ++i) r |= ((v >> i) & 1) << (bits - 1 - i);
-    return r;
-}
-template <int LOG2N> constexpr int x_points() { return (1 << LOG2N) / 2 / kWave; }
-#ifndef SOTS_X_WAVES12
-#define SOTS_X_WAVES12 16
-#endif
-// wavefronts (independent rows) per workgroup: what the registers allow (MODE 0, the spectrum writer of the stage-separated
-// path, needs a few more than the fused kernel)
-template <int LOG2N, int MODE = 1> constexpr int x_waves() { return LOG2N >= 13 ? 8 : LOG2N == 12 ? (MODE == 0 ? 12 : SOTS_X_WAVES12) : 16; }
-template <int LOG2N> constexpr bool x_applies() { return LOG2N >= 10 && LOG2N <= 13; }
-
-// target bin of entry (lane l, register r) of k_fft_x's target table.  A lane turns out its own bin
-// for the first register of a pair (RR, R2 = bitrev(E - bitrev(RR))) and its PARTNER lane's bin M - k for the second, so the
-// second register's entry holds that bin's target: the partner is lane l ^ 63 (p' = 63 - p), its bin at r is q + E (63 - p).
-template <int E, int EB>
-__device__ __forceinline__ uint32_t x_target_bin(uint32_t l, uint32_t r)
-{
-    const uint32_t q = __brev(r) >> (32 - EB), pp = __brev(l) >> 26;
-    const uint32_t r2 = q == 0 ? 0u : __brev((uint32_t)E - q) >> (32 - EB);
-    return r2 < r ? q + E * (63u - pp) : q + E * pp;
-}
-
-// Complex values are 2-vectors here (register pairs): the transform is VALU-bound (85 % busy at 2400 one-float
-// instructions per row in its first form), and v_pk_add/mul/fma_f32 do a complex add, or half a complex multiply, per
-// instruction.
-__device__ __forceinline__ v2f_t x_row_load(const float2 *p)
-{
-    return __builtin_nontemporal_load(reinterpret_cast<const v2f_t *>(p)); // rows are read once
-}
-// one radix-2 DIF stage of the E-point transform over the registers: pairs (a, a + H) inside groups of 2 H
-template <int H, int E, int N>
-__device__ __forceinline__ void x_reg_stage(v2f_t (&x)[E], const float2 *__restrict__ tw)
-{
-    static_for<0, E / 2>([&](auto i_tag) {
-        constexpr int I = decltype(i_tag)::value, A0 = (I / H) * 2 * H, A = A0 + I % H;
-        constexpr int IDX = (A - A0) * (E / (2 * H)); // the twiddle is W_E^IDX
-        const v2f_t u = x[A] + x[A + H], d = x[A] - x[A + H];
-        x[A] = u;
-        if constexpr (IDX == 0) x[A + H] = d;
-        else if constexpr (IDX == E / 4) x[A + H] = xc_mul_neg_i(d);
-        else x[A + H] = xc_mul(d, xv(tw[IDX * (N / E)]));
-    });
-    if constexpr (H > 1) x_reg_stage<H / 2, E, N>(x, tw);
-}
-
-
-// one radix-2 DIF stage over the lanes, partner l ^ H, on every register: own * (+-1) + partner, times the lane's
-// constant (1 where bit H is clear)
-template <uint32_t H, int E>
-__device__ __forceinline__ void x_lane_stage(v2f_t (&x)[E], float sgn, v2f_t wl)
-{
-#pragma unroll
-    for (int r = 0; r < E; ++r) {
-        const v2f_t p = v2f_t{lane_xor_f<H>(x[r].x), lane_xor_f<H>(x[r].y)};
-        if constexpr (H != 1) { // the butterfly and its twiddle as one statement (see xc_mul)
-            v2f_t t, u = x[r];
-            asm("v_pk_fma_f32 %0, %0, %2, %3\n\t"
-                "v_pk_mul_f32 %1, %0, %4 op_sel:[0,0] op_sel_hi:[1,0]\n\t"
-                "v_pk_fma_f32 %0, %0, %4, %1 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_lo:[1,0,0]"
-                : "+v"(u), "=&v"(t) : "v"(v2f_t{sgn, sgn}), "v"(p), "v"(wl));
-            x[r] = u;
-        } else {
-            x[r] = x[r] * v2f_t{sgn, sgn} + p; // (the last stage's twiddle is 1)
-        }
-        if (r % 4 == 3) __builtin_amdgcn_sched_barrier(0); // (four registers' partner fetches in flight at a time)
-    }
-}
-
-// The stages with partner l ^ 32 and l ^ 16 take the registers two at a time: v_permlane32_swap / v_permlane16_swap
-// (new in gfx950) exchange the upper half (odd rows of 16) of one register with the lower half (even rows) of the other, so
-// after swapping A with B the lanes with bit H clear hold BOTH inputs of register A's butterfly and the others both
-// inputs of B's; every lane computes one whole butterfly (sum, difference times W_2H^{l mod H}) and a second pair of
-// swaps puts the results where they belong.  Four swaps and four packed operations per pair of complex values, no
-// per-lane signs, no select.
-template <uint32_t H>
-__device__ __forceinline__ void x_swap2(v2f_t &a, v2f_t &b)
-{
-    if constexpr (H == 32) {
-        const auto r0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.x), __float_as_uint(b.x), false, false);
-        const auto r1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.y), __float_as_uint(b.y), false, false);
-        a = v2f_t{__uint_as_float(r0[0]), __uint_as_float(r1[0])}, b = v2f_t{__uint_as_float(r0[1]), __uint_as_float(r1[1])};
-    } else {
-        const auto r0 = __builtin_amdgcn_permlane16_swap(__float_as_uint(a.x), __float_as_uint(b.x), false, false);
-        const auto r1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(a.y), __float_as_uint(b.y), false, false);
-        a = v2f_t{__uint_as_float(r0[0]), __uint_as_float(r1[0])}, b = v2f_t{__uint_as_float(r0[1]), __uint_as_float(r1[1])};
-    }
-}
-template <uint32_t H, int E>
-__device__ __forceinline__ void x_lane_stage_pairs(v2f_t (&x)[E], v2f_t w)
-{
-#pragma unroll
-    for (int r = 0; r < E; r += 2) {
-        x_swap2<H>(x[r], x[r + 1]);
-        v2f_t sum = x[r] + x[r + 1], dif = xc_mul(x[r] - x[r + 1], w);
-        x_swap2<H>(sum, dif);
-        x[r] = sum, x[r + 1] = dif;
-        if (r % 4 == 2) __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// WG: wavefronts per workgroup.  The default fills a CU with one workgroup (the tables are made once per workgroup); a SMALL
-// population - fewer such workgroups than CUs - runs workgroups of four instead, a wavefront per SIMD on four times as many
-// CUs: a row is then transformed at a lone wavefront's pace, not at a quarter of it (1024 rows of N = 4096: 24.6 -> ... us).
-// floats of the per-(lane, register) tables as they lie in LDS: step-2 twiddles, split twiddles, window (float2 each), target
-template <int LOG2N> constexpr int x_table_floats() { return 3 * 2 * kWave * (x_points<LOG2N>() + 2) + kWave * (x_points<LOG2N>() + 4); }
-
-// `image` (fused kernel with window only; may be null): the four tables as they lie in LDS, made once per target by
-// k_x_tables - the workgroups then copy them in by LDS-DMA, one round trip, instead of four dependent-index loads per entry
-#ifndef SOTS_X_MIN_WAVES // (experiment: minimum wavefronts per SIMD the register allocation must allow, e.g. 5 with two workgroups of ten)
-#define SOTS_X_MIN_WAVES 1
-#endif
-// floats of one chunk's target table in a segmented target image (SEG): the tgt_s part of the LDS tables, same layout
-template <int LOG2N> constexpr uint32_t x_seg_stride() { return kWave * (x_points<LOG2N>() + 4); }
-// SEG: as k_fft's - every row reads its chunk's target entries (lane, register) from the segmented image in global memory
-// WGT: the weight table u in the layout of the target table (entry (l, r) at l (E + 4) + r: a one-chunk segmented image
-// made from u[N/2]), read by (lane, register) from global memory - the LDS tables and their image stay as they are
-template <int LOG2N, int MODE, bool WIN, int WG = x_waves<LOG2N, MODE>(), bool SEG = false, int OBJ = kObjMagnitude, bool WGT = false, typename... FLOOR>
-__global__ __launch_bounds__((WG * kWave), (LOG2N == 12 && MODE == 1 ? SOTS_X_MIN_WAVES : 1)) void k_fft_x(const float *__restrict__ audio, float *__restrict__ spectrum,
-                                                                   const float *__restrict__ target, float *__restrict__ fitness,
-                                                                   const float2 *__restrict__ tw, const float *__restrict__ window,
-                                                                   uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch,
-                                                                   const float *__restrict__ image, FLOOR... floor)
-{
-    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0) && ((OBJ == kObjMagnitude && !WGT) || MODE == 1), "the log instantiation (fitness epilogue only) takes the floor, the weighted one its table");
-    static_assert(!WGT || WIN, "the weighted forms exist with a window only");
-    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, floor...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, floor...);
-    constexpr int N = 1 << LOG2N, M = N / 2, E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), W = WG;
-    constexpr int S2 = E + 2, S1 = E + 4; // lane strides of the float2 / float tables (16-byte reads, spread over the banks)
-    __shared__ __attribute__((aligned(16))) float xt_s[x_table_floats<LOG2N>()]; // (the variants without window or target leave theirs unused)
-    float2 *const tw2_s = reinterpret_cast<float2 *>(xt_s), *const tws_s = tw2_s + kWave * S2, *const win_s = tws_s + kWave * S2;
-    float *const tgt_s = reinterpret_cast<float *>(win_s + kWave * S2);
-    __shared__ uint32_t next_s; // the workgroup's rows are dealt out as its wavefronts ask for them (below)
-    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid / kWave);
-    if (tid == 0) next_s = W;
-#ifdef SOTS_STAMP
-    const unsigned long long xs_begin = __builtin_amdgcn_s_memrealtime(), xs_begin_clk = __builtin_amdgcn_s_memtime();
-    unsigned long long xs_wait = 0, xs_rows = 0, xs_split = 0;
-#endif
-    if (MODE == 1 && WIN && image != nullptr) { // (launch_x_tables makes images only where the tables are whole 1 KiB pieces: N >= 2048)
-        typedef __attribute__((address_space(3))) void *lds_ptr_t;
-        for (uint32_t ch = wave; ch < (uint32_t)x_table_floats<LOG2N>() / 256u; ch += W)
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t *>(image) + ch * 256u + lane * 4u, (lds_ptr_t)(xt_s + ch * 256u), 16, 0, 0);
-        __builtin_amdgcn_s_waitcnt(0); // vmcnt(0): this wavefront's pieces have landed (the barrier below covers the others')
-    } else
-    for (uint32_t e = tid; e < kWave * E; e += W * kWave) {
-        const uint32_t l = e / E, r = e % E;
-        const uint32_t q = __brev(r) >> (32 - EB), pp = __brev(l) >> 26, k = q + E * pp;
-        tw2_s[l * S2 + r] = tw[2u * l * q]; // W_M^{l q} = W_N^{2 l q}
-        tws_s[l * S2 + r] = tw[k];          // W_N^k
-        if constexpr (WIN) win_s[l * S2 + r] = reinterpret_cast<const float2 *>(window)[l + kWave * r]; // r = input register j here
-        if constexpr (MODE == 1 && !SEG) tgt_s[l * S1 + r] = target[x_target_bin<E, EB>(l, r)];
-    }
-    const uint32_t seg_rows = SEG ? seg_target_rows(target) : 1u;
-    // per-lane constants of the six lane stages
-    const float sg8 = (lane & 8u) ? -1.0f : 1.0f;
-    const float sg4 = (lane & 4u) ? -1.0f : 1.0f, sg2 = (lane & 2u) ? -1.0f : 1.0f, sg1 = (lane & 1u) ? -1.0f : 1.0f;
-    const v2f_t one = v2f_t{1.0f, 0.0f};
-    const v2f_t w32 = xv(tw[(lane & 31u) * (N / 64)]), w16 = xv(tw[(lane & 15u) * (N / 32)]); // (every lane makes a difference there)
-    const v2f_t w8 = (lane & 8u) ? xv(tw[(lane & 7u) * (N / 16)]) : one, w4 = (lane & 4u) ? xv(tw[(lane & 3u) * (N / 8)]) : one;
-    const v2f_t w2 = (lane & 2u) ? xv(tw[(lane & 1u) * (N / 4)]) : one;
-    const uint32_t pp = __brev(lane) >> 26;
-    const int addr_flip = (int)((lane ^ 63u) * 4u);                        // partner lane of the registers with q >= 1
-    const int addr_zero = (int)((__brev((64u - pp) & 63u) >> 26) * 4u);    // ... and of register 0 (q = 0): Z[E (64 - p)]
-    const float half_scale = 0.5f * (inv_n * inv_wf);
-    __syncthreads();
-
-    // Rows: workgroup b owns rows b W + w + i grid W (w < W, i = 0, 1, ...).  Its wavefronts start with i = 0, wavefront w
-    // on row b W + w, and then take the workgroup's remaining rows in that order AS THEY FINISH: the SIMD issues for its
-    // oldest wavefront first, so with a fixed deal of 8 rows each the wavefronts of one launch end anywhere between 77
-    // and 148 us (N = 4096, P = 32768) and the last ones run alone, far below the issue rate (tools/fftx_probe.py).
-    // Which wavefront transforms a row changes nothing in its result.
-    uint32_t row = blockIdx.x * W + wave;
-    if (row >= p_len) return;
-#ifdef SOTS_STAMP
-    const unsigned long long xs_tables = __builtin_amdgcn_s_memrealtime();
-#endif
-    v2f_t x[E];
-    {
-        const float2 *__restrict__ in = reinterpret_cast<const float2 *>(audio + (size_t)row * pitch);
-#pragma unroll
-        for (int j = 0; j < E; ++j) x[j] = x_row_load(in + lane + kWave * j);
-    }
-    while (true) {
-        uint32_t take = 0;
-        if (lane == 0) take = atomicAdd(&next_s, 1u); // (answered long before the split below needs it)
-        take = __builtin_amdgcn_readfirstlane(take);
-        const uint32_t nxt = blockIdx.x * W + take % W + (take / W) * gridDim.x * W;
-        const bool more = nxt < p_len; // (rows past the end: every later take is past it too)
-        __builtin_amdgcn_sched_barrier(0);
-#ifdef SOTS_STAMP
-        {
-            const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            xs_wait += __builtin_amdgcn_s_memtime() - t0, xs_rows += 1;
-        }
-#endif
-        if constexpr (WIN) {
-#pragma unroll
-            for (int j = 0; j < E; j += 2) {
-                const float4 wv = *reinterpret_cast<const float4 *>(&win_s[lane * S2 + j]);
-                x[j] = x[j] * v2f_t{wv.x, wv.y};
-                x[j + 1] = x[j + 1] * v2f_t{wv.z, wv.w};
-                if (j % 8 == 6) __builtin_amdgcn_sched_barrier(0); // (table reads a few at a time: the row already fills 2 E registers)
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        // 1. E-point DIF over the registers
-        x_reg_stage<E / 2, E, N>(x, tw);
-        __builtin_amdgcn_sched_barrier(0);
-        // 2. W_M^{l q}
-#pragma unroll
-        for (int r = 0; r < E; r += 2) {
-            const float4 t = *reinterpret_cast<const float4 *>(&tw2_s[lane * S2 + r]);
-            if (r) x[r] = xc_mul(x[r], v2f_t{t.x, t.y}); // register 0: q = 0
-            x[r + 1] = xc_mul(x[r + 1], v2f_t{t.z, t.w});
-            if (r % 8 == 6) __builtin_amdgcn_sched_barrier(0);
-        }
-        // 3. 64-point DIF over the lanes
-        x_lane_stage_pairs<32>(x, w32);
-        __builtin_amdgcn_sched_barrier(0);
-        x_lane_stage_pairs<16>(x, w16);
-        __builtin_amdgcn_sched_barrier(0);
-        x_lane_stage<8>(x, sg8, w8);
-        __builtin_amdgcn_sched_barrier(0);
-        x_lane_stage<4>(x, sg4, w4);
-        __builtin_amdgcn_sched_barrier(0);
-        x_lane_stage<2>(x, sg2, w2);
-        __builtin_amdgcn_sched_barrier(0);
-        x_lane_stage<1>(x, sg1, one);
-        __builtin_amdgcn_sched_barrier(0);
-        // split: this lane's E bins k = bitrev(r) + E p
-#ifdef SOTS_STAMP
-        const unsigned long long xs_t2 = __builtin_amdgcn_s_memtime();
-#endif
-        float acc = 0.0f;
-        // one bin: register RR of this lane with its partner Z[M - k]
-        auto bin2x = [&](auto r_tag) -> v2f_t {
-            constexpr int RR = decltype(r_tag)::value, Q = x_bitrev(RR, EB), R2 = Q == 0 ? 0 : x_bitrev(E - Q, EB);
-            const int addr = Q == 0 ? addr_zero : addr_flip;
-            const v2f_t zm = v2f_t{__int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(x[R2].x))),
-                                   __int_as_float(__builtin_amdgcn_ds_bpermute(addr, __float_as_int(x[R2].y)))};
-            const v2f_t w = xv(tws_s[lane * S2 + RR]);
-            const v2f_t ee = xc_add_conj(x[RR], zm), dd = xc_sub_conj(x[RR], zm);
-            return ee + xc_mul_negi_w(dd, w); // 2 X[k] = (Z[k] + conj Z[M-k]) + W_N^k (-i) (Z[k] - conj Z[M-k])
-        };
-        // BOTH bins of the pair (k, M - k) from this lane's Z[k] (register RR) and the partner lane's Z[M - k] (its register
-        // R2): ee and t = W_N^k (-i) dd once, 2 X[k] = ee + t and 2 conj X[M - k] = ee - t.  The partner lane does the same with
-        // ITS register RR and this lane's R2, so every lane still turns out E bins - half of them its partner's - with half
-        // the exchanges and a packed subtraction in place of a second add / subtract / multiply chain.
-        auto pair2x = [&](auto r_tag, v2f_t &xa, v2f_t &xb) {
-            constexpr int RR = decltype(r_tag)::value, Q = x_bitrev(RR, EB), R2 = x_bitrev(E - Q, EB);
-            static_assert(Q != 0 && R2 != RR, "registers 0 and bitrev(E / 2) pair with themselves: bin2x");
-            const v2f_t zm = v2f_t{__int_as_float(__builtin_amdgcn_ds_bpermute(addr_flip, __float_as_int(x[R2].x))),
-                                   __int_as_float(__builtin_amdgcn_ds_bpermute(addr_flip, __float_as_int(x[R2].y)))};
-            const v2f_t w = xv(tws_s[lane * S2 + RR]);
-            const v2f_t ee = xc_add_conj(x[RR], zm), t = xc_mul_negi_w(xc_sub_conj(x[RR], zm), w);
-            xa = ee + t, xb = ee - t;
-        };
-        if constexpr (MODE == 1) {
-            // target entry (this lane, register RR): the workgroup's table in LDS, or (SEG) the row's chunk's in global memory
-            const float *__restrict__ tg = SEG ? seg_target_chunk(target, row / seg_rows, x_seg_stride<LOG2N>()) + lane * S1 : nullptr;
-            auto tgt_at = [&](int rr) -> float {
-                if constexpr (SEG) return tg[rr];
-                else return tgt_s[lane * S1 + rr];
-            };
-            [[maybe_unused]] const float *__restrict__ ul = WGT ? wgt_u + lane * S1 : nullptr;
-            [[maybe_unused]] auto u_at = [&](int rr) -> float {
-                if constexpr (WGT) return ul[rr];
-                else return 0.0f;
-            };
-            // Registers RR and R2 = bitrev(E - bitrev(RR)) need each other and nobody else: the bins are taken in such
-            // pairs (this is the summation order, k_fitness_x repeats it), and a pair that is done is free - the NEXT
-            // row's loads into those two registers go out at once, so by the end of the split most of the next row is on
-            // its way without a second set of registers.
-            // (a wavefront's last row has no successor: it re-reads row 0, which every wavefront of the launch then finds in
-            // L2 - loads under `if (more)` cost the compiler its register allocation)
-            // the next row's address as a uniform base (scalar registers: audio + row offset) plus the lane's byte offset, instead
-            // of the loop-invariant 64-bit pointer audio + lane offset plus a uniform row offset: with the pair split that pointer
-            // was the one value too many for the 128 registers (an 8-byte spill, reloaded once per row; 130 against 127 us)
-            // (the builtin returns a SIGNED int - the halves are widened as unsigned: the first attempt sign-extended the low
-            // half and faulted on rows whose address has bit 31 set)
-            const uint64_t in_next_u = reinterpret_cast<uint64_t>(audio + (size_t)(more ? nxt : 0u) * pitch);
-            const uint32_t in_next_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)in_next_u);
-            const uint32_t in_next_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(in_next_u >> 32));
-            typedef const __attribute__((address_space(1))) char *x_gptr_t; // global, not generic: global_load, not flat_load
-            const x_gptr_t in_next_base = (x_gptr_t)(((uint64_t)in_next_hi << 32) | (uint64_t)in_next_lo);
-            const uint32_t lane_bytes = lane * 8u;
-            static_for<0, E>([&](auto r_tag) {
-                constexpr int RR = decltype(r_tag)::value, Q = x_bitrev(RR, EB), R2 = Q == 0 ? 0 : x_bitrev(E - Q, EB);
-                if constexpr (R2 >= RR) {
-                    if constexpr (R2 != RR) {
-                        v2f_t xa, xb;
-                        pair2x(ic<RR>{}, xa, xb);
-                        acc += bin_error<OBJ, WGT>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps, u_at(RR));
-                        acc += bin_error<OBJ, WGT>(make_float2(xb.x, xb.y), tgt_at(R2), half_scale, floor_eps, u_at(R2)); // the partner lane's bin M - k: x_target_bin
-                    } else {
-                        const v2f_t xa = bin2x(ic<RR>{});
-                        acc += bin_error<OBJ, WGT>(make_float2(xa.x, xa.y), tgt_at(RR), half_scale, floor_eps, u_at(RR));
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    typedef const __attribute__((address_space(1))) v2f_t *x_gv2_t;
-                    x[RR] = __builtin_nontemporal_load((x_gv2_t)(in_next_base + (lane_bytes + 8u * kWave * RR)));
-                    if constexpr (R2 != RR) x[R2] = __builtin_nontemporal_load((x_gv2_t)(in_next_base + (lane_bytes + 8u * kWave * R2)));
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            });
-        } else
-        static_for<0, E>([&](auto r_tag) { // MODE 0, the fused kernel's pairs: the same values, written where they belong
-            constexpr int RR = decltype(r_tag)::value, Q = x_bitrev(RR, EB), R2 = Q == 0 ? 0 : x_bitrev(E - Q, EB);
-            if constexpr (R2 >= RR) {
-                float2 *__restrict__ bins = reinterpret_cast<float2 *>(spectrum + (size_t)row * (N + 8));
-                const uint32_t k = E * pp + Q;
-                if constexpr (R2 != RR) {
-                    v2f_t xa, xb;
-                    pair2x(ic<RR>{}, xa, xb);
-                    bins[k] = make_float2(0.5f * xa.x, 0.5f * xa.y);
-                    bins[M - k] = make_float2(0.5f * xb.x, -0.5f * xb.y);
-                } else {
-                    const v2f_t xa = bin2x(ic<RR>{});
-                    bins[k] = make_float2(0.5f * xa.x, 0.5f * xa.y);
-                }
-            }
-            if constexpr (RR % 4 == 3) __builtin_amdgcn_sched_barrier(0);
-        });
-        if constexpr (MODE == 0) {
-            // the Nyquist bin X[M] = Re Z0 - Im Z0, from Z0 itself: lane 0 still holds it in register 0
-            if (lane == 0) reinterpret_cast<float2 *>(spectrum + (size_t)row * (N + 8))[M] = make_float2(x[0].x - x[0].y, 0.0f);
-        } else {
-            acc = wave_sum(acc);
-            if (lane == 0) fitness[row] = acc;
-        }
-#ifdef SOTS_STAMP
-        xs_split += __builtin_amdgcn_s_memtime() - xs_t2;
-        if (lane == 0 && blockIdx.x * W + wave < 2048) { // per wavefront: 8 words
-            unsigned long long *o = g_stamps + (blockIdx.x * W + wave) * 8;
-            o[0] = xs_begin, o[1] = xs_tables, o[2] = __builtin_amdgcn_s_memrealtime(), o[3] = xs_rows;
-            o[4] = xs_wait, o[5] = xs_split, o[6] = __builtin_amdgcn_s_memtime() - xs_begin_clk;
-        }
-#endif
-        if (!more) break;
-        if constexpr (MODE == 0) { // (MODE 1 has asked for the row already, pair by pair)
-            const float2 *__restrict__ in = reinterpret_cast<const float2 *>(audio + (size_t)nxt * pitch);
-            static_for<0, E>([&](auto j_tag) { x[decltype(j_tag)::value] = x_row_load(in + lane + kWave * decltype(j_tag)::value); });
-        }
-        row = nxt;
-    }
-}
-
-// ------------------------------------------------------------------------------------
-// Rows of N = 16384 and 32768 samples (round 4: the reference takes any audioLengthLog2, main.cpp:90, and renders 2^14
-// samples of its best match, main.cpp:273): a WORKGROUP per row.  Such a row is 128 or 256 registers per lane of one
-// wavefront, more than k_fft_x can hold; here its M = N / 2 complex points live in LDS (64 or 128 KiB), 512 threads run an
-// in-place radix-2 DIF (natural order in, bit-reversed out) with one workgroup barrier per stage, and the real-input split
-// reads Z[k] and Z[M - k] at their bit-reversed places.  Coverage, not speed: nothing of BASELINE's configs runs here.
-//   MODE 0: spectrum row (bins 0 .. M) to memory; MODE 1: squared error against the target, bins 0 .. M-1
-//   (Evolutionary_Strategy_CPU.hpp:235).  Thread t takes bins t, t + 512, ... in rising order, the wavefront totals are added
-//   in wavefront order; k_fitness_big repeats map and order on a materialised row (bit-identical sums).
-// ------------------------------------------------------------------------------------
-constexpr int kBigThreads = 512;
-template <int LOG2N> constexpr bool big_applies() { return LOG2N == 14 || LOG2N == 15; }
-
-__device__ __forceinline__ float big_block_sum(float acc, float *__restrict__ red)
-{
-    acc = wave_sum(acc);
-    const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    if (lane == 0) red[wave] = acc;
-    __syncthreads();
-    float total = 0.0f;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < kBigThreads / kWave; ++w) total += red[w];
-    return total; // (thread 0's)
-}
-
-// SEG: `target` is a segmented target image (k_fft's); row r takes its chunk's bins
-template <int LOG2N, int MODE, bool WIN, bool SEG = false, int OBJ = kObjMagnitude, bool WGT = false, typename... FLOOR>
-__global__ __launch_bounds__(kBigThreads) void k_fft_big(const float *__restrict__ audio, float *__restrict__ spectrum,
-                                                         const float *__restrict__ target, float *__restrict__ fitness,
-                                                         const float2 *__restrict__ tw, const float *__restrict__ window,
-                                                         uint32_t p_len, float inv_n, float inv_wf, uint32_t pitch, FLOOR... floor)
-{
-    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0) && ((OBJ == kObjMagnitude && !WGT) || MODE == 1), "the log instantiation (fitness epilogue only) takes the floor, the weighted one its table");
-    static_assert(!WGT || WIN, "the weighted forms exist with a window only");
-    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, floor...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, floor...);
-    constexpr uint32_t N = 1u << LOG2N, M = N / 2, LM = LOG2N - 1, T = kBigThreads;
-    extern __shared__ float2 big_z[]; // M complex points (the launch asks for M * 8 + 64 bytes)
-    float *__restrict__ red = reinterpret_cast<float *>(big_z + M);
-    const uint32_t t = threadIdx.x;
-    for (uint32_t row = blockIdx.x; row < p_len; row += gridDim.x) {
-        const float2 *__restrict__ in = reinterpret_cast<const float2 *>(audio + (size_t)row * pitch);
-        for (uint32_t i = t; i < M; i += T) {
-            float2 v = in[i];
-            if constexpr (WIN) {
-                const float2 w = reinterpret_cast<const float2 *>(window)[i];
-                v.x *= w.x, v.y *= w.y;
-            }
-            big_z[i] = v;
-        }
-        __syncthreads();
-        // in-place radix-2 DIF: stage s pairs i and i + half, half = M >> (s + 1); the difference takes W_{2 half}^{j} = W_N^{j N / (2 half)}
-        for (uint32_t st = 0; st < LM; ++st) {
-            const uint32_t half = M >> (st + 1), tw_step = N / (2u * half);
-            for (uint32_t b = t; b < M / 2; b += T) {
-                const uint32_t j = b & (half - 1), i0 = ((b - j) << 1) + j, i1 = i0 + half;
-                const float2 a = big_z[i0], c = big_z[i1];
-                big_z[i0] = cadd(a, c);
-                const float2 d = csub(a, c);
-                big_z[i1] = j == 0 ? d : cmul(d, tw[j * tw_step]);
-            }
-            __syncthreads();
-        }
-        // Z[k] now lies at bitrev(k).  X[k] = (Z[k] + conj Z[M-k]) / 2 + W_N^k (-i) (Z[k] - conj Z[M-k]) / 2, Z[M] read as Z[0]
-        auto bin = [&](uint32_t k) -> float2 {
-            const uint32_t km = (M - k) & (M - 1);
-            const float2 a = big_z[__brev(k) >> (32 - LM)], bz = big_z[__brev(km) >> (32 - LM)];
-            const float2 ee = make_float2(0.5f * (a.x + bz.x), 0.5f * (a.y - bz.y)), dd = make_float2(0.5f * (a.x - bz.x), 0.5f * (a.y + bz.y));
-            const float2 o = make_float2(dd.y, -dd.x); // -i dd
-            const float2 w = tw[k];
-            return make_float2(ee.x + (o.x * w.x - o.y * w.y), ee.y + (o.x * w.y + o.y * w.x));
-        };
-        if constexpr (MODE == 0) {
-            float2 *__restrict__ dst = reinterpret_cast<float2 *>(spectrum + (size_t)row * (N + 8));
-            for (uint32_t k = t; k < M; k += T) dst[k] = bin(k);
-            if (t == 0) dst[M] = make_float2(big_z[0].x - big_z[0].y, 0.0f); // the Nyquist bin X[M] = Re Z0 - Im Z0
-        } else {
-            float acc = 0.0f;
-            const float *__restrict__ tg = SEG ? seg_target_chunk(target, row / seg_target_rows(target), M) : target;
-            for (uint32_t k = t; k < M; k += T) acc += bin_error<OBJ, WGT>(bin(k), tg[k], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f);
-            const float total = big_block_sum(acc, red);
-            if (t == 0) fitness[row] = total;
-        }
-        __syncthreads(); // the next row overwrites big_z and red
-    }
-}
-
-template <int LOG2N, int OBJ = kObjMagnitude, bool WGT = false, typename... FLOOR>
-__global__ __launch_bounds__(kBigThreads) void k_fitness_big(const float *__restrict__ spectrum, const float *__restrict__ target,
-                                                             float *__restrict__ fitness, uint32_t p_len, float inv_n, float inv_wf, FLOOR... floor)
-{
-    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the log instantiation takes the floor, the weighted one its table");
-    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, floor...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, floor...);
-    constexpr uint32_t N = 1u << LOG2N, M = N / 2, T = kBigThreads;
-    __shared__ float red[kBigThreads / kWave];
-    for (uint32_t row = blockIdx.x; row < p_len; row += gridDim.x) {
-        const float2 *__restrict__ src = reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8));
-        float acc = 0.0f;
-        for (uint32_t k = threadIdx.x; k < M; k += T) acc += bin_error<OBJ, WGT>(src[k], target[k], inv_n * inv_wf, floor_eps, WGT ? wgt_u[k] : 0.0f);
-        const float total = big_block_sum(acc, red);
-        if (threadIdx.x == 0) fitness[row] = total;
-        __syncthreads();
-    }
-}
-
-// fitnessPopulation on materialised rows with k_fft_x's bin -> (lane, register) map and summation order
-template <int LOG2N, int OBJ = kObjMagnitude, bool WGT = false, typename... FLOOR>
-__global__ __launch_bounds__(x_waves<LOG2N>() * kWave) void k_fitness_x(const float *__restrict__ spectrum, const float *__restrict__ target,
-                                                                       float *__restrict__ fitness, uint32_t p_len, float inv_n, float inv_wf, FLOOR... floor)
-{
-    static_assert(sizeof...(FLOOR) == (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the log instantiation takes the floor, the weighted one its table");
-    [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, floor...);
-    [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, floor...);
-    constexpr int N = 1 << LOG2N, E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), W = x_waves<LOG2N>();
-    const uint32_t lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const uint32_t pp = __brev(lane) >> 26;
-    for (uint32_t row = blockIdx.x * W + wave; row < p_len; row += gridDim.x * W) {
-        const float2 *__restrict__ src = reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8)) + E * pp;
-        float acc = 0.0f;
-        if constexpr (WGT) {
-            // The same pairs in the same order, as a loop: unrolled like the form below, the compiler reads row, target and
-            // weights of all E registers ahead, and the third set of E registers spilled at N = 4096 and 8192.
-            const float2 *__restrict__ bins = reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8));
-#pragma unroll 2
-            for (int rr = 0; rr < E; ++rr) {
-                const int q = x_bitrev(rr, EB), r2 = q == 0 ? 0 : x_bitrev(E - q, EB);
-                if (r2 < rr) continue;
-                const int k = E * pp + q;
-                acc += bin_error<OBJ, true>(bins[k], target[k], inv_n * inv_wf, floor_eps, wgt_u[k]);
-                if (r2 != rr) {
-                    const int k2 = N / 2 - k;
-                    acc += bin_error<OBJ, true>(bins[k2], target[k2], inv_n * inv_wf, floor_eps, wgt_u[k2]);
-                }
-            }
-        } else
-        static_for<0, E>([&](auto r_tag) { // k_fft_x's order: register pairs (RR, R2 = bitrev(E - bitrev(RR)))
-            constexpr int RR = decltype(r_tag)::value, Q = x_bitrev(RR, EB), R2 = Q == 0 ? 0 : x_bitrev(E - Q, EB);
-            if constexpr (R2 >= RR) {
-                acc += bin_error<OBJ, WGT>(src[Q], target[E * pp + Q], inv_n * inv_wf, floor_eps, WGT ? wgt_u[E * pp + Q] : 0.0f);
-                // the pair's second bin is the PARTNER lane's: M - k (k_fft_x's pair2x)
-                if constexpr (R2 != RR)
-                    acc += bin_error<OBJ, WGT>(reinterpret_cast<const float2 *>(spectrum + (size_t)row * (N + 8))[N / 2 - (E * pp + Q)], target[N / 2 - (E * pp + Q)], inv_n * inv_wf, floor_eps, WGT ? wgt_u[N / 2 - (E * pp + Q)] : 0.0f);
-            }
-        });
-        acc = wave_sum(acc);
-        if (lane == 0) fitness[row] = acc;
-    }
-}
-// the table image of the fused kernel (k_fft_x<LOG2N, 1, true>), entry by entry what its workgroups would make themselves
-template <int LOG2N>
-__global__ __launch_bounds__(256) void k_x_tables(float *__restrict__ image, const float2 *__restrict__ tw,
-                                                  const float *__restrict__ window, const float *__restrict__ target)
-{
-    constexpr int E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), S2 = E + 2, S1 = E + 4;
-    float2 *const tw2_s = reinterpret_cast<float2 *>(image), *const tws_s = tw2_s + kWave * S2, *const win_s = tws_s + kWave * S2;
-    float *const tgt_s = reinterpret_cast<float *>(win_s + kWave * S2);
-    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < (uint32_t)(kWave * E); e += gridDim.x * blockDim.x) {
-        const uint32_t l = e / E, r = e % E;
-        const uint32_t q = __brev(r) >> (32 - EB), pp = __brev(l) >> 26, k = q + E * pp;
-        tw2_s[l * S2 + r] = tw[2u * l * q];
-        tws_s[l * S2 + r] = tw[k];
-        win_s[l * S2 + r] = reinterpret_cast<const float2 *>(window)[l + kWave * r];
-        tgt_s[l * S1 + r] = target[x_target_bin<E, EB>(l, r)];
-    }
-}
-// the target part of those tables for every chunk (segmented target image of k_fft_x<.., SEG>): chunk c's table from
-// targets[c][N/2], entry (l, r) at l (E + 4) + r as in tgt_s (the padding entries stay as the caller left them)
-// (one chunk's table, entry le = l E + r of its kWave E entries: the one copy both writers use - k_x_seg_targets for every chunk of a
-// batch, the chunk queue's turnover for the slot it refills)
-template <int LOG2N>
-__device__ __forceinline__ void x_seg_target_entry(float *__restrict__ table, const float *__restrict__ target, uint32_t le)
-{
-    constexpr int E = x_points<LOG2N>(), EB = (E == 2 ? 1 : E == 4 ? 2 : E == 8 ? 3 : E == 16 ? 4 : E == 32 ? 5 : 6), S1 = E + 4;
-    const uint32_t l = le / E, r = le % E;
-    table[l * S1 + r] = target[x_target_bin<E, EB>(l, r)];
-}
-template <int LOG2N>
-__global__ __launch_bounds__(256) void k_x_seg_targets(float *__restrict__ tables, const float *__restrict__ targets, uint32_t chunks)
-{
-    constexpr int E = x_points<LOG2N>();
-    constexpr uint32_t M = (1u << LOG2N) / 2;
-    const uint32_t total = chunks * (uint32_t)(kWave * E);
-    for (uint32_t e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
-        const uint32_t c = e / (kWave * E), le = e - c * (kWave * E);
-        x_seg_target_entry<LOG2N>(tables + (size_t)c * x_seg_stride<LOG2N>(), targets + (size_t)c * M, le);
-    }
-}
-#pragma clang fp contract(off)
 
 // ------------------------------------------------------------------------------------
 // island exchange: rows of [fitness, values, steps]

@@ -36,7 +36,7 @@ u = 2^-24 (round to nearest), to first order and worst case:
   - the term: e = x - t rounds once (u, relative to e; 2 u in e^2); under weights u_k = fp32 sqrt(w_k) is off by u and
     the product e u_k rounds once (4 u in the square); the square rounds once (u).  3 u without weights, 7 u with them.
   - the sum: every term is >= 0, so a sum tree in which a term passes through at most D additions is off by at most
-    D u of the exact sum.  D from the kernels' reduction orders (csrc/sots_kernels.hip; wave_sum: csrc/kernels/common.h):
+    D u of the exact sum.  D from the kernels' reduction orders (csrc/kernels/spectral_*.h; wave_sum: csrc/kernels/common.h):
       k_fft, k_fitness (N = 512, 1024; one wavefront, wide and list forms alike): a lane adds N/256 terms into each half
         of a 2-vector, adds the halves (1), four DPP levels inside a row of 16 lanes (4), the four row totals in turn (3):
         D = N/256 + 8, 10 and 12.
@@ -245,7 +245,7 @@ def table_read_late(tables, c):                             # (g) chunk c's tabl
 
 
 def x_image_bins(n):
-    """bin of entry (lane l, register r) of k_fft_x's target table, [64][N/128] (x_target_bin, csrc/sots_kernels.hip): the
+    """bin of entry (lane l, register r) of k_fft_x's target table, [64][N/128] (x_target_bin, csrc/kernels/spectral_x.h): the
     lane's own bin bitrev(r) + E bitrev6(l) for the first register of a pair (r, bitrev(E - bitrev(r))), its partner
     lane's bin for the second"""
     e = n // 128
