@@ -48,7 +48,8 @@ enum sots_synth_kind {
     SOTS_SYNTH_2OP = 0,        /* D=4,  ocl_program.cl:280-330, Evolutionary_Strategy.hpp:368-402 */
     SOTS_SYNTH_3OP_SERIES = 1, /* D=6,  ocl_program.cl:332-386, Evolutionary_Strategy.hpp:403-449 */
     SOTS_SYNTH_TRIPLE_PAR = 2, /* D=12, ocl_program.cl:388-443, Evolutionary_Strategy.hpp:450-495 */
-    SOTS_SYNTH_4OP_SERIES = 3  /* D=8,  build-defined 4-operator series chain (BASELINE config 4) */
+    SOTS_SYNTH_4OP_SERIES = 3, /* D=8,  build-defined 4-operator series chain (BASELINE config 4) */
+    SOTS_SYNTH_GRAPH = 4       /* D=2*OPS, an operator graph given at creation: sots_voice_graph below */
 };
 
 /* Stage ids, in the order of the reference's kernelNames_
@@ -135,6 +136,54 @@ const char *sots_last_error(const sots_ctx *ctx);
 /* run every later launch/copy on this hipStream_t (NULL = the context's own stream) */
 int sots_set_stream(sots_ctx *ctx, void *hip_stream);
 int sots_synchronize(sots_ctx *ctx);
+
+/* ---- operator-graph voice (new: SOTS_SYNTH_GRAPH, user-defined feed-forward FM algorithms of 2 to 8 operators) ----
+ * The topology travels beside sots_config (which cannot grow): cfg.synth_kind must be SOTS_SYNTH_GRAPH and
+ * cfg.num_dimensions must be 2 * num_operators.  sots_create, sots_batch_create and sots_group_create refuse kind 4
+ * (SOTS_ERR_INVALID; the text names sots_create_graph); islands do not take the voice.
+ *
+ * The voice.  OPS operators, 2 <= OPS <= 8, D = 2 OPS genes.
+ * Genes and scaling:
+ *   - Gene 2j is operator j's frequency f_j.  Gene 2j+1 is its level a_j.
+ *   - Scaled per gene, as everywhere else: p_g = pmin_g + v_g (pmax_g - pmin_g), all fp32.
+ *   - There is no `& 3` folding of the ranges as in the triple voice.
+ * Topology:
+ *   - modulators[j] is a bit mask.  Only bits i < j may be set.  Bit i set means operator i's output modulates
+ *     operator j.  Feed-forward only: no feedback.
+ *   - carriers is a bit mask and is not empty.
+ *   - Every operator is exactly one of two things.  Either it is a carrier and modulates nobody, or it is not a carrier
+ *     and modulates at least one operator.  Everything else is refused.
+ * Per-operator values:
+ *   - A_j = f_j a_j if j is a modulator.  Its output is a frequency deviation in Hz and a_j is the modulation index, as
+ *     in the 2-op voice.
+ *   - A_j = a_j if j is a carrier.
+ *   - c = (float)W / (float)44100, with W the wavetable size.  All phases start at 0.
+ * Per sample n, operators in ascending j:
+ *   1. o_j = tab_at(pos_j) A_j.  tab_at is table[clamp((int)pos, 0, W-1)]: the index is clamped on the float, and NaN or
+ *      a negative value gives entry 0.
+ *   2. An unmodulated operator has cur = f_j.  A modulated one has cur = ((o_i1 + o_i2) + ...) + f_j, over the set bits
+ *      in ascending i.  An operator whose bit is clear is skipped, not added as 0.
+ *   3. pos_j += c cur.  Multiply, then add.  No contraction.
+ *   4. If pos_j >= W, subtract W.  For a modulated operator only: if pos_j < 0, add W afterwards.  An unmodulated
+ *      operator has no lower wrap.  This is the 2-op voice's rule.
+ * Output of sample n:
+ *   - audio[n] = ((o_c1 + o_c2) + ...) over the carriers in ascending j.
+ *   - With more than one carrier, that sum is divided by (float)count with a correctly rounded fp32 division.
+ * Anchors: the graph {0->1, carrier 1} is SOTS_SYNTH_2OP bit for bit, and {0->1, 2->3, 4->5, carriers 1, 3, 5}, with
+ * the ranges of genes 0..3 repeated per pair, is SOTS_SYNTH_TRIPLE_PAR bit for bit.  The two series voices are NOT
+ * reproduced by any graph: their genes mean something else (operator frequencies in genes 1, 3, 5, 7 and a carrier
+ * amplitude that is the product of two genes).
+ * Not for the voice: SOTS_ARITH_DEVICE_KERNELS (SOTS_ERR_INVALID, as for the 4-op voice) and sots_render_continuous
+ * (SOTS_ERR_INVALID: its scans are written per fixed voice).  sots_render_overlap_add and everything else serve it. */
+typedef struct sots_voice_graph {
+    uint32_t struct_size;   /* = sizeof(sots_voice_graph) */
+    uint32_t num_operators; /* OPS, 2..8 */
+    uint32_t carriers;      /* bit j: operator j is heard */
+    uint32_t modulators[8]; /* [j] bit i (i < j): operator i modulates operator j; entries >= OPS are 0 */
+} sots_voice_graph;
+int sots_create_graph(const sots_config *cfg, const sots_voice_graph *graph, sots_ctx **out);
+/* the context's graph; SOTS_ERR_STATE for a context of a fixed voice */
+int sots_get_voice_graph(const sots_ctx *ctx, sots_voice_graph *graph);
 
 /* ---- target (replaces setTargetAudio, ...OpenCL.hpp:563-570; Objective::calculateFFT,
  *      Evolutionary_Strategy.hpp:524-542) ---- */
@@ -432,6 +481,8 @@ int sots_group_best(sots_group *group, uint32_t *island, float *fitness);
  * Rows are chunk-major: chunk c holds rows [c P, (c+1) P) of each rotation half. */
 typedef struct sots_batch sots_batch;
 int sots_batch_create(const sots_config *cfg, uint32_t max_chunks, sots_batch **out);
+/* chunks of the operator-graph voice (sots_create_graph above: the same rules for cfg and graph) */
+int sots_batch_create_graph(const sots_config *cfg, const sots_voice_graph *graph, uint32_t max_chunks, sots_batch **out);
 void sots_batch_destroy(sots_batch *b);
 /* text of the last failure on b (or of the last failed sots_batch_create when b == NULL) */
 const char *sots_batch_last_error(const sots_batch *b);

@@ -17,10 +17,11 @@ MAX_DIMS = 16
 WAVETABLE_SIZE = 32768
 SAMPLE_RATE = 44100
 
-SYNTH_2OP, SYNTH_3OP_SERIES, SYNTH_TRIPLE_PAR, SYNTH_4OP_SERIES = 0, 1, 2, 3
-SYNTH_DIMS = {SYNTH_2OP: 4, SYNTH_3OP_SERIES: 6, SYNTH_TRIPLE_PAR: 12, SYNTH_4OP_SERIES: 8}
+SYNTH_2OP, SYNTH_3OP_SERIES, SYNTH_TRIPLE_PAR, SYNTH_4OP_SERIES, SYNTH_GRAPH = 0, 1, 2, 3, 4
+SYNTH_DIMS = {SYNTH_2OP: 4, SYNTH_3OP_SERIES: 6, SYNTH_TRIPLE_PAR: 12, SYNTH_4OP_SERIES: 8}  # the fixed voices
 SYNTH_NAMES = {"2op": SYNTH_2OP, "3op_series": SYNTH_3OP_SERIES,
-               "triple_parallel": SYNTH_TRIPLE_PAR, "4op_series": SYNTH_4OP_SERIES}
+               "triple_parallel": SYNTH_TRIPLE_PAR, "4op_series": SYNTH_4OP_SERIES, "graph": SYNTH_GRAPH}
+GRAPH_MAX_OPERATORS = 8
 
 (STAGE_INIT, STAGE_RECOMBINE, STAGE_MUTATE, STAGE_SYNTHESISE, STAGE_WINDOW, STAGE_FFT,
  STAGE_FITNESS, STAGE_SORT, STAGE_ROTATE, STAGE_FUSED_VARIATION, STAGE_FUSED_SYNTH,
@@ -72,6 +73,7 @@ EXPORTS = [
     "sots_render_continuous",
     "sots_batch_queue_set_carry", "sots_batch_queue_get_carry",
     "sots_batch_set_analysis", "sots_batch_get_analysis", "sots_batch_analyse_audio_hop", "sots_batch_queue_score_audio_hop",
+    "sots_create_graph", "sots_batch_create_graph", "sots_get_voice_graph",
 ]
 ANALYSIS_HOST, ANALYSIS_DEVICE = 0, 1  # enum sots_analysis
 QUEUE_NO_CHUNK = 0xFFFFFFFF
@@ -97,6 +99,50 @@ class Config(C.Structure):
         ("device", C.c_int32), ("gid_base", C.c_uint32), ("seed", C.c_uint64),
         ("param_min", C.c_float * MAX_DIMS), ("param_max", C.c_float * MAX_DIMS),
     ]
+
+
+class VoiceGraph(C.Structure):
+    """sots_voice_graph: the topology of the operator-graph voice (SYNTH_GRAPH)"""
+    _fields_ = [("struct_size", C.c_uint32), ("num_operators", C.c_uint32), ("carriers", C.c_uint32),
+                ("modulators", C.c_uint32 * GRAPH_MAX_OPERATORS)]
+
+
+def _mask(bits):
+    """a bit mask from an int or from a list of operator indices"""
+    if isinstance(bits, int):
+        return bits
+    m = 0
+    for i in bits:
+        m |= 1 << int(i)
+    return m
+
+
+def make_voice_graph(operators, modulators, carriers):
+    """modulators[j]: the operators that modulate operator j, carriers: the operators that are heard; each a list of
+    indices or a bit mask.  Nothing is checked here: the library's rule refuses a malformed graph with its own text."""
+    g = VoiceGraph()
+    g.struct_size = C.sizeof(VoiceGraph)
+    g.num_operators = operators
+    g.carriers = _mask(carriers) & 0xFFFFFFFF
+    for j, m in enumerate(list(modulators)[:GRAPH_MAX_OPERATORS]):
+        g.modulators[j] = _mask(m) & 0xFFFFFFFF
+    return g
+
+
+def as_voice_graph(graph):
+    """None, a VoiceGraph, or the JSON form {"operators": n, "modulators": [[...], ...], "carriers": [...]}"""
+    if graph is None or isinstance(graph, VoiceGraph):
+        return graph
+    return make_voice_graph(graph["operators"], graph["modulators"], graph["carriers"])
+
+
+def synth_dims(synth_kind, graph=None):
+    """genes of a voice: the fixed voices' by kind, two per operator of a graph"""
+    if synth_kind == SYNTH_GRAPH:
+        if graph is None:
+            raise ValueError("SYNTH_GRAPH needs graph=")
+        return 2 * int(as_voice_graph(graph).num_operators)
+    return SYNTH_DIMS[synth_kind]
 
 
 class Info(C.Structure):
@@ -292,6 +338,9 @@ def load():
     L.sots_batch_get_analysis.argtypes = [vp, C.POINTER(u32)]
     L.sots_batch_analyse_audio_hop.argtypes = [vp, vp, C.c_uint64, u32, u32, vp, C.c_uint64]
     L.sots_batch_queue_score_audio_hop.argtypes = [vp, vp, C.c_uint64, u32, vp, u32]
+    L.sots_create_graph.argtypes = [C.POINTER(Config), C.POINTER(VoiceGraph), C.POINTER(vp)]
+    L.sots_batch_create_graph.argtypes = [C.POINTER(Config), C.POINTER(VoiceGraph), u32, C.POINTER(vp)]
+    L.sots_get_voice_graph.argtypes = [vp, C.POINTER(VoiceGraph)]
     _lib = L
     return L
 
@@ -309,8 +358,8 @@ def _nbytes(a):
 
 
 def make_config(num_parents, num_offspring, synth_kind=SYNTH_2OP, audio_log2=10, param_min=None, param_max=None,
-                seed=0x5EED0001, workgroup_size=32, device=0, gid_base=0, num_generations=0):
-    d = SYNTH_DIMS[synth_kind]
+                seed=0x5EED0001, workgroup_size=32, device=0, gid_base=0, num_generations=0, graph=None):
+    d = synth_dims(synth_kind, graph)
     cfg = Config()
     cfg.struct_size = C.sizeof(Config)
     cfg.num_parents, cfg.num_offspring, cfg.num_dimensions = num_parents, num_offspring, d
@@ -342,26 +391,21 @@ class HipES:
 
     def __init__(self, num_parents, num_offspring, synth_kind=SYNTH_2OP, audio_log2=10,
                  param_min=None, param_max=None, seed=0x5EED0001, workgroup_size=32,
-                 device=0, gid_base=0, num_generations=0):
+                 device=0, gid_base=0, num_generations=0, graph=None):
+        """graph (with synth_kind=SYNTH_GRAPH): a VoiceGraph or its JSON form, see as_voice_graph"""
         self.L = load()
         self._borrowed = False
-        d = SYNTH_DIMS[synth_kind]
-        cfg = Config()
-        cfg.struct_size = C.sizeof(Config)
-        cfg.num_parents, cfg.num_offspring, cfg.num_dimensions = num_parents, num_offspring, d
-        cfg.audio_length_log2, cfg.num_generations = audio_log2, num_generations
-        cfg.synth_kind, cfg.workgroup_size = synth_kind, workgroup_size
-        cfg.device, cfg.gid_base, cfg.seed = device, gid_base, seed
-        pmin = list(param_min) if param_min is not None else [0.0] * d
-        pmax = list(param_max)
-        for i in range(MAX_DIMS):
-            cfg.param_min[i] = float(pmin[i]) if i < len(pmin) else 0.0
-            cfg.param_max[i] = float(pmax[i]) if i < len(pmax) else 0.0
+        self.graph = as_voice_graph(graph)
+        cfg = make_config(num_parents, num_offspring, synth_kind, audio_log2, param_min, param_max, seed, workgroup_size,
+                          device, gid_base, num_generations, graph=self.graph)
         self.cfg = cfg
-        self.P, self.D, self.N = num_parents + num_offspring, d, 1 << audio_log2
+        self.P, self.D, self.N = num_parents + num_offspring, cfg.num_dimensions, 1 << audio_log2
         self.num_parents = num_parents
         h = C.c_void_p()
-        rc = self.L.sots_create(C.byref(cfg), C.byref(h))
+        if self.graph is not None:
+            rc = self.L.sots_create_graph(C.byref(cfg), C.byref(self.graph), C.byref(h))
+        else:
+            rc = self.L.sots_create(C.byref(cfg), C.byref(h))
         if rc != 0:
             raise SotsError(rc, self.L.sots_last_error(None).decode())
         self._h = h
@@ -388,6 +432,11 @@ class HipES:
 
     def synchronize(self):
         self._check(self.L.sots_synchronize(self._h))
+
+    def voice_graph(self):
+        g = VoiceGraph()
+        self._check(self.L.sots_get_voice_graph(self._h, C.byref(g)))
+        return g
 
     def info(self):
         i = Info()
@@ -682,16 +731,20 @@ class HipBatch:
     HipES of the same arguments computes after init_population(first + c)."""
 
     def __init__(self, max_chunks, num_parents, num_offspring, synth_kind=SYNTH_2OP, audio_log2=10, param_min=None,
-                 param_max=None, seed=0x5EED0001, workgroup_size=32, device=0, gid_base=0, num_generations=0):
+                 param_max=None, seed=0x5EED0001, workgroup_size=32, device=0, gid_base=0, num_generations=0, graph=None):
         self.L = load()
+        self.graph = as_voice_graph(graph)
         self.cfg = make_config(num_parents, num_offspring, synth_kind, audio_log2, param_min, param_max, seed, workgroup_size,
-                               device, gid_base, num_generations)
-        self.P, self.D, self.N = num_parents + num_offspring, SYNTH_DIMS[synth_kind], 1 << audio_log2
+                               device, gid_base, num_generations, graph=self.graph)
+        self.P, self.D, self.N = num_parents + num_offspring, self.cfg.num_dimensions, 1 << audio_log2
         self.max_chunks = max_chunks
         self.active = 0
         self.queued = 0
         h = C.c_void_p()
-        rc = self.L.sots_batch_create(C.byref(self.cfg), max_chunks, C.byref(h))
+        if self.graph is not None:
+            rc = self.L.sots_batch_create_graph(C.byref(self.cfg), C.byref(self.graph), max_chunks, C.byref(h))
+        else:
+            rc = self.L.sots_batch_create(C.byref(self.cfg), max_chunks, C.byref(h))
         if rc != 0:
             raise SotsError(rc, self.L.sots_batch_last_error(None).decode())
         self._h = h

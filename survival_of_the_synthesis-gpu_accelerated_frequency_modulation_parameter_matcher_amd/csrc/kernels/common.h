@@ -1,5 +1,5 @@
 // common.h -- what every kernel family uses: the wavefront size, packed-float and compile-time-index types and the
-// cross-lane primitives (wavefront sum, value of lane ^ J).
+// cross-lane primitives (wavefront sum, value of lane ^ J); the synthesis kernels' wavetable on its way into LDS.
 #pragma once
 #include "../sots_kernels.h"
 #include <type_traits>
@@ -60,6 +60,25 @@ template <uint32_t J> __device__ __forceinline__ float lane_xor_f(float v)
 {
     if constexpr (J == 8) return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x128, 0xf, 0xf, true)); // row_ror:8
     else return __uint_as_float(lane_xor<J>(__float_as_uint(v)));
+}
+
+// The synthesis kernels' wavetable, global -> LDS (every thread of the workgroup calls it; tab holds kWavetableSize floats)
+__device__ __forceinline__ void request_wavetable(float *__restrict__ tab, const float *__restrict__ wavetable)
+{
+    // global -> LDS directly (global_load_lds_dwordx4): one wavefront instruction lands 1 KiB at a
+    // wavefront-uniform LDS base + lane * 16 B, no registers in between, all 128 in flight at once
+    typedef __attribute__((address_space(3))) void *lds_ptr_t;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave), lane = threadIdx.x & (kWave - 1);
+    const uint32_t waves = blockDim.x / kWave;
+    constexpr uint32_t kChunk = kWave * 4; // floats per instruction
+    for (uint32_t ch = wave; ch < kWavetableSize / kChunk; ch += waves)
+        __builtin_amdgcn_global_load_lds(wavetable + ch * kChunk + lane * 4u, (lds_ptr_t)(tab + ch * kChunk), 16, 0, 0);
+}
+// ... and the wait for it, after whatever else the kernel can start meanwhile
+__device__ __forceinline__ void wavetable_ready()
+{
+    __builtin_amdgcn_s_waitcnt(0); // vmcnt(0): the copies have landed
+    __syncthreads();
 }
 
 // Audio rows are read exactly once per generation: non-temporal loads keep them from

@@ -241,12 +241,12 @@ template <class Fill> int queue_store(sots_batch *b, uint32_t num_chunks, Fill f
 
 extern "C" {
 
-int sots_batch_create(const sots_config *cfg, uint32_t max_chunks, sots_batch **out)
+// sots_batch_create (graph == nullptr) and sots_batch_create_graph
+static int create_batch(const sots_config *cfg, const sots_voice_graph *graph, uint32_t max_chunks, sots_batch **out)
 {
-    if (!cfg || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_batch_create: null argument");
     *out = nullptr;
     // the configuration first, then the batch's own limits: a machine without a GPU still tells a bad one from a good one
-    SOTS_REFUSE(nullptr, config_check(*cfg, kNoPopulationLimit));
+    SOTS_REFUSE(nullptr, config_check(*cfg, kNoPopulationLimit, graph));
     const uint64_t p64 = (uint64_t)cfg->num_parents + cfg->num_offspring;
     if (p64 > kBatchMaxPopulation)
         return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "a batch takes chunk populations of at most %u, got %llu (larger ones fill the GPU alone: sots_create)",
@@ -256,7 +256,7 @@ int sots_batch_create(const sots_config *cfg, uint32_t max_chunks, sots_batch **
         return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "max_chunks %u x population %llu exceeds 2^26 rows", max_chunks, (unsigned long long)p64);
 
     sots_batch *b = new sots_batch();
-    if (int rc = engine_create(*b, *cfg, 32)) return abandon(b, rc); // (the pad of sots_create: rows off the power-of-two stride)
+    if (int rc = engine_create(*b, *cfg, graph, 32)) return abandon(b, rc); // (the pad of sots_create: rows off the power-of-two stride)
     b->max_chunks = max_chunks;
 #define CREATE_HIP(call) SOTS_HIP_OR(b, call, return abandon(b, rc_))
     const size_t pd_bytes = (size_t)2 * b->rows() * b->D * sizeof(float);
@@ -288,6 +288,18 @@ int sots_batch_create(const sots_config *cfg, uint32_t max_chunks, sots_batch **
 #undef CREATE_HIP
     *out = b;
     return SOTS_OK;
+}
+
+int sots_batch_create(const sots_config *cfg, uint32_t max_chunks, sots_batch **out)
+{
+    if (!cfg || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_batch_create: null argument");
+    return create_batch(cfg, nullptr, max_chunks, out);
+}
+
+int sots_batch_create_graph(const sots_config *cfg, const sots_voice_graph *graph, uint32_t max_chunks, sots_batch **out)
+{
+    if (!cfg || !graph || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_batch_create_graph: null argument");
+    return create_batch(cfg, graph, max_chunks, out);
 }
 
 void sots_batch_destroy(sots_batch *b) { free_batch(b); }

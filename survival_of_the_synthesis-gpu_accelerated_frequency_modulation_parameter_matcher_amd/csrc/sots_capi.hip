@@ -391,11 +391,11 @@ int record_generation(sots_ctx *ctx)
 // =======================================================================================
 extern "C" {
 
-int sots_create(const sots_config *cfg, sots_ctx **out)
+// sots_create (graph == nullptr) and sots_create_graph
+static int create_context(const sots_config *cfg, const sots_voice_graph *graph, sots_ctx **out)
 {
-    if (!cfg || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_create: null argument");
     *out = nullptr;
-    SOTS_REFUSE(nullptr, config_check(*cfg, 1ull << 26));
+    SOTS_REFUSE(nullptr, config_check(*cfg, 1ull << 26, graph));
 
     sots_ctx *ctx = new sots_ctx();
     // audio rows are padded off the power-of-two stride (see sots_kernels.h)
@@ -406,7 +406,7 @@ int sots_create(const sots_config *cfg, sots_ctx **out)
     if (const char *e = getenv("SOTS_FUSE_VARIATION")) ctx->fuse_variation = atoi(e) != 0 ? 1 : 0;
     if (const char *e = getenv("SOTS_SKIP_STAGE")) ctx->skip_stage = atoi(e); // 1: no synthesis, 2: no spectral kernel (timing ablations)
 #endif
-    if (int rc = engine_create(*ctx, *cfg, pad)) return abandon(ctx, rc);
+    if (int rc = engine_create(*ctx, *cfg, graph, pad)) return abandon(ctx, rc);
 #define CREATE_HIP(call) SOTS_HIP_OR(ctx, call, return abandon(ctx, rc_))
     const size_t pd_bytes = (size_t)2 * ctx->P * ctx->D * sizeof(float);
     const size_t audio_bytes = (size_t)ctx->P * ctx->pitch * sizeof(float);
@@ -444,6 +444,27 @@ int sots_create(const sots_config *cfg, sots_ctx **out)
     CREATE_HIP(hipStreamSynchronize(ctx->stream));
 #undef CREATE_HIP
     *out = ctx;
+    return SOTS_OK;
+}
+
+int sots_create(const sots_config *cfg, sots_ctx **out)
+{
+    if (!cfg || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_create: null argument");
+    return create_context(cfg, nullptr, out);
+}
+
+int sots_create_graph(const sots_config *cfg, const sots_voice_graph *graph, sots_ctx **out)
+{
+    if (!cfg || !graph || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_create_graph: null argument");
+    return create_context(cfg, graph, out);
+}
+
+int sots_get_voice_graph(const sots_ctx *ctx, sots_voice_graph *graph)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (!graph) return SOTS_FAIL(ctx, SOTS_ERR_INVALID, "sots_get_voice_graph: null argument");
+    if (ctx->cfg.synth_kind != SOTS_SYNTH_GRAPH) return SOTS_FAIL(ctx, SOTS_ERR_STATE, "sots_get_voice_graph: the context runs a fixed voice (synth_kind %u)", ctx->cfg.synth_kind);
+    *graph = ctx->graph;
     return SOTS_OK;
 }
 
@@ -770,7 +791,8 @@ int sots_execute_generations(sots_ctx *ctx, uint32_t n)
         // (one launch less, 151 vs 157 us per generation at P = 65536); with few wavefronts per CU or
         // more genes the serial per-lane variation costs more than the launch it saves (measured).
         const bool device_arith = ctx->synth_arith == SOTS_ARITH_DEVICE_KERNELS; // (compatibility kernel: makes no individuals)
-        const bool fuse_variation = device_arith ? false : ctx->fuse_variation >= 0 ? ctx->fuse_variation == 1
+        const bool graph_voice = ctx->cfg.synth_kind == SOTS_SYNTH_GRAPH;        // (its kernel makes no individuals either)
+        const bool fuse_variation = device_arith || graph_voice ? false : ctx->fuse_variation >= 0 ? ctx->fuse_variation == 1
                                                              : (ctx->pd.d <= 4 && ctx->P >= 192u * (ctx->num_cus ? ctx->num_cus : 256u)) ||
                                                                    // a few individuals per CU: k_synth_tp makes them, a thread per gene
                                                                    (ctx->allow_cut && synth_time_parallel(ctx->cfg.synth_kind, ctx->P, ctx->num_cus)) ||
@@ -1095,6 +1117,7 @@ int sots_render_continuous(sots_ctx *ctx, const float *values, size_t values_byt
                            float *out, uint64_t out_samples)
 {
     SOTS_REQUIRE_CTX(ctx);
+    SOTS_REFUSE(ctx, render_continuous_voice_check(ctx->cfg.synth_kind));
     SOTS_REFUSE(ctx, render_continuous_check(args, ctx->N, ctx->D, ctx->synth_arith, values, values_bytes, num_rows, out, out_samples));
     if (int rc = engine_bind(*ctx)) return rc;
     const uint32_t N = ctx->N, D = ctx->D, hop = args->hop, kind = ctx->cfg.synth_kind;

@@ -53,6 +53,7 @@ __attribute__((format(printf, 3, 4))) inline int fail_to(std::string &err, int c
 
 struct Engine {
     sots_config cfg{};
+    sots_voice_graph graph{}; // SOTS_SYNTH_GRAPH: the topology that came with cfg (num_operators 0 for a fixed voice)
     PopDims pd{};
     MutateConsts mc{};
     SynthParams sp{};
@@ -81,14 +82,15 @@ inline std::string &err_of(const Engine &e) { return e.err; }
 
 // The device, the stream, the sizes and constants of a configuration that config_check has passed, and the tables' device
 // memory.  row_pad: floats behind the N of an audio row (rows off the power-of-two stride, see sots_kernels.h).  On a
-// failure the text is in e.err and the caller releases.
-inline int engine_create(Engine &e, const sots_config &cfg, uint32_t row_pad)
+// failure the text is in e.err and the caller releases.  graph: with SOTS_SYNTH_GRAPH, null otherwise.
+inline int engine_create(Engine &e, const sots_config &cfg, const sots_voice_graph *graph, uint32_t row_pad)
 {
     int ndev = 0;
     hipError_t err = hipGetDeviceCount(&ndev);
     if (err != hipSuccess || ndev <= 0) return SOTS_FAIL(e, SOTS_ERR_NO_DEVICE, "no HIP device (%s)", hipGetErrorString(err));
     if (cfg.device < 0 || cfg.device >= ndev) return SOTS_FAIL(e, SOTS_ERR_NO_DEVICE, "device %d not in 0..%d", cfg.device, ndev - 1);
     e.cfg = cfg;
+    if (graph) e.graph = *graph;
     e.device = cfg.device;
     SOTS_HIP(e, hipSetDevice(e.device));
     hipDeviceProp_t prop;
@@ -102,7 +104,7 @@ inline int engine_create(Engine &e, const sots_config &cfg, uint32_t row_pad)
     e.stream = e.own_stream;
 
     e.P = cfg.num_parents + cfg.num_offspring;
-    e.D = dims_of(cfg.synth_kind);
+    e.D = graph ? 2u * graph->num_operators : dims_of(cfg.synth_kind);
     e.log2n = cfg.audio_length_log2;
     e.N = 1u << e.log2n;
     e.pitch = e.N + row_pad;
@@ -157,9 +159,7 @@ inline int engine_bind(const Engine &e)
 // ---- settings ----
 inline int engine_set_synth_arithmetic(Engine &e, uint32_t arith)
 {
-    if (arith > SOTS_ARITH_DEVICE_KERNELS) return SOTS_FAIL(e, SOTS_ERR_INVALID, "unknown synthesis arithmetic %u", arith);
-    if (arith == SOTS_ARITH_DEVICE_KERNELS && e.cfg.synth_kind == SOTS_SYNTH_4OP_SERIES)
-        return SOTS_FAIL(e, SOTS_ERR_INVALID, "the reference has no device kernel for the build-defined 4-op voice");
+    SOTS_REFUSE(e, synth_arithmetic_check(arith, e.cfg.synth_kind));
     e.synth_arith = arith;
     return SOTS_OK;
 }
@@ -219,7 +219,7 @@ inline hipError_t engine_synthesise(const Engine &e, const float *values, float 
 {
     if (e.synth_arith == SOTS_ARITH_DEVICE_KERNELS)
         return launch_synth_device_arith(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch);
-    return launch_synth(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch, e.num_cus, var, allow_cut);
+    return launch_synth(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch, e.num_cus, var, allow_cut, &e.graph);
 }
 
 } // namespace sots

@@ -336,24 +336,6 @@ __device__ __forceinline__ void wrap_both(float &p)
     p = __uint_as_float(min(min(__float_as_uint(bc.x), __float_as_uint(bc.y)), __float_as_uint(p)));
 }
 
-__device__ __forceinline__ void request_wavetable(float *__restrict__ tab, const float *__restrict__ wavetable)
-{
-    // global -> LDS directly (global_load_lds_dwordx4): one wavefront instruction lands 1 KiB at a
-    // wavefront-uniform LDS base + lane * 16 B, no registers in between, all 128 in flight at once
-    typedef __attribute__((address_space(3))) void *lds_ptr_t;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave), lane = threadIdx.x & (kWave - 1);
-    const uint32_t waves = blockDim.x / kWave;
-    constexpr uint32_t kChunk = kWave * 4; // floats per instruction
-    for (uint32_t ch = wave; ch < kWavetableSize / kChunk; ch += waves)
-        __builtin_amdgcn_global_load_lds(wavetable + ch * kChunk + lane * 4u, (lds_ptr_t)(tab + ch * kChunk), 16, 0, 0);
-}
-// ... and the wait for it, after whatever else the kernel can start meanwhile
-__device__ __forceinline__ void wavetable_ready()
-{
-    __builtin_amdgcn_s_waitcnt(0); // vmcnt(0): the copies have landed
-    __syncthreads();
-}
-
 // ---- every voice, one lane per individual, whole-line stores through LDS -------------------
 // Each wavefront owns an 8 KiB tile [64 rows][8 chunks of 16 B], XOR-swizzled by row so that
 // both the row-wise writes (lane = row) and the transposed reads (lane = 8 rows x 8 chunks) are
@@ -1545,8 +1527,13 @@ hipError_t launch_synth_device_arith(hipStream_t st, uint32_t kind, const float 
 
 hipError_t launch_synth(hipStream_t st, uint32_t kind, const float *values, const float *wavetable,
                         float *audio, const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch,
-                        uint32_t num_cus, const Variation *variation, bool allow_cut)
+                        uint32_t num_cus, const Variation *variation, bool allow_cut, const sots_voice_graph *graph)
 {
+    // the operator-graph voice has one kernel form, in a file of its own; it makes no individuals
+    if (kind == SOTS_SYNTH_GRAPH) {
+        if (!graph || variation) return hipErrorInvalidValue;
+        return launch_synth_graph(st, *graph, values, wavetable, audio, sp, p, log2n, pitch, num_cus);
+    }
     Variation var = {};
     if (variation) var = *variation;
     const uint32_t n = 1u << log2n;

@@ -45,14 +45,58 @@ inline uint32_t dims_of(uint32_t kind)
     }
 }
 
+// ---- operator-graph voice (SOTS_SYNTH_GRAPH; the definition: include/sots_hip.h) ----
+constexpr uint32_t kGraphMinOps = 2, kGraphMaxOps = 8;
+// operators that operator j's output modulates, as a bit mask (bits above j)
+inline uint32_t graph_targets_of(const sots_voice_graph &g, uint32_t j)
+{
+    uint32_t t = 0;
+    for (uint32_t k = j + 1; k < g.num_operators && k < kGraphMaxOps; ++k)
+        if (g.modulators[k] >> j & 1u) t |= 1u << k;
+    return t;
+}
+// A feed-forward graph in which every operator is heard or modulates, never both and never neither
+inline Fault voice_graph_check(const sots_voice_graph *g)
+{
+    if (!g) return fault(SOTS_ERR_INVALID, "voice graph: null pointer");
+    if (g->struct_size != sizeof(sots_voice_graph))
+        return fault(SOTS_ERR_INVALID, "sots_voice_graph.struct_size %u != %zu", g->struct_size, sizeof(sots_voice_graph));
+    const uint32_t ops = g->num_operators;
+    if (ops < kGraphMinOps || ops > kGraphMaxOps)
+        return fault(SOTS_ERR_INVALID, "voice graph: %u operators outside %u..%u", ops, kGraphMinOps, kGraphMaxOps);
+    const uint32_t all = (1u << ops) - 1u;
+    if (g->carriers & ~all) return fault(SOTS_ERR_INVALID, "voice graph: carriers 0x%x has bits beyond operator %u", g->carriers, ops - 1u);
+    for (uint32_t j = ops; j < kGraphMaxOps; ++j)
+        if (g->modulators[j]) return fault(SOTS_ERR_INVALID, "voice graph: modulators[%u] = 0x%x beyond operator %u", j, g->modulators[j], ops - 1u);
+    for (uint32_t j = 0; j < ops; ++j)
+        if (g->modulators[j] >> j)
+            return fault(SOTS_ERR_INVALID, "voice graph: modulators[%u] = 0x%x has a bit at or above %u (feed-forward only: operator i < j modulates j)",
+                         j, g->modulators[j], j);
+    if (g->carriers == 0) return fault(SOTS_ERR_INVALID, "voice graph: no carrier");
+    for (uint32_t j = 0; j < ops; ++j) {
+        const bool carrier = g->carriers >> j & 1u, modulates = graph_targets_of(*g, j) != 0;
+        if (carrier && modulates) return fault(SOTS_ERR_INVALID, "voice graph: operator %u is a carrier and modulates (one or the other)", j);
+        if (!carrier && !modulates) return fault(SOTS_ERR_INVALID, "voice graph: operator %u is dead: neither a carrier nor a modulator", j);
+    }
+    return Fault{};
+}
+
 // Everything a configuration must satisfy whoever takes it; max_population is the caller's own limit on numParents +
-// numOffspring.  Needs no device: a machine without a GPU still tells a bad configuration from a good one.
+// numOffspring.  Needs no device: a machine without a GPU still tells a bad configuration from a good one.  graph: the
+// topology that came with the configuration (sots_create_graph, sots_batch_create_graph), null from every other entry point.
 constexpr uint64_t kNoPopulationLimit = ~0ull; // (a caller that words its limit itself)
-inline Fault config_check(const sots_config &cfg, uint64_t max_population)
+inline Fault config_check(const sots_config &cfg, uint64_t max_population, const sots_voice_graph *graph = nullptr)
 {
     if (cfg.struct_size != sizeof(sots_config))
         return fault(SOTS_ERR_INVALID, "sots_config.struct_size %u != %zu", cfg.struct_size, sizeof(sots_config));
-    const uint32_t d = dims_of(cfg.synth_kind);
+    if (graph && cfg.synth_kind != SOTS_SYNTH_GRAPH)
+        return fault(SOTS_ERR_INVALID, "a voice graph needs synth_kind %u (SOTS_SYNTH_GRAPH), got %u", (uint32_t)SOTS_SYNTH_GRAPH, cfg.synth_kind);
+    if (!graph && cfg.synth_kind == SOTS_SYNTH_GRAPH)
+        return fault(SOTS_ERR_INVALID, "synth_kind %u (SOTS_SYNTH_GRAPH) needs its topology: sots_create_graph / sots_batch_create_graph",
+                     cfg.synth_kind);
+    if (graph)
+        if (const Fault f = voice_graph_check(graph)) return f;
+    const uint32_t d = graph ? 2u * graph->num_operators : dims_of(cfg.synth_kind);
     if (d == 0) return fault(SOTS_ERR_INVALID, "unknown synth_kind %u", cfg.synth_kind);
     if (cfg.num_dimensions != d)
         return fault(SOTS_ERR_INVALID, "synth_kind %u needs numDimensions %u, got %u", cfg.synth_kind, d, cfg.num_dimensions);
@@ -64,6 +108,17 @@ inline Fault config_check(const sots_config &cfg, uint64_t max_population)
     if (cfg.workgroup_size == 0 || p64 % cfg.workgroup_size != 0)
         return fault(SOTS_ERR_INVALID, "populationLength %llu must be a multiple of workgroupSize %u (the recombination block)",
                      (unsigned long long)p64, cfg.workgroup_size);
+    return Fault{};
+}
+
+// sots_set_synth_arithmetic: the reference's device kernels exist for its own three voices only
+inline Fault synth_arithmetic_check(uint32_t arith, uint32_t kind)
+{
+    if (arith > SOTS_ARITH_DEVICE_KERNELS) return fault(SOTS_ERR_INVALID, "unknown synthesis arithmetic %u", arith);
+    if (arith == SOTS_ARITH_DEVICE_KERNELS && kind == SOTS_SYNTH_4OP_SERIES)
+        return fault(SOTS_ERR_INVALID, "the reference has no device kernel for the build-defined 4-op voice");
+    if (arith == SOTS_ARITH_DEVICE_KERNELS && kind == SOTS_SYNTH_GRAPH)
+        return fault(SOTS_ERR_INVALID, "the reference has no device kernel for the operator-graph voice");
     return Fault{};
 }
 
@@ -190,6 +245,13 @@ inline Fault analysis_frames_check(const char *who, const void *audio, uint64_t 
 }
 
 // ---- phase-continuous rendering ----
+// its scans are written per fixed voice: the operator-graph voice renders by overlap-add only
+inline Fault render_continuous_voice_check(uint32_t kind)
+{
+    if (kind == SOTS_SYNTH_GRAPH)
+        return fault(SOTS_ERR_INVALID, "sots_render_continuous: not for the operator-graph voice (sots_render_overlap_add renders it)");
+    return Fault{};
+}
 // sots_render_continuous: what it refuses before anything touches the device.  n, d, synth_arith: the context's audio
 // length, genes per row and arithmetic mode.
 inline Fault render_continuous_check(const sots_render_continuous_args *args, uint32_t n, uint32_t d, uint32_t synth_arith, const void *values,

@@ -1,0 +1,189 @@
+// sots_synth_graph.hip -- the operator-graph voice (SOTS_SYNTH_GRAPH): one synthesis kernel for every feed-forward FM
+// algorithm of 2 to 8 operators.  The voice is defined in include/sots_hip.h (sots_voice_graph); this file follows that
+// definition operation by operation, unfused (-ffp-contract=off), so the audio equals the serial model bit for bit.
+//
+// Shape, after k_synth<K, 0> (sots_kernels.hip): a lane per individual, the 128 KiB wavetable staged into LDS once per
+// persistent workgroup (one workgroup per CU), finished samples parked in a per-wavefront swizzled LDS tile and stored as
+// whole lines of a row.  What differs:
+//   * the topology is an ARGUMENT: the masks arrive as kernel arguments (scalar registers), and every test on them is
+//     wavefront-uniform.  The loops over operators j and modulators i < j are unrolled with compile-time indices, so
+//     phases, frequencies and levels stay in registers;
+//   * no software pipeline across loop trips and no cut forms: samples go in blocks of U, operator by operator inside a
+//     block, so that an operator's U table reads are in flight together and waited for once (sample by sample, each read
+//     is waited for where it is used: 117 us for the 2-op graph at P = 65 536 against 99 in blocks).
+// A cleared bit is SKIPPED, as the definition says: a sum starts from -0.0f, for which -0 + x == x bit for bit for every
+// x (+0 and -0 included), and only operators whose bit is set are added to it.
+#include "kernels/common.h"
+#include <cstdlib>
+
+#pragma clang fp contract(off)
+namespace sots {
+namespace {
+
+struct GraphMasks {
+    uint32_t carriers;
+    uint32_t modulators[8];
+};
+
+// CH: 16-byte chunks per tile row = 4 CH samples per flush.  The 32 KiB beside the table are 32 / CH tiles of 64 rows:
+// CH = 8, four wavefronts (one per SIMD) and whole 128-byte lines; CH = 4, eight wavefronts (two per SIMD) and half lines.
+template <int OPS, int CH>
+__global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *__restrict__ values, const float *__restrict__ wavetable,
+                                                                  float *__restrict__ audio, SynthParams sp, GraphMasks gm, uint32_t p_len,
+                                                                  uint32_t n, uint32_t pitch)
+{
+    constexpr int D = 2 * OPS, WAVES = 32 / CH;
+    constexpr int RPI = kWave / CH; // rows per transposed read / store instruction (CH of them per flush)
+    constexpr int U = OPS <= 4 ? 8 : 4;            // samples per block: o[OPS][U] stays in registers
+    constexpr int kUnroll = OPS <= 2 ? CH / (U / 4) : 1; // blocks unrolled per flush: the code stays in the instruction cache
+    static_assert(U % 4 == 0 && CH % (U / 4) == 0, "whole 16-byte chunks, whole blocks per flush");
+    static_assert(OPS >= 2 && OPS <= 8 && D <= SOTS_MAX_DIMS && (CH == 8 || CH == 4), "2 to 8 operators; whole or half lines");
+    __shared__ float tab[kWavetableSize];
+    __shared__ float4 stage_all[WAVES * kWave * CH];
+    request_wavetable(tab, wavetable);
+    const float wf = (float)kWavetableSize;
+    const float c = (float)kWavetableSize / (float)SOTS_SAMPLE_RATE;
+    const uint32_t lane = threadIdx.x & (kWave - 1);
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
+    // the tile (k_synth's): lane = row on the write side, chunk q of a row in slot q ^ swz(row); on the read side lane =
+    // (row within a group of RPI rows, chunk), and group g lies 64 slots further
+    float4 *stage = stage_all + wave * kWave * CH;
+    auto swz = [](uint32_t row) { return CH == 8 ? (row & 7u) : ((row >> 1) & 3u); };
+    float4 *wr = stage + lane * CH;
+    const uint32_t l7 = swz(lane);
+    const uint32_t r8 = lane / CH, rch = lane % CH;
+    const float4 *rd = stage + r8 * CH + (rch ^ swz(r8));
+
+    // table[clamp((int)pos, 0, W-1)], the clamp decided on the float: NaN and negatives give entry 0
+    auto tab_at = [&](float pos) { return tab[(uint32_t)fminf(fmaxf(pos, 0.0f), wf - 1.0f)]; };
+    uint32_t num_carriers = 0;
+#pragma unroll
+    for (int j = 0; j < OPS; ++j) num_carriers += gm.carriers >> j & 1u;
+    const float carriers_f = (float)num_carriers;
+
+    wavetable_ready();
+    const uint32_t rows_per_block = blockDim.x; // a row per lane
+    for (uint32_t base = blockIdx.x * rows_per_block; base < p_len; base += gridDim.x * rows_per_block) {
+        const uint32_t row0 = base + wave * kWave; // first row of this wavefront
+        if (row0 >= p_len) continue;               // (wavefront-uniform; no workgroup barrier below)
+        const uint32_t ind = row0 + lane < p_len ? row0 + lane : p_len - 1u;
+        float f[OPS], amp[OPS], pos[OPS];
+#pragma unroll
+        for (int j = 0; j < OPS; ++j) {
+            const float a = sp.pmin[2 * j + 1] + values[(size_t)ind * D + 2 * j + 1] * (sp.pmax[2 * j + 1] - sp.pmin[2 * j + 1]);
+            f[j] = sp.pmin[2 * j] + values[(size_t)ind * D + 2 * j] * (sp.pmax[2 * j] - sp.pmin[2 * j]);
+            amp[j] = (gm.carriers >> j & 1u) ? a : f[j] * a;
+            pos[j] = 0.0f;
+        }
+        // U samples at a time, operator by operator: operator j's sample u needs its own phase and the outputs o[i][u] of
+        // the operators i < j, which the block already holds - the order of the definition, sample by sample, is kept for
+        // every value.  An operator's U table reads are issued with nothing but its phase recurrence between them and
+        // waited for once, before its outputs are made.
+        auto block = [&](float(&y)[U]) {
+            float o[OPS][U];
+            static_for<0, OPS>([&](auto j_tag) {
+                constexpr int J = decltype(j_tag)::value;
+                float cur[U], tv[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) cur[u] = -0.0f;
+                static_for<0, J>([&](auto i_tag) {
+                    constexpr int I = decltype(i_tag)::value;
+                    if (gm.modulators[J] >> I & 1u) {
+#pragma unroll
+                        for (int u = 0; u < U; ++u) cur[u] += o[I][u];
+                    }
+                });
+                const bool modulated = gm.modulators[J] != 0u;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    tv[u] = tab_at(pos[J]);
+                    pos[J] += c * (cur[u] + f[J]);
+                    if (pos[J] >= wf) pos[J] -= wf;
+                    if (modulated && pos[J] < 0.0f) pos[J] += wf;
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) o[J][u] = tv[u] * amp[J];
+            });
+#pragma unroll
+            for (int u = 0; u < U; ++u) y[u] = -0.0f;
+            static_for<0, OPS>([&](auto j_tag) {
+                constexpr int J = decltype(j_tag)::value;
+                if (gm.carriers >> J & 1u) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) y[u] += o[J][u];
+                }
+            });
+            if (num_carriers > 1u) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) y[u] = y[u] / carriers_f;
+            }
+        };
+        for (uint32_t i0 = 0; i0 < n; i0 += 4u * CH) {
+#pragma unroll kUnroll
+            for (uint32_t q = 0; q < (uint32_t)CH; q += U / 4) {
+                float y[U];
+                block(y);
+#pragma unroll
+                for (int k = 0; k < U / 4; ++k) wr[(q + k) ^ l7] = make_float4(y[4 * k], y[4 * k + 1], y[4 * k + 2], y[4 * k + 3]);
+            }
+            // 4 CH samples of 64 rows are parked: read back transposed, RPI rows x whole (half) lines per store
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("" ::: "memory");
+#pragma unroll 4 // (four lines in flight: all eight at once cost the 8-operator form its 128 registers)
+            for (uint32_t g = 0; g < (uint32_t)CH; ++g) {
+                const uint32_t row = row0 + g * RPI + r8;
+                if (row < p_len) *reinterpret_cast<float4 *>(audio + (size_t)row * pitch + i0 + 4u * rch) = rd[g * kWave];
+            }
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("" ::: "memory");
+        }
+    }
+}
+
+template <int OPS>
+hipError_t launch_ops(hipStream_t st, const GraphMasks &gm, const float *values, const float *wavetable, float *audio, const SynthParams &sp,
+                      uint32_t p, uint32_t n, uint32_t pitch, uint32_t cus)
+{
+    // one workgroup per CU (the table), sized to the CU's share of the population up to one wavefront per SIMD; larger
+    // populations loop over tiles
+    uint32_t max_waves = 4;
+#ifdef SOTS_EXPERIMENT
+    if (const char *e = getenv("SOTS_GRAPH_WAVES")) max_waves = atoi(e) == 8 ? 8 : 4; // 8: two per SIMD, half-line tiles
+#endif
+    const uint32_t share = (p + cus - 1) / cus;
+    uint32_t waves = (share + kWave - 1) / kWave;
+    if (waves > max_waves) waves = max_waves;
+    const uint32_t rows = waves * kWave, tiles = (p + rows - 1) / rows, grid = tiles < cus ? tiles : cus;
+#ifdef SOTS_EXPERIMENT
+    if (max_waves == 8) {
+        k_synth_graph<OPS, 4><<<grid, rows, 0, st>>>(values, wavetable, audio, sp, gm, p, n, pitch);
+        return hipGetLastError();
+    }
+#endif
+    k_synth_graph<OPS, 8><<<grid, rows, 0, st>>>(values, wavetable, audio, sp, gm, p, n, pitch);
+    return hipGetLastError();
+}
+
+} // namespace
+
+hipError_t launch_synth_graph(hipStream_t st, const sots_voice_graph &graph, const float *values, const float *wavetable, float *audio,
+                              const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus)
+{
+    if (p == 0 || log2n < 8 || pitch < (1u << log2n) || pitch % 4u != 0) return hipErrorInvalidValue; // (a flush is 32 samples; 16-byte stores)
+    GraphMasks gm;
+    gm.carriers = graph.carriers;
+    for (int j = 0; j < 8; ++j) gm.modulators[j] = graph.modulators[j];
+    const uint32_t n = 1u << log2n, cus = num_cus ? num_cus : 256;
+    switch (graph.num_operators) {
+    case 2: return launch_ops<2>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
+    case 3: return launch_ops<3>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
+    case 4: return launch_ops<4>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
+    case 5: return launch_ops<5>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
+    case 6: return launch_ops<6>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
+    case 7: return launch_ops<7>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
+    case 8: return launch_ops<8>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+} // namespace sots

@@ -192,6 +192,37 @@ public:
             aAudioBuffer[i] = (parts[0][i] + parts[1][i] + parts[2][i]) / 3.0;
     }
 
+    // the operator-graph voice (sots_voice_graph, include/sots_hip.h: the definition this follows step by step; no reference
+    // counterpart): ops operators, gene 2j operator j's frequency, gene 2j+1 its level; bit i of modulators[j]: operator i
+    // modulates operator j; bit j of carriers: operator j is heard.  The graph is the library's to check.
+    SOTS_NO_CONTRACT_ATTR void synthesiseAudioGraph(uint32_t ops, uint32_t carriers, const uint32_t *modulators, const std::vector<float> aParams,
+                                                    float *aAudioBuffer)
+    {
+        SOTS_NO_CONTRACT
+        float f[8], level[8], pos[8], o[8];
+        uint32_t heard = 0;
+        for (uint32_t j = 0; j < ops && j < 8; ++j) {
+            f[j] = scaled(aParams[2 * j], 2 * j);
+            const float a = scaled(aParams[2 * j + 1], 2 * j + 1);
+            level[j] = (carriers >> j & 1u) ? a : f[j] * a;
+            pos[j] = 0.0f;
+            heard += carriers >> j & 1u;
+        }
+        for (uint32_t i = 0; i < audioLength; i++) {
+            float y = -0.0f; // (-0 + x is x bit for bit: the sums below add only what is there)
+            for (uint32_t j = 0; j < ops && j < 8; ++j) {
+                o[j] = tableAt(pos[j]) * level[j];
+                float cur = -0.0f;
+                for (uint32_t k = 0; k < j; ++k)
+                    if (modulators[j] >> k & 1u) cur += o[k];
+                cur += f[j];
+                advance(pos[j], w2srRatio * cur, modulators[j] != 0u);
+                if (carriers >> j & 1u) y += o[j];
+            }
+            aAudioBuffer[i] = heard > 1 ? y / (float)heard : y;
+        }
+    }
+
     // window -> forward real DFT (fp64) -> |X|/N/windowFactor for k < N/2 (:524-542)
     void calculateFFT(float *input, float *output)
     {

@@ -44,6 +44,12 @@ struct Evolutionary_Strategy_HIP_Arguments
     uint64_t seed = 0x5EED0001ull;    // replaces the wall-clock seed
     uint32_t gidBase = 0;             // island offset of individual 0
     int32_t synthKind = -1;           // -1: derive from numDimensions (4, 6, 8, 12)
+    // The operator-graph voice (type.HIP.synth "graph" with type.HIP.voiceGraph; sots_create_graph): with
+    // synthKind SOTS_SYNTH_GRAPH the topology, numDimensions = 2 x num_operators.  One device; matchPath, renderMatch
+    // (overlap-add), matchReport, chunksInFlight and chunkQueue work with it; renderMode 1 and 2 with renderMatch and
+    // deviceKernelArithmetic do not: the constructor throws - before any device work - and a malformed graph is refused there
+    // with the library's own text.
+    sots_voice_graph voiceGraph{};
     bool fusedGenerations = true;     // executeAllGenerations uses the fused kernel loop
     // general.isBenchmarking (parameters.json:7, main.cpp:85).  true: every launch is bracketed by a
     // hipEvent pair and lands in the CSV under the reference's stage names (an event pair costs
@@ -200,6 +206,16 @@ private:
         case 12: return SOTS_SYNTH_TRIPLE_PAR;
         default: return -1;
         }
+    }
+    // the chunks in flight: a batch of the context's configuration (and graph)
+    void createBatch()
+    {
+        const bool graphVoice = cfg_.synth_kind == SOTS_SYNTH_GRAPH;
+        const int rc = graphVoice ? sots_batch_create_graph(&cfg_, &args_.voiceGraph, args_.chunksInFlight, &batch_)
+                                  : sots_batch_create(&cfg_, args_.chunksInFlight, &batch_);
+        if (rc != SOTS_OK)
+            throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + (graphVoice ? "sots_batch_create_graph: " : "sots_batch_create: ") +
+                                     sots_batch_last_error(nullptr));
     }
     void check(int rc, const char *what) const
     {
@@ -369,6 +385,11 @@ public:
         const int kind = args_.synthKind >= 0 ? args_.synthKind : kindFromDims(population.numDimensions);
         if (kind < 0) throw std::runtime_error("Evolutionary_Strategy_HIP: numDimensions must be 4, 6, 8 or 12");
         cfg_.synth_kind = (uint32_t)kind;
+        const bool graphVoice = kind == SOTS_SYNTH_GRAPH;
+        if (graphVoice && args_.renderMatch && args_.renderMode != 0u)
+            throw std::runtime_error("Evolutionary_Strategy_HIP: renderMode 1 and 2 (sots_render_continuous) are not available with the operator-graph voice");
+        if (graphVoice && args_.deviceKernelArithmetic)
+            throw std::runtime_error("Evolutionary_Strategy_HIP: deviceKernelArithmetic is not available with the operator-graph voice");
         cfg_.workgroup_size = args_.workgroupX * args_.workgroupY * args_.workgroupZ;
         cfg_.device = args_.deviceOrdinal;
         cfg_.gid_base = args_.gidBase;
@@ -397,8 +418,9 @@ public:
             if (rc != SOTS_OK) throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_group_create: ") + sots_group_last_error(nullptr));
             ctx_ = sots_group_island(group_, 0);
         } else {
-            const int rc = sots_create(&cfg_, &ctx_);
-            if (rc != SOTS_OK) throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_create: ") + sots_last_error(nullptr));
+            const int rc = graphVoice ? sots_create_graph(&cfg_, &args_.voiceGraph, &ctx_) : sots_create(&cfg_, &ctx_);
+            if (rc != SOTS_OK)
+                throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + (graphVoice ? "sots_create_graph: " : "sots_create: ") + sots_last_error(nullptr));
         }
         targetFFT_.assign(objective.fftHalfSize, 0.0f);
         if (args_.fullSortEveryGeneration)
@@ -621,8 +643,7 @@ private:
     void matchChunkQueue(const float *aTargetAudio)
     {
         const uint32_t half = objective.fftHalfSize, d = population.numDimensions, P = population.populationLength;
-        if (!batch_ && sots_batch_create(&cfg_, args_.chunksInFlight, &batch_) != SOTS_OK)
-            throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_batch_create: ") + sots_batch_last_error(nullptr));
+        if (!batch_) createBatch();
         auto checkBatch = [&](int rc, const char *what) {
             if (rc != SOTS_OK) throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + what + ": " + sots_batch_last_error(batch_));
         };
@@ -676,8 +697,7 @@ private:
         const uint32_t half = objective.fftHalfSize, d = population.numDimensions, P = population.populationLength;
         const uint32_t perBatch = std::min(args_.chunksInFlight, numChunks_);
         if (perBatch == 0) return;
-        if (!batch_ && sots_batch_create(&cfg_, args_.chunksInFlight, &batch_) != SOTS_OK)
-            throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_batch_create: ") + sots_batch_last_error(nullptr));
+        if (!batch_) createBatch();
         auto checkBatch = [&](int rc, const char *what) {
             if (rc != SOTS_OK) throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + what + ": " + sots_batch_last_error(batch_));
         };

@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/sots_hip.h" // sots_voice_graph (the struct only: nothing here calls the library)
 #include "Match_track.hpp"
 #include "Objective_weights.hpp"
 
@@ -275,6 +276,55 @@ inline bool readAnalysisKeys(const Json &h, uint64_t populationLength, bool &dev
     deviceAnalysis = device;
     matchReport = report;
     return device || !report.empty();
+}
+
+// type.HIP.synth "graph" with type.HIP.voiceGraph (sots_voice_graph, include/sots_hip.h): the operator-graph
+// voice, e.g. {"operators": 3, "modulators": [[], [0], [1]], "carriers": [2]} - modulators[j] lists the operators that
+// modulate operator j, carriers the operators that are heard.  Returns whether the voice is the graph; throws - like the keys
+// above, before any device work - where one key comes without the other, on a shape that is not the one above, on
+// numDimensions other than 2 x operators, and on renderMode "continuous" / "continuousGlide" with renderMatch (the
+// phase-continuous renderer is written per fixed voice).  Whether the topology is a valid one is the library's rule
+// (csrc/sots_rules.h), which sots_create_graph applies before it touches a device.
+inline bool readVoiceGraphKeys(const Json &h, uint32_t numDimensions, bool renderMatch, uint32_t renderMode, sots_voice_graph &graph)
+{
+    const bool named = h.has("synth") && h["synth"].kind == Json::String && h["synth"].str == "graph";
+    const std::string what = "parameters.json: type.HIP.voiceGraph";
+    if (!named && !h.has("voiceGraph")) return false;
+    if (!named) throw std::runtime_error(what + " needs type.HIP.synth \"graph\"");
+    if (!h.has("voiceGraph")) throw std::runtime_error("parameters.json: type.HIP.synth \"graph\" needs type.HIP.voiceGraph");
+    const Json &v = h["voiceGraph"];
+    const char *shape = " must be {\"operators\": n, \"modulators\": [[...], ...], \"carriers\": [...]}";
+    if (v.kind != Json::Object || !v.has("operators") || !v.has("modulators") || !v.has("carriers") || v.obj.size() != 3 ||
+        v["operators"].kind != Json::Number || v["modulators"].kind != Json::Array || v["carriers"].kind != Json::Array)
+        throw std::runtime_error(what + shape);
+    // an operator index as a mask bit; one that no mask holds becomes bit 31, which the library's rule names
+    auto mask = [&](const Json &list) {
+        if (list.kind != Json::Array) throw std::runtime_error(what + shape);
+        uint32_t m = 0;
+        for (const Json &e : list.arr) {
+            if (e.kind != Json::Number || !(e.num >= 0.0) || e.num != std::floor(e.num))
+                throw std::runtime_error(what + ": operator indices are whole numbers, 0 or more");
+            m |= 1u << (e.num < 31.0 ? (uint32_t)e.num : 31u);
+        }
+        return m;
+    };
+    const double ops = v["operators"].num;
+    if (!(ops >= 0.0) || ops != std::floor(ops)) throw std::runtime_error(what + ": operators must be a whole number");
+    sots_voice_graph g{};
+    g.struct_size = sizeof g;
+    g.num_operators = ops >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)ops;
+    if (v["modulators"].arr.size() != (size_t)ops || ops > 8.0)
+        throw std::runtime_error(what + ": modulators needs one list per operator (" + std::to_string(v["modulators"].arr.size()) + " lists, " +
+                                 std::to_string((unsigned long long)std::fmin(ops, 1.8e19)) + " operators, at most 8)");
+    for (size_t j = 0; j < v["modulators"].arr.size(); ++j) g.modulators[j] = mask(v["modulators"].arr[j]);
+    g.carriers = mask(v["carriers"]);
+    if (numDimensions != 2u * g.num_operators)
+        throw std::runtime_error("parameters.json: evolutionary.numDimensions " + std::to_string(numDimensions) + " must be 2 x type.HIP.voiceGraph.operators = " +
+                                 std::to_string(2u * g.num_operators));
+    if (renderMatch && renderMode != 0u)
+        throw std::runtime_error("parameters.json: type.HIP.renderMode \"continuous\" and \"continuousGlide\" are not available with type.HIP.synth \"graph\"");
+    graph = g;
+    return true;
 }
 
 #endif

@@ -1,7 +1,7 @@
 // sots_match.cpp -- command-line driver with the reference's interface (main.cpp:25-305):
 //     sots_match -j parameters.json
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
-// "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "numDevices", "numElites",
+// "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "voiceGraph", "numDevices", "numElites",
 // "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight", "chunkQueue",
 // "carryRows", "segmentChunks", "survivors", "objective", "objectiveFloor", "objectiveWeights", "hopSize", "renderMatch", "renderMode", "matchPath", "deviceAnalysis", "matchReport", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
@@ -19,6 +19,11 @@
 //                 no comb filter where they overlap; chunk i's parameters hold around its centre i hopSize + N/2 - or
 //                 "continuousGlide", the same with the parameters interpolated from centre to centre.  Same length.
 //                 Ignored without "renderMatch"; not available with "deviceKernelArithmetic".
+//   "voiceGraph"  with "synth": "graph", the operator-graph voice (sots_create_graph): {"operators": n, "modulators":
+//                 [[...], ...], "carriers": [...]} - modulators[j] lists the operators that modulate operator j (each
+//                 below j), carriers the operators that are heard; gene 2j is operator j's frequency, gene 2j+1 its level,
+//                 so evolutionary.numDimensions is 2 n and paramMins / paramMaxs hold 2 n entries.  One device; not with
+//                 "continuous" / "continuousGlide" rendering or "deviceKernelArithmetic".
 //   "matchPath"   a CSV of the parameter track, one row per chunk:
 //                 chunk,start_sample,generations,fitness,u0..u{D-1},p0..p{D-1} - u the unit-range genes (%.9g: the fp32
 //                 bits), p the scaled parameters; with returnBestEver the best-ever individual of each chunk.
@@ -147,14 +152,19 @@ int main(int argc, char *argv[])
             if (h.has("synth")) {
                 const std::string s = h["synth"].str;
                 args.synthKind = s == "2op" ? SOTS_SYNTH_2OP : s == "3op_series" ? SOTS_SYNTH_3OP_SERIES
-                               : s == "triple_parallel" ? SOTS_SYNTH_TRIPLE_PAR : s == "4op_series" ? SOTS_SYNTH_4OP_SERIES : -1;
+                               : s == "triple_parallel" ? SOTS_SYNTH_TRIPLE_PAR : s == "4op_series" ? SOTS_SYNTH_4OP_SERIES
+                               : s == "graph" ? SOTS_SYNTH_GRAPH : -1;
             }
+            // the operator-graph voice: "synth": "graph" with "voiceGraph" (Match_JSON.hpp)
+            (void)readVoiceGraphKeys(h, args.es_args.pop.numDimensions, args.renderMatch, args.renderMode, args.voiceGraph);
         }
         const uint32_t D = args.es_args.pop.numDimensions;
         Evolutionary_Strategy_HIP *hipEs = new Evolutionary_Strategy_HIP(args);
         std::unique_ptr<Evolutionary_Strategy> es(hipEs);
+        const sots_voice_graph &vg = args.voiceGraph;
         auto synthesise = [&](Objective &obj, const std::vector<float> &p, float *out) {
-            if (D == 4) obj.synthesiseAudio(p, out);
+            if (args.synthKind == SOTS_SYNTH_GRAPH) obj.synthesiseAudioGraph(vg.num_operators, vg.carriers, vg.modulators, p, out);
+            else if (D == 4) obj.synthesiseAudio(p, out);
             else if (D == 6) obj.synthesiseAudioDoubleSeries(p, out);
             else if (D == 8) obj.synthesiseAudioQuadSeries(p, out);
             else obj.synthesiseAudioTriple(p, out);
@@ -171,7 +181,7 @@ int main(int argc, char *argv[])
             if (raw.size() < D) throw std::runtime_error("type.params needs numDimensions entries");
             std::vector<float> unit(D);
             for (uint32_t i = 0; i < D; ++i) {
-                const uint32_t s = D == 12 ? (i & 3u) : i;
+                const uint32_t s = D == 12 && args.synthKind != SOTS_SYNTH_GRAPH ? (i & 3u) : i;
                 const float lo = args.es_args.paramMin[s], hi = args.es_args.paramMax[s];
                 unit[i] = (raw[i] - lo) / (hi - lo);
             }
