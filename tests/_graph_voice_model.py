@@ -16,6 +16,12 @@ GRAPHS = {
     "one_mod_two_carriers": (3, [0, 0b1, 0b1], 0b110),                # 0 into 1 and into 2
     "additive": (2, [0, 0], 0b11),                                    # two unmodulated carriers
     "chain8": (8, [0] + [1 << (j - 1) for j in range(1, 8)], 1 << 7), # D = 16
+    "fan3": (4, [0, 0, 0, 0b0111], 0b1000),                           # 4 operators: a sum of three
+    "stacks5": (5, [0, 0b1, 0b10, 0, 0b1000], 0b10100),               # 5 operators, D = 10: a chain of three and a pair
+    "seven": (7, [0, 0b1, 0b10, 0, 0, 0, 0b0111000], 0b1000100),      # 7 operators, D = 14: a chain beside a fan
+    "dense8": (8, [0] + [(1 << min(j, 6)) - 1 for j in range(1, 8)], 0b11000000),  # every modulator into everything after it: fan-in 6
+    "additive8": (8, [0] * 8, 0xFF),                                  # a sum of eight and a division by 8
+    "one_to_seven": (8, [0] + [1] * 7, 0xFE),                         # one output read by seven operators
 }
 
 
@@ -34,8 +40,9 @@ def tab_at(table, pos):
     return table[idx.astype(np.int64)]
 
 
-def graph_synth(graph, values, pmin, pmax, n, table):
-    """audio[rows][n] of values[rows][2 OPS]"""
+def graph_synth(graph, values, pmin, pmax, n, table, seen=None):
+    """audio[rows][n] of values[rows][2 OPS].  seen: a dict that is told whether any operator output and any phase was
+    infinite or NaN (keys output_inf, output_nan, phase_inf, phase_nan)"""
     ops, mods, carriers = graph
     p = scale(np.atleast_2d(values), pmin, pmax)
     rows = p.shape[0]
@@ -44,7 +51,8 @@ def graph_synth(graph, values, pmin, pmax, n, table):
     wf = F32(W)
     f = [p[:, 2 * j] for j in range(ops)]
     a = [p[:, 2 * j + 1] for j in range(ops)]
-    amp = [a[j] if carriers >> j & 1 else f[j] * a[j] for j in range(ops)]
+    with np.errstate(over="ignore"):
+        amp = [a[j] if carriers >> j & 1 else f[j] * a[j] for j in range(ops)]
     pos = [np.zeros(rows, F32) for _ in range(ops)]
     count = bin(carriers).count("1")
     audio = np.zeros((rows, n), F32)
@@ -63,6 +71,10 @@ def graph_synth(graph, values, pmin, pmax, n, table):
                 if mods[j]:
                     q = np.where(q < F32(0), q + wf, q)
                 pos[j] = q.astype(F32)
+                if seen is not None:
+                    for key, x, test in (("output_inf", o[j], np.isinf), ("output_nan", o[j], np.isnan),
+                                         ("phase_inf", pos[j], np.isinf), ("phase_nan", pos[j], np.isnan)):
+                        seen[key] = seen.get(key, False) or bool(test(x).any())
             y = None
             for j in range(ops):
                 if carriers >> j & 1:
@@ -77,7 +89,8 @@ def graph_synth_scalar(graph, values, pmin, pmax, n, table):
     p = scale(values, pmin, pmax)
     c = F32(W) / F32(SAMPLE_RATE)
     wf = F32(W)
-    amp = [p[2 * j + 1] if carriers >> j & 1 else p[2 * j] * p[2 * j + 1] for j in range(ops)]
+    with np.errstate(over="ignore"):
+        amp = [p[2 * j + 1] if carriers >> j & 1 else p[2 * j] * p[2 * j + 1] for j in range(ops)]
     pos = [F32(0)] * ops
     count = bin(carriers).count("1")
     out = np.zeros(n, F32)
@@ -134,4 +147,14 @@ def ranges(ops, negative=True, strong=True):
     for j in range(ops):
         pmin += [-880.0 if negative else 0.0, -2.0 if negative else 0.0]
         pmax += [3520.0, 64.0 if strong and j == 0 else 8.0]
+    return pmin, pmax
+
+
+def overflow_ranges(ops):
+    """ranges(ops) with operator 0's maxima at 3e19: its genes are finite, its level f * a is +inf in fp32 wherever
+    v_0 v_1 > 0.38, so its output is NaN at a table entry of 0 (the first sample) and +-inf elsewhere, and the phases of what
+    it modulates are not finite.  The index is clamped on the float, so such a phase reads entry W-1 or 0 and nothing else;
+    operator 0 is never a carrier, so the audio stays finite"""
+    pmin, pmax = ranges(ops)
+    pmax[0] = pmax[1] = 3e19
     return pmin, pmax

@@ -4,11 +4,16 @@ Synthesis is compared bit for bit with the NumPy model of the definition (tests/
 tests/test_graph_voice_cpu.py pins to the oracle on the two graphs that restate a fixed voice.  Whole runs of those two
 graphs are compared bit for bit with the fixed-voice contexts they restate: that holds the stand-alone variation launch,
 the new kernel and the generation loop together against kernels that already pass.  Batch and queue are compared with
-sequential tracked contexts of the same graph."""
+sequential tracked contexts of the same graph.
+Covered: every operator count 2 to 8 (both block sizes, U = 8 and U = 4), fan-in up to 6, fan-out up to 7, 1 to 8 carriers;
+workgroups of 1, 2, 3 and 4 wavefronts and a population that ends inside a transposed group of 8 rows; log2 N = 8, 9, 10 and
+15; infinite and NaN modulator outputs and NaN phases from finite genes; the rest of a generation at D = 10, 14 and 16 is in
+tests/test_gpu_graph_dims.py.  Left out: islands and continuous rendering (refused), non-finite genes, log2 N = 11 to 14,
+the eight-wavefront experiment build, and a phase that is inf rather than NaN (tests/test_graph_voice_cpu.py says why)."""
 import numpy as np
 import pytest
 
-from _graph_voice_model import GRAPHS, edge_rows, graph_synth, ranges
+from _graph_voice_model import GRAPHS, edge_rows, graph_synth, overflow_ranges, ranges
 from _survivors_model import SEED, targets
 
 pytestmark = pytest.mark.gpu
@@ -24,9 +29,9 @@ def same_bits(a, b):
     return np.array_equal(bits(a), bits(b))
 
 
-def graph_es(pkg, name, parents, offspring, log2n, pmin, pmax, **kw):
+def graph_es(pkg, name, parents, offspring, log2n, pmin, pmax, block=32, **kw):
     return pkg.HipES(parents, offspring, synth_kind=pkg.capi.SYNTH_GRAPH, audio_log2=log2n, param_min=pmin, param_max=pmax,
-                     seed=SEED, workgroup_size=32, graph=pkg.capi.make_voice_graph(*GRAPHS[name]), **kw)
+                     seed=SEED, workgroup_size=block, graph=pkg.capi.make_voice_graph(*GRAPHS[name]), **kw)
 
 
 def synthesised(es, values):
@@ -36,7 +41,9 @@ def synthesised(es, values):
 
 
 # ---- 1. synthesis against the model, bit for bit ------------------------------------------------------------------------------
-POPULATIONS = {64: (32, 32), 96: (32, 64), 1056: (32, 1024)}  # one wavefront; a partial one; several workgroups and a partial tile
+# (parents, offspring, block): one wavefront; a partial one; two workgroups, the second ending inside a group of eight rows
+# (100 = 64 + 4 x 8 + 4); several workgroups and a partial tile
+POPULATIONS = {64: (32, 32, 32), 96: (32, 64, 32), 100: (50, 50, 50), 1056: (32, 1024, 32)}
 _MODEL = {}
 
 
@@ -61,7 +68,8 @@ def model_rows(name, n, table):
 @pytest.mark.parametrize("name", sorted(GRAPHS))
 def test_synthesis_equals_the_model(pkg, table, name, log2n, p):
     pmin, pmax, v, want = model_rows(name, 1 << log2n, table)
-    es = graph_es(pkg, name, *POPULATIONS[p], log2n, pmin, pmax)
+    parents, offspring, block = POPULATIONS[p]
+    es = graph_es(pkg, name, parents, offspring, log2n, pmin, pmax, block=block)
     got = synthesised(es, v[:p])
     es.close()
     wrong = np.flatnonzero((bits(got) != bits(want[:p])).any(axis=1))
@@ -81,6 +89,60 @@ def test_synthesis_of_a_population_that_loops_over_tiles(pkg, table):
     es.close()
     wrong = np.flatnonzero((bits(got) != bits(want)[idx]).any(axis=1))
     assert wrong.size == 0, (wrong[:8], wrong.size)
+
+
+def periodic_case(pkg, table, name, p, period, log2n, block, seed):
+    """rows that repeat with a prime period, so that the model is computed for one period only"""
+    g = GRAPHS[name]
+    pmin, pmax = ranges(g[0])
+    base = edge_rows(2 * g[0], period, seed)
+    want = graph_synth(g, base, pmin, pmax, 1 << log2n, table)
+    idx = np.arange(p) % period
+    es = graph_es(pkg, name, block, p - block, log2n, pmin, pmax, block=block)
+    got = synthesised(es, base[idx])
+    es.close()
+    wrong = np.flatnonzero((bits(got) != bits(want)[idx]).any(axis=1))
+    assert wrong.size == 0, (name, p, wrong[:8], wrong.size)
+
+
+@pytest.mark.parametrize("name", ["fan3", "stacks5"])  # samples in blocks of U = 8, and of U = 4
+@pytest.mark.parametrize("p", [16392, 33032])
+def test_synthesis_in_workgroups_of_two_and_three_wavefronts(pkg, table, name, p):
+    """on 256 CUs P = 16 392 is a share of 65 rows per CU (two wavefronts, the second with one row in most workgroups) and
+    P = 33 032 one of 130 (three): the wavefronts' tiles lie at stage_all + 1 and + 2 times kWave CH"""
+    periodic_case(pkg, table, name, p, 1031, 8, 8, p)
+
+
+@pytest.mark.parametrize("name,log2n,p", [("seven", 9, 96), ("chain3", 15, 64)])
+def test_synthesis_at_other_lengths(pkg, table, name, log2n, p):
+    """N = 512, and N = 32 768: the longest row, 1024 flushes of a tile"""
+    g = GRAPHS[name]
+    pmin, pmax = ranges(g[0])
+    v = edge_rows(2 * g[0], p, 7 + log2n)
+    want = graph_synth(g, v, pmin, pmax, 1 << log2n, table)
+    es = graph_es(pkg, name, 32, p - 32, log2n, pmin, pmax)
+    got = synthesised(es, v)
+    es.close()
+    wrong = np.flatnonzero((bits(got) != bits(want)).any(axis=1))
+    assert wrong.size == 0, (name, log2n, wrong[:8])
+
+
+@pytest.mark.parametrize("name", ["fan3", "dense8"])
+def test_synthesis_with_an_infinite_modulator_level(pkg, table, name):
+    """finite genes under overflow_ranges: operator 0's level is +inf, its output -inf or NaN, and the phases of what it
+    modulates are NaN (tests/test_graph_voice_cpu.py shows that they occur).  The index is clamped on the float, so every
+    such read is of entry 0 or W-1: nothing here is outside the definition.  Bit for bit; a NaN matches any NaN"""
+    g = GRAPHS[name]
+    pmin, pmax = overflow_ranges(g[0])
+    v = edge_rows(2 * g[0], 96, 1256)
+    want = graph_synth(g, v, pmin, pmax, 256, table)
+    es = graph_es(pkg, name, 32, 64, 8, pmin, pmax)
+    got = synthesised(es, v)
+    es.close()
+    same = (bits(got) == bits(want)) | (np.isnan(got) & np.isnan(want))
+    wrong = np.flatnonzero(~same.all(axis=1))
+    assert wrong.size == 0, (name, wrong[:8], got[wrong[:1]], want[wrong[:1]])
+    assert np.isfinite(want).all()
 
 
 # ---- 2. whole runs against the fixed voices the anchors restate ---------------------------------------------------------------

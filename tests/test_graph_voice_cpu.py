@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from _graph_voice_model import GRAPHS, edge_rows, graph_synth, graph_synth_scalar, ranges
+from _graph_voice_model import GRAPHS, edge_rows, graph_synth, graph_synth_scalar, overflow_ranges, ranges
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG_DIR = os.path.join(ROOT, "survival_of_the_synthesis-gpu_accelerated_frequency_modulation_parameter_matcher_amd")
@@ -74,6 +74,35 @@ def test_the_edge_ranges_reach_the_clamp_and_the_lower_wrap(table):
     step = np.abs(p[:, 0] * p[:, 1]) * np.float32(32768 / 44100)
     assert (step > 2 * 32768).any() and (p[:, 2] < 0).any()
     assert np.isfinite(graph_synth(g, edge_rows(4, 64, 3), pmin, pmax, 256, table)).all()
+
+
+def test_the_new_graphs_are_the_operator_counts_and_shapes_they_are_named_for():
+    """OPS 4, 5 and 7 (the three forms of the kernel no older graph reaches), a fan-in of 6, eight carriers, a fan-out of 7"""
+    assert {g[0] for g in GRAPHS.values()} == {2, 3, 4, 5, 6, 7, 8}
+    assert (GRAPHS["fan3"][0], GRAPHS["stacks5"][0], GRAPHS["seven"][0]) == (4, 5, 7)
+    assert GRAPHS["dense8"][1] == [0, 1, 3, 7, 15, 31, 63, 63] and max(bin(m).count("1") for m in GRAPHS["dense8"][1]) == 6
+    assert bin(GRAPHS["additive8"][2]).count("1") == 8 and not any(GRAPHS["additive8"][1])
+    assert sum(m & 1 for m in GRAPHS["one_to_seven"][1]) == 7
+
+
+@pytest.mark.parametrize("name", ["fan3", "dense8"])
+def test_the_overflow_ranges_make_infinite_and_nan_outputs_and_phases(table, name):
+    """what the GPU test's overflow ranges are for: finite genes, yet modulator outputs that are inf and that are NaN and
+    phases that are NaN do occur in the model - and the audio stays finite, since no carrier is overflowed.  (No phase is
+    inf under these ranges: every phase starts at 0 and table[0] is 0, so an infinite level gives 0 x inf = NaN at sample 0
+    and the phases it feeds are NaN from there on; the outputs are -inf from sample 1, where operator 0 reads entry W-1.)"""
+    g = GRAPHS[name]
+    pmin, pmax = overflow_ranges(g[0])
+    v = edge_rows(2 * g[0], 96, 1256)  # the rows of the GPU case
+    assert np.isfinite(v).all() and np.isfinite(pmin).all() and np.isfinite(pmax).all()
+    seen = {}
+    audio = graph_synth(g, v, pmin, pmax, 256, table, seen)
+    assert table[0] == 0.0
+    assert seen["output_inf"] and seen["output_nan"] and seen["phase_nan"], seen
+    assert np.isfinite(audio).all() and np.abs(audio).max() > 0.01
+    for r in (1, 2, 95):
+        want = graph_synth_scalar(g, v[r], pmin, pmax, 256, table)
+        assert np.array_equal(audio[r].view(np.uint32), want.view(np.uint32)), (name, r)
 
 
 # ---- the rules, stand-alone, under the sanitizers ----
