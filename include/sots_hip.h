@@ -185,6 +185,37 @@ int sots_create_graph(const sots_config *cfg, const sots_voice_graph *graph, sot
 /* the context's graph; SOTS_ERR_STATE for a context of a fixed voice */
 int sots_get_voice_graph(const sots_ctx *ctx, sots_voice_graph *graph);
 
+/* ---- operator waveforms of the graph voice (new: shapes cut out of the one sine table, as OPL2/OPL3 and TX81Z do) ----
+ * Every operator of a sots_voice_graph has a waveform code; all are SOTS_WAVE_SINE until set.  Step 1 of the voice
+ * above becomes
+ *     o_j = shape(w_j, i) A_j
+ * with i the index tab_at uses, clamp((int)pos_j, 0, W-1) decided on the float (NaN and negatives give 0), W = 32768
+ * and T the wavetable:
+ *     0 SOTS_WAVE_SINE       T[i]
+ *     1 SOTS_WAVE_HALF       i < W/2 ? T[i] : +0.0f
+ *     2 SOTS_WAVE_ABS        fabsf(T[i])                       (the sign bit cleared)
+ *     3 SOTS_WAVE_PULSE      (i & W/4) == 0 ? fabsf(T[i]) : +0.0f
+ *     4 SOTS_WAVE_EVEN       i < W/2 ? T[2i] : +0.0f
+ *     5 SOTS_WAVE_ABS_EVEN   i < W/2 ? fabsf(T[2i]) : +0.0f
+ *     6 SOTS_WAVE_SQUARE     i < W/2 ? +1.0f : -1.0f
+ *     7 SOTS_WAVE_SAW        (float)i * 2^-14 - 1.0f           (both operations exact in fp32 for i < 2^15)
+ * Every case is decided on the integer index, never on the sign of a table entry (the table is sinf(i/(W-1) 2 pi): its
+ * last entry is a tiny value of either sign).  The product with A_j is always formed: +0 x inf is NaN and +0 x negative
+ * is -0.  Everything else in the voice - the sums from -0, the wraps, the carrier mean - is unchanged, and with all codes
+ * 0 the voice is the one above bit for bit.
+ * sots_set_voice_waveforms: codes[count], count == the graph's num_operators, every code < 8; (NULL, 0) sets all sine.
+ * SOTS_ERR_STATE for a context of a fixed voice, SOTS_ERR_INVALID for the rest; everything is checked before anything
+ * changes, and a refused call leaves the old setting.  A successful call acts like a new objective: the run record is
+ * cleared, the stored selection splitters and key lists are dropped; the population stays.  It may come before or after
+ * the target, the objective and the weights.  sots_get_voice_waveforms writes all eight codes (0 beyond the operators).
+ * Islands (sots_group) do not take the voice and have no such setting. */
+enum {
+    SOTS_WAVE_SINE = 0, SOTS_WAVE_HALF = 1, SOTS_WAVE_ABS = 2, SOTS_WAVE_PULSE = 3,
+    SOTS_WAVE_EVEN = 4, SOTS_WAVE_ABS_EVEN = 5, SOTS_WAVE_SQUARE = 6, SOTS_WAVE_SAW = 7
+};
+int sots_set_voice_waveforms(sots_ctx *ctx, const uint32_t *codes, uint32_t count);
+int sots_get_voice_waveforms(const sots_ctx *ctx, uint32_t codes[8]);
+
 /* ---- target (replaces setTargetAudio, ...OpenCL.hpp:563-570; Objective::calculateFFT,
  *      Evolutionary_Strategy.hpp:524-542) ---- */
 int sots_set_target_audio(sots_ctx *ctx, const float *audio, uint32_t num_samples);
@@ -511,6 +542,11 @@ int sots_batch_set_objective(sots_batch *b, uint32_t objective, float floor);
  * one table for all chunks, active and queued.  Every chunk's run record is cleared.  Before or after the targets and
  * the objective, with the same result. */
 int sots_batch_set_objective_weights(sots_batch *b, const float *weights, uint32_t num_bins);
+/* sots_set_voice_waveforms for every chunk of a graph-voice batch (new), in sots_batch_execute_* and
+ * sots_batch_queue_run alike: one setting for all chunks, the same rules and refusals.  Every chunk's run record is
+ * cleared.  Before or after the targets, the objective and the weights, with the same result. */
+int sots_batch_set_voice_waveforms(sots_batch *b, const uint32_t *codes, uint32_t count);
+int sots_batch_get_voice_waveforms(const sots_batch *b, uint32_t codes[8]);
 /* row 0 (the best) of every active chunk: values [active][D], fitness [active] (either may be NULL); blocking */
 int sots_batch_read_best(sots_batch *b, float *values, size_t values_bytes, float *fitness, size_t fitness_bytes);
 /* one active chunk's current half; byte counts as sots_read_population; blocking */

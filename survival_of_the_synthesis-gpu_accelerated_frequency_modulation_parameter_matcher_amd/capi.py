@@ -22,6 +22,10 @@ SYNTH_DIMS = {SYNTH_2OP: 4, SYNTH_3OP_SERIES: 6, SYNTH_TRIPLE_PAR: 12, SYNTH_4OP
 SYNTH_NAMES = {"2op": SYNTH_2OP, "3op_series": SYNTH_3OP_SERIES,
                "triple_parallel": SYNTH_TRIPLE_PAR, "4op_series": SYNTH_4OP_SERIES, "graph": SYNTH_GRAPH}
 GRAPH_MAX_OPERATORS = 8
+# operator waveforms of the graph voice (SOTS_WAVE_*): shapes cut out of the one sine table
+WAVE_SINE, WAVE_HALF, WAVE_ABS, WAVE_PULSE, WAVE_EVEN, WAVE_ABS_EVEN, WAVE_SQUARE, WAVE_SAW = range(8)
+WAVE_NAMES = {"sine": WAVE_SINE, "half": WAVE_HALF, "abs": WAVE_ABS, "pulse": WAVE_PULSE, "even": WAVE_EVEN,
+              "absEven": WAVE_ABS_EVEN, "square": WAVE_SQUARE, "saw": WAVE_SAW}
 
 (STAGE_INIT, STAGE_RECOMBINE, STAGE_MUTATE, STAGE_SYNTHESISE, STAGE_WINDOW, STAGE_FFT,
  STAGE_FITNESS, STAGE_SORT, STAGE_ROTATE, STAGE_FUSED_VARIATION, STAGE_FUSED_SYNTH,
@@ -74,6 +78,7 @@ EXPORTS = [
     "sots_batch_queue_set_carry", "sots_batch_queue_get_carry",
     "sots_batch_set_analysis", "sots_batch_get_analysis", "sots_batch_analyse_audio_hop", "sots_batch_queue_score_audio_hop",
     "sots_create_graph", "sots_batch_create_graph", "sots_get_voice_graph",
+    "sots_set_voice_waveforms", "sots_get_voice_waveforms", "sots_batch_set_voice_waveforms", "sots_batch_get_voice_waveforms",
 ]
 ANALYSIS_HOST, ANALYSIS_DEVICE = 0, 1  # enum sots_analysis
 QUEUE_NO_CHUNK = 0xFFFFFFFF
@@ -134,6 +139,15 @@ def as_voice_graph(graph):
     if graph is None or isinstance(graph, VoiceGraph):
         return graph
     return make_voice_graph(graph["operators"], graph["modulators"], graph["carriers"])
+
+
+def _waveform_codes(waveforms):
+    """(pointer, count) of sots_set_voice_waveforms from None (all sine) or one code or WAVE_NAMES name per operator.
+    Nothing else is checked here: the library's rule refuses with its own text."""
+    if waveforms is None:
+        return None, 0
+    codes = [WAVE_NAMES[w] if isinstance(w, str) else int(w) for w in waveforms]
+    return (C.c_uint32 * len(codes))(*[c & 0xFFFFFFFF for c in codes]), len(codes)
 
 
 def synth_dims(synth_kind, graph=None):
@@ -341,6 +355,10 @@ def load():
     L.sots_create_graph.argtypes = [C.POINTER(Config), C.POINTER(VoiceGraph), C.POINTER(vp)]
     L.sots_batch_create_graph.argtypes = [C.POINTER(Config), C.POINTER(VoiceGraph), u32, C.POINTER(vp)]
     L.sots_get_voice_graph.argtypes = [vp, C.POINTER(VoiceGraph)]
+    L.sots_set_voice_waveforms.argtypes = [vp, C.POINTER(u32), u32]
+    L.sots_get_voice_waveforms.argtypes = [vp, C.POINTER(u32)]
+    L.sots_batch_set_voice_waveforms.argtypes = [vp, C.POINTER(u32), u32]
+    L.sots_batch_get_voice_waveforms.argtypes = [vp, C.POINTER(u32)]
     _lib = L
     return L
 
@@ -391,8 +409,9 @@ class HipES:
 
     def __init__(self, num_parents, num_offspring, synth_kind=SYNTH_2OP, audio_log2=10,
                  param_min=None, param_max=None, seed=0x5EED0001, workgroup_size=32,
-                 device=0, gid_base=0, num_generations=0, graph=None):
-        """graph (with synth_kind=SYNTH_GRAPH): a VoiceGraph or its JSON form, see as_voice_graph"""
+                 device=0, gid_base=0, num_generations=0, graph=None, waveforms=None):
+        """graph (with synth_kind=SYNTH_GRAPH): a VoiceGraph or its JSON form, see as_voice_graph; waveforms: that
+        graph's operator waveforms, see set_voice_waveforms"""
         self.L = load()
         self._borrowed = False
         self.graph = as_voice_graph(graph)
@@ -409,6 +428,8 @@ class HipES:
         if rc != 0:
             raise SotsError(rc, self.L.sots_last_error(None).decode())
         self._h = h
+        if waveforms is not None:
+            self.set_voice_waveforms(waveforms)
 
     # -- plumbing --
     def _check(self, rc):
@@ -437,6 +458,18 @@ class HipES:
         g = VoiceGraph()
         self._check(self.L.sots_get_voice_graph(self._h, C.byref(g)))
         return g
+
+    def set_voice_waveforms(self, waveforms):
+        """one WAVE_* code or WAVE_NAMES name per operator of the graph, or None: all sine.  Like a new objective: the run
+        record is cleared"""
+        codes, count = _waveform_codes(waveforms)
+        self._check(self.L.sots_set_voice_waveforms(self._h, codes, count))
+
+    def voice_waveforms(self):
+        """the codes of the graph's operators"""
+        codes = (C.c_uint32 * GRAPH_MAX_OPERATORS)()
+        self._check(self.L.sots_get_voice_waveforms(self._h, codes))
+        return list(codes)[:self.D // 2]
 
     def info(self):
         i = Info()
@@ -731,7 +764,8 @@ class HipBatch:
     HipES of the same arguments computes after init_population(first + c)."""
 
     def __init__(self, max_chunks, num_parents, num_offspring, synth_kind=SYNTH_2OP, audio_log2=10, param_min=None,
-                 param_max=None, seed=0x5EED0001, workgroup_size=32, device=0, gid_base=0, num_generations=0, graph=None):
+                 param_max=None, seed=0x5EED0001, workgroup_size=32, device=0, gid_base=0, num_generations=0, graph=None,
+                 waveforms=None):
         self.L = load()
         self.graph = as_voice_graph(graph)
         self.cfg = make_config(num_parents, num_offspring, synth_kind, audio_log2, param_min, param_max, seed, workgroup_size,
@@ -748,6 +782,8 @@ class HipBatch:
         if rc != 0:
             raise SotsError(rc, self.L.sots_batch_last_error(None).decode())
         self._h = h
+        if waveforms is not None:
+            self.set_voice_waveforms(waveforms)
 
     def _check(self, rc):
         if rc != 0:
@@ -812,6 +848,16 @@ class HipBatch:
             return
         w = _f32(weights)
         self._check(self.L.sots_batch_set_objective_weights(self._h, _ptr(w), w.size))
+
+    def set_voice_waveforms(self, waveforms):
+        """HipES.set_voice_waveforms for every chunk (one setting), in execute_generations / execute_until and queue_run alike"""
+        codes, count = _waveform_codes(waveforms)
+        self._check(self.L.sots_batch_set_voice_waveforms(self._h, codes, count))
+
+    def voice_waveforms(self):
+        codes = (C.c_uint32 * GRAPH_MAX_OPERATORS)()
+        self._check(self.L.sots_batch_get_voice_waveforms(self._h, codes))
+        return list(codes)[:self.D // 2]
 
     def read_best(self):
         """(values[active][D], fitness[active]): row 0 of every active chunk"""

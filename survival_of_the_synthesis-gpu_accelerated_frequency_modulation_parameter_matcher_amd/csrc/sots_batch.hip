@@ -402,6 +402,23 @@ int sots_batch_set_objective_weights(sots_batch *b, const float *weights, uint32
     return SOTS_OK;
 }
 
+// one setting for all chunks, active and queued; what the chunks had found with the old voice says nothing
+int sots_batch_set_voice_waveforms(sots_batch *b, const uint32_t *codes, uint32_t count)
+{
+    BATCH_REQUIRE(b);
+    SOTS_REFUSE(b, voice_waveforms_check(b->cfg.synth_kind, b->graph.num_operators, codes, count));
+    if (int rc = engine_bind(*b)) return rc;
+    SOTS_HIP(b, track_clear(b->track, b->stream));
+    SOTS_HIP(b, hipStreamSynchronize(b->stream));
+    return engine_set_voice_waveforms(*b, codes, count);
+}
+
+int sots_batch_get_voice_waveforms(const sots_batch *b, uint32_t codes[8])
+{
+    BATCH_REQUIRE(b);
+    return engine_get_voice_waveforms(*b, codes);
+}
+
 int sots_batch_execute_generations(sots_batch *b, uint32_t n)
 {
     BATCH_REQUIRE(b);

@@ -1024,6 +1024,27 @@ int sots_set_objective_weights(sots_ctx *ctx, const float *weights, uint32_t num
     return SOTS_OK;
 }
 
+// Like a new objective: another landscape for the same population - the run record, the stored splitters and the key lists
+// say nothing under the new voice.  The target's images do not depend on the voice and stay.  Everything is checked, and
+// the record cleared, before the setting changes.
+int sots_set_voice_waveforms(sots_ctx *ctx, const uint32_t *codes, uint32_t count)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    SOTS_REFUSE(ctx, voice_waveforms_check(ctx->cfg.synth_kind, ctx->graph.num_operators, codes, count));
+    if (int rc = engine_bind(*ctx)) return rc;
+    SOTS_HIP(ctx, track_clear(ctx->track, ctx->stream));
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->spl_valid = false;
+    ctx->lists_ready = false;
+    return engine_set_voice_waveforms(*ctx, codes, count);
+}
+
+int sots_get_voice_waveforms(const sots_ctx *ctx, uint32_t codes[8])
+{
+    SOTS_REQUIRE_CTX(ctx);
+    return engine_get_voice_waveforms(*ctx, codes);
+}
+
 int sots_get_objective_weights(const sots_ctx *ctx, float *weights, uint32_t num_bins, uint32_t *is_set)
 {
     SOTS_REQUIRE_CTX(ctx);

@@ -54,6 +54,7 @@ __attribute__((format(printf, 3, 4))) inline int fail_to(std::string &err, int c
 struct Engine {
     sots_config cfg{};
     sots_voice_graph graph{}; // SOTS_SYNTH_GRAPH: the topology that came with cfg (num_operators 0 for a fixed voice)
+    uint32_t waveforms[8] = {0}; // ... and its operators' waveform codes (sots_set_voice_waveforms; all sine until set)
     PopDims pd{};
     MutateConsts mc{};
     SynthParams sp{};
@@ -172,6 +173,20 @@ inline int engine_set_survivors(Engine &e, uint32_t n)
     return SOTS_OK;
 }
 
+// Checked before anything changes; the caller clears what a new voice makes stale (its run record, its stored splitters)
+inline int engine_set_voice_waveforms(Engine &e, const uint32_t *codes, uint32_t count)
+{
+    SOTS_REFUSE(e, voice_waveforms_set(e.cfg.synth_kind, e.graph.num_operators, codes, count, e.waveforms));
+    return SOTS_OK;
+}
+inline int engine_get_voice_waveforms(const Engine &e, uint32_t codes[8])
+{
+    if (!codes) return SOTS_FAIL(e, SOTS_ERR_INVALID, "voice waveforms: null argument");
+    SOTS_REFUSE(e, voice_waveforms_check(e.cfg.synth_kind, e.graph.num_operators, nullptr, 0));
+    memcpy(codes, e.waveforms, sizeof e.waveforms);
+    return SOTS_OK;
+}
+
 // ---- objective ----
 // Both setters check everything before anything changes, then leave the objective they replaced in *old: the caller derives
 // what depends on the new one (its target images, its run record) and, where that fails, puts *old back with
@@ -219,7 +234,8 @@ inline hipError_t engine_synthesise(const Engine &e, const float *values, float 
 {
     if (e.synth_arith == SOTS_ARITH_DEVICE_KERNELS)
         return launch_synth_device_arith(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch);
-    return launch_synth(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch, e.num_cus, var, allow_cut, &e.graph);
+    return launch_synth(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch, e.num_cus, var, allow_cut, &e.graph,
+                        pack_waveforms(e.waveforms));
 }
 
 } // namespace sots

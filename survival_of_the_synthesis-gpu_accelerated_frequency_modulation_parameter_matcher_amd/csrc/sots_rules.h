@@ -81,6 +81,40 @@ inline Fault voice_graph_check(const sots_voice_graph *g)
     return Fault{};
 }
 
+// ---- operator waveforms of the graph voice (sots_set_voice_waveforms; the definition: include/sots_hip.h) ----
+constexpr uint32_t kWaveformCount = 8;
+// codes[count] for a handle of synthesis kind `kind` whose graph has `ops` operators; (null, 0): all sine
+inline Fault voice_waveforms_check(uint32_t kind, uint32_t ops, const uint32_t *codes, uint32_t count)
+{
+    if (kind != SOTS_SYNTH_GRAPH)
+        return fault(SOTS_ERR_STATE, "voice waveforms: the handle runs a fixed voice (synth_kind %u)", kind);
+    if (!codes && count == 0) return Fault{};
+    if (!codes) return fault(SOTS_ERR_INVALID, "voice waveforms: null codes with a count of %u", count);
+    if (count != ops) return fault(SOTS_ERR_INVALID, "voice waveforms: %u codes for a graph of %u operators", count, ops);
+    for (uint32_t j = 0; j < count; ++j)
+        if (codes[j] >= kWaveformCount)
+            return fault(SOTS_ERR_INVALID, "voice waveforms: code %u of operator %u is not a waveform (0..%u)", codes[j], j, kWaveformCount - 1u);
+    return Fault{};
+}
+// What the shaped kernel takes: 3 bits per operator, operator j in bits 3j..3j+2.  0: all sine.
+inline uint32_t pack_waveforms(const uint32_t codes[8])
+{
+    uint32_t packed = 0;
+    for (uint32_t j = 0; j < kGraphMaxOps; ++j) packed |= (codes[j] & 7u) << (3u * j);
+    return packed;
+}
+inline void unpack_waveforms(uint32_t packed, uint32_t codes[8])
+{
+    for (uint32_t j = 0; j < kGraphMaxOps; ++j) codes[j] = packed >> (3u * j) & 7u;
+}
+// Checks, then writes all eight codes of `held` (0 beyond the operators); a refusal leaves `held` as it was
+inline Fault voice_waveforms_set(uint32_t kind, uint32_t ops, const uint32_t *codes, uint32_t count, uint32_t held[8])
+{
+    if (const Fault f = voice_waveforms_check(kind, ops, codes, count)) return f;
+    for (uint32_t j = 0; j < kGraphMaxOps; ++j) held[j] = codes && j < count ? codes[j] : 0u;
+    return Fault{};
+}
+
 // Everything a configuration must satisfy whoever takes it; max_population is the caller's own limit on numParents +
 // numOffspring.  Needs no device: a machine without a GPU still tells a bad configuration from a good one.  graph: the
 // topology that came with the configuration (sots_create_graph, sots_batch_create_graph), null from every other entry point.

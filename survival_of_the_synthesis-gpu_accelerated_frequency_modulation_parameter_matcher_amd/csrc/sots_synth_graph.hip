@@ -15,6 +15,7 @@
 // x (+0 and -0 included), and only operators whose bit is set are added to it.
 #include "kernels/common.h"
 #include <cstdlib>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 namespace sots {
@@ -25,13 +26,25 @@ struct GraphMasks {
     uint32_t modulators[8];
 };
 
+// The operators' waveforms (sots_set_voice_waveforms, include/sots_hip.h).  SHAPES is empty or one uint32_t: the kernel
+// with no such argument is the all-sine voice with the arguments it always had; with it, every operator's table value goes
+// through shape(w_j, i) before its level multiplies it.  The argument holds the codes, 3 bits per operator, in a scalar
+// register, and an operator's block of U reads runs under a wavefront-uniform branch on its code: each shape is its own
+// straight-line statement of the definition, decided on the integer index, and SQUARE and SAW read no table at all.
+// (The form that lost, DESIGN.md 4.14: one branchless body with per-operator scalar constants - index shift, sign mask,
+// zeroing index bit, two overrides - costs every code the instructions of all of them.)
 // CH: 16-byte chunks per tile row = 4 CH samples per flush.  The 32 KiB beside the table are 32 / CH tiles of 64 rows:
 // CH = 8, four wavefronts (one per SIMD) and whole 128-byte lines; CH = 4, eight wavefronts (two per SIMD) and half lines.
-template <int OPS, int CH>
+template <int OPS, int CH, typename... SHAPES>
 __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *__restrict__ values, const float *__restrict__ wavetable,
                                                                   float *__restrict__ audio, SynthParams sp, GraphMasks gm, uint32_t p_len,
-                                                                  uint32_t n, uint32_t pitch)
+                                                                  uint32_t n, uint32_t pitch, SHAPES... shapes)
 {
+    constexpr bool SHAPED = sizeof...(SHAPES) != 0;
+    // (an experiment build also has the form that lost: the codes as int32_t)
+    constexpr bool BRANCHES = SHAPED && (std::is_same_v<SHAPES, uint32_t> || ...);
+    static_assert(sizeof...(SHAPES) <= 1 && ((std::is_same_v<SHAPES, uint32_t> || std::is_same_v<SHAPES, int32_t>) && ...),
+                  "no argument, or the packed codes");
     constexpr int D = 2 * OPS, WAVES = 32 / CH;
     constexpr int RPI = kWave / CH; // rows per transposed read / store instruction (CH of them per flush)
     constexpr int U = OPS <= 4 ? 8 : 4;            // samples per block: o[OPS][U] stays in registers
@@ -55,7 +68,8 @@ __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *
     const float4 *rd = stage + r8 * CH + (rch ^ swz(r8));
 
     // table[clamp((int)pos, 0, W-1)], the clamp decided on the float: NaN and negatives give entry 0
-    auto tab_at = [&](float pos) { return tab[(uint32_t)fminf(fmaxf(pos, 0.0f), wf - 1.0f)]; };
+    auto index_of = [&](float pos) { return (uint32_t)fminf(fmaxf(pos, 0.0f), wf - 1.0f); };
+    auto tab_at = [&](float pos) { return tab[index_of(pos)]; };
     uint32_t num_carriers = 0;
 #pragma unroll
     for (int j = 0; j < OPS; ++j) num_carriers += gm.carriers >> j & 1u;
@@ -94,12 +108,69 @@ __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *
                     }
                 });
                 const bool modulated = gm.modulators[J] != 0u;
+                if constexpr (BRANCHES) {
+                    // (the code is taken from the argument here, block by block: the tests on it held in scalar registers
+                    // across the sample loop for every operator cost the wide forms register lanes)
+                    uint32_t packed = (shapes, ...);
+                    asm volatile("" : "+s"(packed));
+                    const uint32_t w = packed >> (3 * J) & 7u;
+                    auto run = [&](auto shape) {
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    tv[u] = tab_at(pos[J]);
-                    pos[J] += c * (cur[u] + f[J]);
-                    if (pos[J] >= wf) pos[J] -= wf;
-                    if (modulated && pos[J] < 0.0f) pos[J] += wf;
+                        for (int u = 0; u < U; ++u) {
+                            tv[u] = shape(index_of(pos[J]));
+                            pos[J] += c * (cur[u] + f[J]);
+                            if (pos[J] >= wf) pos[J] -= wf;
+                            if (modulated && pos[J] < 0.0f) pos[J] += wf;
+                        }
+                    };
+                    constexpr uint32_t H = (uint32_t)kWavetableSize / 2u, Q = (uint32_t)kWavetableSize / 4u;
+                    switch (w) {
+                    case SOTS_WAVE_HALF: run([&](uint32_t i) { return i < H ? tab[i] : 0.0f; }); break;
+                    case SOTS_WAVE_ABS: run([&](uint32_t i) { return fabsf(tab[i]); }); break;
+                    case SOTS_WAVE_PULSE: run([&](uint32_t i) { return (i & Q) == 0 ? fabsf(tab[i]) : 0.0f; }); break;
+                    case SOTS_WAVE_EVEN: run([&](uint32_t i) { return i < H ? tab[2u * i] : 0.0f; }); break;
+                    case SOTS_WAVE_ABS_EVEN: run([&](uint32_t i) { return i < H ? fabsf(tab[2u * i]) : 0.0f; }); break;
+                    case SOTS_WAVE_SQUARE: run([&](uint32_t i) { return i < H ? 1.0f : -1.0f; }); break;
+                    case SOTS_WAVE_SAW: run([&](uint32_t i) { return (float)i * 0x1p-14f - 1.0f; }); break;
+                    default: run([&](uint32_t i) { return tab[i]; }); break;
+                    }
+                } else if constexpr (SHAPED) {
+                    // (the constants are derived here, block by block: held across the sample loop for every operator they
+                    // cost the 7-operator form 36 bytes of scratch)
+                    uint32_t packed = (uint32_t)(shapes, ...);
+                    asm volatile("" : "+s"(packed));
+                    const uint32_t w = packed >> (3 * J) & 7u;
+                    const uint32_t shift = (w == SOTS_WAVE_EVEN || w == SOTS_WAVE_ABS_EVEN) ? 1u : 0u;
+                    const uint32_t keep = (w == SOTS_WAVE_ABS || w == SOTS_WAVE_PULSE || w == SOTS_WAVE_ABS_EVEN) ? 0x7fffffffu : 0xffffffffu;
+                    const uint32_t zero_at = w == SOTS_WAVE_PULSE ? (uint32_t)kWavetableSize / 4u
+                                             : (w == SOTS_WAVE_HALF || w == SOTS_WAVE_EVEN || w == SOTS_WAVE_ABS_EVEN) ? (uint32_t)kWavetableSize / 2u : 0u;
+                    uint32_t at[U];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        at[u] = index_of(pos[J]);
+                        tv[u] = tab[(at[u] << shift) & ((uint32_t)kWavetableSize - 1u)]; // (inside the table whatever the code)
+                        pos[J] += c * (cur[u] + f[J]);
+                        if (pos[J] >= wf) pos[J] -= wf;
+                        if (modulated && pos[J] < 0.0f) pos[J] += wf;
+                    }
+                    if (w == SOTS_WAVE_SQUARE) {
+#pragma unroll
+                        for (int u = 0; u < U; ++u) tv[u] = at[u] < (uint32_t)kWavetableSize / 2u ? 1.0f : -1.0f;
+                    } else if (w == SOTS_WAVE_SAW) {
+#pragma unroll
+                        for (int u = 0; u < U; ++u) tv[u] = (float)at[u] * 0x1p-14f - 1.0f; // (both exact below 2^15)
+                    } else {
+#pragma unroll
+                        for (int u = 0; u < U; ++u) tv[u] = (at[u] & zero_at) ? 0.0f : __uint_as_float(__float_as_uint(tv[u]) & keep);
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        tv[u] = tab_at(pos[J]);
+                        pos[J] += c * (cur[u] + f[J]);
+                        if (pos[J] >= wf) pos[J] -= wf;
+                        if (modulated && pos[J] < 0.0f) pos[J] += wf;
+                    }
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) o[J][u] = tv[u] * amp[J];
@@ -142,7 +213,7 @@ __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *
 
 template <int OPS>
 hipError_t launch_ops(hipStream_t st, const GraphMasks &gm, const float *values, const float *wavetable, float *audio, const SynthParams &sp,
-                      uint32_t p, uint32_t n, uint32_t pitch, uint32_t cus)
+                      uint32_t p, uint32_t n, uint32_t pitch, uint32_t cus, uint32_t shapes)
 {
     // one workgroup per CU (the table), sized to the CU's share of the population up to one wavefront per SIMD; larger
     // populations loop over tiles
@@ -153,7 +224,18 @@ hipError_t launch_ops(hipStream_t st, const GraphMasks &gm, const float *values,
     const uint32_t share = (p + cus - 1) / cus;
     uint32_t waves = (share + kWave - 1) / kWave;
     if (waves > max_waves) waves = max_waves;
+    if (shapes && waves > 4) waves = 4; // (the CH = 4 experiment form is not shaped)
     const uint32_t rows = waves * kWave, tiles = (p + rows - 1) / rows, grid = tiles < cus ? tiles : cus;
+#ifdef SOTS_EXPERIMENT
+    if (const char *e = getenv("SOTS_GRAPH_SHAPE_CONSTANTS"); shapes && e && atoi(e) == 1) {
+        k_synth_graph<OPS, 8, int32_t><<<grid, rows, 0, st>>>(values, wavetable, audio, sp, gm, p, n, pitch, (int32_t)shapes);
+        return hipGetLastError();
+    }
+#endif
+    if (shapes) { // any setting but all sine
+        k_synth_graph<OPS, 8, uint32_t><<<grid, rows, 0, st>>>(values, wavetable, audio, sp, gm, p, n, pitch, shapes);
+        return hipGetLastError();
+    }
 #ifdef SOTS_EXPERIMENT
     if (max_waves == 8) {
         k_synth_graph<OPS, 4><<<grid, rows, 0, st>>>(values, wavetable, audio, sp, gm, p, n, pitch);
@@ -167,21 +249,23 @@ hipError_t launch_ops(hipStream_t st, const GraphMasks &gm, const float *values,
 } // namespace
 
 hipError_t launch_synth_graph(hipStream_t st, const sots_voice_graph &graph, const float *values, const float *wavetable, float *audio,
-                              const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus)
+                              const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus, uint32_t waveforms)
 {
     if (p == 0 || log2n < 8 || pitch < (1u << log2n) || pitch % 4u != 0) return hipErrorInvalidValue; // (a flush is 32 samples; 16-byte stores)
     GraphMasks gm;
     gm.carriers = graph.carriers;
     for (int j = 0; j < 8; ++j) gm.modulators[j] = graph.modulators[j];
     const uint32_t n = 1u << log2n, cus = num_cus ? num_cus : 256;
+    // (checked codes hold nothing beyond the operators: all sine is 0 and launches the kernel without the argument)
+    const uint32_t shapes = graph.num_operators < 8 ? waveforms & ((1u << 3 * graph.num_operators) - 1u) : waveforms & 0xFFFFFFu;
     switch (graph.num_operators) {
-    case 2: return launch_ops<2>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
-    case 3: return launch_ops<3>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
-    case 4: return launch_ops<4>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
-    case 5: return launch_ops<5>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
-    case 6: return launch_ops<6>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
-    case 7: return launch_ops<7>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
-    case 8: return launch_ops<8>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus);
+    case 2: return launch_ops<2>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
+    case 3: return launch_ops<3>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
+    case 4: return launch_ops<4>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
+    case 5: return launch_ops<5>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
+    case 6: return launch_ops<6>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
+    case 7: return launch_ops<7>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
+    case 8: return launch_ops<8>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
     default: return hipErrorInvalidValue;
     }
 }

@@ -198,6 +198,13 @@ public:
     SOTS_NO_CONTRACT_ATTR void synthesiseAudioGraph(uint32_t ops, uint32_t carriers, const uint32_t *modulators, const std::vector<float> aParams,
                                                     float *aAudioBuffer)
     {
+        synthesiseAudioGraph(ops, carriers, modulators, nullptr, aParams, aAudioBuffer);
+    }
+    // ... with the operators' waveforms (sots_set_voice_waveforms, include/sots_hip.h): waveforms[j] is operator j's
+    // SOTS_WAVE_* code, null is all sine
+    SOTS_NO_CONTRACT_ATTR void synthesiseAudioGraph(uint32_t ops, uint32_t carriers, const uint32_t *modulators, const uint32_t *waveforms,
+                                                    const std::vector<float> aParams, float *aAudioBuffer)
+    {
         SOTS_NO_CONTRACT
         float f[8], level[8], pos[8], o[8];
         uint32_t heard = 0;
@@ -211,7 +218,7 @@ public:
         for (uint32_t i = 0; i < audioLength; i++) {
             float y = -0.0f; // (-0 + x is x bit for bit: the sums below add only what is there)
             for (uint32_t j = 0; j < ops && j < 8; ++j) {
-                o[j] = tableAt(pos[j]) * level[j];
+                o[j] = shapeAt(waveforms ? waveforms[j] : 0u, pos[j]) * level[j];
                 float cur = -0.0f;
                 for (uint32_t k = 0; k < j; ++k)
                     if (modulators[j] >> k & 1u) cur += o[k];
@@ -244,6 +251,22 @@ private:
         if (pos >= (float)wavetableSize) return wavetable[wavetableSize - 1];
         if (!(pos > 0.0f)) return wavetable[0];
         return wavetable[(int32_t)pos];
+    }
+    // shape(w, i) of the graph voice's operator waveforms, i the index tableAt reads: every case decided on the index
+    float shapeAt(uint32_t w, float pos) const
+    {
+        const uint32_t W = wavetableSize;
+        const uint32_t i = pos >= (float)W ? W - 1 : !(pos > 0.0f) ? 0u : (uint32_t)(int32_t)pos;
+        switch (w) {
+        default: return wavetable[i];                                               // SOTS_WAVE_SINE
+        case 1: return i < W / 2 ? wavetable[i] : 0.0f;                             // SOTS_WAVE_HALF
+        case 2: return std::fabs(wavetable[i]);                                     // SOTS_WAVE_ABS
+        case 3: return (i & (W / 4)) == 0 ? std::fabs(wavetable[i]) : 0.0f;         // SOTS_WAVE_PULSE
+        case 4: return i < W / 2 ? wavetable[2 * i] : 0.0f;                         // SOTS_WAVE_EVEN
+        case 5: return i < W / 2 ? std::fabs(wavetable[2 * i]) : 0.0f;              // SOTS_WAVE_ABS_EVEN
+        case 6: return i < W / 2 ? 1.0f : -1.0f;                                    // SOTS_WAVE_SQUARE
+        case 7: return (float)i * 6.103515625e-05f - 1.0f;                          // SOTS_WAVE_SAW: 2^-14, both exact
+        }
     }
     void advance(float &pos, float by, bool bothEnds) const
     {

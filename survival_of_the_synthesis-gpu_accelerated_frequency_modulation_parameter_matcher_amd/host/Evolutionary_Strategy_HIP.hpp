@@ -50,6 +50,9 @@ struct Evolutionary_Strategy_HIP_Arguments
     // deviceKernelArithmetic do not: the constructor throws - before any device work - and a malformed graph is refused there
     // with the library's own text.
     sots_voice_graph voiceGraph{};
+    // ... and its operators' waveforms (type.HIP.voiceWaveforms; sots_set_voice_waveforms): SOTS_WAVE_* per
+    // operator, or empty: all sine.  Only with the graph voice: the constructor throws before any device work otherwise.
+    std::vector<uint32_t> voiceWaveforms;
     bool fusedGenerations = true;     // executeAllGenerations uses the fused kernel loop
     // general.isBenchmarking (parameters.json:7, main.cpp:85).  true: every launch is bracketed by a
     // hipEvent pair and lands in the CSV under the reference's stage names (an event pair costs
@@ -216,6 +219,9 @@ private:
         if (rc != SOTS_OK)
             throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + (graphVoice ? "sots_batch_create_graph: " : "sots_batch_create: ") +
                                      sots_batch_last_error(nullptr));
+        if (!args_.voiceWaveforms.empty() &&
+            sots_batch_set_voice_waveforms(batch_, args_.voiceWaveforms.data(), (uint32_t)args_.voiceWaveforms.size()) != SOTS_OK)
+            throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_batch_set_voice_waveforms: ") + sots_batch_last_error(batch_));
     }
     void check(int rc, const char *what) const
     {
@@ -390,6 +396,8 @@ public:
             throw std::runtime_error("Evolutionary_Strategy_HIP: renderMode 1 and 2 (sots_render_continuous) are not available with the operator-graph voice");
         if (graphVoice && args_.deviceKernelArithmetic)
             throw std::runtime_error("Evolutionary_Strategy_HIP: deviceKernelArithmetic is not available with the operator-graph voice");
+        if (!graphVoice && !args_.voiceWaveforms.empty())
+            throw std::runtime_error("Evolutionary_Strategy_HIP: voiceWaveforms need the operator-graph voice");
         cfg_.workgroup_size = args_.workgroupX * args_.workgroupY * args_.workgroupZ;
         cfg_.device = args_.deviceOrdinal;
         cfg_.gid_base = args_.gidBase;
@@ -423,6 +431,8 @@ public:
                 throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + (graphVoice ? "sots_create_graph: " : "sots_create: ") + sots_last_error(nullptr));
         }
         targetFFT_.assign(objective.fftHalfSize, 0.0f);
+        if (!args_.voiceWaveforms.empty()) // (the graph voice: one device, no group)
+            check(sots_set_voice_waveforms(ctx_, args_.voiceWaveforms.data(), (uint32_t)args_.voiceWaveforms.size()), "sots_set_voice_waveforms");
         if (args_.fullSortEveryGeneration)
             for (uint32_t i = 0; i < numIslands(); ++i)
                 check(sots_set_sort_mode(group_ ? sots_group_island(group_, i) : ctx_, SOTS_SORT_FULL), "sots_set_sort_mode");

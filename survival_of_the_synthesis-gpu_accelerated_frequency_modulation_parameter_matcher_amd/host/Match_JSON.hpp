@@ -327,4 +327,31 @@ inline bool readVoiceGraphKeys(const Json &h, uint32_t numDimensions, bool rende
     return true;
 }
 
+// type.HIP.voiceWaveforms (sots_set_voice_waveforms, include/sots_hip.h): the graph voice's operator
+// waveforms, one name per operator - "sine", "half", "abs", "pulse", "even", "absEven", "square", "saw" - a key of its own
+// beside voiceGraph.  Returns whether the key is there; codes receives SOTS_WAVE_* per operator.  Throws - before any device
+// work - without type.HIP.synth "graph", on anything but a list of `operators` strings, and on a name that is no waveform.
+inline bool readVoiceWaveformsKey(const Json &h, bool graphVoice, uint32_t operators, std::vector<uint32_t> &codes)
+{
+    if (!h.has("voiceWaveforms")) return false;
+    const std::string what = "parameters.json: type.HIP.voiceWaveforms";
+    if (!graphVoice) throw std::runtime_error(what + " needs type.HIP.synth \"graph\"");
+    const Json &v = h["voiceWaveforms"];
+    if (v.kind != Json::Array || v.arr.size() != operators)
+        throw std::runtime_error(what + " needs one name per operator (" + (v.kind == Json::Array ? std::to_string(v.arr.size()) + " names" : std::string("not a list")) +
+                                 ", " + std::to_string(operators) + " operators)");
+    static const char *const names[8] = {"sine", "half", "abs", "pulse", "even", "absEven", "square", "saw"};
+    std::vector<uint32_t> out;
+    for (const Json &e : v.arr) {
+        uint32_t w = 0;
+        while (w < 8 && !(e.kind == Json::String && e.str == names[w])) ++w;
+        if (w == 8)
+            throw std::runtime_error(what + ": " + (e.kind == Json::String ? "\"" + e.str + "\"" : std::string("an entry that is no string")) +
+                                     " is no waveform (sine, half, abs, pulse, even, absEven, square, saw)");
+        out.push_back(w);
+    }
+    codes = out;
+    return true;
+}
+
 #endif

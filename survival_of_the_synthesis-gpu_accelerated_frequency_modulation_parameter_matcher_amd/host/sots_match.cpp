@@ -1,7 +1,7 @@
 // sots_match.cpp -- command-line driver with the reference's interface (main.cpp:25-305):
 //     sots_match -j parameters.json
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
-// "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "voiceGraph", "numDevices", "numElites",
+// "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "voiceGraph", "voiceWaveforms", "numDevices", "numElites",
 // "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight", "chunkQueue",
 // "carryRows", "segmentChunks", "survivors", "objective", "objectiveFloor", "objectiveWeights", "hopSize", "renderMatch", "renderMode", "matchPath", "deviceAnalysis", "matchReport", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
@@ -24,6 +24,9 @@
 //                 below j), carriers the operators that are heard; gene 2j is operator j's frequency, gene 2j+1 its level,
 //                 so evolutionary.numDimensions is 2 n and paramMins / paramMaxs hold 2 n entries.  One device; not with
 //                 "continuous" / "continuousGlide" rendering or "deviceKernelArithmetic".
+//   "voiceWaveforms" with "voiceGraph": one waveform per operator, each of "sine" (the default), "half", "abs", "pulse",
+//                 "even", "absEven", "square", "saw" - shapes cut out of the one sine table (sots_set_voice_waveforms), so
+//                 that an operator emits a harmonic series.  Search, rendering, report and the host's own synthesiser use it.
 //   "matchPath"   a CSV of the parameter track, one row per chunk:
 //                 chunk,start_sample,generations,fitness,u0..u{D-1},p0..p{D-1} - u the unit-range genes (%.9g: the fp32
 //                 bits), p the scaled parameters; with returnBestEver the best-ever individual of each chunk.
@@ -156,14 +159,17 @@ int main(int argc, char *argv[])
                                : s == "graph" ? SOTS_SYNTH_GRAPH : -1;
             }
             // the operator-graph voice: "synth": "graph" with "voiceGraph" (Match_JSON.hpp)
-            (void)readVoiceGraphKeys(h, args.es_args.pop.numDimensions, args.renderMatch, args.renderMode, args.voiceGraph);
+            const bool graphVoice = readVoiceGraphKeys(h, args.es_args.pop.numDimensions, args.renderMatch, args.renderMode, args.voiceGraph);
+            // ... and its operators' waveforms: "voiceWaveforms", one name per operator (Match_JSON.hpp)
+            (void)readVoiceWaveformsKey(h, graphVoice, args.voiceGraph.num_operators, args.voiceWaveforms);
         }
         const uint32_t D = args.es_args.pop.numDimensions;
         Evolutionary_Strategy_HIP *hipEs = new Evolutionary_Strategy_HIP(args);
         std::unique_ptr<Evolutionary_Strategy> es(hipEs);
         const sots_voice_graph &vg = args.voiceGraph;
         auto synthesise = [&](Objective &obj, const std::vector<float> &p, float *out) {
-            if (args.synthKind == SOTS_SYNTH_GRAPH) obj.synthesiseAudioGraph(vg.num_operators, vg.carriers, vg.modulators, p, out);
+            if (args.synthKind == SOTS_SYNTH_GRAPH)
+                obj.synthesiseAudioGraph(vg.num_operators, vg.carriers, vg.modulators, args.voiceWaveforms.empty() ? nullptr : args.voiceWaveforms.data(), p, out);
             else if (D == 4) obj.synthesiseAudio(p, out);
             else if (D == 6) obj.synthesiseAudioDoubleSeries(p, out);
             else if (D == 8) obj.synthesiseAudioQuadSeries(p, out);
