@@ -149,7 +149,8 @@ int sots_synchronize(sots_ctx *ctx);
  *   - There is no `& 3` folding of the ranges as in the triple voice.
  * Topology:
  *   - modulators[j] is a bit mask.  Only bits i < j may be set.  Bit i set means operator i's output modulates
- *     operator j.  Feed-forward only: no feedback.
+ *     operator j.  Feed-forward only: no operator modulates an earlier one or itself.  An operator's feedback onto its
+ *     own phase is a setting of its own, not an edge of the graph: sots_set_voice_feedback, below.
  *   - carriers is a bit mask and is not empty.
  *   - Every operator is exactly one of two things.  Either it is a carrier and modulates nobody, or it is not a carrier
  *     and modulates at least one operator.  Everything else is refused.
@@ -215,6 +216,34 @@ enum {
 };
 int sots_set_voice_waveforms(sots_ctx *ctx, const uint32_t *codes, uint32_t count);
 int sots_get_voice_waveforms(const sots_ctx *ctx, uint32_t codes[8]);
+
+/* ---- per-operator feedback of the graph voice (new: an operator's phase offset by its own output, as in hardware FM) ----
+ * Every operator j of a sots_voice_graph has a feedback index beta_j, +0 until set, and keeps two more state words, h1_j
+ * and h2_j, both +0 at sample 0.  For an operator with beta_j != 0, step 1 of the voice becomes, all fp32 and uncontracted:
+ *     K   = 0x1.45f306p+12f                     (5215.18896484375, the fp32 nearest W / 2 pi)
+ *     B_j = beta_j * K                          (one fp32 product)
+ *     g   = (h1_j + h2_j) * 0.5f
+ *     z   = pos_j + B_j * g                     (multiply, then add)
+ *     if (z >= W) z -= W;  if (z < 0) z += W;   (in this order, once each)
+ *     i   = clamp((int)z, 0, W-1) decided on the float, NaN and negatives to 0   (as for pos_j)
+ *     t_j = shape(w_j, i);   o_j = t_j * A_j
+ *     h2_j = h1_j;  h1_j = t_j
+ * h is the shaped table value BEFORE the level: its magnitude is at most 1 for every shape, so with beta_j <= 2 one wrap
+ * each way suffices for a phase in [0, W); any other phase is caught by the clamp, as it always was.  An operator with
+ * beta_j == 0 is skipped: its index is that of pos_j, not of pos_j plus an offset of 0.  Steps 2 to 4 (increment, pos_j
+ * update, wraps) and the carrier sum are untouched: feedback never changes pos_j and does not make an operator
+ * "modulated" for the lower wrap.  With all beta zero the voice is the one above bit for bit.  Feedback combines freely
+ * with the waveform codes and with any role.  The indices belong to the algorithm, like the codes: they are not evolved,
+ * and the voice keeps its 2 num_operators genes.
+ * sots_set_voice_feedback: index[count], count == the graph's num_operators, every index in [0, 2] (NaN, infinite,
+ * negative and larger values are refused; -0 is taken as 0); (NULL, 0) sets all zero.  SOTS_ERR_STATE for a context of a
+ * fixed voice, SOTS_ERR_INVALID for the rest; everything is checked before anything changes, and a refused call leaves
+ * the old setting.  A successful call acts like sots_set_voice_waveforms: the run record is cleared, the stored selection
+ * splitters and key lists are dropped; population and target stay.  In any order with target, objective, weights and
+ * waveforms.  sots_get_voice_feedback writes all eight indices (0 beyond the operators).  Islands have no such setting;
+ * sots_render_continuous and device-kernel arithmetic refuse the graph voice as before. */
+int sots_set_voice_feedback(sots_ctx *ctx, const float *index, uint32_t count);
+int sots_get_voice_feedback(const sots_ctx *ctx, float index[8]);
 
 /* ---- target (replaces setTargetAudio, ...OpenCL.hpp:563-570; Objective::calculateFFT,
  *      Evolutionary_Strategy.hpp:524-542) ---- */
@@ -547,6 +576,10 @@ int sots_batch_set_objective_weights(sots_batch *b, const float *weights, uint32
  * cleared.  Before or after the targets, the objective and the weights, with the same result. */
 int sots_batch_set_voice_waveforms(sots_batch *b, const uint32_t *codes, uint32_t count);
 int sots_batch_get_voice_waveforms(const sots_batch *b, uint32_t codes[8]);
+/* sots_set_voice_feedback for every chunk of a graph-voice batch (new): one setting for all chunks, the same rules and
+ * refusals.  Every chunk's run record is cleared.  In any order with the targets, objective, weights and waveforms. */
+int sots_batch_set_voice_feedback(sots_batch *b, const float *index, uint32_t count);
+int sots_batch_get_voice_feedback(const sots_batch *b, float index[8]);
 /* row 0 (the best) of every active chunk: values [active][D], fitness [active] (either may be NULL); blocking */
 int sots_batch_read_best(sots_batch *b, float *values, size_t values_bytes, float *fitness, size_t fitness_bytes);
 /* one active chunk's current half; byte counts as sots_read_population; blocking */

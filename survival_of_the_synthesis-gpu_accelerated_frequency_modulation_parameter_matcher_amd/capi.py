@@ -79,6 +79,7 @@ EXPORTS = [
     "sots_batch_set_analysis", "sots_batch_get_analysis", "sots_batch_analyse_audio_hop", "sots_batch_queue_score_audio_hop",
     "sots_create_graph", "sots_batch_create_graph", "sots_get_voice_graph",
     "sots_set_voice_waveforms", "sots_get_voice_waveforms", "sots_batch_set_voice_waveforms", "sots_batch_get_voice_waveforms",
+    "sots_set_voice_feedback", "sots_get_voice_feedback", "sots_batch_set_voice_feedback", "sots_batch_get_voice_feedback",
 ]
 ANALYSIS_HOST, ANALYSIS_DEVICE = 0, 1  # enum sots_analysis
 QUEUE_NO_CHUNK = 0xFFFFFFFF
@@ -148,6 +149,15 @@ def _waveform_codes(waveforms):
         return None, 0
     codes = [WAVE_NAMES[w] if isinstance(w, str) else int(w) for w in waveforms]
     return (C.c_uint32 * len(codes))(*[c & 0xFFFFFFFF for c in codes]), len(codes)
+
+
+def _feedback_indices(feedback):
+    """(pointer, count) of sots_set_voice_feedback from None (no feedback) or one index per operator.  Nothing is checked
+    here: the library's rule refuses with its own text."""
+    if feedback is None:
+        return None, 0
+    index = [float(b) for b in feedback]
+    return (C.c_float * len(index))(*index), len(index)
 
 
 def synth_dims(synth_kind, graph=None):
@@ -359,6 +369,10 @@ def load():
     L.sots_get_voice_waveforms.argtypes = [vp, C.POINTER(u32)]
     L.sots_batch_set_voice_waveforms.argtypes = [vp, C.POINTER(u32), u32]
     L.sots_batch_get_voice_waveforms.argtypes = [vp, C.POINTER(u32)]
+    L.sots_set_voice_feedback.argtypes = [vp, C.POINTER(C.c_float), u32]
+    L.sots_get_voice_feedback.argtypes = [vp, C.POINTER(C.c_float)]
+    L.sots_batch_set_voice_feedback.argtypes = [vp, C.POINTER(C.c_float), u32]
+    L.sots_batch_get_voice_feedback.argtypes = [vp, C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -409,9 +423,10 @@ class HipES:
 
     def __init__(self, num_parents, num_offspring, synth_kind=SYNTH_2OP, audio_log2=10,
                  param_min=None, param_max=None, seed=0x5EED0001, workgroup_size=32,
-                 device=0, gid_base=0, num_generations=0, graph=None, waveforms=None):
+                 device=0, gid_base=0, num_generations=0, graph=None, waveforms=None, feedback=None):
         """graph (with synth_kind=SYNTH_GRAPH): a VoiceGraph or its JSON form, see as_voice_graph; waveforms: that
-        graph's operator waveforms, see set_voice_waveforms"""
+        graph's operator waveforms, see set_voice_waveforms; feedback: its operators' feedback indices, see
+        set_voice_feedback"""
         self.L = load()
         self._borrowed = False
         self.graph = as_voice_graph(graph)
@@ -430,6 +445,8 @@ class HipES:
         self._h = h
         if waveforms is not None:
             self.set_voice_waveforms(waveforms)
+        if feedback is not None:
+            self.set_voice_feedback(feedback)
 
     # -- plumbing --
     def _check(self, rc):
@@ -470,6 +487,18 @@ class HipES:
         codes = (C.c_uint32 * GRAPH_MAX_OPERATORS)()
         self._check(self.L.sots_get_voice_waveforms(self._h, codes))
         return list(codes)[:self.D // 2]
+
+    def set_voice_feedback(self, feedback):
+        """one feedback index in [0, 2] per operator of the graph, or None: no feedback.  Like set_voice_waveforms: the run
+        record is cleared"""
+        index, count = _feedback_indices(feedback)
+        self._check(self.L.sots_set_voice_feedback(self._h, index, count))
+
+    def voice_feedback(self):
+        """the feedback indices of the graph's operators"""
+        index = (C.c_float * GRAPH_MAX_OPERATORS)()
+        self._check(self.L.sots_get_voice_feedback(self._h, index))
+        return list(index)[:self.D // 2]
 
     def info(self):
         i = Info()
@@ -765,7 +794,7 @@ class HipBatch:
 
     def __init__(self, max_chunks, num_parents, num_offspring, synth_kind=SYNTH_2OP, audio_log2=10, param_min=None,
                  param_max=None, seed=0x5EED0001, workgroup_size=32, device=0, gid_base=0, num_generations=0, graph=None,
-                 waveforms=None):
+                 waveforms=None, feedback=None):
         self.L = load()
         self.graph = as_voice_graph(graph)
         self.cfg = make_config(num_parents, num_offspring, synth_kind, audio_log2, param_min, param_max, seed, workgroup_size,
@@ -784,6 +813,8 @@ class HipBatch:
         self._h = h
         if waveforms is not None:
             self.set_voice_waveforms(waveforms)
+        if feedback is not None:
+            self.set_voice_feedback(feedback)
 
     def _check(self, rc):
         if rc != 0:
@@ -858,6 +889,16 @@ class HipBatch:
         codes = (C.c_uint32 * GRAPH_MAX_OPERATORS)()
         self._check(self.L.sots_batch_get_voice_waveforms(self._h, codes))
         return list(codes)[:self.D // 2]
+
+    def set_voice_feedback(self, feedback):
+        """HipES.set_voice_feedback for every chunk (one setting), in execute_generations / execute_until and queue_run alike"""
+        index, count = _feedback_indices(feedback)
+        self._check(self.L.sots_batch_set_voice_feedback(self._h, index, count))
+
+    def voice_feedback(self):
+        index = (C.c_float * GRAPH_MAX_OPERATORS)()
+        self._check(self.L.sots_batch_get_voice_feedback(self._h, index))
+        return list(index)[:self.D // 2]
 
     def read_best(self):
         """(values[active][D], fitness[active]): row 0 of every active chunk"""

@@ -419,6 +419,22 @@ int sots_batch_get_voice_waveforms(const sots_batch *b, uint32_t codes[8])
     return engine_get_voice_waveforms(*b, codes);
 }
 
+int sots_batch_set_voice_feedback(sots_batch *b, const float *index, uint32_t count)
+{
+    BATCH_REQUIRE(b);
+    SOTS_REFUSE(b, voice_feedback_check(b->cfg.synth_kind, b->graph.num_operators, index, count));
+    if (int rc = engine_bind(*b)) return rc;
+    SOTS_HIP(b, track_clear(b->track, b->stream));
+    SOTS_HIP(b, hipStreamSynchronize(b->stream));
+    return engine_set_voice_feedback(*b, index, count);
+}
+
+int sots_batch_get_voice_feedback(const sots_batch *b, float index[8])
+{
+    BATCH_REQUIRE(b);
+    return engine_get_voice_feedback(*b, index);
+}
+
 int sots_batch_execute_generations(sots_batch *b, uint32_t n)
 {
     BATCH_REQUIRE(b);

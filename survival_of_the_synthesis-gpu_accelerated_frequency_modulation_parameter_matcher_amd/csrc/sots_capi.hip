@@ -1045,6 +1045,25 @@ int sots_get_voice_waveforms(const sots_ctx *ctx, uint32_t codes[8])
     return engine_get_voice_waveforms(*ctx, codes);
 }
 
+// ... and so is a new feedback setting
+int sots_set_voice_feedback(sots_ctx *ctx, const float *index, uint32_t count)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    SOTS_REFUSE(ctx, voice_feedback_check(ctx->cfg.synth_kind, ctx->graph.num_operators, index, count));
+    if (int rc = engine_bind(*ctx)) return rc;
+    SOTS_HIP(ctx, track_clear(ctx->track, ctx->stream));
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->spl_valid = false;
+    ctx->lists_ready = false;
+    return engine_set_voice_feedback(*ctx, index, count);
+}
+
+int sots_get_voice_feedback(const sots_ctx *ctx, float index[8])
+{
+    SOTS_REQUIRE_CTX(ctx);
+    return engine_get_voice_feedback(*ctx, index);
+}
+
 int sots_get_objective_weights(const sots_ctx *ctx, float *weights, uint32_t num_bins, uint32_t *is_set)
 {
     SOTS_REQUIRE_CTX(ctx);

@@ -55,6 +55,7 @@ struct Engine {
     sots_config cfg{};
     sots_voice_graph graph{}; // SOTS_SYNTH_GRAPH: the topology that came with cfg (num_operators 0 for a fixed voice)
     uint32_t waveforms[8] = {0}; // ... and its operators' waveform codes (sots_set_voice_waveforms; all sine until set)
+    float feedback[8] = {0};     // ... and their feedback indices (sots_set_voice_feedback; +0, no feedback, until set)
     PopDims pd{};
     MutateConsts mc{};
     SynthParams sp{};
@@ -187,6 +188,19 @@ inline int engine_get_voice_waveforms(const Engine &e, uint32_t codes[8])
     return SOTS_OK;
 }
 
+inline int engine_set_voice_feedback(Engine &e, const float *index, uint32_t count)
+{
+    SOTS_REFUSE(e, voice_feedback_set(e.cfg.synth_kind, e.graph.num_operators, index, count, e.feedback));
+    return SOTS_OK;
+}
+inline int engine_get_voice_feedback(const Engine &e, float index[8])
+{
+    if (!index) return SOTS_FAIL(e, SOTS_ERR_INVALID, "voice feedback: null argument");
+    SOTS_REFUSE(e, voice_feedback_check(e.cfg.synth_kind, e.graph.num_operators, nullptr, 0));
+    memcpy(index, e.feedback, sizeof e.feedback);
+    return SOTS_OK;
+}
+
 // ---- objective ----
 // Both setters check everything before anything changes, then leave the objective they replaced in *old: the caller derives
 // what depends on the new one (its target images, its run record) and, where that fails, puts *old back with
@@ -235,7 +249,7 @@ inline hipError_t engine_synthesise(const Engine &e, const float *values, float 
     if (e.synth_arith == SOTS_ARITH_DEVICE_KERNELS)
         return launch_synth_device_arith(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch);
     return launch_synth(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch, e.num_cus, var, allow_cut, &e.graph,
-                        pack_waveforms(e.waveforms));
+                        pack_waveforms(e.waveforms), e.feedback);
 }
 
 } // namespace sots

@@ -115,6 +115,43 @@ inline Fault voice_waveforms_set(uint32_t kind, uint32_t ops, const uint32_t *co
     return Fault{};
 }
 
+// ---- per-operator feedback of the graph voice (sots_set_voice_feedback; the definition: include/sots_hip.h) ----
+constexpr float kFeedbackMax = 2.0f;
+// K of the definition: the fp32 nearest W / 2 pi, table entries per unit of h at an index of 1
+constexpr float kFeedbackScale = 0x1.45f306p+12f;
+// index[count] for a handle of synthesis kind `kind` whose graph has `ops` operators; (null, 0): no feedback
+inline Fault voice_feedback_check(uint32_t kind, uint32_t ops, const float *index, uint32_t count)
+{
+    if (kind != SOTS_SYNTH_GRAPH)
+        return fault(SOTS_ERR_STATE, "voice feedback: the handle runs a fixed voice (synth_kind %u)", kind);
+    if (!index && count == 0) return Fault{};
+    if (!index) return fault(SOTS_ERR_INVALID, "voice feedback: null indices with a count of %u", count);
+    if (count != ops) return fault(SOTS_ERR_INVALID, "voice feedback: %u indices for a graph of %u operators", count, ops);
+    for (uint32_t j = 0; j < count; ++j)
+        if (!(index[j] >= 0.0f && index[j] <= kFeedbackMax)) // (NaN fails both; -0 >= 0 holds)
+            return fault(SOTS_ERR_INVALID, "voice feedback: index %g of operator %u is outside 0..%g", (double)index[j], j, (double)kFeedbackMax);
+    return Fault{};
+}
+// Checks, then writes all eight indices of `held` (+0 beyond the operators and for -0); a refusal leaves `held` as it was
+inline Fault voice_feedback_set(uint32_t kind, uint32_t ops, const float *index, uint32_t count, float held[8])
+{
+    if (const Fault f = voice_feedback_check(kind, ops, index, count)) return f;
+    for (uint32_t j = 0; j < kGraphMaxOps; ++j) held[j] = index && j < count && index[j] != 0.0f ? index[j] : 0.0f;
+    return Fault{};
+}
+// What the feedback kernel takes: B_j = beta_j K, one fp32 product each (this header is built uncontracted wherever it is
+// used, and a lone product has nothing to contract with); returns whether any operator feeds back
+inline bool scale_feedback(const float index[8], uint32_t ops, float scaled[8])
+{
+    bool any = false;
+    for (uint32_t j = 0; j < kGraphMaxOps; ++j) {
+        const float b = j < ops ? index[j] : 0.0f;
+        scaled[j] = b * kFeedbackScale;
+        any = any || b != 0.0f;
+    }
+    return any;
+}
+
 // Everything a configuration must satisfy whoever takes it; max_population is the caller's own limit on numParents +
 // numOffspring.  Needs no device: a machine without a GPU still tells a bad configuration from a good one.  graph: the
 // topology that came with the configuration (sots_create_graph, sots_batch_create_graph), null from every other entry point.

@@ -25,6 +25,14 @@ struct GraphMasks {
     uint32_t carriers;
     uint32_t modulators[8];
 };
+struct GraphFeedback {
+    float b[8]; // beta_j K
+};
+template <typename T, typename... R>
+__device__ __forceinline__ T first_of(T first, R...)
+{
+    return first;
+}
 
 // The operators' waveforms (sots_set_voice_waveforms, include/sots_hip.h).  SHAPES is empty or one uint32_t: the kernel
 // with no such argument is the all-sine voice with the arguments it always had; with it, every operator's table value goes
@@ -33,6 +41,12 @@ struct GraphMasks {
 // straight-line statement of the definition, decided on the integer index, and SQUARE and SAW read no table at all.
 // (The form that lost, DESIGN.md 4.14: one branchless body with per-operator scalar constants - index shift, sign mask,
 // zeroing index bit, two overrides - costs every code the instructions of all of them.)
+// Feedback (sots_set_voice_feedback, include/sots_hip.h): SHAPES is the codes and GraphFeedback, the eight
+// B_j = beta_j K as scalar arguments.  An operator with B_j != 0 (wavefront-uniform) reads the table at its phase offset by
+// B_j times the mean of its own last two shaped values: its block of U reads is a serial chain offset -> wraps -> index ->
+// read -> next offset, so its U phases are advanced first (they do not depend on the feedback) and the chain runs after
+// them.  h1 and h2 stay in registers across blocks, flushes and tiles and are reset per row.  An operator with B_j == 0
+// runs the shaped form's block as it stands.
 // CH: 16-byte chunks per tile row = 4 CH samples per flush.  The 32 KiB beside the table are 32 / CH tiles of 64 rows:
 // CH = 8, four wavefronts (one per SIMD) and whole 128-byte lines; CH = 4, eight wavefronts (two per SIMD) and half lines.
 template <int OPS, int CH, typename... SHAPES>
@@ -43,12 +57,14 @@ __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *
     constexpr bool SHAPED = sizeof...(SHAPES) != 0;
     // (an experiment build also has the form that lost: the codes as int32_t)
     constexpr bool BRANCHES = SHAPED && (std::is_same_v<SHAPES, uint32_t> || ...);
-    static_assert(sizeof...(SHAPES) <= 1 && ((std::is_same_v<SHAPES, uint32_t> || std::is_same_v<SHAPES, int32_t>) && ...),
-                  "no argument, or the packed codes");
+    constexpr bool FEEDBACK = (std::is_same_v<SHAPES, GraphFeedback> || ...);
+    static_assert((sizeof...(SHAPES) <= 1 && ((std::is_same_v<SHAPES, uint32_t> || std::is_same_v<SHAPES, int32_t>) && ...)) ||
+                      (sizeof...(SHAPES) == 2 && BRANCHES && FEEDBACK),
+                  "no argument, the packed codes, or the packed codes and the feedback indices");
     constexpr int D = 2 * OPS, WAVES = 32 / CH;
     constexpr int RPI = kWave / CH; // rows per transposed read / store instruction (CH of them per flush)
     constexpr int U = OPS <= 4 ? 8 : 4;            // samples per block: o[OPS][U] stays in registers
-    constexpr int kUnroll = OPS <= 2 ? CH / (U / 4) : 1; // blocks unrolled per flush: the code stays in the instruction cache
+    constexpr int kUnroll = OPS <= 2 && !FEEDBACK ? CH / (U / 4) : 1; // blocks unrolled per flush: the code stays in the instruction cache
     static_assert(U % 4 == 0 && CH % (U / 4) == 0, "whole 16-byte chunks, whole blocks per flush");
     static_assert(OPS >= 2 && OPS <= 8 && D <= SOTS_MAX_DIMS && (CH == 8 || CH == 4), "2 to 8 operators; whole or half lines");
     __shared__ float tab[kWavetableSize];
@@ -82,6 +98,11 @@ __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *
         if (row0 >= p_len) continue;               // (wavefront-uniform; no workgroup barrier below)
         const uint32_t ind = row0 + lane < p_len ? row0 + lane : p_len - 1u;
         float f[OPS], amp[OPS], pos[OPS];
+        [[maybe_unused]] float h1[OPS], h2[OPS]; // (feedback: an operator's last two shaped values, +0 at sample 0)
+        if constexpr (FEEDBACK) {
+#pragma unroll
+            for (int j = 0; j < OPS; ++j) h1[j] = h2[j] = 0.0f;
+        }
 #pragma unroll
         for (int j = 0; j < OPS; ++j) {
             const float a = sp.pmin[2 * j + 1] + values[(size_t)ind * D + 2 * j + 1] * (sp.pmax[2 * j + 1] - sp.pmin[2 * j + 1]);
@@ -111,10 +132,42 @@ __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *
                 if constexpr (BRANCHES) {
                     // (the code is taken from the argument here, block by block: the tests on it held in scalar registers
                     // across the sample loop for every operator cost the wide forms register lanes)
-                    uint32_t packed = (shapes, ...);
+                    uint32_t packed = first_of(shapes...);
                     asm volatile("" : "+s"(packed));
                     const uint32_t w = packed >> (3 * J) & 7u;
+                    [[maybe_unused]] uint32_t fb_bits = 0u; // B_J's bits: checked indices are +0 or positive, so 0 is "off"
+                    if constexpr (FEEDBACK) {
+                        fb_bits = __float_as_uint((shapes, ...).b[J]);
+                        asm volatile("" : "+s"(fb_bits));
+                    }
                     auto run = [&](auto shape) {
+                        if constexpr (FEEDBACK) {
+                            if (fb_bits != 0u) {
+                                const float bj = __uint_as_float(fb_bits);
+                                float ph[U];
+#pragma unroll
+                                for (int u = 0; u < U; ++u) {
+                                    ph[u] = pos[J];
+                                    pos[J] += c * (cur[u] + f[J]);
+                                    if (pos[J] >= wf) pos[J] -= wf;
+                                    if (modulated && pos[J] < 0.0f) pos[J] += wf;
+                                }
+                                float a1 = h1[J], a2 = h2[J];
+#pragma unroll
+                                for (int u = 0; u < U; ++u) {
+                                    const float g = (a1 + a2) * 0.5f;
+                                    float z = ph[u] + bj * g;
+                                    if (z >= wf) z -= wf;
+                                    if (z < 0.0f) z += wf;
+                                    tv[u] = shape(index_of(z));
+                                    a2 = a1;
+                                    a1 = tv[u];
+                                }
+                                h1[J] = a1;
+                                h2[J] = a2;
+                                return;
+                            }
+                        }
 #pragma unroll
                         for (int u = 0; u < U; ++u) {
                             tv[u] = shape(index_of(pos[J]));
@@ -213,7 +266,7 @@ __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *
 
 template <int OPS>
 hipError_t launch_ops(hipStream_t st, const GraphMasks &gm, const float *values, const float *wavetable, float *audio, const SynthParams &sp,
-                      uint32_t p, uint32_t n, uint32_t pitch, uint32_t cus, uint32_t shapes)
+                      uint32_t p, uint32_t n, uint32_t pitch, uint32_t cus, uint32_t shapes, const GraphFeedback *fb)
 {
     // one workgroup per CU (the table), sized to the CU's share of the population up to one wavefront per SIMD; larger
     // populations loop over tiles
@@ -224,8 +277,12 @@ hipError_t launch_ops(hipStream_t st, const GraphMasks &gm, const float *values,
     const uint32_t share = (p + cus - 1) / cus;
     uint32_t waves = (share + kWave - 1) / kWave;
     if (waves > max_waves) waves = max_waves;
-    if (shapes && waves > 4) waves = 4; // (the CH = 4 experiment form is not shaped)
+    if ((shapes || fb) && waves > 4) waves = 4; // (the CH = 4 experiment form is not shaped)
     const uint32_t rows = waves * kWave, tiles = (p + rows - 1) / rows, grid = tiles < cus ? tiles : cus;
+    if (fb) { // any operator feeds back: the codes go through this form too (all sine through the switch's default)
+        k_synth_graph<OPS, 8, uint32_t, GraphFeedback><<<grid, rows, 0, st>>>(values, wavetable, audio, sp, gm, p, n, pitch, shapes, *fb);
+        return hipGetLastError();
+    }
 #ifdef SOTS_EXPERIMENT
     if (const char *e = getenv("SOTS_GRAPH_SHAPE_CONSTANTS"); shapes && e && atoi(e) == 1) {
         k_synth_graph<OPS, 8, int32_t><<<grid, rows, 0, st>>>(values, wavetable, audio, sp, gm, p, n, pitch, (int32_t)shapes);
@@ -249,7 +306,8 @@ hipError_t launch_ops(hipStream_t st, const GraphMasks &gm, const float *values,
 } // namespace
 
 hipError_t launch_synth_graph(hipStream_t st, const sots_voice_graph &graph, const float *values, const float *wavetable, float *audio,
-                              const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus, uint32_t waveforms)
+                              const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus, uint32_t waveforms,
+                              const float *feedback)
 {
     if (p == 0 || log2n < 8 || pitch < (1u << log2n) || pitch % 4u != 0) return hipErrorInvalidValue; // (a flush is 32 samples; 16-byte stores)
     GraphMasks gm;
@@ -258,14 +316,17 @@ hipError_t launch_synth_graph(hipStream_t st, const sots_voice_graph &graph, con
     const uint32_t n = 1u << log2n, cus = num_cus ? num_cus : 256;
     // (checked codes hold nothing beyond the operators: all sine is 0 and launches the kernel without the argument)
     const uint32_t shapes = graph.num_operators < 8 ? waveforms & ((1u << 3 * graph.num_operators) - 1u) : waveforms & 0xFFFFFFu;
+    // (checked indices are +0 beyond the operators; all zero launches what is launched without the setting)
+    GraphFeedback scaled;
+    const GraphFeedback *fb = feedback && scale_feedback(feedback, graph.num_operators, scaled.b) ? &scaled : nullptr;
     switch (graph.num_operators) {
-    case 2: return launch_ops<2>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
-    case 3: return launch_ops<3>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
-    case 4: return launch_ops<4>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
-    case 5: return launch_ops<5>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
-    case 6: return launch_ops<6>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
-    case 7: return launch_ops<7>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
-    case 8: return launch_ops<8>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes);
+    case 2: return launch_ops<2>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
+    case 3: return launch_ops<3>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
+    case 4: return launch_ops<4>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
+    case 5: return launch_ops<5>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
+    case 6: return launch_ops<6>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
+    case 7: return launch_ops<7>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
+    case 8: return launch_ops<8>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
     default: return hipErrorInvalidValue;
     }
 }

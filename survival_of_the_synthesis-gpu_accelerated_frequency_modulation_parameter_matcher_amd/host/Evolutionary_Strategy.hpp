@@ -205,20 +205,42 @@ public:
     SOTS_NO_CONTRACT_ATTR void synthesiseAudioGraph(uint32_t ops, uint32_t carriers, const uint32_t *modulators, const uint32_t *waveforms,
                                                     const std::vector<float> aParams, float *aAudioBuffer)
     {
+        synthesiseAudioGraph(ops, carriers, modulators, waveforms, nullptr, aParams, aAudioBuffer);
+    }
+    // ... and with their feedback indices (sots_set_voice_feedback, include/sots_hip.h): feedback[j] is operator j's index in
+    // [0, 2], null is none.  An operator with an index other than 0 reads at its phase offset by index x K x the mean of its
+    // last two shaped values; its phase itself is untouched.
+    SOTS_NO_CONTRACT_ATTR void synthesiseAudioGraph(uint32_t ops, uint32_t carriers, const uint32_t *modulators, const uint32_t *waveforms,
+                                                    const float *feedback, const std::vector<float> aParams, float *aAudioBuffer)
+    {
         SOTS_NO_CONTRACT
-        float f[8], level[8], pos[8], o[8];
+        float f[8], level[8], pos[8], o[8], fb[8], h1[8], h2[8];
         uint32_t heard = 0;
+        const float wf = (float)wavetableSize;
         for (uint32_t j = 0; j < ops && j < 8; ++j) {
             f[j] = scaled(aParams[2 * j], 2 * j);
             const float a = scaled(aParams[2 * j + 1], 2 * j + 1);
             level[j] = (carriers >> j & 1u) ? a : f[j] * a;
             pos[j] = 0.0f;
+            fb[j] = feedback ? feedback[j] * 0x1.45f306p+12f : 0.0f; // K: the fp32 nearest W / 2 pi
+            h1[j] = h2[j] = 0.0f;
             heard += carriers >> j & 1u;
         }
         for (uint32_t i = 0; i < audioLength; i++) {
             float y = -0.0f; // (-0 + x is x bit for bit: the sums below add only what is there)
             for (uint32_t j = 0; j < ops && j < 8; ++j) {
-                o[j] = shapeAt(waveforms ? waveforms[j] : 0u, pos[j]) * level[j];
+                float at = pos[j];
+                if (feedback && feedback[j] != 0.0f) {
+                    const float g = (h1[j] + h2[j]) * 0.5f;
+                    const float offset = fb[j] * g; // (multiply, then add)
+                    at = pos[j] + offset;
+                    if (at >= wf) at -= wf;
+                    if (at < 0.0f) at += wf;
+                }
+                const float t = shapeAt(waveforms ? waveforms[j] : 0u, at);
+                h2[j] = h1[j];
+                h1[j] = t;
+                o[j] = t * level[j];
                 float cur = -0.0f;
                 for (uint32_t k = 0; k < j; ++k)
                     if (modulators[j] >> k & 1u) cur += o[k];

@@ -53,6 +53,9 @@ struct Evolutionary_Strategy_HIP_Arguments
     // ... and its operators' waveforms (type.HIP.voiceWaveforms; sots_set_voice_waveforms): SOTS_WAVE_* per
     // operator, or empty: all sine.  Only with the graph voice: the constructor throws before any device work otherwise.
     std::vector<uint32_t> voiceWaveforms;
+    // ... and their feedback indices (type.HIP.voiceFeedback; sots_set_voice_feedback): one number in [0, 2]
+    // per operator, or empty: none.  Only with the graph voice, as the waveforms.
+    std::vector<float> voiceFeedback;
     bool fusedGenerations = true;     // executeAllGenerations uses the fused kernel loop
     // general.isBenchmarking (parameters.json:7, main.cpp:85).  true: every launch is bracketed by a
     // hipEvent pair and lands in the CSV under the reference's stage names (an event pair costs
@@ -222,6 +225,9 @@ private:
         if (!args_.voiceWaveforms.empty() &&
             sots_batch_set_voice_waveforms(batch_, args_.voiceWaveforms.data(), (uint32_t)args_.voiceWaveforms.size()) != SOTS_OK)
             throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_batch_set_voice_waveforms: ") + sots_batch_last_error(batch_));
+        if (!args_.voiceFeedback.empty() &&
+            sots_batch_set_voice_feedback(batch_, args_.voiceFeedback.data(), (uint32_t)args_.voiceFeedback.size()) != SOTS_OK)
+            throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_batch_set_voice_feedback: ") + sots_batch_last_error(batch_));
     }
     void check(int rc, const char *what) const
     {
@@ -398,6 +404,8 @@ public:
             throw std::runtime_error("Evolutionary_Strategy_HIP: deviceKernelArithmetic is not available with the operator-graph voice");
         if (!graphVoice && !args_.voiceWaveforms.empty())
             throw std::runtime_error("Evolutionary_Strategy_HIP: voiceWaveforms need the operator-graph voice");
+        if (!graphVoice && !args_.voiceFeedback.empty())
+            throw std::runtime_error("Evolutionary_Strategy_HIP: voiceFeedback needs the operator-graph voice");
         cfg_.workgroup_size = args_.workgroupX * args_.workgroupY * args_.workgroupZ;
         cfg_.device = args_.deviceOrdinal;
         cfg_.gid_base = args_.gidBase;
@@ -433,6 +441,8 @@ public:
         targetFFT_.assign(objective.fftHalfSize, 0.0f);
         if (!args_.voiceWaveforms.empty()) // (the graph voice: one device, no group)
             check(sots_set_voice_waveforms(ctx_, args_.voiceWaveforms.data(), (uint32_t)args_.voiceWaveforms.size()), "sots_set_voice_waveforms");
+        if (!args_.voiceFeedback.empty())
+            check(sots_set_voice_feedback(ctx_, args_.voiceFeedback.data(), (uint32_t)args_.voiceFeedback.size()), "sots_set_voice_feedback");
         if (args_.fullSortEveryGeneration)
             for (uint32_t i = 0; i < numIslands(); ++i)
                 check(sots_set_sort_mode(group_ ? sots_group_island(group_, i) : ctx_, SOTS_SORT_FULL), "sots_set_sort_mode");

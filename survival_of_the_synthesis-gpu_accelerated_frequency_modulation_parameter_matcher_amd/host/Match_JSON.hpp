@@ -354,4 +354,28 @@ inline bool readVoiceWaveformsKey(const Json &h, bool graphVoice, uint32_t opera
     return true;
 }
 
+// type.HIP.voiceFeedback (sots_set_voice_feedback, include/sots_hip.h): the graph voice's per-operator
+// feedback indices, one number in [0, 2] per operator, a key of its own beside voiceGraph.  Returns whether the key is there.
+// Throws - before any device work - without type.HIP.synth "graph", on anything but a list of `operators` numbers, and on a
+// number outside [0, 2].
+inline bool readVoiceFeedbackKey(const Json &h, bool graphVoice, uint32_t operators, std::vector<float> &index)
+{
+    if (!h.has("voiceFeedback")) return false;
+    const std::string what = "parameters.json: type.HIP.voiceFeedback";
+    if (!graphVoice) throw std::runtime_error(what + " needs type.HIP.synth \"graph\"");
+    const Json &v = h["voiceFeedback"];
+    if (v.kind != Json::Array || v.arr.size() != operators)
+        throw std::runtime_error(what + " needs one number per operator (" + (v.kind == Json::Array ? std::to_string(v.arr.size()) + " numbers" : std::string("not a list")) +
+                                 ", " + std::to_string(operators) + " operators)");
+    std::vector<float> out;
+    for (const Json &e : v.arr) {
+        if (e.kind != Json::Number) throw std::runtime_error(what + ": an entry that is no number");
+        if (!(e.num >= 0.0 && e.num <= 2.0)) throw std::runtime_error(what + ": " + std::to_string(e.num) + " is outside 0..2");
+        const float b = (float)e.num; // (decided on the double: a number beyond fp32 never reaches the conversion)
+        out.push_back(b == 0.0f ? 0.0f : b);
+    }
+    index = out;
+    return true;
+}
+
 #endif

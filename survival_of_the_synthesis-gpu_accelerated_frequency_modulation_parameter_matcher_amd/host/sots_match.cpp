@@ -1,7 +1,7 @@
 // sots_match.cpp -- command-line driver with the reference's interface (main.cpp:25-305):
 //     sots_match -j parameters.json
 // Reads the reference's parameters.json schema (general / audio / evolutionary / type), with
-// "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "voiceGraph", "voiceWaveforms", "numDevices", "numElites",
+// "type": {"implementation": "HIP", "HIP": {"workgroupSize", "device", "seed", "synth", "voiceGraph", "voiceWaveforms", "voiceFeedback", "numDevices", "numElites",
 // "migrationInterval", "overlapMigration", "devices", "fullSortEveryGeneration", "deviceKernelArithmetic", "chunksInFlight", "chunkQueue",
 // "carryRows", "segmentChunks", "survivors", "objective", "objectiveFloor", "objectiveWeights", "hopSize", "renderMatch", "renderMode", "matchPath", "deviceAnalysis", "matchReport", "returnBestEver", "historyEvery", "historyPath", "targetFitness", "stallGenerations", "stopCheckInterval"}},
 // builds the target from "params" (synthesised) or "audio" (a mono WAV file), matches every
@@ -27,6 +27,9 @@
 //   "voiceWaveforms" with "voiceGraph": one waveform per operator, each of "sine" (the default), "half", "abs", "pulse",
 //                 "even", "absEven", "square", "saw" - shapes cut out of the one sine table (sots_set_voice_waveforms), so
 //                 that an operator emits a harmonic series.  Search, rendering, report and the host's own synthesiser use it.
+//   "voiceFeedback" with "voiceGraph": one feedback index in [0, 2] per operator, 0 (the default) for none: the operator's phase
+//                 is offset by index x W / 2 pi x the mean of its own last two values (sots_set_voice_feedback), so that a
+//                 sine operator emits a harmonic series whose brightness follows the index.  Used wherever the waveforms are.
 //   "matchPath"   a CSV of the parameter track, one row per chunk:
 //                 chunk,start_sample,generations,fitness,u0..u{D-1},p0..p{D-1} - u the unit-range genes (%.9g: the fp32
 //                 bits), p the scaled parameters; with returnBestEver the best-ever individual of each chunk.
@@ -162,6 +165,8 @@ int main(int argc, char *argv[])
             const bool graphVoice = readVoiceGraphKeys(h, args.es_args.pop.numDimensions, args.renderMatch, args.renderMode, args.voiceGraph);
             // ... and its operators' waveforms: "voiceWaveforms", one name per operator (Match_JSON.hpp)
             (void)readVoiceWaveformsKey(h, graphVoice, args.voiceGraph.num_operators, args.voiceWaveforms);
+            // ... and their feedback indices: "voiceFeedback", one number per operator (Match_JSON.hpp)
+            (void)readVoiceFeedbackKey(h, graphVoice, args.voiceGraph.num_operators, args.voiceFeedback);
         }
         const uint32_t D = args.es_args.pop.numDimensions;
         Evolutionary_Strategy_HIP *hipEs = new Evolutionary_Strategy_HIP(args);
@@ -169,7 +174,8 @@ int main(int argc, char *argv[])
         const sots_voice_graph &vg = args.voiceGraph;
         auto synthesise = [&](Objective &obj, const std::vector<float> &p, float *out) {
             if (args.synthKind == SOTS_SYNTH_GRAPH)
-                obj.synthesiseAudioGraph(vg.num_operators, vg.carriers, vg.modulators, args.voiceWaveforms.empty() ? nullptr : args.voiceWaveforms.data(), p, out);
+                obj.synthesiseAudioGraph(vg.num_operators, vg.carriers, vg.modulators, args.voiceWaveforms.empty() ? nullptr : args.voiceWaveforms.data(),
+                                         args.voiceFeedback.empty() ? nullptr : args.voiceFeedback.data(), p, out);
             else if (D == 4) obj.synthesiseAudio(p, out);
             else if (D == 6) obj.synthesiseAudioDoubleSeries(p, out);
             else if (D == 8) obj.synthesiseAudioQuadSeries(p, out);
