@@ -175,7 +175,8 @@ int sots_synchronize(sots_ctx *ctx);
  * reproduced by any graph: their genes mean something else (operator frequencies in genes 1, 3, 5, 7 and a carrier
  * amplitude that is the product of two genes).
  * Not for the voice: SOTS_ARITH_DEVICE_KERNELS (SOTS_ERR_INVALID, as for the 4-op voice) and sots_render_continuous
- * (SOTS_ERR_INVALID: its scans are written per fixed voice).  sots_render_overlap_add and everything else serve it. */
+ * (SOTS_ERR_INVALID: its scans are written per fixed voice; sots_render_graph_continuous, below, is the voice's own
+ * phase-continuous renderer).  sots_render_overlap_add and everything else serve it. */
 typedef struct sots_voice_graph {
     uint32_t struct_size;   /* = sizeof(sots_voice_graph) */
     uint32_t num_operators; /* OPS, 2..8 */
@@ -241,7 +242,8 @@ int sots_get_voice_waveforms(const sots_ctx *ctx, uint32_t codes[8]);
  * the old setting.  A successful call acts like sots_set_voice_waveforms: the run record is cleared, the stored selection
  * splitters and key lists are dropped; population and target stay.  In any order with target, objective, weights and
  * waveforms.  sots_get_voice_feedback writes all eight indices (0 beyond the operators).  Islands have no such setting;
- * sots_render_continuous and device-kernel arithmetic refuse the graph voice as before. */
+ * sots_render_continuous and device-kernel arithmetic refuse the graph voice as before, and sots_render_graph_continuous
+ * refuses a voice with any index != 0. */
 int sots_set_voice_feedback(sots_ctx *ctx, const float *index, uint32_t count);
 int sots_get_voice_feedback(const sots_ctx *ctx, float index[8]);
 
@@ -436,6 +438,47 @@ typedef struct sots_render_continuous_args {
 } sots_render_continuous_args;
 int sots_render_continuous(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
                            const sots_render_continuous_args *args, float *out, uint64_t out_samples);
+
+/* ---- phase-continuous rendering of a parameter track of the operator-graph voice (new) ----
+ * sots_render_continuous for a context of sots_create_graph: the track as ONE graph voice whose oscillators never restart.
+ * Inputs, row position of sample n, HOLD / SOTS_RENDER_GLIDE, fix(), S = (num_rows - 1) hop + N and "+0 at n >= S" are those
+ * of sots_render_continuous; sots_render_continuous_args and its flags are reused.  The graph, its waveform codes w_j and
+ * param_min / param_max are the context's.
+ * Genes at n are scaled as the graph voice scales them: p_g = pmin_g + g_g (pmax_g - pmin_g), no `& 3` folding, D = 2 OPS.
+ *   f_j = p(2j), a_j = p(2j+1); A_j = f_j a_j for a modulator, a_j for a carrier; c = (float)W / 44100.
+ * Operators in ascending j, all fp32 and uncontracted:
+ *   Phi_j(0) = 0.
+ *   t_j(n)   = shape(w_j, Phi_j(n) >> 17), o_j(n) = t_j(n) A_j(n).  shape is the table of sots_set_voice_waveforms, on the
+ *              integer index; the index is always in range, so there is no clamp.  The product is always formed.
+ *   cur_j(n) = f_j for an unmodulated operator, otherwise ((o_i1 + o_i2) + ...) + f_j over the set bits of modulators[j] in
+ *              ascending i: the sum starts from the first term, and a clear bit is skipped, not added as 0.
+ *   Phi_j(n+1) = Phi_j(n) + fix(c cur_j(n)) mod 2^32.  A non-finite or huge cur gives an increment of 0, as fix says.  There
+ *              is no wrap test and no lower-wrap distinction between modulated and unmodulated operators: the word wraps.
+ *   out[n]   = ((o_c1 + o_c2) + ...) over the carriers in ascending j, divided by (float)count, correctly rounded, where
+ *              there is more than one.
+ * Every operator's phase is the exclusive prefix sum of its increments, so the bits do not depend on tiles, grids or passes;
+ * tests/_render_graph_continuous_model.py (NumPy, cumsum in uint32) is exact.
+ * Anchors, both bit for bit: the graph {0->1, carrier 1} is sots_render_continuous of SOTS_SYNTH_2OP, and {0->1, 2->3, 4->5,
+ * carriers 1, 3, 5} with the ranges of genes 0..3 repeated per pair is that of SOTS_SYNTH_TRIPLE_PAR.
+ * Feedback is not rendered: with beta_j != 0, t_j(n) depends on t_j(n-1) and t_j(n-2) through a table lookup, a serial,
+ * non-associative recurrence over the whole rendering that no scan computes.  A context with any beta_j != 0 is refused;
+ * sots_render_overlap_add renders such a voice.
+ *
+ *   renderer                       voices                                  a row's phase          overlapping rows
+ *   sots_render_overlap_add        all five, waveforms, feedback           restarts at 0          window-weighted mean (a comb)
+ *   sots_render_continuous         the four fixed voices                   carried, 15.17 words   one voice
+ *   sots_render_graph_continuous   the graph voice, waveforms, no feedback carried, 15.17 words   one voice
+ *
+ * The work goes in passes of samples_per_pass output samples (0: the library's choice, the most that keeps the phase words
+ * of a pass, one per operator and sample, within 96 MiB: 2^22 samples up to 6 operators, 3 592 192 for 7, 3 145 728 for 8);
+ * a pass starts from the end phases of the pass before it, one word per operator: all the state there is.  Render scratch of
+ * the context's own as above.  Blocking; population, audio, spectrum, fitness, generation counter, run record, splitters and
+ * lists are untouched.
+ * SOTS_ERR_STATE for a context of a fixed voice and for a context with a feedback index != 0 (the text names
+ * sots_set_voice_feedback); SOTS_ERR_INVALID for null or mis-sized args, a hop outside 1 .. N, unknown flag bits,
+ * num_rows == 0, S >= 2^31 or a null out with out_samples > 0; SOTS_ERR_SIZE for values_bytes != num_rows * D * 4. */
+int sots_render_graph_continuous(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
+                                 const sots_render_continuous_args *args, float *out, uint64_t out_samples);
 
 /* ---- per-stage device timing (feeds Benchmarker::addTimer, Benchmarker.hpp:109-130) ---- */
 int sots_timing_enable(sots_ctx *ctx, int enabled);

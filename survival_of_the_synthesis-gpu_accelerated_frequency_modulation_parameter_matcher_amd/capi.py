@@ -74,7 +74,7 @@ EXPORTS = [
     "sots_set_objective_weights", "sots_get_objective_weights", "sots_batch_set_objective_weights",
     "sots_group_set_objective_weights",
     "sots_render_overlap_add", "sots_batch_set_target_audio_hop", "sots_batch_queue_targets_audio_hop",
-    "sots_render_continuous",
+    "sots_render_continuous", "sots_render_graph_continuous",
     "sots_batch_queue_set_carry", "sots_batch_queue_get_carry",
     "sots_batch_set_analysis", "sots_batch_get_analysis", "sots_batch_analyse_audio_hop", "sots_batch_queue_score_audio_hop",
     "sots_create_graph", "sots_batch_create_graph", "sots_get_voice_graph",
@@ -354,6 +354,7 @@ def load():
     L.sots_queue_makespan.argtypes = [C.POINTER(u32), u32, u32, u64p]
     L.sots_render_overlap_add.argtypes = [vp, vp, sz, u32, C.POINTER(RenderArgs), vp, C.c_uint64]
     L.sots_render_continuous.argtypes = [vp, vp, sz, u32, C.POINTER(RenderContinuousArgs), vp, C.c_uint64]
+    L.sots_render_graph_continuous.argtypes = [vp, vp, sz, u32, C.POINTER(RenderContinuousArgs), vp, C.c_uint64]
     L.sots_batch_set_target_audio_hop.argtypes = [vp, vp, u32, u32, u32]
     L.sots_batch_queue_targets_audio_hop.argtypes = [vp, vp, C.c_uint64, u32, u32]
     L.sots_batch_queue_set_carry.argtypes = [vp, u32, u32]
@@ -586,6 +587,18 @@ class HipES:
         out = np.empty(max(n_out, 0), np.float32)
         args = RenderContinuousArgs(C.sizeof(RenderContinuousArgs), hop, RENDER_GLIDE if glide else 0, samples_per_pass)
         self._check(self.L.sots_render_continuous(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
+        return out
+
+    # -- phase-continuous rendering of a parameter track of the operator-graph voice --
+    def render_graph_continuous(self, values, hop, glide=False, samples_per_pass=0, out_samples=None):
+        """render_continuous for a context of the graph voice (graph=...), with its waveforms: values[M][2 x operators].
+        A context with a feedback index other than 0 is refused (render_overlap_add renders it)."""
+        v = _f32(values).reshape(-1, self.D)
+        rows = v.shape[0]
+        n_out = (rows - 1) * hop + self.N if out_samples is None else int(out_samples)
+        out = np.empty(max(n_out, 0), np.float32)
+        args = RenderContinuousArgs(C.sizeof(RenderContinuousArgs), hop, RENDER_GLIDE if glide else 0, samples_per_pass)
+        self._check(self.L.sots_render_graph_continuous(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
         return out
 
     # -- stages --

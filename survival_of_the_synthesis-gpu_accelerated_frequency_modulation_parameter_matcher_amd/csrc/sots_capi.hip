@@ -1202,6 +1202,56 @@ int sots_render_continuous(sots_ctx *ctx, const float *values, size_t values_byt
     return SOTS_OK;
 }
 
+// ---- phase-continuous rendering of the operator-graph voice ---------------------
+int sots_render_graph_continuous(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
+                                 const sots_render_continuous_args *args, float *out, uint64_t out_samples)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    SOTS_REFUSE(ctx, render_graph_continuous_check(ctx->cfg.synth_kind, ctx->feedback, args, ctx->N, ctx->D, values, values_bytes, num_rows, out,
+                                                   out_samples));
+    if (int rc = engine_bind(*ctx)) return rc;
+    const uint32_t N = ctx->N, D = ctx->D, hop = args->hop, ops = ctx->graph.num_operators;
+    const uint64_t covered = (uint64_t)(num_rows - 1u) * hop + N, want = out_samples < covered ? out_samples : covered;
+    // A pass is limited by its phase buffers (graph_continuous_max_pass: a buffer per operator) and by the rows of genes its
+    // samples look at: at most count / hop + 3 of them, kContMaxValueFloats floats.
+    const uint64_t cap = graph_continuous_max_pass(ops), by_rows = (uint64_t)(kContMaxValueFloats / D - 3u) * hop;
+    uint64_t pass = args->samples_per_pass ? args->samples_per_pass : cap;
+    pass = pass > cap ? cap : pass;
+    pass = pass > by_rows ? by_rows : pass;
+    pass = pass > want ? (want ? want : 1u) : pass;
+    const GraphContLayout lay = graph_cont_layout(ops, (uint32_t)pass);
+    const size_t max_rows = (size_t)(pass / hop) + 3u;
+    hipError_t e = render_reserve(ctx->render, max_rows * D, 0, lay.stride);
+    if (e == hipSuccess) e = render_reserve_words(ctx->render, lay.words);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return SOTS_FAIL(ctx, SOTS_ERR_HIP, "sots_render_graph_continuous: scratch allocation failed: %s", hipGetErrorString(e));
+    }
+    // every operator starts at phase 0; a pass leaves its end phases for the next one
+    SOTS_HIP(ctx, hipMemsetAsync(ctx->render.words + lay.carry, 0, 8u * sizeof(uint32_t), ctx->stream));
+    for (uint64_t s0 = 0; s0 < want; s0 += pass) {
+        const uint32_t count = (uint32_t)(want - s0 < pass ? want - s0 : pass);
+        uint32_t k0, k1, r;
+        cont_position((uint32_t)s0, N / 2u, hop, num_rows, k0, r);
+        cont_position((uint32_t)s0 + count - 1u, N / 2u, hop, num_rows, k1, r);
+        k1 = k1 + 1u < num_rows ? k1 + 1u : num_rows - 1u; // (the row after: the second half of a hop, the far end of a glide)
+        SOTS_HIP(ctx, hipMemcpyAsync(ctx->render.values, values + (size_t)k0 * D, (size_t)(k1 - k0 + 1u) * D * sizeof(float),
+                                     hipMemcpyHostToDevice, ctx->stream));
+        GraphContPass ps{};
+        ps.values = ctx->render.values, ps.wavetable = ctx->wavetable, ps.words = ctx->render.words, ps.out = ctx->render.out;
+        ps.lay = lay;
+        ps.row_base = k0, ps.num_rows = num_rows, ps.hop = hop, ps.half_n = N / 2u, ps.glide = args->flags & SOTS_RENDER_GLIDE;
+        ps.n0 = (uint32_t)s0, ps.count = count;
+        ps.sp = ctx->sp;
+        SOTS_HIP(ctx, launch_graph_continuous_pass(ctx->stream, ctx->graph, ctx->waveforms, ps, ctx->num_cus));
+        // (stream order keeps the next pass off the scratch until this copy has read it)
+        SOTS_HIP(ctx, hipMemcpyAsync(out + s0, ctx->render.out, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (out_samples > covered) memset(out + covered, 0, (size_t)(out_samples - covered) * sizeof(float));
+    return SOTS_OK;
+}
+
 // ---- timing ----------------------------------------------------------------------------------
 int sots_timing_enable(sots_ctx *ctx, int enabled)
 {

@@ -1,6 +1,7 @@
 // sots_render.h -- overlap-add resynthesis of a parameter track (sots_render.hip) and its phase-continuous
-// rendering (sots_render_continuous.hip).
-// Internal to libsots_hip.so; the public boundary is sots_render_overlap_add / sots_render_continuous in include/sots_hip.h.
+// rendering (sots_render_continuous.hip), for the operator-graph voice sots_render_graph_continuous.hip (4.16).
+// Internal to libsots_hip.so; the public boundary is sots_render_overlap_add / sots_render_continuous /
+// sots_render_graph_continuous in include/sots_hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -103,5 +104,38 @@ struct ContPass {
 };
 // every stage of one pass; the carries (lay.carry) are the caller's to clear before the first pass
 hipError_t launch_continuous_pass(hipStream_t st, uint32_t kind, const ContPass &pass, uint32_t num_cus);
+
+// ---- phase-continuous rendering of the operator-graph voice (sots_render_graph_continuous.hip) ----
+// Passes, tiles and the three launches are those above, per LEVEL of the graph (graph_levels, sots_rules.h) with the level's
+// operators in grid.y; every operator keeps a phase buffer of its own, a word per sample of the pass, and a last launch
+// mixes the carriers.  Where the words lie, for passes of at most pass_samples samples:
+struct GraphContLayout {
+    uint32_t stride, tiles; // words between the operators' phase buffers (a multiple of 4), tiles of a full pass
+    size_t totals, carry, words; // phase buffer j lies at j * stride; totals: 8 x tiles; carry: 8 words, by position in GraphLevels::ops
+};
+inline GraphContLayout graph_cont_layout(uint32_t ops, uint32_t pass_samples)
+{
+    GraphContLayout l{};
+    l.stride = (pass_samples + 3u) & ~3u;
+    l.tiles = (pass_samples + kContTile - 1u) / kContTile;
+    l.totals = (size_t)ops * l.stride;
+    l.carry = l.totals + (((size_t)8u * l.tiles + 3u) & ~(size_t)3u);
+    l.words = l.carry + 8u;
+    return l;
+}
+struct GraphContPass {
+    const float *values;    // genes of rows row_base ..., 2 x operators floats each: every row a sample of the pass looks at
+    const float *wavetable; // kWavetableSize floats
+    uint32_t *words;        // RenderScratch::words
+    float *out;             // count floats (16-byte aligned)
+    GraphContLayout lay;
+    uint32_t row_base, num_rows, hop, half_n, glide;
+    uint32_t n0, count;
+    SynthParams sp;
+};
+// every level of one pass and the mix; the carries (lay.carry) are the caller's to clear before the first pass.
+// waveforms: the eight codes (sots_set_voice_waveforms).
+hipError_t launch_graph_continuous_pass(hipStream_t st, const sots_voice_graph &graph, const uint32_t waveforms[8], const GraphContPass &pass,
+                                        uint32_t num_cus);
 
 } // namespace sots

@@ -316,7 +316,7 @@ inline Fault analysis_frames_check(const char *who, const void *audio, uint64_t 
 }
 
 // ---- phase-continuous rendering ----
-// its scans are written per fixed voice: the operator-graph voice renders by overlap-add only
+// its scans are written per fixed voice: the operator-graph voice has sots_render_graph_continuous (below)
 inline Fault render_continuous_voice_check(uint32_t kind)
 {
     if (kind == SOTS_SYNTH_GRAPH)
@@ -344,6 +344,84 @@ inline Fault render_continuous_check(const sots_render_continuous_args *args, ui
     if (!out && out_samples) return fault(SOTS_ERR_INVALID, "sots_render_continuous: null output");
     if (synth_arith == SOTS_ARITH_DEVICE_KERNELS)
         return fault(SOTS_ERR_STATE, "sots_render_continuous: not under SOTS_ARITH_DEVICE_KERNELS (that mode is the reference's kernels bit for bit)");
+    return Fault{};
+}
+
+// ---- phase-continuous rendering of the operator-graph voice (sots_render_graph_continuous) ----
+// level(j) = 0 for an unmodulated operator, else 1 + the largest level among its modulators: the operators of one level do
+// not read each other and share three launches.  ops lists the operators by (level, j); level l holds ops[first[l]] ..
+// ops[first[l + 1] - 1].  For a graph that voice_graph_check accepts.
+struct GraphLevels {
+    uint32_t count;                   // levels: 1 (a sum of unmodulated carriers) .. num_operators (a chain)
+    uint32_t level_of[kGraphMaxOps];  // by operator
+    uint32_t ops[kGraphMaxOps];       // operators, by (level, j)
+    uint32_t first[kGraphMaxOps + 1]; // by level, into ops; first[count] = num_operators
+};
+inline GraphLevels graph_levels(const sots_voice_graph &g)
+{
+    GraphLevels l{};
+    const uint32_t ops = g.num_operators < kGraphMaxOps ? g.num_operators : kGraphMaxOps;
+    for (uint32_t j = 0; j < ops; ++j) {
+        uint32_t lv = 0;
+        for (uint32_t i = 0; i < j; ++i)
+            if ((g.modulators[j] >> i & 1u) && l.level_of[i] + 1u > lv) lv = l.level_of[i] + 1u;
+        l.level_of[j] = lv;
+        if (lv + 1u > l.count) l.count = lv + 1u;
+    }
+    uint32_t filled = 0;
+    for (uint32_t lv = 0; lv < l.count; ++lv) {
+        l.first[lv] = filled;
+        for (uint32_t j = 0; j < ops; ++j)
+            if (l.level_of[j] == lv) l.ops[filled++] = j;
+    }
+    l.first[l.count] = filled;
+    return l;
+}
+// whether reading operator i's output needs the wavetable: SQUARE and SAW are functions of the index alone
+inline bool waveform_reads_table(uint32_t code) { return code != SOTS_WAVE_SQUARE && code != SOTS_WAVE_SAW; }
+// whether the launches of level `level` read the table: some operator of the level has a modulator whose shape does
+inline bool graph_level_reads_table(const sots_voice_graph &g, const GraphLevels &l, const uint32_t codes[8], uint32_t level)
+{
+    for (uint32_t s = l.first[level]; s < l.first[level + 1u]; ++s)
+        for (uint32_t i = 0; i < l.ops[s]; ++i)
+            if ((g.modulators[l.ops[s]] >> i & 1u) && waveform_reads_table(codes[i])) return true;
+    return false;
+}
+// Samples of a pass: every operator keeps one phase word per sample, and the phase words of a pass stay within the 96 MiB
+// that the fixed voices' renderer needs at the most (6 buffers of 2^22 words); whole tiles of 4096, at most 2^22 samples.
+inline uint32_t graph_continuous_max_pass(uint32_t ops)
+{
+    const uint64_t words = (96ull << 20) / sizeof(uint32_t) / (ops ? ops : 1u);
+    const uint64_t whole = words / 4096u * 4096u;
+    return whole < (1u << 22) ? (uint32_t)whole : 1u << 22;
+}
+// sots_render_graph_continuous: what it refuses before anything touches the device.  kind, feedback: the context's voice and
+// its feedback indices; n, d: its audio length and genes per row.
+inline Fault render_graph_continuous_check(uint32_t kind, const float feedback[8], const sots_render_continuous_args *args, uint32_t n, uint32_t d,
+                                           const void *values, size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples)
+{
+    if (kind != SOTS_SYNTH_GRAPH)
+        return fault(SOTS_ERR_STATE, "sots_render_graph_continuous: the handle runs a fixed voice (synth_kind %u; sots_render_continuous renders it)", kind);
+    for (uint32_t j = 0; j < kGraphMaxOps; ++j)
+        if (feedback[j] != 0.0f)
+            return fault(SOTS_ERR_STATE,
+                         "sots_render_graph_continuous: operator %u has feedback index %g (sots_set_voice_feedback): a feedback operator's phase "
+                         "offset is a serial recurrence that no scan computes; sots_render_overlap_add renders such a voice",
+                         j, (double)feedback[j]);
+    if (!args || args->struct_size != sizeof(sots_render_continuous_args))
+        return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: null args or sots_render_continuous_args.struct_size != %zu",
+                     sizeof(sots_render_continuous_args));
+    if (args->hop < 1u || args->hop > n) return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: hop %u outside 1..%u", args->hop, n);
+    if (args->flags & ~(uint32_t)SOTS_RENDER_GLIDE) return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: unknown flags 0x%x", args->flags);
+    if (num_rows == 0) return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: num_rows must be at least 1");
+    const uint64_t covered = (uint64_t)(num_rows - 1u) * args->hop + n;
+    if (covered >= (1ull << 31))
+        return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: %u rows at hop %u are %llu samples, 2^31 or more", num_rows, args->hop,
+                     (unsigned long long)covered);
+    if (!values || values_bytes != (size_t)num_rows * d * sizeof(float))
+        return fault(SOTS_ERR_SIZE, "sots_render_graph_continuous: %u rows need %zu bytes of values, got %zu", num_rows,
+                     (size_t)num_rows * d * sizeof(float), values_bytes);
+    if (!out && out_samples) return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: null output");
     return Fault{};
 }
 

@@ -46,7 +46,7 @@ struct Evolutionary_Strategy_HIP_Arguments
     int32_t synthKind = -1;           // -1: derive from numDimensions (4, 6, 8, 12)
     // The operator-graph voice (type.HIP.synth "graph" with type.HIP.voiceGraph; sots_create_graph): with
     // synthKind SOTS_SYNTH_GRAPH the topology, numDimensions = 2 x num_operators.  One device; matchPath, renderMatch
-    // (overlap-add), matchReport, chunksInFlight and chunkQueue work with it; renderMode 1 and 2 with renderMatch and
+    // (overlap-add, or renderMode 3 and 4), matchReport, chunksInFlight and chunkQueue work with it; renderMode 1 and 2 with renderMatch and
     // deviceKernelArithmetic do not: the constructor throws - before any device work - and a malformed graph is refused there
     // with the library's own text.
     sots_voice_graph voiceGraph{};
@@ -155,7 +155,8 @@ struct Evolutionary_Strategy_HIP_Arguments
     //   renderMode  : which renderer renderMatch() uses: 0 = overlap-add (the default), 1 = phase-continuous
     //                 (sots_render_continuous: one voice whose oscillators never restart, parameters held from chunk centre to
     //                 chunk centre), 2 = phase-continuous with the parameters interpolated between the centres.  Takes effect
-    //                 only with renderMatch; 1 and 2 are not available with deviceKernelArithmetic.
+    //                 only with renderMatch; 1 and 2 are not available with deviceKernelArithmetic.  3 and 4 are 1 and 2 for the
+    //                 operator-graph voice (sots_render_graph_continuous) and need it.
     //   matchPath   : sots_match writes the parameter track there, one CSV row per chunk (Match_track.hpp)
     uint32_t hopSize = 0;
     bool renderMatch = false;
@@ -340,7 +341,8 @@ public:
     // match stands for samples [i hop, i hop + N); where chunks overlap (hop < N) they are cross-faded with the analysis
     // window and normalised by its sum, at hop = N they follow each other as they are.  (numChunks - 1) hop + N samples.
     // With renderMode 1 or 2 the same track goes through sots_render_continuous instead: the same length, one voice from the
-    // first sample to the last, chunk i's parameters reached at its centre i hop + N/2.
+    // first sample to the last, chunk i's parameters reached at its centre i hop + N/2.  With 3 or 4 (the operator-graph
+    // voice) through sots_render_graph_continuous, which is the same for a voice graph.
     void renderMatch(std::vector<float> &out)
     {
         const uint32_t d = population.numDimensions, chunks = (uint32_t)bestPerChunk_.size();
@@ -352,8 +354,9 @@ public:
             sots_render_continuous_args ca{};
             ca.struct_size = sizeof ca;
             ca.hop = hop_;
-            ca.flags = args_.renderMode == 2u ? (uint32_t)SOTS_RENDER_GLIDE : 0u;
-            check(sots_render_continuous(ctx_, values.data(), values.size() * sizeof(float), chunks, &ca, out.data(), out.size()), "renderMatch");
+            ca.flags = args_.renderMode == 2u || args_.renderMode == 4u ? (uint32_t)SOTS_RENDER_GLIDE : 0u;
+            const auto render = args_.renderMode >= 3u ? sots_render_graph_continuous : sots_render_continuous;
+            check(render(ctx_, values.data(), values.size() * sizeof(float), chunks, &ca, out.data(), out.size()), "renderMatch");
             return;
         }
         sots_render_args ra{};
@@ -398,10 +401,12 @@ public:
         if (kind < 0) throw std::runtime_error("Evolutionary_Strategy_HIP: numDimensions must be 4, 6, 8 or 12");
         cfg_.synth_kind = (uint32_t)kind;
         const bool graphVoice = kind == SOTS_SYNTH_GRAPH;
-        if (graphVoice && args_.renderMatch && args_.renderMode != 0u)
+        if (graphVoice && args_.renderMatch && (args_.renderMode == 1u || args_.renderMode == 2u))
             throw std::runtime_error("Evolutionary_Strategy_HIP: renderMode 1 and 2 (sots_render_continuous) are not available with the operator-graph voice");
         if (graphVoice && args_.deviceKernelArithmetic)
             throw std::runtime_error("Evolutionary_Strategy_HIP: deviceKernelArithmetic is not available with the operator-graph voice");
+        if (!graphVoice && args_.renderMode >= 3u)
+            throw std::runtime_error("Evolutionary_Strategy_HIP: renderMode 3 and 4 (sots_render_graph_continuous) need the operator-graph voice");
         if (!graphVoice && !args_.voiceWaveforms.empty())
             throw std::runtime_error("Evolutionary_Strategy_HIP: voiceWaveforms need the operator-graph voice");
         if (!graphVoice && !args_.voiceFeedback.empty())

@@ -201,17 +201,34 @@ inline bool readHopSizeKey(const Json &h, uint32_t audioLength, uint32_t &hopSiz
 // type.HIP.renderMode: which renderer renderMatch uses.  "overlapAdd" (0, the default: sots_render_overlap_add, every chunk's
 // match from phase 0, cross-faded), "continuous" (1: sots_render_continuous, one voice whose oscillators never restart, the
 // parameters held from chunk centre to chunk centre) or "continuousGlide" (2: the same with the parameters interpolated
-// between the centres).  Returns whether the key was there; throws - before any device work - on anything else.
+// between the centres); for the operator-graph voice "graphContinuous" (3) and "graphContinuousGlide" (4): the same two
+// through sots_render_graph_continuous.  Returns whether the key was there; throws - before any device
+// work - on anything else.
 inline bool readRenderModeKey(const Json &h, uint32_t &renderMode)
 {
     if (!h.has("renderMode")) return false;
     const Json &v = h["renderMode"];
-    const char *names[] = {"overlapAdd", "continuous", "continuousGlide"};
+    const char *names[] = {"overlapAdd", "continuous", "continuousGlide", "graphContinuous", "graphContinuousGlide"};
     if (v.kind == Json::String)
-        for (uint32_t m = 0; m < 3; ++m)
+        for (uint32_t m = 0; m < 5; ++m)
             if (v.str == names[m]) return renderMode = m, true;
-    throw std::runtime_error("parameters.json: type.HIP.renderMode must be \"overlapAdd\", \"continuous\" or \"continuousGlide\"" +
+    throw std::runtime_error("parameters.json: type.HIP.renderMode must be \"overlapAdd\", \"continuous\" or \"continuousGlide\" (with type.HIP.synth "
+                             "\"graph\": \"overlapAdd\", \"graphContinuous\" or \"graphContinuousGlide\")" +
                              (v.kind == Json::String ? ", not \"" + v.str + "\"" : std::string()));
+}
+// renderMode "graphContinuous" / "graphContinuousGlide" belong to the operator-graph voice, and to one without feedback
+// (sots_render_graph_continuous refuses a feedback index other than 0: no scan computes that recurrence).  Throws - before
+// any device work - otherwise; the feedback is looked at only where the match is rendered.
+inline void checkGraphRenderMode(uint32_t renderMode, bool graphVoice, bool renderMatch, const std::vector<float> &voiceFeedback)
+{
+    if (renderMode != 3u && renderMode != 4u) return;
+    if (!graphVoice)
+        throw std::runtime_error("parameters.json: type.HIP.renderMode \"graphContinuous\" and \"graphContinuousGlide\" need type.HIP.synth \"graph\"");
+    if (!renderMatch) return;
+    for (float b : voiceFeedback)
+        if (b != 0.0f)
+            throw std::runtime_error("parameters.json: type.HIP.renderMode \"graphContinuous\" and \"graphContinuousGlide\" are not available with "
+                                     "type.HIP.voiceFeedback other than 0 (\"overlapAdd\" renders such a voice)");
 }
 
 // type.HIP.carryRows / type.HIP.segmentChunks (sots_batch_queue_set_carry): inside a segment of
@@ -282,8 +299,8 @@ inline bool readAnalysisKeys(const Json &h, uint64_t populationLength, bool &dev
 // voice, e.g. {"operators": 3, "modulators": [[], [0], [1]], "carriers": [2]} - modulators[j] lists the operators that
 // modulate operator j, carriers the operators that are heard.  Returns whether the voice is the graph; throws - like the keys
 // above, before any device work - where one key comes without the other, on a shape that is not the one above, on
-// numDimensions other than 2 x operators, and on renderMode "continuous" / "continuousGlide" with renderMatch (the
-// phase-continuous renderer is written per fixed voice).  Whether the topology is a valid one is the library's rule
+// numDimensions other than 2 x operators, and on renderMode "continuous" / "continuousGlide" with renderMatch (that
+// phase-continuous renderer is written per fixed voice; "graphContinuous" / "graphContinuousGlide" are the graph voice's).  Whether the topology is a valid one is the library's rule
 // (csrc/sots_rules.h), which sots_create_graph applies before it touches a device.
 inline bool readVoiceGraphKeys(const Json &h, uint32_t numDimensions, bool renderMatch, uint32_t renderMode, sots_voice_graph &graph)
 {
@@ -321,7 +338,7 @@ inline bool readVoiceGraphKeys(const Json &h, uint32_t numDimensions, bool rende
     if (numDimensions != 2u * g.num_operators)
         throw std::runtime_error("parameters.json: evolutionary.numDimensions " + std::to_string(numDimensions) + " must be 2 x type.HIP.voiceGraph.operators = " +
                                  std::to_string(2u * g.num_operators));
-    if (renderMatch && renderMode != 0u)
+    if (renderMatch && (renderMode == 1u || renderMode == 2u))
         throw std::runtime_error("parameters.json: type.HIP.renderMode \"continuous\" and \"continuousGlide\" are not available with type.HIP.synth \"graph\"");
     graph = g;
     return true;

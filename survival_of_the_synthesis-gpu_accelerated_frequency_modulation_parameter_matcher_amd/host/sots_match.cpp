@@ -18,12 +18,15 @@
 //                 as ONE voice whose oscillators never restart (sots_render_continuous): no phase jumps between chunks and
 //                 no comb filter where they overlap; chunk i's parameters hold around its centre i hopSize + N/2 - or
 //                 "continuousGlide", the same with the parameters interpolated from centre to centre.  Same length.
-//                 Ignored without "renderMatch"; not available with "deviceKernelArithmetic".
+//                 Ignored without "renderMatch"; not available with "deviceKernelArithmetic".  With "synth": "graph" the two
+//                 are "graphContinuous" and "graphContinuousGlide" (sots_render_graph_continuous): the same rendering for
+//                 any voice graph and its waveforms, not with a "voiceFeedback" other than 0; refused with any other synth.
 //   "voiceGraph"  with "synth": "graph", the operator-graph voice (sots_create_graph): {"operators": n, "modulators":
 //                 [[...], ...], "carriers": [...]} - modulators[j] lists the operators that modulate operator j (each
 //                 below j), carriers the operators that are heard; gene 2j is operator j's frequency, gene 2j+1 its level,
 //                 so evolutionary.numDimensions is 2 n and paramMins / paramMaxs hold 2 n entries.  One device; not with
-//                 "continuous" / "continuousGlide" rendering or "deviceKernelArithmetic".
+//                 "continuous" / "continuousGlide" rendering (its own: "graphContinuous" / "graphContinuousGlide") or
+//                 "deviceKernelArithmetic".
 //   "voiceWaveforms" with "voiceGraph": one waveform per operator, each of "sine" (the default), "half", "abs", "pulse",
 //                 "even", "absEven", "square", "saw" - shapes cut out of the one sine table (sots_set_voice_waveforms), so
 //                 that an operator emits a harmonic series.  Search, rendering, report and the host's own synthesiser use it.
@@ -140,7 +143,7 @@ int main(int argc, char *argv[])
             (void)readHopSizeKey(h, 1u << audioLengthLog2, args.hopSize);
             if (h.has("renderMatch")) args.renderMatch = h["renderMatch"].b;
             (void)readRenderModeKey(h, args.renderMode);
-            if (args.renderMatch && args.renderMode != 0u && h.has("deviceKernelArithmetic") && h["deviceKernelArithmetic"].b)
+            if (args.renderMatch && (args.renderMode == 1u || args.renderMode == 2u) && h.has("deviceKernelArithmetic") && h["deviceKernelArithmetic"].b)
                 throw std::runtime_error("parameters.json: type.HIP.renderMode \"continuous\" and \"continuousGlide\" are not available with deviceKernelArithmetic");
             if (h.has("matchPath")) args.matchPath = h["matchPath"].str;
             // the targets analysed on the device, and the report that scores the rendered match against them (Match_JSON.hpp)
@@ -167,6 +170,8 @@ int main(int argc, char *argv[])
             (void)readVoiceWaveformsKey(h, graphVoice, args.voiceGraph.num_operators, args.voiceWaveforms);
             // ... and their feedback indices: "voiceFeedback", one number per operator (Match_JSON.hpp)
             (void)readVoiceFeedbackKey(h, graphVoice, args.voiceGraph.num_operators, args.voiceFeedback);
+            // "graphContinuous" / "graphContinuousGlide" rendering: the graph voice's, without feedback (Match_JSON.hpp)
+            checkGraphRenderMode(args.renderMode, graphVoice, args.renderMatch, args.voiceFeedback);
         }
         const uint32_t D = args.es_args.pop.numDimensions;
         Evolutionary_Strategy_HIP *hipEs = new Evolutionary_Strategy_HIP(args);
