@@ -243,7 +243,7 @@ int sots_get_voice_waveforms(const sots_ctx *ctx, uint32_t codes[8]);
  * splitters and key lists are dropped; population and target stay.  In any order with target, objective, weights and
  * waveforms.  sots_get_voice_feedback writes all eight indices (0 beyond the operators).  Islands have no such setting;
  * sots_render_continuous and device-kernel arithmetic refuse the graph voice as before, and sots_render_graph_continuous
- * refuses a voice with any index != 0. */
+ * refuses a voice with any index != 0; sots_render_graph_feedback renders such a voice phase-continuously. */
 int sots_set_voice_feedback(sots_ctx *ctx, const float *index, uint32_t count);
 int sots_get_voice_feedback(const sots_ctx *ctx, float index[8]);
 
@@ -468,6 +468,7 @@ int sots_render_continuous(sots_ctx *ctx, const float *values, size_t values_byt
  *   sots_render_overlap_add        all five, waveforms, feedback           restarts at 0          window-weighted mean (a comb)
  *   sots_render_continuous         the four fixed voices                   carried, 15.17 words   one voice
  *   sots_render_graph_continuous   the graph voice, waveforms, no feedback carried, 15.17 words   one voice
+ *   sots_render_graph_feedback     the graph voice, waveforms, feedback    carried, words + h1 h2 one voice
  *
  * The work goes in passes of samples_per_pass output samples (0: the library's choice, the most that keeps the phase words
  * of a pass, one per operator and sample, within 96 MiB: 2^22 samples up to 6 operators, 3 592 192 for 7, 3 145 728 for 8);
@@ -479,6 +480,52 @@ int sots_render_continuous(sots_ctx *ctx, const float *values, size_t values_byt
  * num_rows == 0, S >= 2^31 or a null out with out_samples > 0; SOTS_ERR_SIZE for values_bytes != num_rows * D * 4. */
 int sots_render_graph_continuous(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
                                  const sots_render_continuous_args *args, float *out, uint64_t out_samples);
+
+/* ---- ... with feedback operators (new) ----
+ * sots_render_graph_continuous for a context whose operators may have a feedback index beta_j (sots_set_voice_feedback).
+ * Everything of sots_render_graph_continuous holds unchanged: inputs, row position, HOLD / SOTS_RENDER_GLIDE, fix(),
+ * S = (num_rows - 1) hop + N and +0 at n >= S, gene scaling, A_j, c, cur_j, Phi_j(n+1) = Phi_j(n) + fix(c cur_j(n)) mod 2^32,
+ * the carrier sum and its division.  Feedback never changes Phi_j: every phase is still the exclusive prefix sum of its
+ * increments.  What differs is t_j(n) of an operator with beta_j != 0.
+ *   beta_j == 0:  t_j(n) = shape(w_j, Phi_j(n) >> 17), as above.
+ *   beta_j != 0:  h1_j = h2_j = +0 at sample 0 of the rendering, and per sample, all fp32 and uncontracted:
+ *       K   = 0x1.45f306p+12f            (the constant of sots_set_voice_feedback)
+ *       B_j = beta_j * K                 (one product)
+ *       g   = (h1_j + h2_j) * 0.5f
+ *       z   = Phi_j(n) + fix(B_j * g)  mod 2^32     (the word wraps: no wrap tests, no clamp)
+ *       t_j(n) = shape(w_j, z >> 17);  o_j(n) = t_j(n) * A_j(n)
+ *       h2_j = h1_j;  h1_j = t_j(n)
+ *     h is the shaped value before the level, so |h| <= 1 and |B_j g| <= 2 K < W: the offset is always finite and fix never
+ *     takes its zero branch.  A modulator's o_i(n), as the operators it modulates and the mix read it, is made from t_i(n).
+ * With every beta zero the call is sots_render_graph_continuous bit for bit (the same launches).  For one row the output is
+ * that row's voice, close to but not bit for bit sots_stage_synthesise's, as above.
+ * t_j(n) depends on t_j(n-1) and t_j(n-2) through a table lookup: a chain over the samples that no scan computes.  The chain
+ * has exactly one solution, since the carry into it is given and every sample is a function of the two before it; however
+ * it is computed (chain_form), the output is that solution, and the bits do not depend on chain_form, relax_cap, tiles,
+ * grids or passes.  tests/_render_graph_feedback_model.py states it twice in NumPy, as a loop and as a relaxation.
+ *   chain_form 1  serial: one wavefront per feedback operator walks the samples in order.
+ *   chain_form 2  relaxation: per tile of 1024 samples, start from the feed-forward values and recompute every sample from
+ *                 its two predecessors in the previous sweep, all samples at once, until a sweep changes no bit (sweep k makes
+ *                 at least the first k samples final); after relax_cap sweeps the tile is finished serially from sample
+ *                 relax_cap on.
+ *   chain_form 0  the library's choice per operator, a rule on beta_j (csrc/sots_rules.h): the relaxation for beta_j <= 1.5,
+ *                 where it was measured to be faster, the serial form above; relax_cap 0 is 1024.
+ * Passes as above; with FB feedback operators a pass holds at most floor(96 MiB / (4 (OPS + FB)) / 4096) tiles of 4096
+ * samples, and at most 1024 tiles; a pass starts from the end phases of the pass before it and from h1_j, h2_j of every
+ * feedback operator.  Blocking; everything else of the context is untouched.
+ * SOTS_ERR_STATE for a context of a fixed voice; SOTS_ERR_INVALID for null or mis-sized args, a hop outside 1 .. N, unknown
+ * flag bits, chain_form > 2, relax_cap > 4096, num_rows == 0, S >= 2^31 or a null out with out_samples > 0; SOTS_ERR_SIZE for
+ * values_bytes != num_rows * D * 4. */
+typedef struct sots_render_graph_feedback_args {
+    uint32_t struct_size;      /* = sizeof(sots_render_graph_feedback_args) */
+    uint32_t hop;              /* as sots_render_continuous_args */
+    uint32_t flags;            /* enum sots_render_continuous_flags */
+    uint32_t samples_per_pass; /* 0 = the library's choice; else output samples per pass, >= 1 */
+    uint32_t chain_form;       /* 0 = the library's choice, 1 = serial, 2 = relaxation */
+    uint32_t relax_cap;        /* sweeps per tile before a tile is finished serially; 0 = the library's choice, else 1..4096 */
+} sots_render_graph_feedback_args;
+int sots_render_graph_feedback(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
+                               const sots_render_graph_feedback_args *args, float *out, uint64_t out_samples);
 
 /* ---- per-stage device timing (feeds Benchmarker::addTimer, Benchmarker.hpp:109-130) ---- */
 int sots_timing_enable(sots_ctx *ctx, int enabled);

@@ -74,7 +74,7 @@ EXPORTS = [
     "sots_set_objective_weights", "sots_get_objective_weights", "sots_batch_set_objective_weights",
     "sots_group_set_objective_weights",
     "sots_render_overlap_add", "sots_batch_set_target_audio_hop", "sots_batch_queue_targets_audio_hop",
-    "sots_render_continuous", "sots_render_graph_continuous",
+    "sots_render_continuous", "sots_render_graph_continuous", "sots_render_graph_feedback",
     "sots_batch_queue_set_carry", "sots_batch_queue_get_carry",
     "sots_batch_set_analysis", "sots_batch_get_analysis", "sots_batch_analyse_audio_hop", "sots_batch_queue_score_audio_hop",
     "sots_create_graph", "sots_batch_create_graph", "sots_get_voice_graph",
@@ -85,6 +85,7 @@ ANALYSIS_HOST, ANALYSIS_DEVICE = 0, 1  # enum sots_analysis
 QUEUE_NO_CHUNK = 0xFFFFFFFF
 RENDER_WINDOWED = 1
 RENDER_GLIDE = 1
+CHAIN_LIBRARY, CHAIN_SERIAL, CHAIN_RELAX = 0, 1, 2  # sots_render_graph_feedback_args.chain_form
 TRACK_BEST_EVER, TRACK_HISTORY = 1, 2
 BATCH_MAX_POPULATION = 1024
 GROUP_OVERLAP, GROUP_FORCE_RCCL, GROUP_UNFUSED, GROUP_EVENT_WAITS = 1, 2, 4, 8
@@ -223,6 +224,12 @@ class RenderContinuousArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("hop", C.c_uint32), ("flags", C.c_uint32), ("samples_per_pass", C.c_uint32)]
 
 
+class RenderGraphFeedbackArgs(C.Structure):
+    """sots_render_graph_feedback_args"""
+    _fields_ = [("struct_size", C.c_uint32), ("hop", C.c_uint32), ("flags", C.c_uint32), ("samples_per_pass", C.c_uint32),
+                ("chain_form", C.c_uint32), ("relax_cap", C.c_uint32)]
+
+
 class QueueStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("slots", C.c_uint32), ("global_generations", C.c_uint64),
                 ("chunk_generations", C.c_uint64)]
@@ -355,6 +362,7 @@ def load():
     L.sots_render_overlap_add.argtypes = [vp, vp, sz, u32, C.POINTER(RenderArgs), vp, C.c_uint64]
     L.sots_render_continuous.argtypes = [vp, vp, sz, u32, C.POINTER(RenderContinuousArgs), vp, C.c_uint64]
     L.sots_render_graph_continuous.argtypes = [vp, vp, sz, u32, C.POINTER(RenderContinuousArgs), vp, C.c_uint64]
+    L.sots_render_graph_feedback.argtypes = [vp, vp, sz, u32, C.POINTER(RenderGraphFeedbackArgs), vp, C.c_uint64]
     L.sots_batch_set_target_audio_hop.argtypes = [vp, vp, u32, u32, u32]
     L.sots_batch_queue_targets_audio_hop.argtypes = [vp, vp, C.c_uint64, u32, u32]
     L.sots_batch_queue_set_carry.argtypes = [vp, u32, u32]
@@ -599,6 +607,19 @@ class HipES:
         out = np.empty(max(n_out, 0), np.float32)
         args = RenderContinuousArgs(C.sizeof(RenderContinuousArgs), hop, RENDER_GLIDE if glide else 0, samples_per_pass)
         self._check(self.L.sots_render_graph_continuous(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
+        return out
+
+    # -- ... with feedback operators --
+    def render_graph_feedback(self, values, hop, glide=False, samples_per_pass=0, chain_form=0, relax_cap=0, out_samples=None):
+        """render_graph_continuous for a context whose operators may have feedback indices (set_voice_feedback).
+        chain_form: CHAIN_LIBRARY, CHAIN_SERIAL or CHAIN_RELAX; relax_cap: sweeps per tile before a tile is finished serially
+        (0: the library's choice).  Neither changes a bit of the result."""
+        v = _f32(values).reshape(-1, self.D)
+        rows = v.shape[0]
+        n_out = (rows - 1) * hop + self.N if out_samples is None else int(out_samples)
+        out = np.empty(max(n_out, 0), np.float32)
+        args = RenderGraphFeedbackArgs(C.sizeof(RenderGraphFeedbackArgs), hop, RENDER_GLIDE if glide else 0, samples_per_pass, chain_form, relax_cap)
+        self._check(self.L.sots_render_graph_feedback(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
         return out
 
     # -- stages --

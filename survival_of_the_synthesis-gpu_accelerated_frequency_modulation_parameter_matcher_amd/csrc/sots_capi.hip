@@ -1252,6 +1252,68 @@ int sots_render_graph_continuous(sots_ctx *ctx, const float *values, size_t valu
     return SOTS_OK;
 }
 
+// ---- ... with feedback operators -------------------------------------------------
+int sots_render_graph_feedback(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
+                               const sots_render_graph_feedback_args *args, float *out, uint64_t out_samples)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    SOTS_REFUSE(ctx, render_graph_feedback_check(ctx->cfg.synth_kind, args, ctx->N, ctx->D, values, values_bytes, num_rows, out, out_samples));
+    if (int rc = engine_bind(*ctx)) return rc;
+    const uint32_t N = ctx->N, D = ctx->D, hop = args->hop, ops = ctx->graph.num_operators;
+    const uint64_t covered = (uint64_t)(num_rows - 1u) * hop + N, want = out_samples < covered ? out_samples : covered;
+    // the flagged operators, their B_j and the form of each one's chain; none flagged: sots_render_graph_continuous's launches
+    GraphFbPass fb{};
+    scale_feedback(ctx->feedback, ops, fb.scaled);
+    for (uint32_t j = 0; j < ops; ++j) {
+        if (ctx->feedback[j] == 0.0f) continue;
+        fb.fb_mask |= 1u << j;
+        const uint32_t form = args->chain_form ? args->chain_form : graph_feedback_form(ctx->feedback[j]);
+        if (form == kChainRelax) fb.forms |= 1u << j;
+    }
+    fb.relax_cap = args->relax_cap ? args->relax_cap : kRelaxCapLibrary;
+    const uint32_t flagged = (uint32_t)__builtin_popcount(fb.fb_mask);
+    // A pass is limited by its phase and t buffers (graph_feedback_max_pass) and by the rows of genes its samples look at: at
+    // most count / hop + 3 of them, kContMaxValueFloats floats.
+    const uint64_t cap = graph_feedback_max_pass(ops, flagged), by_rows = (uint64_t)(kContMaxValueFloats / D - 3u) * hop;
+    uint64_t pass = args->samples_per_pass ? args->samples_per_pass : cap;
+    pass = pass > cap ? cap : pass;
+    pass = pass > by_rows ? by_rows : pass;
+    pass = pass > want ? (want ? want : 1u) : pass;
+    const GraphFbLayout lay = graph_fb_layout(ops, flagged, (uint32_t)pass);
+    const size_t max_rows = (size_t)(pass / hop) + 3u;
+    hipError_t e = render_reserve(ctx->render, max_rows * D, 0, lay.g.stride);
+    if (e == hipSuccess) e = render_reserve_words(ctx->render, lay.words);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return SOTS_FAIL(ctx, SOTS_ERR_HIP, "sots_render_graph_feedback: scratch allocation failed: %s", hipGetErrorString(e));
+    }
+    // every operator starts at phase 0 with h1 = h2 = +0; a pass leaves its end phases and h for the next one
+    SOTS_HIP(ctx, hipMemsetAsync(ctx->render.words + lay.g.carry, 0, 8u * sizeof(uint32_t), ctx->stream));
+    SOTS_HIP(ctx, hipMemsetAsync(ctx->render.words + lay.hist, 0, 16u * sizeof(uint32_t), ctx->stream));
+    for (uint64_t s0 = 0; s0 < want; s0 += pass) {
+        const uint32_t count = (uint32_t)(want - s0 < pass ? want - s0 : pass);
+        uint32_t k0, k1, r;
+        cont_position((uint32_t)s0, N / 2u, hop, num_rows, k0, r);
+        cont_position((uint32_t)s0 + count - 1u, N / 2u, hop, num_rows, k1, r);
+        k1 = k1 + 1u < num_rows ? k1 + 1u : num_rows - 1u; // (the row after: the second half of a hop, the far end of a glide)
+        SOTS_HIP(ctx, hipMemcpyAsync(ctx->render.values, values + (size_t)k0 * D, (size_t)(k1 - k0 + 1u) * D * sizeof(float),
+                                     hipMemcpyHostToDevice, ctx->stream));
+        GraphContPass &ps = fb.g;
+        ps.values = ctx->render.values, ps.wavetable = ctx->wavetable, ps.words = ctx->render.words, ps.out = ctx->render.out;
+        ps.lay = lay.g;
+        ps.row_base = k0, ps.num_rows = num_rows, ps.hop = hop, ps.half_n = N / 2u, ps.glide = args->flags & SOTS_RENDER_GLIDE;
+        ps.n0 = (uint32_t)s0, ps.count = count;
+        ps.sp = ctx->sp;
+        fb.tbuf = lay.tbuf, fb.hist = lay.hist;
+        SOTS_HIP(ctx, launch_graph_feedback_pass(ctx->stream, ctx->graph, ctx->waveforms, fb, ctx->num_cus));
+        // (stream order keeps the next pass off the scratch until this copy has read it)
+        SOTS_HIP(ctx, hipMemcpyAsync(out + s0, ctx->render.out, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (out_samples > covered) memset(out + covered, 0, (size_t)(out_samples - covered) * sizeof(float));
+    return SOTS_OK;
+}
+
 // ---- timing ----------------------------------------------------------------------------------
 int sots_timing_enable(sots_ctx *ctx, int enabled)
 {

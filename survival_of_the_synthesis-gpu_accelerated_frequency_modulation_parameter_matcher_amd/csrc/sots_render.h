@@ -138,4 +138,34 @@ struct GraphContPass {
 hipError_t launch_graph_continuous_pass(hipStream_t st, const sots_voice_graph &graph, const uint32_t waveforms[8], const GraphContPass &pass,
                                         uint32_t num_cus);
 
+// ---- ... with feedback operators (sots_render_graph_feedback.hip) ----
+// Everything above stands: feedback never touches a phase.  An operator with beta != 0 ("flagged", a bit of fb_mask) has in
+// addition a buffer of its shaped values t_j, a float per sample of the pass, that one chain launch per level fills after
+// the level's apply and that later levels and the mix read in place of its phase words; and two floats of state, h1 and h2,
+// that a pass leaves for the next.  The words of GraphContLayout come first and are laid out as above; behind them:
+struct GraphFbLayout {
+    GraphContLayout g;
+    size_t tbuf, hist, words; // t buffer of the s-th flagged operator (ascending j) at tbuf + s * g.stride; hist: 16 floats, h1 h2 per slot
+};
+inline GraphFbLayout graph_fb_layout(uint32_t ops, uint32_t flagged, uint32_t pass_samples)
+{
+    GraphFbLayout l{};
+    l.g = graph_cont_layout(ops, pass_samples);
+    l.tbuf = (l.g.words + 3u) & ~(size_t)3u;
+    l.hist = l.tbuf + (size_t)flagged * l.g.stride;
+    l.words = l.hist + 16u;
+    return l;
+}
+struct GraphFbPass {
+    GraphContPass g;   // g.lay = lay.g
+    size_t tbuf, hist; // GraphFbLayout's, into g.words
+    uint32_t fb_mask;  // the flagged operators
+    float scaled[8];   // B_j = beta_j K (scale_feedback, sots_rules.h)
+    uint32_t forms;    // bit j: operator j's chain runs as a relaxation (else serially)
+    uint32_t relax_cap; // sweeps per tile before a tile is finished serially, 1..4096
+};
+// every level of one pass with its chains, and the mix; carries and hist are the caller's to clear before the first pass
+hipError_t launch_graph_feedback_pass(hipStream_t st, const sots_voice_graph &graph, const uint32_t waveforms[8], const GraphFbPass &pass,
+                                      uint32_t num_cus);
+
 } // namespace sots

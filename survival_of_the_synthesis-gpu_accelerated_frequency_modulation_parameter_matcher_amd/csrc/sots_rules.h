@@ -425,6 +425,54 @@ inline Fault render_graph_continuous_check(uint32_t kind, const float feedback[8
     return Fault{};
 }
 
+// ---- ... with feedback operators (sots_render_graph_feedback) ----
+// Samples of a pass: a phase word per operator and sample and a shaped value per feedback operator and sample stay together
+// within the same 96 MiB; whole tiles of 4096, at most 1024 of them.  Without feedback operators: graph_continuous_max_pass.
+inline uint32_t graph_feedback_max_pass(uint32_t ops, uint32_t flagged)
+{
+    const uint32_t buffers = ops + flagged ? ops + flagged : 1u;
+    const uint64_t tiles = (96ull << 20) / (sizeof(uint32_t) * buffers) / 4096u;
+    return (uint32_t)(tiles < 1024u ? tiles : 1024u) * 4096u;
+}
+// How a feedback operator's chain over the samples is computed (sots_render_graph_feedback_args.chain_form)
+constexpr uint32_t kChainLibrary = 0, kChainSerial = 1, kChainRelax = 2;
+constexpr uint32_t kRelaxCapMax = 4096, kRelaxCapLibrary = 1024;
+// The library's choice of form for an operator of feedback index beta (!= 0), and of the cap.  The relaxation is chosen only
+// for indices at which it beat the serial form in every repetition of the measurement of DESIGN.md 4.17
+// (profiles/r27_render_graph_feedback.json): it did at 0.25, 0.5, 0.75, 1 and 1.5 (28 to 3.3 times faster) and did not at 2,
+// where the chain is chaotic and a tile takes its thousand sweeps; nothing between 1.5 and 2 was measured.  The cap of 1024
+// was the fastest or within a percent of it at every index.
+constexpr float kRelaxBetaMax = 1.5f;
+inline uint32_t graph_feedback_form(float beta) { return beta <= kRelaxBetaMax ? kChainRelax : kChainSerial; }
+// sots_render_graph_feedback: what it refuses before anything touches the device; those of render_graph_continuous_check
+// without the feedback one, and the two of its own arguments.
+inline Fault render_graph_feedback_check(uint32_t kind, const sots_render_graph_feedback_args *args, uint32_t n, uint32_t d, const void *values,
+                                         size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples)
+{
+    if (kind != SOTS_SYNTH_GRAPH)
+        return fault(SOTS_ERR_STATE, "sots_render_graph_feedback: the handle runs a fixed voice (synth_kind %u; sots_render_continuous renders it)", kind);
+    if (!args || args->struct_size != sizeof(sots_render_graph_feedback_args))
+        return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: null args or sots_render_graph_feedback_args.struct_size != %zu",
+                     sizeof(sots_render_graph_feedback_args));
+    if (args->hop < 1u || args->hop > n) return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: hop %u outside 1..%u", args->hop, n);
+    if (args->flags & ~(uint32_t)SOTS_RENDER_GLIDE) return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: unknown flags 0x%x", args->flags);
+    if (args->chain_form > kChainRelax)
+        return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: chain_form %u is not a form (0 = the library's choice, 1 = serial, 2 = relaxation)",
+                     args->chain_form);
+    if (args->relax_cap > kRelaxCapMax)
+        return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: relax_cap %u outside 0..%u", args->relax_cap, kRelaxCapMax);
+    if (num_rows == 0) return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: num_rows must be at least 1");
+    const uint64_t covered = (uint64_t)(num_rows - 1u) * args->hop + n;
+    if (covered >= (1ull << 31))
+        return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: %u rows at hop %u are %llu samples, 2^31 or more", num_rows, args->hop,
+                     (unsigned long long)covered);
+    if (!values || values_bytes != (size_t)num_rows * d * sizeof(float))
+        return fault(SOTS_ERR_SIZE, "sots_render_graph_feedback: %u rows need %zu bytes of values, got %zu", num_rows,
+                     (size_t)num_rows * d * sizeof(float), values_bytes);
+    if (!out && out_samples) return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: null output");
+    return Fault{};
+}
+
 // ---- run record, stop rules ----
 constexpr uint64_t kTrackMaxRecords = 1ull << 24; // chunks x history_capacity (1.5 GiB of records)
 // sots_track / sots_batch_track: known flags, a history with a period and room, and no more than kTrackMaxRecords records

@@ -156,7 +156,8 @@ struct Evolutionary_Strategy_HIP_Arguments
     //                 (sots_render_continuous: one voice whose oscillators never restart, parameters held from chunk centre to
     //                 chunk centre), 2 = phase-continuous with the parameters interpolated between the centres.  Takes effect
     //                 only with renderMatch; 1 and 2 are not available with deviceKernelArithmetic.  3 and 4 are 1 and 2 for the
-    //                 operator-graph voice (sots_render_graph_continuous) and need it.
+    //                 operator-graph voice (sots_render_graph_continuous) and need it.  5 and 6 are 3 and 4 for a
+    //                 graph voice with feedback indices (sots_render_graph_feedback).
     //   matchPath   : sots_match writes the parameter track there, one CSV row per chunk (Match_track.hpp)
     uint32_t hopSize = 0;
     bool renderMatch = false;
@@ -342,7 +343,8 @@ public:
     // window and normalised by its sum, at hop = N they follow each other as they are.  (numChunks - 1) hop + N samples.
     // With renderMode 1 or 2 the same track goes through sots_render_continuous instead: the same length, one voice from the
     // first sample to the last, chunk i's parameters reached at its centre i hop + N/2.  With 3 or 4 (the operator-graph
-    // voice) through sots_render_graph_continuous, which is the same for a voice graph.
+    // voice) through sots_render_graph_continuous, which is the same for a voice graph, and with 5 or 6 through
+    // sots_render_graph_feedback, which is the same for a voice graph with feedback indices.
     void renderMatch(std::vector<float> &out)
     {
         const uint32_t d = population.numDimensions, chunks = (uint32_t)bestPerChunk_.size();
@@ -350,6 +352,14 @@ public:
         if (!chunks) return;
         std::vector<float> values((size_t)chunks * d);
         for (uint32_t c = 0; c < chunks; ++c) std::copy(bestPerChunk_[c].begin(), bestPerChunk_[c].begin() + d, values.begin() + (size_t)c * d);
+        if (args_.renderMode == 5u || args_.renderMode == 6u) {
+            sots_render_graph_feedback_args fa{};
+            fa.struct_size = sizeof fa;
+            fa.hop = hop_;
+            fa.flags = args_.renderMode == 6u ? (uint32_t)SOTS_RENDER_GLIDE : 0u;
+            check(sots_render_graph_feedback(ctx_, values.data(), values.size() * sizeof(float), chunks, &fa, out.data(), out.size()), "renderMatch");
+            return;
+        }
         if (args_.renderMode != 0u) {
             sots_render_continuous_args ca{};
             ca.struct_size = sizeof ca;
@@ -406,7 +416,9 @@ public:
         if (graphVoice && args_.deviceKernelArithmetic)
             throw std::runtime_error("Evolutionary_Strategy_HIP: deviceKernelArithmetic is not available with the operator-graph voice");
         if (!graphVoice && args_.renderMode >= 3u)
-            throw std::runtime_error("Evolutionary_Strategy_HIP: renderMode 3 and 4 (sots_render_graph_continuous) need the operator-graph voice");
+            throw std::runtime_error(args_.renderMode >= 5u
+                                         ? "Evolutionary_Strategy_HIP: renderMode 5 and 6 (sots_render_graph_feedback) need the operator-graph voice"
+                                         : "Evolutionary_Strategy_HIP: renderMode 3 and 4 (sots_render_graph_continuous) need the operator-graph voice");
         if (!graphVoice && !args_.voiceWaveforms.empty())
             throw std::runtime_error("Evolutionary_Strategy_HIP: voiceWaveforms need the operator-graph voice");
         if (!graphVoice && !args_.voiceFeedback.empty())

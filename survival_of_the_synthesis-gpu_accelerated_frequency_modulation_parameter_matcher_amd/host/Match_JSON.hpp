@@ -202,25 +202,32 @@ inline bool readHopSizeKey(const Json &h, uint32_t audioLength, uint32_t &hopSiz
 // match from phase 0, cross-faded), "continuous" (1: sots_render_continuous, one voice whose oscillators never restart, the
 // parameters held from chunk centre to chunk centre) or "continuousGlide" (2: the same with the parameters interpolated
 // between the centres); for the operator-graph voice "graphContinuous" (3) and "graphContinuousGlide" (4): the same two
-// through sots_render_graph_continuous.  Returns whether the key was there; throws - before any device
-// work - on anything else.
+// through sots_render_graph_continuous, and "graphFeedback" (5) and "graphFeedbackGlide" (6): the same two
+// through sots_render_graph_feedback, which renders a voice with type.HIP.voiceFeedback too.  Returns whether
+// the key was there; throws - before any device work - on anything else.
 inline bool readRenderModeKey(const Json &h, uint32_t &renderMode)
 {
     if (!h.has("renderMode")) return false;
     const Json &v = h["renderMode"];
-    const char *names[] = {"overlapAdd", "continuous", "continuousGlide", "graphContinuous", "graphContinuousGlide"};
+    const char *names[] = {"overlapAdd", "continuous", "continuousGlide", "graphContinuous", "graphContinuousGlide", "graphFeedback", "graphFeedbackGlide"};
     if (v.kind == Json::String)
-        for (uint32_t m = 0; m < 5; ++m)
+        for (uint32_t m = 0; m < 7; ++m)
             if (v.str == names[m]) return renderMode = m, true;
     throw std::runtime_error("parameters.json: type.HIP.renderMode must be \"overlapAdd\", \"continuous\" or \"continuousGlide\" (with type.HIP.synth "
-                             "\"graph\": \"overlapAdd\", \"graphContinuous\" or \"graphContinuousGlide\")" +
+                             "\"graph\": \"overlapAdd\", \"graphContinuous\" or \"graphContinuousGlide\", \"graphFeedback\" or \"graphFeedbackGlide\")" +
                              (v.kind == Json::String ? ", not \"" + v.str + "\"" : std::string()));
 }
 // renderMode "graphContinuous" / "graphContinuousGlide" belong to the operator-graph voice, and to one without feedback
-// (sots_render_graph_continuous refuses a feedback index other than 0: no scan computes that recurrence).  Throws - before
-// any device work - otherwise; the feedback is looked at only where the match is rendered.
+// (sots_render_graph_continuous refuses a feedback index other than 0: no scan computes that recurrence); "graphFeedback" /
+// "graphFeedbackGlide" belong to the operator-graph voice, with or without feedback.  Throws - before any device work -
+// otherwise; the feedback is looked at only where the match is rendered.
 inline void checkGraphRenderMode(uint32_t renderMode, bool graphVoice, bool renderMatch, const std::vector<float> &voiceFeedback)
 {
+    if (renderMode == 5u || renderMode == 6u) {
+        if (!graphVoice)
+            throw std::runtime_error("parameters.json: type.HIP.renderMode \"graphFeedback\" and \"graphFeedbackGlide\" need type.HIP.synth \"graph\"");
+        return;
+    }
     if (renderMode != 3u && renderMode != 4u) return;
     if (!graphVoice)
         throw std::runtime_error("parameters.json: type.HIP.renderMode \"graphContinuous\" and \"graphContinuousGlide\" need type.HIP.synth \"graph\"");
@@ -228,7 +235,8 @@ inline void checkGraphRenderMode(uint32_t renderMode, bool graphVoice, bool rend
     for (float b : voiceFeedback)
         if (b != 0.0f)
             throw std::runtime_error("parameters.json: type.HIP.renderMode \"graphContinuous\" and \"graphContinuousGlide\" are not available with "
-                                     "type.HIP.voiceFeedback other than 0 (\"overlapAdd\" renders such a voice)");
+                                     "type.HIP.voiceFeedback other than 0 (\"overlapAdd\" renders such a voice, and \"graphFeedback\" renders it "
+                                     "phase-continuously)");
 }
 
 // type.HIP.carryRows / type.HIP.segmentChunks (sots_batch_queue_set_carry): inside a segment of

@@ -21,6 +21,7 @@
 //                 Ignored without "renderMatch"; not available with "deviceKernelArithmetic".  With "synth": "graph" the two
 //                 are "graphContinuous" and "graphContinuousGlide" (sots_render_graph_continuous): the same rendering for
 //                 any voice graph and its waveforms, not with a "voiceFeedback" other than 0; refused with any other synth.
+//                 "graphFeedback" and "graphFeedbackGlide" (sots_render_graph_feedback) are those two with any "voiceFeedback".
 //   "voiceGraph"  with "synth": "graph", the operator-graph voice (sots_create_graph): {"operators": n, "modulators":
 //                 [[...], ...], "carriers": [...]} - modulators[j] lists the operators that modulate operator j (each
 //                 below j), carriers the operators that are heard; gene 2j is operator j's frequency, gene 2j+1 its level,
