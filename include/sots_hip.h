@@ -235,7 +235,7 @@ int sots_get_voice_waveforms(const sots_ctx *ctx, uint32_t codes[8]);
  * update, wraps) and the carrier sum are untouched: feedback never changes pos_j and does not make an operator
  * "modulated" for the lower wrap.  With all beta zero the voice is the one above bit for bit.  Feedback combines freely
  * with the waveform codes and with any role.  The indices belong to the algorithm, like the codes: they are not evolved,
- * and the voice keeps its 2 num_operators genes.
+ * and the voice keeps its 2 num_operators genes (sots_create_graph_genes, below, makes chosen operators' indices genes).
  * sots_set_voice_feedback: index[count], count == the graph's num_operators, every index in [0, 2] (NaN, infinite,
  * negative and larger values are refused; -0 is taken as 0); (NULL, 0) sets all zero.  SOTS_ERR_STATE for a context of a
  * fixed voice, SOTS_ERR_INVALID for the rest; everything is checked before anything changes, and a refused call leaves
@@ -246,6 +246,37 @@ int sots_get_voice_waveforms(const sots_ctx *ctx, uint32_t codes[8]);
  * refuses a voice with any index != 0; sots_render_graph_feedback renders such a voice phase-continuously. */
 int sots_set_voice_feedback(sots_ctx *ctx, const float *index, uint32_t count);
 int sots_get_voice_feedback(const sots_ctx *ctx, float index[8]);
+
+/* ---- feedback indices as genes (new: the matcher searches beta per individual) ----
+ * sots_create_graph_genes is sots_create_graph with a mask feedback_genes: bit j set (j < OPS only) makes operator j's
+ * feedback index a gene of the individual instead of a setting of the context.  Mask 0 is sots_create_graph in every
+ * respect.
+ * Gene layout.  E = popcount(feedback_genes); the voice has D = 2 OPS + E genes, D <= SOTS_MAX_DIMS, and
+ * cfg.num_dimensions must be that D (the rule "kind 4 needs numDimensions 2 OPS" stays for sots_create_graph).  Genes
+ * 0 .. 2 OPS - 1 mean what they mean above.  Gene 2 OPS + r holds the index of the operator with the r-th set bit of the
+ * mask, ascending.  It is scaled like every gene, p = pmin_g + v (pmax_g - pmin_g) in fp32, and for these genes the
+ * configuration must have 0 <= pmin_g <= pmax_g <= 2.
+ * The effective index.  Mutation's reflection can leave v outside [0, 1], so the voice uses
+ *     beta = p > 0 ? fminf(p, 2) : +0            (NaN, negative values and -0 give +0; values above 2 give 2)
+ *     B    = beta * K                            (one fp32 product, as for the fixed setting)
+ * A gene operator ALWAYS runs the feedback step of sots_set_voice_feedback, with its row's B: it is never "skipped", not
+ * even where its beta is +0.  It keeps h1 and h2 and applies both wraps to z.  With pos_j in [0, W) and beta = +0, z is
+ * pos_j and both wraps leave it: the index is that of pos_j, as for a skipped operator; a pos_j outside [0, W) (an
+ * unmodulated operator of negative frequency, a NaN) meets the wraps of z before the clamp.  Everything else in the
+ * voice is untouched.
+ * Anchor: a row whose effective index is b on every gene operator gives the audio of sots_create_graph with
+ * sots_set_voice_feedback = b on those operators, bit for bit, for b in (0, 2].
+ * The other operators keep their setting: sots_set_voice_feedback refuses an index other than 0 on a gene operator
+ * (SOTS_ERR_INVALID; nothing changes) and sots_get_voice_feedback reports 0 for it.  sots_get_voice_feedback_genes gives
+ * the mask (0 for a context of sots_create_graph; SOTS_ERR_STATE for a fixed voice).
+ * Refusals, all SOTS_ERR_INVALID and before any device work, each with a text of its own: a mask bit at or beyond OPS,
+ * D > 16, cfg.num_dimensions != 2 OPS + E, a gene range outside [0, 2] or inverted.
+ * Variation, selection, the run record, batch, queue, carried rows and survivors are generic in D and serve the voice;
+ * sots_render_overlap_add and the match report render each row with its own beta.  sots_render_graph_continuous and
+ * sots_render_graph_feedback take beta from the context and refuse a context whose mask is not 0 (SOTS_ERR_STATE; the
+ * text names sots_render_overlap_add).  Islands do not take the voice. */
+int sots_create_graph_genes(const sots_config *cfg, const sots_voice_graph *graph, uint32_t feedback_genes, sots_ctx **out);
+int sots_get_voice_feedback_genes(const sots_ctx *ctx, uint32_t *feedback_genes);
 
 /* ---- target (replaces setTargetAudio, ...OpenCL.hpp:563-570; Objective::calculateFFT,
  *      Evolutionary_Strategy.hpp:524-542) ---- */
@@ -670,6 +701,10 @@ int sots_batch_get_voice_waveforms(const sots_batch *b, uint32_t codes[8]);
  * refusals.  Every chunk's run record is cleared.  In any order with the targets, objective, weights and waveforms. */
 int sots_batch_set_voice_feedback(sots_batch *b, const float *index, uint32_t count);
 int sots_batch_get_voice_feedback(const sots_batch *b, float index[8]);
+/* sots_create_graph_genes for a batch (new): every chunk's individuals carry the feedback indices of the masked operators */
+int sots_batch_create_graph_genes(const sots_config *cfg, const sots_voice_graph *graph, uint32_t feedback_genes, uint32_t max_chunks,
+                                  sots_batch **out);
+int sots_batch_get_voice_feedback_genes(const sots_batch *b, uint32_t *feedback_genes);
 /* row 0 (the best) of every active chunk: values [active][D], fitness [active] (either may be NULL); blocking */
 int sots_batch_read_best(sots_batch *b, float *values, size_t values_bytes, float *fitness, size_t fitness_bytes);
 /* one active chunk's current half; byte counts as sots_read_population; blocking */

@@ -80,6 +80,7 @@ EXPORTS = [
     "sots_create_graph", "sots_batch_create_graph", "sots_get_voice_graph",
     "sots_set_voice_waveforms", "sots_get_voice_waveforms", "sots_batch_set_voice_waveforms", "sots_batch_get_voice_waveforms",
     "sots_set_voice_feedback", "sots_get_voice_feedback", "sots_batch_set_voice_feedback", "sots_batch_get_voice_feedback",
+    "sots_create_graph_genes", "sots_batch_create_graph_genes", "sots_get_voice_feedback_genes", "sots_batch_get_voice_feedback_genes",
 ]
 ANALYSIS_HOST, ANALYSIS_DEVICE = 0, 1  # enum sots_analysis
 QUEUE_NO_CHUNK = 0xFFFFFFFF
@@ -161,13 +162,22 @@ def _feedback_indices(feedback):
     return (C.c_float * len(index))(*index), len(index)
 
 
-def synth_dims(synth_kind, graph=None):
-    """genes of a voice: the fixed voices' by kind, two per operator of a graph"""
+def synth_dims(synth_kind, graph=None, feedback_genes=None):
+    """genes of a voice: the fixed voices' by kind, two per operator of a graph and one per operator whose feedback index
+    is a gene (feedback_genes: a mask or a list of operator indices)"""
     if synth_kind == SYNTH_GRAPH:
         if graph is None:
             raise ValueError("SYNTH_GRAPH needs graph=")
-        return 2 * int(as_voice_graph(graph).num_operators)
+        return 2 * int(as_voice_graph(graph).num_operators) + bin(_mask(feedback_genes or 0) & 0xFFFFFFFF).count("1")
+    if feedback_genes is not None:  # (also a mask of 0: the caller believes the voice is a graph)
+        raise ValueError("feedback_genes needs SYNTH_GRAPH and graph=: a fixed voice has no feedback indices")
     return SYNTH_DIMS[synth_kind]
+
+
+def _operators(handle):
+    """operators of a handle's graph (a view of somebody else's context has only its genes to go by)"""
+    g = getattr(handle, "graph", None)
+    return handle.D // 2 if g is None else int(g.num_operators)
 
 
 class Info(C.Structure):
@@ -382,6 +392,10 @@ def load():
     L.sots_get_voice_feedback.argtypes = [vp, C.POINTER(C.c_float)]
     L.sots_batch_set_voice_feedback.argtypes = [vp, C.POINTER(C.c_float), u32]
     L.sots_batch_get_voice_feedback.argtypes = [vp, C.POINTER(C.c_float)]
+    L.sots_create_graph_genes.argtypes = [C.POINTER(Config), C.POINTER(VoiceGraph), u32, C.POINTER(vp)]
+    L.sots_batch_create_graph_genes.argtypes = [C.POINTER(Config), C.POINTER(VoiceGraph), u32, u32, C.POINTER(vp)]
+    L.sots_get_voice_feedback_genes.argtypes = [vp, C.POINTER(u32)]
+    L.sots_batch_get_voice_feedback_genes.argtypes = [vp, C.POINTER(u32)]
     _lib = L
     return L
 
@@ -399,8 +413,8 @@ def _nbytes(a):
 
 
 def make_config(num_parents, num_offspring, synth_kind=SYNTH_2OP, audio_log2=10, param_min=None, param_max=None,
-                seed=0x5EED0001, workgroup_size=32, device=0, gid_base=0, num_generations=0, graph=None):
-    d = synth_dims(synth_kind, graph)
+                seed=0x5EED0001, workgroup_size=32, device=0, gid_base=0, num_generations=0, graph=None, feedback_genes=None):
+    d = synth_dims(synth_kind, graph, feedback_genes)
     cfg = Config()
     cfg.struct_size = C.sizeof(Config)
     cfg.num_parents, cfg.num_offspring, cfg.num_dimensions = num_parents, num_offspring, d
@@ -432,20 +446,24 @@ class HipES:
 
     def __init__(self, num_parents, num_offspring, synth_kind=SYNTH_2OP, audio_log2=10,
                  param_min=None, param_max=None, seed=0x5EED0001, workgroup_size=32,
-                 device=0, gid_base=0, num_generations=0, graph=None, waveforms=None, feedback=None):
+                 device=0, gid_base=0, num_generations=0, graph=None, waveforms=None, feedback=None, feedback_genes=None):
         """graph (with synth_kind=SYNTH_GRAPH): a VoiceGraph or its JSON form, see as_voice_graph; waveforms: that
         graph's operator waveforms, see set_voice_waveforms; feedback: its operators' feedback indices, see
-        set_voice_feedback"""
+        set_voice_feedback; feedback_genes: the operators whose feedback index is a gene of the individual instead (a
+        mask or a list of operator indices, sots_create_graph_genes): D grows by one per operator, and param_min /
+        param_max carry those genes' ranges, within [0, 2], behind the 2 OPS others"""
         self.L = load()
         self._borrowed = False
         self.graph = as_voice_graph(graph)
         cfg = make_config(num_parents, num_offspring, synth_kind, audio_log2, param_min, param_max, seed, workgroup_size,
-                          device, gid_base, num_generations, graph=self.graph)
+                          device, gid_base, num_generations, graph=self.graph, feedback_genes=feedback_genes)
         self.cfg = cfg
         self.P, self.D, self.N = num_parents + num_offspring, cfg.num_dimensions, 1 << audio_log2
         self.num_parents = num_parents
         h = C.c_void_p()
-        if self.graph is not None:
+        if self.graph is not None and feedback_genes is not None:
+            rc = self.L.sots_create_graph_genes(C.byref(cfg), C.byref(self.graph), _mask(feedback_genes), C.byref(h))
+        elif self.graph is not None:
             rc = self.L.sots_create_graph(C.byref(cfg), C.byref(self.graph), C.byref(h))
         else:
             rc = self.L.sots_create(C.byref(cfg), C.byref(h))
@@ -495,7 +513,7 @@ class HipES:
         """the codes of the graph's operators"""
         codes = (C.c_uint32 * GRAPH_MAX_OPERATORS)()
         self._check(self.L.sots_get_voice_waveforms(self._h, codes))
-        return list(codes)[:self.D // 2]
+        return list(codes)[:_operators(self)]
 
     def set_voice_feedback(self, feedback):
         """one feedback index in [0, 2] per operator of the graph, or None: no feedback.  Like set_voice_waveforms: the run
@@ -507,7 +525,13 @@ class HipES:
         """the feedback indices of the graph's operators"""
         index = (C.c_float * GRAPH_MAX_OPERATORS)()
         self._check(self.L.sots_get_voice_feedback(self._h, index))
-        return list(index)[:self.D // 2]
+        return list(index)[:_operators(self)]
+
+    def voice_feedback_genes(self):
+        """the mask of the operators whose feedback index is a gene (0: none)"""
+        mask = C.c_uint32()
+        self._check(self.L.sots_get_voice_feedback_genes(self._h, C.byref(mask)))
+        return mask.value
 
     def info(self):
         i = Info()
@@ -828,17 +852,20 @@ class HipBatch:
 
     def __init__(self, max_chunks, num_parents, num_offspring, synth_kind=SYNTH_2OP, audio_log2=10, param_min=None,
                  param_max=None, seed=0x5EED0001, workgroup_size=32, device=0, gid_base=0, num_generations=0, graph=None,
-                 waveforms=None, feedback=None):
+                 waveforms=None, feedback=None, feedback_genes=None):
+        """feedback_genes: as for HipES (sots_batch_create_graph_genes)"""
         self.L = load()
         self.graph = as_voice_graph(graph)
         self.cfg = make_config(num_parents, num_offspring, synth_kind, audio_log2, param_min, param_max, seed, workgroup_size,
-                               device, gid_base, num_generations, graph=self.graph)
+                               device, gid_base, num_generations, graph=self.graph, feedback_genes=feedback_genes)
         self.P, self.D, self.N = num_parents + num_offspring, self.cfg.num_dimensions, 1 << audio_log2
         self.max_chunks = max_chunks
         self.active = 0
         self.queued = 0
         h = C.c_void_p()
-        if self.graph is not None:
+        if self.graph is not None and feedback_genes is not None:
+            rc = self.L.sots_batch_create_graph_genes(C.byref(self.cfg), C.byref(self.graph), _mask(feedback_genes), max_chunks, C.byref(h))
+        elif self.graph is not None:
             rc = self.L.sots_batch_create_graph(C.byref(self.cfg), C.byref(self.graph), max_chunks, C.byref(h))
         else:
             rc = self.L.sots_batch_create(C.byref(self.cfg), max_chunks, C.byref(h))
@@ -922,7 +949,7 @@ class HipBatch:
     def voice_waveforms(self):
         codes = (C.c_uint32 * GRAPH_MAX_OPERATORS)()
         self._check(self.L.sots_batch_get_voice_waveforms(self._h, codes))
-        return list(codes)[:self.D // 2]
+        return list(codes)[:_operators(self)]
 
     def set_voice_feedback(self, feedback):
         """HipES.set_voice_feedback for every chunk (one setting), in execute_generations / execute_until and queue_run alike"""
@@ -932,7 +959,12 @@ class HipBatch:
     def voice_feedback(self):
         index = (C.c_float * GRAPH_MAX_OPERATORS)()
         self._check(self.L.sots_batch_get_voice_feedback(self._h, index))
-        return list(index)[:self.D // 2]
+        return list(index)[:_operators(self)]
+
+    def voice_feedback_genes(self):
+        mask = C.c_uint32()
+        self._check(self.L.sots_batch_get_voice_feedback_genes(self._h, C.byref(mask)))
+        return mask.value
 
     def read_best(self):
         """(values[active][D], fitness[active]): row 0 of every active chunk"""

@@ -241,12 +241,12 @@ template <class Fill> int queue_store(sots_batch *b, uint32_t num_chunks, Fill f
 
 extern "C" {
 
-// sots_batch_create (graph == nullptr) and sots_batch_create_graph
-static int create_batch(const sots_config *cfg, const sots_voice_graph *graph, uint32_t max_chunks, sots_batch **out)
+// sots_batch_create (graph == nullptr), sots_batch_create_graph (feedback_genes == 0) and sots_batch_create_graph_genes
+static int create_batch(const sots_config *cfg, const sots_voice_graph *graph, uint32_t feedback_genes, uint32_t max_chunks, sots_batch **out)
 {
     *out = nullptr;
     // the configuration first, then the batch's own limits: a machine without a GPU still tells a bad one from a good one
-    SOTS_REFUSE(nullptr, config_check(*cfg, kNoPopulationLimit, graph));
+    SOTS_REFUSE(nullptr, config_check(*cfg, kNoPopulationLimit, graph, feedback_genes));
     const uint64_t p64 = (uint64_t)cfg->num_parents + cfg->num_offspring;
     if (p64 > kBatchMaxPopulation)
         return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "a batch takes chunk populations of at most %u, got %llu (larger ones fill the GPU alone: sots_create)",
@@ -256,7 +256,7 @@ static int create_batch(const sots_config *cfg, const sots_voice_graph *graph, u
         return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "max_chunks %u x population %llu exceeds 2^26 rows", max_chunks, (unsigned long long)p64);
 
     sots_batch *b = new sots_batch();
-    if (int rc = engine_create(*b, *cfg, graph, 32)) return abandon(b, rc); // (the pad of sots_create: rows off the power-of-two stride)
+    if (int rc = engine_create(*b, *cfg, graph, 32, feedback_genes)) return abandon(b, rc); // (the pad of sots_create: rows off the power-of-two stride)
     b->max_chunks = max_chunks;
 #define CREATE_HIP(call) SOTS_HIP_OR(b, call, return abandon(b, rc_))
     const size_t pd_bytes = (size_t)2 * b->rows() * b->D * sizeof(float);
@@ -293,13 +293,26 @@ static int create_batch(const sots_config *cfg, const sots_voice_graph *graph, u
 int sots_batch_create(const sots_config *cfg, uint32_t max_chunks, sots_batch **out)
 {
     if (!cfg || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_batch_create: null argument");
-    return create_batch(cfg, nullptr, max_chunks, out);
+    return create_batch(cfg, nullptr, 0, max_chunks, out);
 }
 
 int sots_batch_create_graph(const sots_config *cfg, const sots_voice_graph *graph, uint32_t max_chunks, sots_batch **out)
 {
     if (!cfg || !graph || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_batch_create_graph: null argument");
-    return create_batch(cfg, graph, max_chunks, out);
+    return create_batch(cfg, graph, 0, max_chunks, out);
+}
+
+int sots_batch_create_graph_genes(const sots_config *cfg, const sots_voice_graph *graph, uint32_t feedback_genes, uint32_t max_chunks,
+                                  sots_batch **out)
+{
+    if (!cfg || !graph || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_batch_create_graph_genes: null argument");
+    return create_batch(cfg, graph, feedback_genes, max_chunks, out);
+}
+
+int sots_batch_get_voice_feedback_genes(const sots_batch *b, uint32_t *feedback_genes)
+{
+    BATCH_REQUIRE(b);
+    return engine_get_voice_feedback_genes(*b, feedback_genes);
 }
 
 void sots_batch_destroy(sots_batch *b) { free_batch(b); }
@@ -422,7 +435,7 @@ int sots_batch_get_voice_waveforms(const sots_batch *b, uint32_t codes[8])
 int sots_batch_set_voice_feedback(sots_batch *b, const float *index, uint32_t count)
 {
     BATCH_REQUIRE(b);
-    SOTS_REFUSE(b, voice_feedback_check(b->cfg.synth_kind, b->graph.num_operators, index, count));
+    SOTS_REFUSE(b, voice_feedback_check(b->cfg.synth_kind, b->graph.num_operators, index, count, b->feedback_genes));
     if (int rc = engine_bind(*b)) return rc;
     SOTS_HIP(b, track_clear(b->track, b->stream));
     SOTS_HIP(b, hipStreamSynchronize(b->stream));

@@ -391,11 +391,11 @@ int record_generation(sots_ctx *ctx)
 // =======================================================================================
 extern "C" {
 
-// sots_create (graph == nullptr) and sots_create_graph
-static int create_context(const sots_config *cfg, const sots_voice_graph *graph, sots_ctx **out)
+// sots_create (graph == nullptr), sots_create_graph (feedback_genes == 0) and sots_create_graph_genes
+static int create_context(const sots_config *cfg, const sots_voice_graph *graph, uint32_t feedback_genes, sots_ctx **out)
 {
     *out = nullptr;
-    SOTS_REFUSE(nullptr, config_check(*cfg, 1ull << 26, graph));
+    SOTS_REFUSE(nullptr, config_check(*cfg, 1ull << 26, graph, feedback_genes));
 
     sots_ctx *ctx = new sots_ctx();
     // audio rows are padded off the power-of-two stride (see sots_kernels.h)
@@ -406,7 +406,7 @@ static int create_context(const sots_config *cfg, const sots_voice_graph *graph,
     if (const char *e = getenv("SOTS_FUSE_VARIATION")) ctx->fuse_variation = atoi(e) != 0 ? 1 : 0;
     if (const char *e = getenv("SOTS_SKIP_STAGE")) ctx->skip_stage = atoi(e); // 1: no synthesis, 2: no spectral kernel (timing ablations)
 #endif
-    if (int rc = engine_create(*ctx, *cfg, graph, pad)) return abandon(ctx, rc);
+    if (int rc = engine_create(*ctx, *cfg, graph, pad, feedback_genes)) return abandon(ctx, rc);
 #define CREATE_HIP(call) SOTS_HIP_OR(ctx, call, return abandon(ctx, rc_))
     const size_t pd_bytes = (size_t)2 * ctx->P * ctx->D * sizeof(float);
     const size_t audio_bytes = (size_t)ctx->P * ctx->pitch * sizeof(float);
@@ -450,13 +450,25 @@ static int create_context(const sots_config *cfg, const sots_voice_graph *graph,
 int sots_create(const sots_config *cfg, sots_ctx **out)
 {
     if (!cfg || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_create: null argument");
-    return create_context(cfg, nullptr, out);
+    return create_context(cfg, nullptr, 0, out);
 }
 
 int sots_create_graph(const sots_config *cfg, const sots_voice_graph *graph, sots_ctx **out)
 {
     if (!cfg || !graph || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_create_graph: null argument");
-    return create_context(cfg, graph, out);
+    return create_context(cfg, graph, 0, out);
+}
+
+int sots_create_graph_genes(const sots_config *cfg, const sots_voice_graph *graph, uint32_t feedback_genes, sots_ctx **out)
+{
+    if (!cfg || !graph || !out) return SOTS_FAIL(nullptr, SOTS_ERR_INVALID, "sots_create_graph_genes: null argument");
+    return create_context(cfg, graph, feedback_genes, out);
+}
+
+int sots_get_voice_feedback_genes(const sots_ctx *ctx, uint32_t *feedback_genes)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    return engine_get_voice_feedback_genes(*ctx, feedback_genes);
 }
 
 int sots_get_voice_graph(const sots_ctx *ctx, sots_voice_graph *graph)
@@ -1049,7 +1061,7 @@ int sots_get_voice_waveforms(const sots_ctx *ctx, uint32_t codes[8])
 int sots_set_voice_feedback(sots_ctx *ctx, const float *index, uint32_t count)
 {
     SOTS_REQUIRE_CTX(ctx);
-    SOTS_REFUSE(ctx, voice_feedback_check(ctx->cfg.synth_kind, ctx->graph.num_operators, index, count));
+    SOTS_REFUSE(ctx, voice_feedback_check(ctx->cfg.synth_kind, ctx->graph.num_operators, index, count, ctx->feedback_genes));
     if (int rc = engine_bind(*ctx)) return rc;
     SOTS_HIP(ctx, track_clear(ctx->track, ctx->stream));
     SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1208,7 +1220,7 @@ int sots_render_graph_continuous(sots_ctx *ctx, const float *values, size_t valu
 {
     SOTS_REQUIRE_CTX(ctx);
     SOTS_REFUSE(ctx, render_graph_continuous_check(ctx->cfg.synth_kind, ctx->feedback, args, ctx->N, ctx->D, values, values_bytes, num_rows, out,
-                                                   out_samples));
+                                                   out_samples, ctx->feedback_genes));
     if (int rc = engine_bind(*ctx)) return rc;
     const uint32_t N = ctx->N, D = ctx->D, hop = args->hop, ops = ctx->graph.num_operators;
     const uint64_t covered = (uint64_t)(num_rows - 1u) * hop + N, want = out_samples < covered ? out_samples : covered;
@@ -1257,7 +1269,8 @@ int sots_render_graph_feedback(sots_ctx *ctx, const float *values, size_t values
                                const sots_render_graph_feedback_args *args, float *out, uint64_t out_samples)
 {
     SOTS_REQUIRE_CTX(ctx);
-    SOTS_REFUSE(ctx, render_graph_feedback_check(ctx->cfg.synth_kind, args, ctx->N, ctx->D, values, values_bytes, num_rows, out, out_samples));
+    SOTS_REFUSE(ctx, render_graph_feedback_check(ctx->cfg.synth_kind, args, ctx->N, ctx->D, values, values_bytes, num_rows, out, out_samples,
+                                                 ctx->feedback_genes));
     if (int rc = engine_bind(*ctx)) return rc;
     const uint32_t N = ctx->N, D = ctx->D, hop = args->hop, ops = ctx->graph.num_operators;
     const uint64_t covered = (uint64_t)(num_rows - 1u) * hop + N, want = out_samples < covered ? out_samples : covered;

@@ -56,6 +56,7 @@ struct Engine {
     sots_voice_graph graph{}; // SOTS_SYNTH_GRAPH: the topology that came with cfg (num_operators 0 for a fixed voice)
     uint32_t waveforms[8] = {0}; // ... and its operators' waveform codes (sots_set_voice_waveforms; all sine until set)
     float feedback[8] = {0};     // ... and their feedback indices (sots_set_voice_feedback; +0, no feedback, until set)
+    uint32_t feedback_genes = 0; // ... and the operators whose index is a gene instead (sots_create_graph_genes; theirs above stays +0)
     PopDims pd{};
     MutateConsts mc{};
     SynthParams sp{};
@@ -84,8 +85,9 @@ inline std::string &err_of(const Engine &e) { return e.err; }
 
 // The device, the stream, the sizes and constants of a configuration that config_check has passed, and the tables' device
 // memory.  row_pad: floats behind the N of an audio row (rows off the power-of-two stride, see sots_kernels.h).  On a
-// failure the text is in e.err and the caller releases.  graph: with SOTS_SYNTH_GRAPH, null otherwise.
-inline int engine_create(Engine &e, const sots_config &cfg, const sots_voice_graph *graph, uint32_t row_pad)
+// failure the text is in e.err and the caller releases.  graph: with SOTS_SYNTH_GRAPH, null otherwise; feedback_genes: its
+// checked mask (sots_create_graph_genes), 0 from every other entry point.
+inline int engine_create(Engine &e, const sots_config &cfg, const sots_voice_graph *graph, uint32_t row_pad, uint32_t feedback_genes = 0)
 {
     int ndev = 0;
     hipError_t err = hipGetDeviceCount(&ndev);
@@ -93,6 +95,7 @@ inline int engine_create(Engine &e, const sots_config &cfg, const sots_voice_gra
     if (cfg.device < 0 || cfg.device >= ndev) return SOTS_FAIL(e, SOTS_ERR_NO_DEVICE, "device %d not in 0..%d", cfg.device, ndev - 1);
     e.cfg = cfg;
     if (graph) e.graph = *graph;
+    e.feedback_genes = graph ? feedback_genes : 0u;
     e.device = cfg.device;
     SOTS_HIP(e, hipSetDevice(e.device));
     hipDeviceProp_t prop;
@@ -106,7 +109,7 @@ inline int engine_create(Engine &e, const sots_config &cfg, const sots_voice_gra
     e.stream = e.own_stream;
 
     e.P = cfg.num_parents + cfg.num_offspring;
-    e.D = graph ? 2u * graph->num_operators : dims_of(cfg.synth_kind);
+    e.D = graph ? graph_dims(graph->num_operators, e.feedback_genes) : dims_of(cfg.synth_kind);
     e.log2n = cfg.audio_length_log2;
     e.N = 1u << e.log2n;
     e.pitch = e.N + row_pad;
@@ -190,7 +193,7 @@ inline int engine_get_voice_waveforms(const Engine &e, uint32_t codes[8])
 
 inline int engine_set_voice_feedback(Engine &e, const float *index, uint32_t count)
 {
-    SOTS_REFUSE(e, voice_feedback_set(e.cfg.synth_kind, e.graph.num_operators, index, count, e.feedback));
+    SOTS_REFUSE(e, voice_feedback_set(e.cfg.synth_kind, e.graph.num_operators, index, count, e.feedback, e.feedback_genes));
     return SOTS_OK;
 }
 inline int engine_get_voice_feedback(const Engine &e, float index[8])
@@ -198,6 +201,13 @@ inline int engine_get_voice_feedback(const Engine &e, float index[8])
     if (!index) return SOTS_FAIL(e, SOTS_ERR_INVALID, "voice feedback: null argument");
     SOTS_REFUSE(e, voice_feedback_check(e.cfg.synth_kind, e.graph.num_operators, nullptr, 0));
     memcpy(index, e.feedback, sizeof e.feedback);
+    return SOTS_OK;
+}
+
+inline int engine_get_voice_feedback_genes(const Engine &e, uint32_t *feedback_genes)
+{
+    SOTS_REFUSE(e, voice_feedback_genes_get_check(e.cfg.synth_kind, feedback_genes));
+    *feedback_genes = e.feedback_genes;
     return SOTS_OK;
 }
 
@@ -249,7 +259,7 @@ inline hipError_t engine_synthesise(const Engine &e, const float *values, float 
     if (e.synth_arith == SOTS_ARITH_DEVICE_KERNELS)
         return launch_synth_device_arith(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch);
     return launch_synth(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch, e.num_cus, var, allow_cut, &e.graph,
-                        pack_waveforms(e.waveforms), e.feedback);
+                        pack_waveforms(e.waveforms), e.feedback, e.feedback_genes);
 }
 
 } // namespace sots

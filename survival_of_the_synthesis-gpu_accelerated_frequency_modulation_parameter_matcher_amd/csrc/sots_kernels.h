@@ -125,14 +125,17 @@ hipError_t launch_synth_device_arith(hipStream_t st, uint32_t kind, const float 
 hipError_t launch_synth(hipStream_t st, uint32_t kind, const float *values, const float *wavetable,
                         float *audio, const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch,
                         uint32_t num_cus, const Variation *var = nullptr, bool allow_cut = true,
-                        const sots_voice_graph *graph = nullptr, uint32_t waveforms = 0, const float *feedback = nullptr);
+                        const sots_voice_graph *graph = nullptr, uint32_t waveforms = 0, const float *feedback = nullptr,
+                        uint32_t feedback_genes = 0);
 // SOTS_SYNTH_GRAPH (sots_synth_graph.hip): a checked graph (voice_graph_check), values[p][2 OPS]; it makes no individuals.
 // waveforms: the operators' checked waveform codes, 3 bits each (pack_waveforms); 0, all sine, launches k_synth_graph,
 // anything else its shaped sibling.  feedback: the operators' eight checked feedback indices (sots_set_voice_feedback) or
-// null; any index other than 0 launches the feedback sibling, with the codes going through it too
+// null; any index other than 0 launches the feedback sibling, with the codes going through it too.  feedback_genes: the
+// checked mask of sots_create_graph_genes; other than 0, values is [p][2 OPS + popcount] and the gene sibling is launched,
+// with the codes and the fixed indices going through it; 0 launches exactly what is launched without it
 hipError_t launch_synth_graph(hipStream_t st, const sots_voice_graph &graph, const float *values, const float *wavetable, float *audio,
                               const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus, uint32_t waveforms = 0,
-                              const float *feedback = nullptr);
+                              const float *feedback = nullptr, uint32_t feedback_genes = 0);
 hipError_t launch_window(hipStream_t st, float *audio, const float *window, uint32_t p, uint32_t log2n,
                          uint32_t pitch);
 // audio[P][pitch] -> spectrum[P][N+8]

@@ -1528,12 +1528,12 @@ hipError_t launch_synth_device_arith(hipStream_t st, uint32_t kind, const float 
 hipError_t launch_synth(hipStream_t st, uint32_t kind, const float *values, const float *wavetable,
                         float *audio, const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch,
                         uint32_t num_cus, const Variation *variation, bool allow_cut, const sots_voice_graph *graph,
-                        uint32_t waveforms, const float *feedback)
+                        uint32_t waveforms, const float *feedback, uint32_t feedback_genes)
 {
     // the operator-graph voice has one kernel form, in a file of its own; it makes no individuals
     if (kind == SOTS_SYNTH_GRAPH) {
         if (!graph || variation) return hipErrorInvalidValue;
-        return launch_synth_graph(st, *graph, values, wavetable, audio, sp, p, log2n, pitch, num_cus, waveforms, feedback);
+        return launch_synth_graph(st, *graph, values, wavetable, audio, sp, p, log2n, pitch, num_cus, waveforms, feedback, feedback_genes);
     }
     Variation var = {};
     if (variation) var = *variation;

@@ -119,8 +119,9 @@ inline Fault voice_waveforms_set(uint32_t kind, uint32_t ops, const uint32_t *co
 constexpr float kFeedbackMax = 2.0f;
 // K of the definition: the fp32 nearest W / 2 pi, table entries per unit of h at an index of 1
 constexpr float kFeedbackScale = 0x1.45f306p+12f;
-// index[count] for a handle of synthesis kind `kind` whose graph has `ops` operators; (null, 0): no feedback
-inline Fault voice_feedback_check(uint32_t kind, uint32_t ops, const float *index, uint32_t count)
+// index[count] for a handle of synthesis kind `kind` whose graph has `ops` operators; (null, 0): no feedback.
+// feedback_genes: the operators whose index is a gene of the individual (sots_create_graph_genes): theirs stays 0 here
+inline Fault voice_feedback_check(uint32_t kind, uint32_t ops, const float *index, uint32_t count, uint32_t feedback_genes = 0)
 {
     if (kind != SOTS_SYNTH_GRAPH)
         return fault(SOTS_ERR_STATE, "voice feedback: the handle runs a fixed voice (synth_kind %u)", kind);
@@ -130,12 +131,16 @@ inline Fault voice_feedback_check(uint32_t kind, uint32_t ops, const float *inde
     for (uint32_t j = 0; j < count; ++j)
         if (!(index[j] >= 0.0f && index[j] <= kFeedbackMax)) // (NaN fails both; -0 >= 0 holds)
             return fault(SOTS_ERR_INVALID, "voice feedback: index %g of operator %u is outside 0..%g", (double)index[j], j, (double)kFeedbackMax);
+    for (uint32_t j = 0; j < count; ++j)
+        if ((feedback_genes >> j & 1u) && index[j] != 0.0f)
+            return fault(SOTS_ERR_INVALID, "voice feedback: index %g for operator %u, whose index is a gene (feedback_genes 0x%x): only 0 can be set",
+                         (double)index[j], j, feedback_genes);
     return Fault{};
 }
 // Checks, then writes all eight indices of `held` (+0 beyond the operators and for -0); a refusal leaves `held` as it was
-inline Fault voice_feedback_set(uint32_t kind, uint32_t ops, const float *index, uint32_t count, float held[8])
+inline Fault voice_feedback_set(uint32_t kind, uint32_t ops, const float *index, uint32_t count, float held[8], uint32_t feedback_genes = 0)
 {
-    if (const Fault f = voice_feedback_check(kind, ops, index, count)) return f;
+    if (const Fault f = voice_feedback_check(kind, ops, index, count, feedback_genes)) return f;
     for (uint32_t j = 0; j < kGraphMaxOps; ++j) held[j] = index && j < count && index[j] != 0.0f ? index[j] : 0.0f;
     return Fault{};
 }
@@ -152,11 +157,61 @@ inline bool scale_feedback(const float index[8], uint32_t ops, float scaled[8])
     return any;
 }
 
+// ---- feedback indices as genes (sots_create_graph_genes; the definition: include/sots_hip.h) ----
+inline uint32_t feedback_gene_count(uint32_t feedback_genes)
+{
+    uint32_t e = 0;
+    for (uint32_t j = 0; j < kGraphMaxOps; ++j) e += feedback_genes >> j & 1u;
+    return e;
+}
+// genes of a graph voice of `ops` operators whose mask is feedback_genes (a checked mask: nothing beyond the operators)
+inline uint32_t graph_dims(uint32_t ops, uint32_t feedback_genes) { return 2u * ops + feedback_gene_count(feedback_genes); }
+// the column of operator j's index (bit j of a checked mask is set): 2 OPS + the number of set bits below j
+inline uint32_t feedback_gene_column(uint32_t ops, uint32_t feedback_genes, uint32_t j)
+{
+    return 2u * ops + feedback_gene_count(feedback_genes & ((1u << j) - 1u));
+}
+// The effective index of a scaled gene p: NaN and everything not above 0 give +0, everything above 2 gives 2
+inline float effective_feedback(float p) { return p > 0.0f ? (p < kFeedbackMax ? p : kFeedbackMax) : 0.0f; }
+// What a mask other than 0 adds to config_check, for a checked graph: the mask lies within the operators, the genes fit a
+// row, the configuration counts them, and each gene column's range lies in [0, 2] in ascending order
+inline Fault voice_feedback_genes_check(const sots_config &cfg, const sots_voice_graph &graph, uint32_t feedback_genes)
+{
+    const uint32_t ops = graph.num_operators;
+    if (feedback_genes >> ops)
+        return fault(SOTS_ERR_INVALID, "voice feedback genes: mask 0x%x has bits beyond operator %u", feedback_genes, ops - 1u);
+    const uint32_t e = feedback_gene_count(feedback_genes), d = 2u * ops + e;
+    if (d > SOTS_MAX_DIMS)
+        return fault(SOTS_ERR_INVALID, "voice feedback genes: %u operators and %u feedback genes are %u genes, more than %u", ops, e, d,
+                     (uint32_t)SOTS_MAX_DIMS);
+    if (cfg.num_dimensions != d)
+        return fault(SOTS_ERR_INVALID, "voice feedback genes: %u operators and %u feedback genes need numDimensions %u, got %u", ops, e, d,
+                     cfg.num_dimensions);
+    for (uint32_t j = 0; j < ops; ++j) {
+        if (!(feedback_genes >> j & 1u)) continue;
+        const uint32_t g = feedback_gene_column(ops, feedback_genes, j);
+        const float lo = cfg.param_min[g], hi = cfg.param_max[g];
+        if (!(lo >= 0.0f && lo <= hi && hi <= kFeedbackMax)) // (false for NaN)
+            return fault(SOTS_ERR_INVALID, "voice feedback genes: gene %u (operator %u's index) has the range %g..%g, not 0 <= min <= max <= %g", g, j,
+                         (double)lo, (double)hi, (double)kFeedbackMax);
+    }
+    return Fault{};
+}
+// the getter's rule
+inline Fault voice_feedback_genes_get_check(uint32_t kind, const void *out)
+{
+    if (kind != SOTS_SYNTH_GRAPH)
+        return fault(SOTS_ERR_STATE, "voice feedback genes: the handle runs a fixed voice (synth_kind %u)", kind);
+    if (!out) return fault(SOTS_ERR_INVALID, "voice feedback genes: null argument");
+    return Fault{};
+}
+
 // Everything a configuration must satisfy whoever takes it; max_population is the caller's own limit on numParents +
 // numOffspring.  Needs no device: a machine without a GPU still tells a bad configuration from a good one.  graph: the
 // topology that came with the configuration (sots_create_graph, sots_batch_create_graph), null from every other entry point.
+// feedback_genes: the mask of sots_create_graph_genes / sots_batch_create_graph_genes, 0 from every other entry point.
 constexpr uint64_t kNoPopulationLimit = ~0ull; // (a caller that words its limit itself)
-inline Fault config_check(const sots_config &cfg, uint64_t max_population, const sots_voice_graph *graph = nullptr)
+inline Fault config_check(const sots_config &cfg, uint64_t max_population, const sots_voice_graph *graph = nullptr, uint32_t feedback_genes = 0)
 {
     if (cfg.struct_size != sizeof(sots_config))
         return fault(SOTS_ERR_INVALID, "sots_config.struct_size %u != %zu", cfg.struct_size, sizeof(sots_config));
@@ -167,7 +222,9 @@ inline Fault config_check(const sots_config &cfg, uint64_t max_population, const
                      cfg.synth_kind);
     if (graph)
         if (const Fault f = voice_graph_check(graph)) return f;
-    const uint32_t d = graph ? 2u * graph->num_operators : dims_of(cfg.synth_kind);
+    if (graph && feedback_genes)
+        if (const Fault f = voice_feedback_genes_check(cfg, *graph, feedback_genes)) return f;
+    const uint32_t d = graph ? graph_dims(graph->num_operators, feedback_genes) : dims_of(cfg.synth_kind);
     if (d == 0) return fault(SOTS_ERR_INVALID, "unknown synth_kind %u", cfg.synth_kind);
     if (cfg.num_dimensions != d)
         return fault(SOTS_ERR_INVALID, "synth_kind %u needs numDimensions %u, got %u", cfg.synth_kind, d, cfg.num_dimensions);
@@ -398,10 +455,16 @@ inline uint32_t graph_continuous_max_pass(uint32_t ops)
 // sots_render_graph_continuous: what it refuses before anything touches the device.  kind, feedback: the context's voice and
 // its feedback indices; n, d: its audio length and genes per row.
 inline Fault render_graph_continuous_check(uint32_t kind, const float feedback[8], const sots_render_continuous_args *args, uint32_t n, uint32_t d,
-                                           const void *values, size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples)
+                                           const void *values, size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples,
+                                           uint32_t feedback_genes = 0)
 {
     if (kind != SOTS_SYNTH_GRAPH)
         return fault(SOTS_ERR_STATE, "sots_render_graph_continuous: the handle runs a fixed voice (synth_kind %u; sots_render_continuous renders it)", kind);
+    if (feedback_genes)
+        return fault(SOTS_ERR_STATE,
+                     "sots_render_graph_continuous: the feedback indices of operators 0x%x are genes (sots_create_graph_genes): every row has its "
+                     "own; sots_render_overlap_add renders such a voice",
+                     feedback_genes);
     for (uint32_t j = 0; j < kGraphMaxOps; ++j)
         if (feedback[j] != 0.0f)
             return fault(SOTS_ERR_STATE,
@@ -447,10 +510,15 @@ inline uint32_t graph_feedback_form(float beta) { return beta <= kRelaxBetaMax ?
 // sots_render_graph_feedback: what it refuses before anything touches the device; those of render_graph_continuous_check
 // without the feedback one, and the two of its own arguments.
 inline Fault render_graph_feedback_check(uint32_t kind, const sots_render_graph_feedback_args *args, uint32_t n, uint32_t d, const void *values,
-                                         size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples)
+                                         size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples, uint32_t feedback_genes = 0)
 {
     if (kind != SOTS_SYNTH_GRAPH)
         return fault(SOTS_ERR_STATE, "sots_render_graph_feedback: the handle runs a fixed voice (synth_kind %u; sots_render_continuous renders it)", kind);
+    if (feedback_genes)
+        return fault(SOTS_ERR_STATE,
+                     "sots_render_graph_feedback: the feedback indices of operators 0x%x are genes (sots_create_graph_genes): every row has its "
+                     "own; sots_render_overlap_add renders such a voice",
+                     feedback_genes);
     if (!args || args->struct_size != sizeof(sots_render_graph_feedback_args))
         return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: null args or sots_render_graph_feedback_args.struct_size != %zu",
                      sizeof(sots_render_graph_feedback_args));

@@ -28,10 +28,24 @@ struct GraphMasks {
 struct GraphFeedback {
     float b[8]; // beta_j K
 };
+constexpr uint32_t kGeneShift = 24; // the gene form's codes word: operator j's code in bits 3j..3j+2, its mask bit at 24 + j
+// Feedback indices as genes (sots_create_graph_genes): which operators, the floats between rows of `values`, and per gene
+// operator its column and that column's range (the entries of SynthParams the column number would pick: an operator
+// number known at compile time picks them here, so nothing is indexed by a run-time value)
+struct GraphGenes {
+    uint32_t mask, stride;
+    uint32_t col[8];
+    float pmin[8], pmax[8];
+};
 template <typename T, typename... R>
 __device__ __forceinline__ T first_of(T first, R...)
 {
     return first;
+}
+template <typename T, typename S, typename... R>
+__device__ __forceinline__ S second_of(T, S second, R...)
+{
+    return second;
 }
 
 // The operators' waveforms (sots_set_voice_waveforms, include/sots_hip.h).  SHAPES is empty or one uint32_t: the kernel
@@ -47,6 +61,12 @@ __device__ __forceinline__ T first_of(T first, R...)
 // read -> next offset, so its U phases are advanced first (they do not depend on the feedback) and the chain runs after
 // them.  h1 and h2 stay in registers across blocks, flushes and tiles and are reset per row.  An operator with B_j == 0
 // runs the shaped form's block as it stands.
+// Feedback genes (sots_create_graph_genes, include/sots_hip.h): SHAPES is the codes, GraphGenes and
+// GraphFeedback (the codes stay first and the indices last, where the feedback form looks for them).  Rows of `values` are
+// genes.stride floats apart.  An operator whose mask bit is set (wavefront-uniform) has B_j in a register per lane, made
+// once per row from its gene - scaled, clamped to the effective index, times K - and ALWAYS runs the chain, also in lanes
+// where B_j is +0; every other operator takes the two paths of the feedback form, its B_j the scalar argument.  The chain
+// is written out once for each: the feedback form's own lines stay as they are, so its code objects do too.
 // CH: 16-byte chunks per tile row = 4 CH samples per flush.  The 32 KiB beside the table are 32 / CH tiles of 64 rows:
 // CH = 8, four wavefronts (one per SIMD) and whole 128-byte lines; CH = 4, eight wavefronts (two per SIMD) and half lines.
 template <int OPS, int CH, typename... SHAPES>
@@ -58,10 +78,11 @@ __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *
     // (an experiment build also has the form that lost: the codes as int32_t)
     constexpr bool BRANCHES = SHAPED && (std::is_same_v<SHAPES, uint32_t> || ...);
     constexpr bool FEEDBACK = (std::is_same_v<SHAPES, GraphFeedback> || ...);
+    constexpr bool GENES = (std::is_same_v<SHAPES, GraphGenes> || ...);
     static_assert((sizeof...(SHAPES) <= 1 && ((std::is_same_v<SHAPES, uint32_t> || std::is_same_v<SHAPES, int32_t>) && ...)) ||
-                      (sizeof...(SHAPES) == 2 && BRANCHES && FEEDBACK),
-                  "no argument, the packed codes, or the packed codes and the feedback indices");
-    constexpr int D = 2 * OPS, WAVES = 32 / CH;
+                      (sizeof...(SHAPES) == 2 && BRANCHES && FEEDBACK && !GENES) || (sizeof...(SHAPES) == 3 && BRANCHES && FEEDBACK && GENES),
+                  "no argument, the packed codes, the packed codes and the feedback indices, or those and the feedback genes");
+    constexpr int D = 2 * OPS, WAVES = 32 / CH; // (D: the genes of the forms without feedback genes)
     constexpr int RPI = kWave / CH; // rows per transposed read / store instruction (CH of them per flush)
     constexpr int U = OPS <= 4 ? 8 : 4;            // samples per block: o[OPS][U] stays in registers
     constexpr int kUnroll = OPS <= 2 && !FEEDBACK ? CH / (U / 4) : 1; // blocks unrolled per flush: the code stays in the instruction cache
@@ -99,14 +120,28 @@ __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *
         const uint32_t ind = row0 + lane < p_len ? row0 + lane : p_len - 1u;
         float f[OPS], amp[OPS], pos[OPS];
         [[maybe_unused]] float h1[OPS], h2[OPS]; // (feedback: an operator's last two shaped values, +0 at sample 0)
+        [[maybe_unused]] float bg[OPS];          // (feedback genes: a gene operator's B_j of this lane's row)
+        uint32_t stride = (uint32_t)D;           // floats between rows of values
+        if constexpr (GENES) {
+            const GraphGenes gg = second_of(shapes...);
+            stride = gg.stride;
+#pragma unroll
+            for (int j = 0; j < OPS; ++j) {
+                bg[j] = 0.0f;
+                if (gg.mask >> j & 1u) { // beta = p > 0 ? fminf(p, 2) : +0 (NaN and negatives: +0); B = beta K
+                    const float p = gg.pmin[j] + values[(size_t)ind * stride + gg.col[j]] * (gg.pmax[j] - gg.pmin[j]);
+                    bg[j] = (p > 0.0f ? fminf(p, 2.0f) : 0.0f) * kFeedbackScale;
+                }
+            }
+        }
         if constexpr (FEEDBACK) {
 #pragma unroll
             for (int j = 0; j < OPS; ++j) h1[j] = h2[j] = 0.0f;
         }
 #pragma unroll
         for (int j = 0; j < OPS; ++j) {
-            const float a = sp.pmin[2 * j + 1] + values[(size_t)ind * D + 2 * j + 1] * (sp.pmax[2 * j + 1] - sp.pmin[2 * j + 1]);
-            f[j] = sp.pmin[2 * j] + values[(size_t)ind * D + 2 * j] * (sp.pmax[2 * j] - sp.pmin[2 * j]);
+            const float a = sp.pmin[2 * j + 1] + values[(size_t)ind * stride + 2 * j + 1] * (sp.pmax[2 * j + 1] - sp.pmin[2 * j + 1]);
+            f[j] = sp.pmin[2 * j] + values[(size_t)ind * stride + 2 * j] * (sp.pmax[2 * j] - sp.pmin[2 * j]);
             amp[j] = (gm.carriers >> j & 1u) ? a : f[j] * a;
             pos[j] = 0.0f;
         }
@@ -142,6 +177,40 @@ __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *
                     }
                     auto run = [&](auto shape) {
                         if constexpr (FEEDBACK) {
+                            if constexpr (GENES) {
+                                // (the mask rides in bits 24..31 of the codes' word, above the eight 3-bit codes: the word the
+                                // block fetches anyway says which path the operator takes.  Measured against it, DESIGN.md 4.18:
+                                // the mask as a scalar of its own (the same), a marker among the scalar B_J (slower) and ONE chain
+                                // for both kinds of operator with the scalar B_J copied into a register (slower))
+                                // (this chain is a copy of the fixed index's below: keep the two identical but for bj)
+                                if (packed >> (kGeneShift + J) & 1u) { // a gene operator always runs the chain, whatever its lanes' B_J
+                                    const float bj = bg[J];
+                                    float ph[U];
+#pragma unroll
+                                    for (int u = 0; u < U; ++u) {
+                                        ph[u] = pos[J];
+                                        pos[J] += c * (cur[u] + f[J]);
+                                        if (pos[J] >= wf) pos[J] -= wf;
+                                        if (modulated && pos[J] < 0.0f) pos[J] += wf;
+                                    }
+                                    float a1 = h1[J], a2 = h2[J];
+#pragma unroll
+                                    for (int u = 0; u < U; ++u) {
+                                        const float g = (a1 + a2) * 0.5f;
+                                        float z = ph[u] + bj * g;
+                                        if (z >= wf) z -= wf;
+                                        if (z < 0.0f) z += wf;
+                                        tv[u] = shape(index_of(z));
+                                        a2 = a1;
+                                        a1 = tv[u];
+                                    }
+                                    h1[J] = a1;
+                                    h2[J] = a2;
+                                    return;
+                                }
+                            }
+                            // (the chain of the fixed index: keep it the gene copy above, statement for statement - only bj's
+                            // source differs)
                             if (fb_bits != 0u) {
                                 const float bj = __uint_as_float(fb_bits);
                                 float ph[U];
@@ -266,7 +335,7 @@ __global__ __launch_bounds__((32 / CH) * kWave) void k_synth_graph(const float *
 
 template <int OPS>
 hipError_t launch_ops(hipStream_t st, const GraphMasks &gm, const float *values, const float *wavetable, float *audio, const SynthParams &sp,
-                      uint32_t p, uint32_t n, uint32_t pitch, uint32_t cus, uint32_t shapes, const GraphFeedback *fb)
+                      uint32_t p, uint32_t n, uint32_t pitch, uint32_t cus, uint32_t shapes, const GraphFeedback *fb, const GraphGenes *genes)
 {
     // one workgroup per CU (the table), sized to the CU's share of the population up to one wavefront per SIMD; larger
     // populations loop over tiles
@@ -277,8 +346,13 @@ hipError_t launch_ops(hipStream_t st, const GraphMasks &gm, const float *values,
     const uint32_t share = (p + cus - 1) / cus;
     uint32_t waves = (share + kWave - 1) / kWave;
     if (waves > max_waves) waves = max_waves;
-    if ((shapes || fb) && waves > 4) waves = 4; // (the CH = 4 experiment form is not shaped)
+    if ((shapes || fb || genes) && waves > 4) waves = 4; // (the CH = 4 experiment form is not shaped)
     const uint32_t rows = waves * kWave, tiles = (p + rows - 1) / rows, grid = tiles < cus ? tiles : cus;
+    if (genes) { // any operator's index is a gene: the codes and the fixed indices (all +0 without any) go through this form too
+        k_synth_graph<OPS, 8, uint32_t, GraphGenes, GraphFeedback>
+            <<<grid, rows, 0, st>>>(values, wavetable, audio, sp, gm, p, n, pitch, shapes | genes->mask << kGeneShift, *genes, fb ? *fb : GraphFeedback{});
+        return hipGetLastError();
+    }
     if (fb) { // any operator feeds back: the codes go through this form too (all sine through the switch's default)
         k_synth_graph<OPS, 8, uint32_t, GraphFeedback><<<grid, rows, 0, st>>>(values, wavetable, audio, sp, gm, p, n, pitch, shapes, *fb);
         return hipGetLastError();
@@ -307,7 +381,7 @@ hipError_t launch_ops(hipStream_t st, const GraphMasks &gm, const float *values,
 
 hipError_t launch_synth_graph(hipStream_t st, const sots_voice_graph &graph, const float *values, const float *wavetable, float *audio,
                               const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus, uint32_t waveforms,
-                              const float *feedback)
+                              const float *feedback, uint32_t feedback_genes)
 {
     if (p == 0 || log2n < 8 || pitch < (1u << log2n) || pitch % 4u != 0) return hipErrorInvalidValue; // (a flush is 32 samples; 16-byte stores)
     GraphMasks gm;
@@ -319,14 +393,29 @@ hipError_t launch_synth_graph(hipStream_t st, const sots_voice_graph &graph, con
     // (checked indices are +0 beyond the operators; all zero launches what is launched without the setting)
     GraphFeedback scaled;
     const GraphFeedback *fb = feedback && scale_feedback(feedback, graph.num_operators, scaled.b) ? &scaled : nullptr;
+    // (a checked mask holds nothing beyond the operators; 0 launches what is launched without it)
+    GraphGenes held{};
+    const GraphGenes *genes = nullptr;
+    if (const uint32_t mask = feedback_genes & ((1u << graph.num_operators) - 1u)) {
+        held.mask = mask;
+        held.stride = graph_dims(graph.num_operators, mask);
+        if (held.stride > SOTS_MAX_DIMS) return hipErrorInvalidValue;
+        for (uint32_t j = 0; j < graph.num_operators; ++j) {
+            if (!(mask >> j & 1u)) continue;
+            held.col[j] = feedback_gene_column(graph.num_operators, mask, j);
+            held.pmin[j] = sp.pmin[held.col[j]];
+            held.pmax[j] = sp.pmax[held.col[j]];
+        }
+        genes = &held;
+    }
     switch (graph.num_operators) {
-    case 2: return launch_ops<2>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
-    case 3: return launch_ops<3>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
-    case 4: return launch_ops<4>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
-    case 5: return launch_ops<5>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
-    case 6: return launch_ops<6>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
-    case 7: return launch_ops<7>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
-    case 8: return launch_ops<8>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb);
+    case 2: return launch_ops<2>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb, genes);
+    case 3: return launch_ops<3>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb, genes);
+    case 4: return launch_ops<4>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb, genes);
+    case 5: return launch_ops<5>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb, genes);
+    case 6: return launch_ops<6>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb, genes);
+    case 7: return launch_ops<7>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb, genes);
+    case 8: return launch_ops<8>(st, gm, values, wavetable, audio, sp, p, n, pitch, cus, shapes, fb, genes);
     default: return hipErrorInvalidValue;
     }
 }

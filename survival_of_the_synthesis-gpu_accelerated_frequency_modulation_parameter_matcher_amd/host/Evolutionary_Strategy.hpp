@@ -213,9 +213,17 @@ public:
     SOTS_NO_CONTRACT_ATTR void synthesiseAudioGraph(uint32_t ops, uint32_t carriers, const uint32_t *modulators, const uint32_t *waveforms,
                                                     const float *feedback, const std::vector<float> aParams, float *aAudioBuffer)
     {
+        synthesiseAudioGraph(ops, carriers, modulators, waveforms, feedback, 0u, aParams, aAudioBuffer);
+    }
+    // ... and with chosen operators' indices as genes (sots_create_graph_genes, include/sots_hip.h): bit j of feedbackGenes
+    // set, operator j's index is the row's gene 2 ops + (set bits below j), scaled like every gene and clamped to the
+    // effective index p > 0 ? min(p, 2) : +0.  Such an operator always takes the feedback step, also with an index of +0.
+    SOTS_NO_CONTRACT_ATTR void synthesiseAudioGraph(uint32_t ops, uint32_t carriers, const uint32_t *modulators, const uint32_t *waveforms,
+                                                    const float *feedback, uint32_t feedbackGenes, const std::vector<float> aParams, float *aAudioBuffer)
+    {
         SOTS_NO_CONTRACT
         float f[8], level[8], pos[8], o[8], fb[8], h1[8], h2[8];
-        uint32_t heard = 0;
+        uint32_t heard = 0, gene = 2 * ops;
         const float wf = (float)wavetableSize;
         for (uint32_t j = 0; j < ops && j < 8; ++j) {
             f[j] = scaled(aParams[2 * j], 2 * j);
@@ -223,6 +231,11 @@ public:
             level[j] = (carriers >> j & 1u) ? a : f[j] * a;
             pos[j] = 0.0f;
             fb[j] = feedback ? feedback[j] * 0x1.45f306p+12f : 0.0f; // K: the fp32 nearest W / 2 pi
+            if (feedbackGenes >> j & 1u) {
+                const float p = scaled(aParams[gene], gene);
+                fb[j] = (p > 0.0f ? (p < 2.0f ? p : 2.0f) : 0.0f) * 0x1.45f306p+12f;
+                ++gene;
+            }
             h1[j] = h2[j] = 0.0f;
             heard += carriers >> j & 1u;
         }
@@ -230,7 +243,7 @@ public:
             float y = -0.0f; // (-0 + x is x bit for bit: the sums below add only what is there)
             for (uint32_t j = 0; j < ops && j < 8; ++j) {
                 float at = pos[j];
-                if (feedback && feedback[j] != 0.0f) {
+                if ((feedbackGenes >> j & 1u) || (feedback && feedback[j] != 0.0f)) {
                     const float g = (h1[j] + h2[j]) * 0.5f;
                     const float offset = fb[j] * g; // (multiply, then add)
                     at = pos[j] + offset;

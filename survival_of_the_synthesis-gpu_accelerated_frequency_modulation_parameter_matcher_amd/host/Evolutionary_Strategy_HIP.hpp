@@ -56,6 +56,10 @@ struct Evolutionary_Strategy_HIP_Arguments
     // ... and their feedback indices (type.HIP.voiceFeedback; sots_set_voice_feedback): one number in [0, 2]
     // per operator, or empty: none.  Only with the graph voice, as the waveforms.
     std::vector<float> voiceFeedback;
+    // ... or, for the operators in this mask, a gene of the individual (type.HIP.voiceFeedbackGenes; sots_create_graph_genes,
+    // DESIGN.md 4.18): numDimensions = 2 x num_operators + the set bits, the genes' ranges behind the others.  Only with the
+    // graph voice and not with renderMode 3 to 6: the constructor throws before any device work; the library refuses the rest.
+    uint32_t voiceFeedbackGenes = 0;
     bool fusedGenerations = true;     // executeAllGenerations uses the fused kernel loop
     // general.isBenchmarking (parameters.json:7, main.cpp:85).  true: every launch is bracketed by a
     // hipEvent pair and lands in the CSV under the reference's stage names (an event pair costs
@@ -219,10 +223,13 @@ private:
     void createBatch()
     {
         const bool graphVoice = cfg_.synth_kind == SOTS_SYNTH_GRAPH;
-        const int rc = graphVoice ? sots_batch_create_graph(&cfg_, &args_.voiceGraph, args_.chunksInFlight, &batch_)
-                                  : sots_batch_create(&cfg_, args_.chunksInFlight, &batch_);
+        const bool genes = graphVoice && args_.voiceFeedbackGenes != 0u;
+        const int rc = genes        ? sots_batch_create_graph_genes(&cfg_, &args_.voiceGraph, args_.voiceFeedbackGenes, args_.chunksInFlight, &batch_)
+                       : graphVoice ? sots_batch_create_graph(&cfg_, &args_.voiceGraph, args_.chunksInFlight, &batch_)
+                                    : sots_batch_create(&cfg_, args_.chunksInFlight, &batch_);
         if (rc != SOTS_OK)
-            throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + (graphVoice ? "sots_batch_create_graph: " : "sots_batch_create: ") +
+            throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") +
+                                     (genes ? "sots_batch_create_graph_genes: " : graphVoice ? "sots_batch_create_graph: " : "sots_batch_create: ") +
                                      sots_batch_last_error(nullptr));
         if (!args_.voiceWaveforms.empty() &&
             sots_batch_set_voice_waveforms(batch_, args_.voiceWaveforms.data(), (uint32_t)args_.voiceWaveforms.size()) != SOTS_OK)
@@ -423,6 +430,11 @@ public:
             throw std::runtime_error("Evolutionary_Strategy_HIP: voiceWaveforms need the operator-graph voice");
         if (!graphVoice && !args_.voiceFeedback.empty())
             throw std::runtime_error("Evolutionary_Strategy_HIP: voiceFeedback needs the operator-graph voice");
+        if (!graphVoice && args_.voiceFeedbackGenes)
+            throw std::runtime_error("Evolutionary_Strategy_HIP: voiceFeedbackGenes need the operator-graph voice");
+        if (args_.voiceFeedbackGenes && args_.renderMode >= 3u)
+            throw std::runtime_error("Evolutionary_Strategy_HIP: renderMode 3 to 6 take the feedback index from the voice, not from the row: "
+                                     "voiceFeedbackGenes are rendered by renderMode 0 (sots_render_overlap_add)");
         cfg_.workgroup_size = args_.workgroupX * args_.workgroupY * args_.workgroupZ;
         cfg_.device = args_.deviceOrdinal;
         cfg_.gid_base = args_.gidBase;
@@ -451,9 +463,13 @@ public:
             if (rc != SOTS_OK) throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_group_create: ") + sots_group_last_error(nullptr));
             ctx_ = sots_group_island(group_, 0);
         } else {
-            const int rc = graphVoice ? sots_create_graph(&cfg_, &args_.voiceGraph, &ctx_) : sots_create(&cfg_, &ctx_);
+            const bool genes = graphVoice && args_.voiceFeedbackGenes != 0u;
+            const int rc = genes        ? sots_create_graph_genes(&cfg_, &args_.voiceGraph, args_.voiceFeedbackGenes, &ctx_)
+                           : graphVoice ? sots_create_graph(&cfg_, &args_.voiceGraph, &ctx_)
+                                        : sots_create(&cfg_, &ctx_);
             if (rc != SOTS_OK)
-                throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") + (graphVoice ? "sots_create_graph: " : "sots_create: ") + sots_last_error(nullptr));
+                throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: ") +
+                                         (genes ? "sots_create_graph_genes: " : graphVoice ? "sots_create_graph: " : "sots_create: ") + sots_last_error(nullptr));
         }
         targetFFT_.assign(objective.fftHalfSize, 0.0f);
         if (!args_.voiceWaveforms.empty()) // (the graph voice: one device, no group)

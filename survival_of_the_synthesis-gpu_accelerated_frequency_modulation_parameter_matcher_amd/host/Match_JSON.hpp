@@ -343,7 +343,7 @@ inline bool readVoiceGraphKeys(const Json &h, uint32_t numDimensions, bool rende
                                  std::to_string((unsigned long long)std::fmin(ops, 1.8e19)) + " operators, at most 8)");
     for (size_t j = 0; j < v["modulators"].arr.size(); ++j) g.modulators[j] = mask(v["modulators"].arr[j]);
     g.carriers = mask(v["carriers"]);
-    if (numDimensions != 2u * g.num_operators)
+    if (numDimensions != 2u * g.num_operators && !h.has("voiceFeedbackGenes")) // (with that key: readVoiceFeedbackGenesKey counts the genes)
         throw std::runtime_error("parameters.json: evolutionary.numDimensions " + std::to_string(numDimensions) + " must be 2 x type.HIP.voiceGraph.operators = " +
                                  std::to_string(2u * g.num_operators));
     if (renderMatch && (renderMode == 1u || renderMode == 2u))
@@ -400,6 +400,48 @@ inline bool readVoiceFeedbackKey(const Json &h, bool graphVoice, uint32_t operat
         out.push_back(b == 0.0f ? 0.0f : b);
     }
     index = out;
+    return true;
+}
+
+// type.HIP.voiceFeedbackGenes (sots_create_graph_genes, include/sots_hip.h): one 0 or 1 per operator, like
+// voiceFeedback; 1 makes that operator's feedback index a gene of the individual - evolutionary.numDimensions is then
+// 2 x operators + the number of 1s, and paramMins / paramMaxs hold that many entries, the genes' ranges (within [0, 2]) behind
+// the others.  Returns whether the key is there; mask receives bit j for operator j.  Throws - before any device work -
+// without type.HIP.synth "graph", on anything but a list of `operators` entries that are 0 or 1, on an operator that also has
+// a voiceFeedback other than 0, on more than 16 genes, on numDimensions / paramMins / paramMaxs that do not count the genes,
+// and on any "graph..." renderMode (those renderers take the index from the voice, not from the row; "overlapAdd" renders
+// every row with its own).  The ranges themselves are the library's rule.
+inline bool readVoiceFeedbackGenesKey(const Json &h, bool graphVoice, uint32_t operators, const std::vector<float> &voiceFeedback, uint32_t numDimensions,
+                                      size_t numParamMins, size_t numParamMaxs, uint32_t renderMode, uint32_t &mask)
+{
+    if (!h.has("voiceFeedbackGenes")) return false;
+    const std::string what = "parameters.json: type.HIP.voiceFeedbackGenes";
+    if (!graphVoice) throw std::runtime_error(what + " needs type.HIP.synth \"graph\"");
+    const Json &v = h["voiceFeedbackGenes"];
+    if (v.kind != Json::Array || v.arr.size() != operators)
+        throw std::runtime_error(what + " needs one 0 or 1 per operator (" + (v.kind == Json::Array ? std::to_string(v.arr.size()) + " entries" : std::string("not a list")) +
+                                 ", " + std::to_string(operators) + " operators)");
+    uint32_t m = 0, genes = 0;
+    for (size_t j = 0; j < v.arr.size(); ++j) {
+        const Json &e = v.arr[j];
+        if (e.kind != Json::Number || (e.num != 0.0 && e.num != 1.0)) throw std::runtime_error(what + ": an entry that is neither 0 nor 1");
+        if (e.num == 0.0) continue;
+        if (j < voiceFeedback.size() && voiceFeedback[j] != 0.0f)
+            throw std::runtime_error(what + ": operator " + std::to_string(j) + " also has a type.HIP.voiceFeedback of " + std::to_string(voiceFeedback[j]) +
+                                     " (one or the other)");
+        m |= 1u << j;
+        ++genes;
+    }
+    const uint32_t d = 2u * operators + genes;
+    const std::string count = ": " + std::to_string(operators) + " operators and " + std::to_string(genes) + " feedback genes ";
+    if (d > 16u) throw std::runtime_error(what + count + "are " + std::to_string(d) + " genes, more than 16");
+    if (numDimensions != d || numParamMins != d || numParamMaxs != d)
+        throw std::runtime_error(what + count + "need numDimensions " + std::to_string(d) + " with " + std::to_string(d) + " paramMins and paramMaxs, got " +
+                                 std::to_string(numDimensions) + ", " + std::to_string(numParamMins) + " and " + std::to_string(numParamMaxs));
+    static const char *const modes[] = {"", "", "", "graphContinuous", "graphContinuousGlide", "graphFeedback", "graphFeedbackGlide"};
+    if (m && renderMode >= 3u && renderMode <= 6u)
+        throw std::runtime_error(what + ": every row has its own feedback index, which type.HIP.renderMode \"" + modes[renderMode] + "\" cannot render (\"overlapAdd\" does)");
+    mask = m;
     return true;
 }
 

@@ -31,6 +31,10 @@
 //   "voiceWaveforms" with "voiceGraph": one waveform per operator, each of "sine" (the default), "half", "abs", "pulse",
 //                 "even", "absEven", "square", "saw" - shapes cut out of the one sine table (sots_set_voice_waveforms), so
 //                 that an operator emits a harmonic series.  Search, rendering, report and the host's own synthesiser use it.
+//   "voiceFeedbackGenes" with "voiceGraph": one 0 or 1 per operator; 1 makes that operator's feedback index a gene of the
+//                 individual (sots_create_graph_genes): "numDimensions" is 2 n + the number of 1s, "paramMins" / "paramMaxs"
+//                 carry the genes' ranges, within [0, 2], behind the others, and "matchPath" writes the index per chunk with
+//                 the other columns.  Not on an operator with a "voiceFeedback" other than 0, not with a "graph..." renderMode.
 //   "voiceFeedback" with "voiceGraph": one feedback index in [0, 2] per operator, 0 (the default) for none: the operator's phase
 //                 is offset by index x W / 2 pi x the mean of its own last two values (sots_set_voice_feedback), so that a
 //                 sine operator emits a harmonic series whose brightness follows the index.  Used wherever the waveforms are.
@@ -171,6 +175,9 @@ int main(int argc, char *argv[])
             (void)readVoiceWaveformsKey(h, graphVoice, args.voiceGraph.num_operators, args.voiceWaveforms);
             // ... and their feedback indices: "voiceFeedback", one number per operator (Match_JSON.hpp)
             (void)readVoiceFeedbackKey(h, graphVoice, args.voiceGraph.num_operators, args.voiceFeedback);
+            // ... or chosen operators' indices as genes of the individual: "voiceFeedbackGenes", a 0 or 1 per operator (Match_JSON.hpp)
+            (void)readVoiceFeedbackGenesKey(h, graphVoice, args.voiceGraph.num_operators, args.voiceFeedback, args.es_args.pop.numDimensions,
+                                            args.es_args.paramMin.size(), args.es_args.paramMax.size(), args.renderMode, args.voiceFeedbackGenes);
             // "graphContinuous" / "graphContinuousGlide" rendering: the graph voice's, without feedback (Match_JSON.hpp)
             checkGraphRenderMode(args.renderMode, graphVoice, args.renderMatch, args.voiceFeedback);
         }
@@ -181,7 +188,7 @@ int main(int argc, char *argv[])
         auto synthesise = [&](Objective &obj, const std::vector<float> &p, float *out) {
             if (args.synthKind == SOTS_SYNTH_GRAPH)
                 obj.synthesiseAudioGraph(vg.num_operators, vg.carriers, vg.modulators, args.voiceWaveforms.empty() ? nullptr : args.voiceWaveforms.data(),
-                                         args.voiceFeedback.empty() ? nullptr : args.voiceFeedback.data(), p, out);
+                                         args.voiceFeedback.empty() ? nullptr : args.voiceFeedback.data(), args.voiceFeedbackGenes, p, out);
             else if (D == 4) obj.synthesiseAudio(p, out);
             else if (D == 6) obj.synthesiseAudioDoubleSeries(p, out);
             else if (D == 8) obj.synthesiseAudioQuadSeries(p, out);
