@@ -596,55 +596,44 @@ class HipES:
         self._check(self.L.sots_read_synth(self._h, None, 0, None, 0, _ptr(t), t.nbytes))
         return t
 
-    # -- overlap-add rendering of a parameter track --
-    def render_overlap_add(self, values, hop, windowed=True, rows_per_pass=0, out_samples=None):
-        """values[M][D] unit-range genes, row c standing for samples [c hop, c hop + N): the windowed (or rectangular)
-        overlap-add of the rows' audio, normalised by the summed window.  out_samples None: the covered (M-1) hop + N."""
+    # -- rendering of a parameter track: the rows, the output and the call that the four renderers share --
+    def _render(self, entry, values, hop, out_samples, args):
         v = _f32(values).reshape(-1, self.D)
         rows = v.shape[0]
         n_out = (rows - 1) * hop + self.N if out_samples is None else int(out_samples)
         out = np.empty(max(n_out, 0), np.float32)
-        args = RenderArgs(C.sizeof(RenderArgs), hop, RENDER_WINDOWED if windowed else 0, rows_per_pass)
-        self._check(self.L.sots_render_overlap_add(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
+        self._check(entry(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
         return out
+
+    # -- overlap-add rendering of a parameter track --
+    def render_overlap_add(self, values, hop, windowed=True, rows_per_pass=0, out_samples=None):
+        """values[M][D] unit-range genes, row c standing for samples [c hop, c hop + N): the windowed (or rectangular)
+        overlap-add of the rows' audio, normalised by the summed window.  out_samples None: the covered (M-1) hop + N."""
+        args = RenderArgs(C.sizeof(RenderArgs), hop, RENDER_WINDOWED if windowed else 0, rows_per_pass)
+        return self._render(self.L.sots_render_overlap_add, values, hop, out_samples, args)
 
     # -- phase-continuous rendering of a parameter track --
     def render_continuous(self, values, hop, glide=False, samples_per_pass=0, out_samples=None):
         """values[M][D] unit-range genes, row c anchored at sample c hop + N/2: the track as one voice whose oscillators
         never restart, the genes held from anchor to anchor (switching half way) or, with glide, interpolated between
         them.  out_samples None: (M-1) hop + N."""
-        v = _f32(values).reshape(-1, self.D)
-        rows = v.shape[0]
-        n_out = (rows - 1) * hop + self.N if out_samples is None else int(out_samples)
-        out = np.empty(max(n_out, 0), np.float32)
         args = RenderContinuousArgs(C.sizeof(RenderContinuousArgs), hop, RENDER_GLIDE if glide else 0, samples_per_pass)
-        self._check(self.L.sots_render_continuous(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
-        return out
+        return self._render(self.L.sots_render_continuous, values, hop, out_samples, args)
 
     # -- phase-continuous rendering of a parameter track of the operator-graph voice --
     def render_graph_continuous(self, values, hop, glide=False, samples_per_pass=0, out_samples=None):
         """render_continuous for a context of the graph voice (graph=...), with its waveforms: values[M][2 x operators].
         A context with a feedback index other than 0 is refused (render_overlap_add renders it)."""
-        v = _f32(values).reshape(-1, self.D)
-        rows = v.shape[0]
-        n_out = (rows - 1) * hop + self.N if out_samples is None else int(out_samples)
-        out = np.empty(max(n_out, 0), np.float32)
         args = RenderContinuousArgs(C.sizeof(RenderContinuousArgs), hop, RENDER_GLIDE if glide else 0, samples_per_pass)
-        self._check(self.L.sots_render_graph_continuous(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
-        return out
+        return self._render(self.L.sots_render_graph_continuous, values, hop, out_samples, args)
 
     # -- ... with feedback operators --
     def render_graph_feedback(self, values, hop, glide=False, samples_per_pass=0, chain_form=0, relax_cap=0, out_samples=None):
         """render_graph_continuous for a context whose operators may have feedback indices (set_voice_feedback).
         chain_form: CHAIN_LIBRARY, CHAIN_SERIAL or CHAIN_RELAX; relax_cap: sweeps per tile before a tile is finished serially
         (0: the library's choice).  Neither changes a bit of the result."""
-        v = _f32(values).reshape(-1, self.D)
-        rows = v.shape[0]
-        n_out = (rows - 1) * hop + self.N if out_samples is None else int(out_samples)
-        out = np.empty(max(n_out, 0), np.float32)
         args = RenderGraphFeedbackArgs(C.sizeof(RenderGraphFeedbackArgs), hop, RENDER_GLIDE if glide else 0, samples_per_pass, chain_form, relax_cap)
-        self._check(self.L.sots_render_graph_feedback(self._h, _ptr(v), v.nbytes, rows, C.byref(args), _ptr(out), out.size))
-        return out
+        return self._render(self.L.sots_render_graph_feedback, values, hop, out_samples, args)
 
     # -- stages --
     def recombine(self):

@@ -386,6 +386,80 @@ int record_generation(sots_ctx *ctx)
     return SOTS_OK;
 }
 
+// ---- phase-continuous rendering: the passes ----
+// What the three entry points share once their checks have passed: the passes.  `who` names the entry point in a refusal;
+// cap: the most samples its scratch lets a pass hold; layout(samples): its pass struct (ContPass, GraphPass) for passes of so
+// many samples, with .lay and whatever else is its own filled in; state_words: the words from lay.carry on that a pass
+// leaves for the next, cleared before the first; launch(pass) enqueues one pass.
+template <class LAYOUT, class LAUNCH>
+int render_passes(sots_ctx *ctx, const char *who, const float *values, uint32_t num_rows, uint32_t hop, uint32_t flags, uint32_t samples_per_pass,
+                  uint64_t cap, uint32_t state_words, float *out, uint64_t out_samples, LAYOUT layout, LAUNCH launch)
+{
+    const uint32_t N = ctx->N, D = ctx->D;
+    const uint64_t covered = (uint64_t)(num_rows - 1u) * hop + N, want = out_samples < covered ? out_samples : covered;
+    // A pass is limited by its scratch (cap) and by the rows of genes its samples look at: at most count / hop + 3 of them,
+    // kContMaxValueFloats floats.
+    uint64_t pass = samples_per_pass ? samples_per_pass : cap;
+    const uint64_t by_rows = (uint64_t)(kContMaxValueFloats / D - 3u) * hop;
+    pass = pass > cap ? cap : pass;
+    pass = pass > by_rows ? by_rows : pass;
+    pass = pass > want ? (want ? want : 1u) : pass;
+    auto ps = layout((uint32_t)pass);
+    const size_t max_rows = (size_t)(pass / hop) + 3u;
+    hipError_t e = render_reserve(ctx->render, max_rows * D, 0, ps.lay.stride);
+    if (e == hipSuccess) e = render_reserve_words(ctx->render, ps.lay.words);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return SOTS_FAIL(ctx, SOTS_ERR_HIP, "%s: scratch allocation failed: %s", who, hipGetErrorString(e));
+    }
+    // every operator starts at phase 0 (a feedback operator with h1 = h2 = +0); a pass leaves its end state for the next one
+    SOTS_HIP(ctx, hipMemsetAsync(ctx->render.words + ps.lay.carry, 0, state_words * sizeof(uint32_t), ctx->stream));
+    ps.values = ctx->render.values, ps.wavetable = ctx->wavetable, ps.words = ctx->render.words, ps.out = ctx->render.out;
+    ps.num_rows = num_rows, ps.hop = hop, ps.half_n = N / 2u, ps.glide = flags & SOTS_RENDER_GLIDE;
+    ps.sp = ctx->sp;
+    for (uint64_t s0 = 0; s0 < want; s0 += pass) {
+        const uint32_t count = (uint32_t)(want - s0 < pass ? want - s0 : pass);
+        uint32_t k0, k1, r;
+        cont_position((uint32_t)s0, N / 2u, hop, num_rows, k0, r);
+        cont_position((uint32_t)s0 + count - 1u, N / 2u, hop, num_rows, k1, r);
+        k1 = k1 + 1u < num_rows ? k1 + 1u : num_rows - 1u; // (the row after: the second half of a hop, the far end of a glide)
+        SOTS_HIP(ctx, hipMemcpyAsync(ctx->render.values, values + (size_t)k0 * D, (size_t)(k1 - k0 + 1u) * D * sizeof(float),
+                                     hipMemcpyHostToDevice, ctx->stream));
+        ps.row_base = k0, ps.n0 = (uint32_t)s0, ps.count = count;
+        SOTS_HIP(ctx, launch(ps));
+        // (stream order keeps the next pass off the scratch until this copy has read it)
+        SOTS_HIP(ctx, hipMemcpyAsync(out + s0, ctx->render.out, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (out_samples > covered) memset(out + covered, 0, (size_t)(out_samples - covered) * sizeof(float));
+    return SOTS_OK;
+}
+
+// the operator-graph voice: the flagged operators (beta != 0), their B_j and the form of each one's chain.  None flagged: no
+// chain launch, and hist, behind the eight carries, is neither cleared nor touched.
+int render_graph_passes(sots_ctx *ctx, const char *who, const float *values, uint32_t num_rows, uint32_t hop, uint32_t flags,
+                        uint32_t samples_per_pass, uint32_t chain_form, uint32_t relax_cap, float *out, uint64_t out_samples)
+{
+    const uint32_t ops = ctx->graph.num_operators;
+    GraphPass fb{};
+    scale_feedback(ctx->feedback, ops, fb.scaled);
+    for (uint32_t j = 0; j < ops; ++j) {
+        if (ctx->feedback[j] == 0.0f) continue;
+        fb.fb_mask |= 1u << j;
+        const uint32_t form = chain_form ? chain_form : graph_feedback_form(ctx->feedback[j]);
+        if (form == kChainRelax) fb.forms |= 1u << j;
+    }
+    fb.relax_cap = relax_cap ? relax_cap : kRelaxCapLibrary;
+    const uint32_t flagged = (uint32_t)__builtin_popcount(fb.fb_mask);
+    return render_passes(
+        ctx, who, values, num_rows, hop, flags, samples_per_pass, graph_feedback_max_pass(ops, flagged), fb.fb_mask ? 8u + 16u : 8u, out, out_samples,
+        [&](uint32_t samples) {
+            fb.lay = graph_layout(ops, flagged, samples);
+            return fb;
+        },
+        [&](const GraphPass &ps) { return launch_graph_pass(ctx->stream, ctx->graph, ctx->waveforms, ps, ctx->num_cus); });
+}
+
 } // namespace
 
 // =======================================================================================
@@ -1164,7 +1238,7 @@ int sots_render_overlap_add(sots_ctx *ctx, const float *values, size_t values_by
     return SOTS_OK;
 }
 
-// ---- phase-continuous rendering ------------------------------------------------
+// ---- phase-continuous rendering --------------------------------------
 int sots_render_continuous(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows, const sots_render_continuous_args *args,
                            float *out, uint64_t out_samples)
 {
@@ -1172,49 +1246,18 @@ int sots_render_continuous(sots_ctx *ctx, const float *values, size_t values_byt
     SOTS_REFUSE(ctx, render_continuous_voice_check(ctx->cfg.synth_kind));
     SOTS_REFUSE(ctx, render_continuous_check(args, ctx->N, ctx->D, ctx->synth_arith, values, values_bytes, num_rows, out, out_samples));
     if (int rc = engine_bind(*ctx)) return rc;
-    const uint32_t N = ctx->N, D = ctx->D, hop = args->hop, kind = ctx->cfg.synth_kind;
-    const uint64_t covered = (uint64_t)(num_rows - 1u) * hop + N, want = out_samples < covered ? out_samples : covered;
-    // A pass is limited by its phase buffers (kContMaxPass) and by the rows of genes its samples look at: at most
-    // count / hop + 3 of them, kContMaxValueFloats floats.
-    uint64_t pass = args->samples_per_pass ? args->samples_per_pass : kContMaxPass;
-    const uint64_t by_rows = (uint64_t)(kContMaxValueFloats / D - 3u) * hop;
-    pass = pass > kContMaxPass ? kContMaxPass : pass;
-    pass = pass > by_rows ? by_rows : pass;
-    pass = pass > want ? (want ? want : 1u) : pass;
-    const ContLayout lay = cont_layout(kind, (uint32_t)pass);
-    const size_t max_rows = (size_t)(pass / hop) + 3u;
-    hipError_t e = render_reserve(ctx->render, max_rows * D, 0, lay.stride);
-    if (e == hipSuccess) e = render_reserve_words(ctx->render, lay.words);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return SOTS_FAIL(ctx, SOTS_ERR_HIP, "sots_render_continuous: scratch allocation failed: %s", hipGetErrorString(e));
-    }
-    // every operator starts at phase 0; a pass leaves its end phases for the next one
-    SOTS_HIP(ctx, hipMemsetAsync(ctx->render.words + lay.carry, 0, kContMaxStages * kContMaxChains * sizeof(uint32_t), ctx->stream));
-    for (uint64_t s0 = 0; s0 < want; s0 += pass) {
-        const uint32_t count = (uint32_t)(want - s0 < pass ? want - s0 : pass);
-        uint32_t k0, k1, r;
-        cont_position((uint32_t)s0, N / 2u, hop, num_rows, k0, r);
-        cont_position((uint32_t)s0 + count - 1u, N / 2u, hop, num_rows, k1, r);
-        k1 = k1 + 1u < num_rows ? k1 + 1u : num_rows - 1u; // (the row after: the second half of a hop, the far end of a glide)
-        SOTS_HIP(ctx, hipMemcpyAsync(ctx->render.values, values + (size_t)k0 * D, (size_t)(k1 - k0 + 1u) * D * sizeof(float),
-                                     hipMemcpyHostToDevice, ctx->stream));
-        ContPass ps{};
-        ps.values = ctx->render.values, ps.wavetable = ctx->wavetable, ps.words = ctx->render.words, ps.out = ctx->render.out;
-        ps.lay = lay;
-        ps.row_base = k0, ps.num_rows = num_rows, ps.hop = hop, ps.half_n = N / 2u, ps.glide = args->flags & SOTS_RENDER_GLIDE;
-        ps.n0 = (uint32_t)s0, ps.count = count;
-        ps.sp = ctx->sp;
-        SOTS_HIP(ctx, launch_continuous_pass(ctx->stream, kind, ps, ctx->num_cus));
-        // (stream order keeps the next pass off the scratch until this copy has read it)
-        SOTS_HIP(ctx, hipMemcpyAsync(out + s0, ctx->render.out, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (out_samples > covered) memset(out + covered, 0, (size_t)(out_samples - covered) * sizeof(float));
-    return SOTS_OK;
+    const uint32_t kind = ctx->cfg.synth_kind;
+    return render_passes(
+        ctx, "sots_render_continuous", values, num_rows, args->hop, args->flags, args->samples_per_pass, kContMaxPass, kContMaxStages * kContMaxChains,
+        out, out_samples,
+        [&](uint32_t samples) {
+            ContPass ps{};
+            ps.lay = cont_layout(kind, samples);
+            return ps;
+        },
+        [&](const ContPass &ps) { return launch_continuous_pass(ctx->stream, kind, ps, ctx->num_cus); });
 }
 
-// ---- phase-continuous rendering of the operator-graph voice ---------------------
 int sots_render_graph_continuous(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
                                  const sots_render_continuous_args *args, float *out, uint64_t out_samples)
 {
@@ -1222,49 +1265,11 @@ int sots_render_graph_continuous(sots_ctx *ctx, const float *values, size_t valu
     SOTS_REFUSE(ctx, render_graph_continuous_check(ctx->cfg.synth_kind, ctx->feedback, args, ctx->N, ctx->D, values, values_bytes, num_rows, out,
                                                    out_samples, ctx->feedback_genes));
     if (int rc = engine_bind(*ctx)) return rc;
-    const uint32_t N = ctx->N, D = ctx->D, hop = args->hop, ops = ctx->graph.num_operators;
-    const uint64_t covered = (uint64_t)(num_rows - 1u) * hop + N, want = out_samples < covered ? out_samples : covered;
-    // A pass is limited by its phase buffers (graph_continuous_max_pass: a buffer per operator) and by the rows of genes its
-    // samples look at: at most count / hop + 3 of them, kContMaxValueFloats floats.
-    const uint64_t cap = graph_continuous_max_pass(ops), by_rows = (uint64_t)(kContMaxValueFloats / D - 3u) * hop;
-    uint64_t pass = args->samples_per_pass ? args->samples_per_pass : cap;
-    pass = pass > cap ? cap : pass;
-    pass = pass > by_rows ? by_rows : pass;
-    pass = pass > want ? (want ? want : 1u) : pass;
-    const GraphContLayout lay = graph_cont_layout(ops, (uint32_t)pass);
-    const size_t max_rows = (size_t)(pass / hop) + 3u;
-    hipError_t e = render_reserve(ctx->render, max_rows * D, 0, lay.stride);
-    if (e == hipSuccess) e = render_reserve_words(ctx->render, lay.words);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return SOTS_FAIL(ctx, SOTS_ERR_HIP, "sots_render_graph_continuous: scratch allocation failed: %s", hipGetErrorString(e));
-    }
-    // every operator starts at phase 0; a pass leaves its end phases for the next one
-    SOTS_HIP(ctx, hipMemsetAsync(ctx->render.words + lay.carry, 0, 8u * sizeof(uint32_t), ctx->stream));
-    for (uint64_t s0 = 0; s0 < want; s0 += pass) {
-        const uint32_t count = (uint32_t)(want - s0 < pass ? want - s0 : pass);
-        uint32_t k0, k1, r;
-        cont_position((uint32_t)s0, N / 2u, hop, num_rows, k0, r);
-        cont_position((uint32_t)s0 + count - 1u, N / 2u, hop, num_rows, k1, r);
-        k1 = k1 + 1u < num_rows ? k1 + 1u : num_rows - 1u; // (the row after: the second half of a hop, the far end of a glide)
-        SOTS_HIP(ctx, hipMemcpyAsync(ctx->render.values, values + (size_t)k0 * D, (size_t)(k1 - k0 + 1u) * D * sizeof(float),
-                                     hipMemcpyHostToDevice, ctx->stream));
-        GraphContPass ps{};
-        ps.values = ctx->render.values, ps.wavetable = ctx->wavetable, ps.words = ctx->render.words, ps.out = ctx->render.out;
-        ps.lay = lay;
-        ps.row_base = k0, ps.num_rows = num_rows, ps.hop = hop, ps.half_n = N / 2u, ps.glide = args->flags & SOTS_RENDER_GLIDE;
-        ps.n0 = (uint32_t)s0, ps.count = count;
-        ps.sp = ctx->sp;
-        SOTS_HIP(ctx, launch_graph_continuous_pass(ctx->stream, ctx->graph, ctx->waveforms, ps, ctx->num_cus));
-        // (stream order keeps the next pass off the scratch until this copy has read it)
-        SOTS_HIP(ctx, hipMemcpyAsync(out + s0, ctx->render.out, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (out_samples > covered) memset(out + covered, 0, (size_t)(out_samples - covered) * sizeof(float));
-    return SOTS_OK;
+    // (the check has seen to it that no operator is flagged)
+    return render_graph_passes(ctx, "sots_render_graph_continuous", values, num_rows, args->hop, args->flags, args->samples_per_pass, 0, 0, out,
+                               out_samples);
 }
 
-// ---- ... with feedback operators -------------------------------------------------
 int sots_render_graph_feedback(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
                                const sots_render_graph_feedback_args *args, float *out, uint64_t out_samples)
 {
@@ -1272,59 +1277,8 @@ int sots_render_graph_feedback(sots_ctx *ctx, const float *values, size_t values
     SOTS_REFUSE(ctx, render_graph_feedback_check(ctx->cfg.synth_kind, args, ctx->N, ctx->D, values, values_bytes, num_rows, out, out_samples,
                                                  ctx->feedback_genes));
     if (int rc = engine_bind(*ctx)) return rc;
-    const uint32_t N = ctx->N, D = ctx->D, hop = args->hop, ops = ctx->graph.num_operators;
-    const uint64_t covered = (uint64_t)(num_rows - 1u) * hop + N, want = out_samples < covered ? out_samples : covered;
-    // the flagged operators, their B_j and the form of each one's chain; none flagged: sots_render_graph_continuous's launches
-    GraphFbPass fb{};
-    scale_feedback(ctx->feedback, ops, fb.scaled);
-    for (uint32_t j = 0; j < ops; ++j) {
-        if (ctx->feedback[j] == 0.0f) continue;
-        fb.fb_mask |= 1u << j;
-        const uint32_t form = args->chain_form ? args->chain_form : graph_feedback_form(ctx->feedback[j]);
-        if (form == kChainRelax) fb.forms |= 1u << j;
-    }
-    fb.relax_cap = args->relax_cap ? args->relax_cap : kRelaxCapLibrary;
-    const uint32_t flagged = (uint32_t)__builtin_popcount(fb.fb_mask);
-    // A pass is limited by its phase and t buffers (graph_feedback_max_pass) and by the rows of genes its samples look at: at
-    // most count / hop + 3 of them, kContMaxValueFloats floats.
-    const uint64_t cap = graph_feedback_max_pass(ops, flagged), by_rows = (uint64_t)(kContMaxValueFloats / D - 3u) * hop;
-    uint64_t pass = args->samples_per_pass ? args->samples_per_pass : cap;
-    pass = pass > cap ? cap : pass;
-    pass = pass > by_rows ? by_rows : pass;
-    pass = pass > want ? (want ? want : 1u) : pass;
-    const GraphFbLayout lay = graph_fb_layout(ops, flagged, (uint32_t)pass);
-    const size_t max_rows = (size_t)(pass / hop) + 3u;
-    hipError_t e = render_reserve(ctx->render, max_rows * D, 0, lay.g.stride);
-    if (e == hipSuccess) e = render_reserve_words(ctx->render, lay.words);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return SOTS_FAIL(ctx, SOTS_ERR_HIP, "sots_render_graph_feedback: scratch allocation failed: %s", hipGetErrorString(e));
-    }
-    // every operator starts at phase 0 with h1 = h2 = +0; a pass leaves its end phases and h for the next one
-    SOTS_HIP(ctx, hipMemsetAsync(ctx->render.words + lay.g.carry, 0, 8u * sizeof(uint32_t), ctx->stream));
-    SOTS_HIP(ctx, hipMemsetAsync(ctx->render.words + lay.hist, 0, 16u * sizeof(uint32_t), ctx->stream));
-    for (uint64_t s0 = 0; s0 < want; s0 += pass) {
-        const uint32_t count = (uint32_t)(want - s0 < pass ? want - s0 : pass);
-        uint32_t k0, k1, r;
-        cont_position((uint32_t)s0, N / 2u, hop, num_rows, k0, r);
-        cont_position((uint32_t)s0 + count - 1u, N / 2u, hop, num_rows, k1, r);
-        k1 = k1 + 1u < num_rows ? k1 + 1u : num_rows - 1u; // (the row after: the second half of a hop, the far end of a glide)
-        SOTS_HIP(ctx, hipMemcpyAsync(ctx->render.values, values + (size_t)k0 * D, (size_t)(k1 - k0 + 1u) * D * sizeof(float),
-                                     hipMemcpyHostToDevice, ctx->stream));
-        GraphContPass &ps = fb.g;
-        ps.values = ctx->render.values, ps.wavetable = ctx->wavetable, ps.words = ctx->render.words, ps.out = ctx->render.out;
-        ps.lay = lay.g;
-        ps.row_base = k0, ps.num_rows = num_rows, ps.hop = hop, ps.half_n = N / 2u, ps.glide = args->flags & SOTS_RENDER_GLIDE;
-        ps.n0 = (uint32_t)s0, ps.count = count;
-        ps.sp = ctx->sp;
-        fb.tbuf = lay.tbuf, fb.hist = lay.hist;
-        SOTS_HIP(ctx, launch_graph_feedback_pass(ctx->stream, ctx->graph, ctx->waveforms, fb, ctx->num_cus));
-        // (stream order keeps the next pass off the scratch until this copy has read it)
-        SOTS_HIP(ctx, hipMemcpyAsync(out + s0, ctx->render.out, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (out_samples > covered) memset(out + covered, 0, (size_t)(out_samples - covered) * sizeof(float));
-    return SOTS_OK;
+    return render_graph_passes(ctx, "sots_render_graph_feedback", values, num_rows, args->hop, args->flags, args->samples_per_pass, args->chain_form,
+                               args->relax_cap, out, out_samples);
 }
 
 // ---- timing ----------------------------------------------------------------------------------

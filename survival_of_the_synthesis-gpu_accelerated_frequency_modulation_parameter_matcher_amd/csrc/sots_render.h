@@ -1,7 +1,7 @@
 // sots_render.h -- overlap-add resynthesis of a parameter track (sots_render.hip) and its phase-continuous
-// rendering (sots_render_continuous.hip), for the operator-graph voice sots_render_graph_continuous.hip (4.16).
-// Internal to libsots_hip.so; the public boundary is sots_render_overlap_add / sots_render_continuous /
-// sots_render_graph_continuous in include/sots_hip.h.
+// rendering (sots_render_continuous.hip), for the operator-graph voice with or without feedback operators
+// sots_render_graph.hip (4.16, 4.17).  Internal to libsots_hip.so; the public boundary is sots_render_overlap_add /
+// sots_render_continuous / sots_render_graph_continuous / sots_render_graph_feedback in include/sots_hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -105,67 +105,47 @@ struct ContPass {
 // every stage of one pass; the carries (lay.carry) are the caller's to clear before the first pass
 hipError_t launch_continuous_pass(hipStream_t st, uint32_t kind, const ContPass &pass, uint32_t num_cus);
 
-// ---- phase-continuous rendering of the operator-graph voice (sots_render_graph_continuous.hip) ----
+// ---- phase-continuous rendering of the operator-graph voice (sots_render_graph.hip) ----
 // Passes, tiles and the three launches are those above, per LEVEL of the graph (graph_levels, sots_rules.h) with the level's
 // operators in grid.y; every operator keeps a phase buffer of its own, a word per sample of the pass, and a last launch
-// mixes the carriers.  Where the words lie, for passes of at most pass_samples samples:
-struct GraphContLayout {
+// mixes the carriers.  Feedback never touches a phase.  An operator with beta != 0 ("flagged", a bit of fb_mask) has in
+// addition a buffer of its shaped values t_j, a float per sample of the pass, that one chain launch per level fills after
+// the level's apply and that later levels and the mix read in place of its phase words; and two floats of state, h1 and h2,
+// that a pass leaves for the next.  A voice without feedback operators is fb_mask == 0, flagged == 0: no chain launch, and
+// neither hist nor a t buffer is ever touched.  Where the words lie, for passes of at most pass_samples samples:
+struct GraphLayout {
     uint32_t stride, tiles; // words between the operators' phase buffers (a multiple of 4), tiles of a full pass
-    size_t totals, carry, words; // phase buffer j lies at j * stride; totals: 8 x tiles; carry: 8 words, by position in GraphLevels::ops
+    size_t totals, carry;   // phase buffer j lies at j * stride; totals: 8 x tiles; carry: 8 words, by position in GraphLevels::ops
+    size_t hist, tbuf, words; // hist: 16 floats behind the carries, h1 h2 per slot; t buffer of the s-th flagged operator (ascending j) at tbuf + s * stride
 };
-inline GraphContLayout graph_cont_layout(uint32_t ops, uint32_t pass_samples)
+inline GraphLayout graph_layout(uint32_t ops, uint32_t flagged, uint32_t pass_samples)
 {
-    GraphContLayout l{};
+    GraphLayout l{};
     l.stride = (pass_samples + 3u) & ~3u;
     l.tiles = (pass_samples + kContTile - 1u) / kContTile;
     l.totals = (size_t)ops * l.stride;
     l.carry = l.totals + (((size_t)8u * l.tiles + 3u) & ~(size_t)3u);
-    l.words = l.carry + 8u;
+    l.hist = l.carry + 8u;
+    l.tbuf = l.hist + 16u;
+    l.words = l.tbuf + (size_t)flagged * l.stride;
     return l;
 }
-struct GraphContPass {
+struct GraphPass {
     const float *values;    // genes of rows row_base ..., 2 x operators floats each: every row a sample of the pass looks at
     const float *wavetable; // kWavetableSize floats
     uint32_t *words;        // RenderScratch::words
     float *out;             // count floats (16-byte aligned)
-    GraphContLayout lay;
+    GraphLayout lay;
     uint32_t row_base, num_rows, hop, half_n, glide;
     uint32_t n0, count;
     SynthParams sp;
+    uint32_t fb_mask;   // the flagged operators
+    float scaled[8];    // B_j = beta_j K (scale_feedback, sots_rules.h)
+    uint32_t forms;     // bit j: operator j's chain runs as a relaxation (else serially)
+    uint32_t relax_cap; // sweeps per tile before a tile is finished serially, 1..4096 (read where fb_mask != 0)
 };
-// every level of one pass and the mix; the carries (lay.carry) are the caller's to clear before the first pass.
-// waveforms: the eight codes (sots_set_voice_waveforms).
-hipError_t launch_graph_continuous_pass(hipStream_t st, const sots_voice_graph &graph, const uint32_t waveforms[8], const GraphContPass &pass,
-                                        uint32_t num_cus);
-
-// ---- ... with feedback operators (sots_render_graph_feedback.hip) ----
-// Everything above stands: feedback never touches a phase.  An operator with beta != 0 ("flagged", a bit of fb_mask) has in
-// addition a buffer of its shaped values t_j, a float per sample of the pass, that one chain launch per level fills after
-// the level's apply and that later levels and the mix read in place of its phase words; and two floats of state, h1 and h2,
-// that a pass leaves for the next.  The words of GraphContLayout come first and are laid out as above; behind them:
-struct GraphFbLayout {
-    GraphContLayout g;
-    size_t tbuf, hist, words; // t buffer of the s-th flagged operator (ascending j) at tbuf + s * g.stride; hist: 16 floats, h1 h2 per slot
-};
-inline GraphFbLayout graph_fb_layout(uint32_t ops, uint32_t flagged, uint32_t pass_samples)
-{
-    GraphFbLayout l{};
-    l.g = graph_cont_layout(ops, pass_samples);
-    l.tbuf = (l.g.words + 3u) & ~(size_t)3u;
-    l.hist = l.tbuf + (size_t)flagged * l.g.stride;
-    l.words = l.hist + 16u;
-    return l;
-}
-struct GraphFbPass {
-    GraphContPass g;   // g.lay = lay.g
-    size_t tbuf, hist; // GraphFbLayout's, into g.words
-    uint32_t fb_mask;  // the flagged operators
-    float scaled[8];   // B_j = beta_j K (scale_feedback, sots_rules.h)
-    uint32_t forms;    // bit j: operator j's chain runs as a relaxation (else serially)
-    uint32_t relax_cap; // sweeps per tile before a tile is finished serially, 1..4096
-};
-// every level of one pass with its chains, and the mix; carries and hist are the caller's to clear before the first pass
-hipError_t launch_graph_feedback_pass(hipStream_t st, const sots_voice_graph &graph, const uint32_t waveforms[8], const GraphFbPass &pass,
-                                      uint32_t num_cus);
+// every level of one pass with its chains, and the mix; the carries (lay.carry) and, where fb_mask != 0, hist are the
+// caller's to clear before the first pass.  waveforms: the eight codes (sots_set_voice_waveforms).
+hipError_t launch_graph_pass(hipStream_t st, const sots_voice_graph &graph, const uint32_t waveforms[8], const GraphPass &pass, uint32_t num_cus);
 
 } // namespace sots

@@ -380,25 +380,50 @@ inline Fault render_continuous_voice_check(uint32_t kind)
         return fault(SOTS_ERR_INVALID, "sots_render_continuous: not for the operator-graph voice (sots_render_overlap_add renders it)");
     return Fault{};
 }
+// What the three phase-continuous entry points refuse alike, in two pieces, since an entry point may have refusals of its own
+// between them.  who, args_type: the entry point's name and its args struct's, for the text; n, d: the context's audio length
+// and genes per row.  The first piece: the args struct, the hop, the flags.
+template <class ARGS> inline Fault render_cont_args_check(const char *who, const char *args_type, const ARGS *args, uint32_t n)
+{
+    if (!args || args->struct_size != sizeof(ARGS)) return fault(SOTS_ERR_INVALID, "%s: null args or %s.struct_size != %zu", who, args_type, sizeof(ARGS));
+    if (args->hop < 1u || args->hop > n) return fault(SOTS_ERR_INVALID, "%s: hop %u outside 1..%u", who, args->hop, n);
+    if (args->flags & ~(uint32_t)SOTS_RENDER_GLIDE) return fault(SOTS_ERR_INVALID, "%s: unknown flags 0x%x", who, args->flags);
+    return Fault{};
+}
+// The second piece: the rows, the samples they cover, the values and the output.
+inline Fault render_cont_track_check(const char *who, uint32_t hop, uint32_t n, uint32_t d, const void *values, size_t values_bytes, uint32_t num_rows,
+                                     const void *out, uint64_t out_samples)
+{
+    if (num_rows == 0) return fault(SOTS_ERR_INVALID, "%s: num_rows must be at least 1", who);
+    const uint64_t covered = (uint64_t)(num_rows - 1u) * hop + n;
+    if (covered >= (1ull << 31))
+        return fault(SOTS_ERR_INVALID, "%s: %u rows at hop %u are %llu samples, 2^31 or more", who, num_rows, hop, (unsigned long long)covered);
+    if (!values || values_bytes != (size_t)num_rows * d * sizeof(float))
+        return fault(SOTS_ERR_SIZE, "%s: %u rows need %zu bytes of values, got %zu", who, num_rows, (size_t)num_rows * d * sizeof(float), values_bytes);
+    if (!out && out_samples) return fault(SOTS_ERR_INVALID, "%s: null output", who);
+    return Fault{};
+}
+// The graph voice's two entry points refuse a fixed voice and a voice whose feedback indices are genes before they look at args.
+inline Fault render_graph_voice_check(const char *who, uint32_t kind, uint32_t feedback_genes)
+{
+    if (kind != SOTS_SYNTH_GRAPH)
+        return fault(SOTS_ERR_STATE, "%s: the handle runs a fixed voice (synth_kind %u; sots_render_continuous renders it)", who, kind);
+    if (feedback_genes)
+        return fault(SOTS_ERR_STATE,
+                     "%s: the feedback indices of operators 0x%x are genes (sots_create_graph_genes): every row has its own; sots_render_overlap_add "
+                     "renders such a voice",
+                     who, feedback_genes);
+    return Fault{};
+}
+
 // sots_render_continuous: what it refuses before anything touches the device.  n, d, synth_arith: the context's audio
 // length, genes per row and arithmetic mode.
 inline Fault render_continuous_check(const sots_render_continuous_args *args, uint32_t n, uint32_t d, uint32_t synth_arith, const void *values,
                                      size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples)
 {
-    if (!args || args->struct_size != sizeof(sots_render_continuous_args))
-        return fault(SOTS_ERR_INVALID, "sots_render_continuous: null args or sots_render_continuous_args.struct_size != %zu",
-                     sizeof(sots_render_continuous_args));
-    if (args->hop < 1u || args->hop > n) return fault(SOTS_ERR_INVALID, "sots_render_continuous: hop %u outside 1..%u", args->hop, n);
-    if (args->flags & ~(uint32_t)SOTS_RENDER_GLIDE) return fault(SOTS_ERR_INVALID, "sots_render_continuous: unknown flags 0x%x", args->flags);
-    if (num_rows == 0) return fault(SOTS_ERR_INVALID, "sots_render_continuous: num_rows must be at least 1");
-    const uint64_t covered = (uint64_t)(num_rows - 1u) * args->hop + n;
-    if (covered >= (1ull << 31))
-        return fault(SOTS_ERR_INVALID, "sots_render_continuous: %u rows at hop %u are %llu samples, 2^31 or more", num_rows, args->hop,
-                     (unsigned long long)covered);
-    if (!values || values_bytes != (size_t)num_rows * d * sizeof(float))
-        return fault(SOTS_ERR_SIZE, "sots_render_continuous: %u rows need %zu bytes of values, got %zu", num_rows, (size_t)num_rows * d * sizeof(float),
-                     values_bytes);
-    if (!out && out_samples) return fault(SOTS_ERR_INVALID, "sots_render_continuous: null output");
+    const char *who = "sots_render_continuous";
+    if (const Fault f = render_cont_args_check(who, "sots_render_continuous_args", args, n)) return f;
+    if (const Fault f = render_cont_track_check(who, args->hop, n, d, values, values_bytes, num_rows, out, out_samples)) return f;
     if (synth_arith == SOTS_ARITH_DEVICE_KERNELS)
         return fault(SOTS_ERR_STATE, "sots_render_continuous: not under SOTS_ARITH_DEVICE_KERNELS (that mode is the reference's kernels bit for bit)");
     return Fault{};
@@ -435,68 +460,45 @@ inline GraphLevels graph_levels(const sots_voice_graph &g)
     return l;
 }
 // whether reading operator i's output needs the wavetable: SQUARE and SAW are functions of the index alone
-inline bool waveform_reads_table(uint32_t code) { return code != SOTS_WAVE_SQUARE && code != SOTS_WAVE_SAW; }
-// whether the launches of level `level` read the table: some operator of the level has a modulator whose shape does
-inline bool graph_level_reads_table(const sots_voice_graph &g, const GraphLevels &l, const uint32_t codes[8], uint32_t level)
+constexpr bool waveform_reads_table(uint32_t code) { return code != SOTS_WAVE_SQUARE && code != SOTS_WAVE_SAW; }
+// whether the launches of level `level` read the table: some operator of the level has a modulator whose value is made from
+// its phase word (it is not `flagged`: a feedback operator's shaped values are read as stored) by a shape that reads the table
+inline bool graph_level_reads_table(const sots_voice_graph &g, const GraphLevels &l, const uint32_t codes[8], uint32_t level, uint32_t flagged = 0)
 {
     for (uint32_t s = l.first[level]; s < l.first[level + 1u]; ++s)
         for (uint32_t i = 0; i < l.ops[s]; ++i)
-            if ((g.modulators[l.ops[s]] >> i & 1u) && waveform_reads_table(codes[i])) return true;
+            if ((g.modulators[l.ops[s]] >> i & 1u) && !(flagged >> i & 1u) && waveform_reads_table(codes[i])) return true;
     return false;
 }
-// Samples of a pass: every operator keeps one phase word per sample, and the phase words of a pass stay within the 96 MiB
-// that the fixed voices' renderer needs at the most (6 buffers of 2^22 words); whole tiles of 4096, at most 2^22 samples.
-inline uint32_t graph_continuous_max_pass(uint32_t ops)
-{
-    const uint64_t words = (96ull << 20) / sizeof(uint32_t) / (ops ? ops : 1u);
-    const uint64_t whole = words / 4096u * 4096u;
-    return whole < (1u << 22) ? (uint32_t)whole : 1u << 22;
-}
-// sots_render_graph_continuous: what it refuses before anything touches the device.  kind, feedback: the context's voice and
-// its feedback indices; n, d: its audio length and genes per row.
-inline Fault render_graph_continuous_check(uint32_t kind, const float feedback[8], const sots_render_continuous_args *args, uint32_t n, uint32_t d,
-                                           const void *values, size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples,
-                                           uint32_t feedback_genes = 0)
-{
-    if (kind != SOTS_SYNTH_GRAPH)
-        return fault(SOTS_ERR_STATE, "sots_render_graph_continuous: the handle runs a fixed voice (synth_kind %u; sots_render_continuous renders it)", kind);
-    if (feedback_genes)
-        return fault(SOTS_ERR_STATE,
-                     "sots_render_graph_continuous: the feedback indices of operators 0x%x are genes (sots_create_graph_genes): every row has its "
-                     "own; sots_render_overlap_add renders such a voice",
-                     feedback_genes);
-    for (uint32_t j = 0; j < kGraphMaxOps; ++j)
-        if (feedback[j] != 0.0f)
-            return fault(SOTS_ERR_STATE,
-                         "sots_render_graph_continuous: operator %u has feedback index %g (sots_set_voice_feedback): a feedback operator's phase "
-                         "offset is a serial recurrence that no scan computes; sots_render_overlap_add renders such a voice",
-                         j, (double)feedback[j]);
-    if (!args || args->struct_size != sizeof(sots_render_continuous_args))
-        return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: null args or sots_render_continuous_args.struct_size != %zu",
-                     sizeof(sots_render_continuous_args));
-    if (args->hop < 1u || args->hop > n) return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: hop %u outside 1..%u", args->hop, n);
-    if (args->flags & ~(uint32_t)SOTS_RENDER_GLIDE) return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: unknown flags 0x%x", args->flags);
-    if (num_rows == 0) return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: num_rows must be at least 1");
-    const uint64_t covered = (uint64_t)(num_rows - 1u) * args->hop + n;
-    if (covered >= (1ull << 31))
-        return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: %u rows at hop %u are %llu samples, 2^31 or more", num_rows, args->hop,
-                     (unsigned long long)covered);
-    if (!values || values_bytes != (size_t)num_rows * d * sizeof(float))
-        return fault(SOTS_ERR_SIZE, "sots_render_graph_continuous: %u rows need %zu bytes of values, got %zu", num_rows,
-                     (size_t)num_rows * d * sizeof(float), values_bytes);
-    if (!out && out_samples) return fault(SOTS_ERR_INVALID, "sots_render_graph_continuous: null output");
-    return Fault{};
-}
-
-// ---- ... with feedback operators (sots_render_graph_feedback, DESIGN.md 4.17) ----
 // Samples of a pass: a phase word per operator and sample and a shaped value per feedback operator and sample stay together
-// within the same 96 MiB; whole tiles of 4096, at most 1024 of them.  Without feedback operators: graph_continuous_max_pass.
+// within the 96 MiB that the fixed voices' renderer needs at the most (6 buffers of 2^22 words); whole tiles of 4096, at most
+// 1024 of them (2^22 samples).
 inline uint32_t graph_feedback_max_pass(uint32_t ops, uint32_t flagged)
 {
     const uint32_t buffers = ops + flagged ? ops + flagged : 1u;
     const uint64_t tiles = (96ull << 20) / (sizeof(uint32_t) * buffers) / 4096u;
     return (uint32_t)(tiles < 1024u ? tiles : 1024u) * 4096u;
 }
+inline uint32_t graph_continuous_max_pass(uint32_t ops) { return graph_feedback_max_pass(ops, 0); }
+// sots_render_graph_continuous: what it refuses before anything touches the device.  kind, feedback: the context's voice and
+// its feedback indices; n, d: its audio length and genes per row.
+inline Fault render_graph_continuous_check(uint32_t kind, const float feedback[8], const sots_render_continuous_args *args, uint32_t n, uint32_t d,
+                                           const void *values, size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples,
+                                           uint32_t feedback_genes = 0)
+{
+    const char *who = "sots_render_graph_continuous";
+    if (const Fault f = render_graph_voice_check(who, kind, feedback_genes)) return f;
+    for (uint32_t j = 0; j < kGraphMaxOps; ++j)
+        if (feedback[j] != 0.0f)
+            return fault(SOTS_ERR_STATE,
+                         "sots_render_graph_continuous: operator %u has feedback index %g (sots_set_voice_feedback): a feedback operator's phase "
+                         "offset is a serial recurrence that no scan computes; sots_render_overlap_add renders such a voice",
+                         j, (double)feedback[j]);
+    if (const Fault f = render_cont_args_check(who, "sots_render_continuous_args", args, n)) return f;
+    return render_cont_track_check(who, args->hop, n, d, values, values_bytes, num_rows, out, out_samples);
+}
+
+// ---- ... with feedback operators (sots_render_graph_feedback, DESIGN.md 4.17) ----
 // How a feedback operator's chain over the samples is computed (sots_render_graph_feedback_args.chain_form)
 constexpr uint32_t kChainLibrary = 0, kChainSerial = 1, kChainRelax = 2;
 constexpr uint32_t kRelaxCapMax = 4096, kRelaxCapLibrary = 1024;
@@ -512,33 +514,15 @@ inline uint32_t graph_feedback_form(float beta) { return beta <= kRelaxBetaMax ?
 inline Fault render_graph_feedback_check(uint32_t kind, const sots_render_graph_feedback_args *args, uint32_t n, uint32_t d, const void *values,
                                          size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples, uint32_t feedback_genes = 0)
 {
-    if (kind != SOTS_SYNTH_GRAPH)
-        return fault(SOTS_ERR_STATE, "sots_render_graph_feedback: the handle runs a fixed voice (synth_kind %u; sots_render_continuous renders it)", kind);
-    if (feedback_genes)
-        return fault(SOTS_ERR_STATE,
-                     "sots_render_graph_feedback: the feedback indices of operators 0x%x are genes (sots_create_graph_genes): every row has its "
-                     "own; sots_render_overlap_add renders such a voice",
-                     feedback_genes);
-    if (!args || args->struct_size != sizeof(sots_render_graph_feedback_args))
-        return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: null args or sots_render_graph_feedback_args.struct_size != %zu",
-                     sizeof(sots_render_graph_feedback_args));
-    if (args->hop < 1u || args->hop > n) return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: hop %u outside 1..%u", args->hop, n);
-    if (args->flags & ~(uint32_t)SOTS_RENDER_GLIDE) return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: unknown flags 0x%x", args->flags);
+    const char *who = "sots_render_graph_feedback";
+    if (const Fault f = render_graph_voice_check(who, kind, feedback_genes)) return f;
+    if (const Fault f = render_cont_args_check(who, "sots_render_graph_feedback_args", args, n)) return f;
     if (args->chain_form > kChainRelax)
         return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: chain_form %u is not a form (0 = the library's choice, 1 = serial, 2 = relaxation)",
                      args->chain_form);
     if (args->relax_cap > kRelaxCapMax)
         return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: relax_cap %u outside 0..%u", args->relax_cap, kRelaxCapMax);
-    if (num_rows == 0) return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: num_rows must be at least 1");
-    const uint64_t covered = (uint64_t)(num_rows - 1u) * args->hop + n;
-    if (covered >= (1ull << 31))
-        return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: %u rows at hop %u are %llu samples, 2^31 or more", num_rows, args->hop,
-                     (unsigned long long)covered);
-    if (!values || values_bytes != (size_t)num_rows * d * sizeof(float))
-        return fault(SOTS_ERR_SIZE, "sots_render_graph_feedback: %u rows need %zu bytes of values, got %zu", num_rows,
-                     (size_t)num_rows * d * sizeof(float), values_bytes);
-    if (!out && out_samples) return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: null output");
-    return Fault{};
+    return render_cont_track_check(who, args->hop, n, d, values, values_bytes, num_rows, out, out_samples);
 }
 
 // ---- run record, stop rules ----

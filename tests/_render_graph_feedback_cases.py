@@ -23,3 +23,15 @@ def waveform_case(w):
 
 # several tiles with a carry: (graph, waves, beta, rows, N, hop) - 17 920 samples, 17.5 tiles of the relaxation, 4.4 of the scans
 CHAIN3_CARRY = ("chain3", None, [0.5, 1.0, 2.0], 70, 256, 256)
+
+# one kernel set with and without feedback (graph, N, hop, rows, samples per pass): 5312 samples, two passes of which the first
+# is one full tile of the scans
+SHARED = ("chain3", 256, 64, 80, 4096)
+
+
+def mixed_level_cases():
+    """dense8 with feedback on operator 2 only: operator 3 reads the flagged operator 2 beside the unflagged 0 and 1.  SQUARE
+    on the flagged one and SINE on the others (the level reads the table for the unflagged ones), and the other way round (no
+    level launch reads it; only operator 2's chain does)"""
+    beta = [0.0, 0.0, 1.0] + [0.0] * 5
+    return [("dense8", [0, 0, 6, 0, 0, 0, 0, 0], beta), ("dense8", [6, 6, 0, 6, 6, 6, 6, 6], beta)]

@@ -16,7 +16,7 @@ import _render_graph_continuous_model as GM  # noqa: E402
 import _render_graph_feedback_model as RM  # noqa: E402
 import _render_model as M  # noqa: E402
 from _graph_voice_match import CHAIN3, NO_DEVICE, run_match  # noqa: E402
-from _render_graph_feedback_cases import BASE, BASE_SHAPE, CHAIN3_CARRY, waveform_case  # noqa: E402
+from _render_graph_feedback_cases import BASE, BASE_SHAPE, CHAIN3_CARRY, SHARED, mixed_level_cases, waveform_case  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG_DIR = os.path.join(ROOT, "survival_of_the_synthesis-gpu_accelerated_frequency_modulation_parameter_matcher_amd")
@@ -180,6 +180,22 @@ def test_every_waveform_is_read_in_every_eighth_by_a_feedback_operator(tab, w):
     seen = {}
     render_case(tab, waveform_case(w), seen=seen)
     assert seen[w] == set(range(8))
+
+
+def test_the_shared_kernel_cases_tell_feedback_from_none(tab):
+    """what a stale t buffer, a stale h or a wrong source for a modulator's value would render differs from what is asserted"""
+    name, n, hop, rows, per_pass = SHARED
+    pmin, pmax = WM.ranges(3)
+    plain = GM.render(GRAPHS[name], None, rows_of(3, rows), pmin, pmax, tab, n, hop)
+    assert per_pass == 4096 < len(plain) < 2 * per_pass  # two passes, the first a whole tile of the scans
+    for beta in ([0.0, 1.0, 0.0], [0.0, 0.0, 0.5]):
+        fed = RM.render(GRAPHS[name], None, beta, rows_of(3, rows), pmin, pmax, tab, n, hop, samples_per_pass=per_pass)
+        assert (RM.bits(fed) != RM.bits(plain)).mean() > 0.9
+    for case in mixed_level_cases():
+        name, waves, beta = case
+        assert GRAPHS[name][1][3] & 0b111 == 0b111 and [b != 0 for b in beta[:3]] == [False, False, True]
+        unfed = render_case(tab, (name, waves, None))
+        assert (RM.bits(render_case(tab, case)) != RM.bits(unfed)).mean() > 0.4
 
 
 # ---- the rules ---------------------------------------------------------------------------------------------------------------
