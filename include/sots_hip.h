@@ -346,6 +346,11 @@ int sots_read_select_splitters(sots_ctx *ctx, uint64_t *keys, uint32_t count);
  * splitters, target, plan or sort mode in between drops the lists again.  SOTS_ERR_STATE where a slot holds more than
  * 256 splitters, or with SOTS_SELECT_LISTS=0 in the environment of sots_create (the selection then always streams). */
 int sots_stage_bucket_fitness(sots_ctx *ctx);
+/* What sots_stage_bucket_fitness filed, for tests of the filing itself (SOTS_ERR_STATE unless it was the last thing to
+ * touch the lists).  With B = sots_select_splitter_count: counts[B * 16] - counter s of bucket j at j * 16 + s, every key
+ * of a closed bucket j < B - 1 counted, also those its segment had no place for; the open bucket B - 1 counts nothing -
+ * and keys[B * 2048]: segment s of bucket j from (j * 16 + s) * 128 on, min(count, 128) keys in the order they arrived. */
+int sots_read_select_lists(sots_ctx *ctx, uint32_t *counts, uint32_t counts_len, uint64_t *keys, uint32_t keys_len);
 /* enum sots_synth_arith; applies to sots_stage_synthesise and to both generation loops from the next call on
  * (replaces nothing: the reference picks its arithmetic by picking a backend, main.cpp:105-163) */
 int sots_set_synth_arithmetic(sots_ctx *ctx, uint32_t arith);

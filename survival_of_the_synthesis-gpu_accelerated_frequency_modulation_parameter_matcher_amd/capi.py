@@ -51,7 +51,7 @@ EXPORTS = [
     "sots_stage_fft", "sots_stage_fitness", "sots_stage_sort", "sots_stage_select", "sots_stage_rotate",
     "sots_set_sort_mode",
     "sots_set_select_plan", "sots_select_splitter_count", "sots_write_select_splitters", "sots_read_select_splitters",
-    "sots_stage_bucket_fitness",
+    "sots_stage_bucket_fitness", "sots_read_select_lists",
     "sots_set_synth_arithmetic", "sots_set_survivors", "sots_get_survivors", "sots_batch_set_survivors",
     "sots_execute_generation", "sots_execute_generations", "sots_get_generation",
     "sots_set_generation", "sots_timing_enable", "sots_timing_reset", "sots_stage_time_ms",
@@ -295,6 +295,7 @@ def load():
     L.sots_write_select_splitters.argtypes = [vp, vp, u32]
     L.sots_read_select_splitters.argtypes = [vp, vp, u32]
     L.sots_stage_bucket_fitness.argtypes = [vp]
+    L.sots_read_select_lists.argtypes = [vp, vp, u32, vp, u32]
     L.sots_set_synth_arithmetic.argtypes = [vp, u32]
     for name in ("recombine", "mutate", "synthesise", "window", "fft", "fitness", "sort", "select", "rotate"):
         getattr(L, "sots_stage_" + name).argtypes = [vp]
@@ -663,6 +664,13 @@ class HipES:
     def bucket_fitness(self):
         """files the current half's keys between the splitters the next select() reads: that select() takes list mode"""
         self._check(self.L.sots_stage_bucket_fitness(self._h))
+
+    def read_select_lists(self):
+        """what bucket_fitness() filed: counts[B, 16] (every key of a closed bucket, per segment) and keys[B, 16, 128]"""
+        b = self.select_splitter_count()
+        counts, keys = np.empty((b, 16), np.uint32), np.empty((b, 16, 128), np.uint64)
+        self._check(self.L.sots_read_select_lists(self._h, counts.ctypes.data_as(C.c_void_p), counts.size, keys.ctypes.data_as(C.c_void_p), keys.size))
+        return counts, keys
 
     def rotate(self):
         self._check(self.L.sots_stage_rotate(self._h))

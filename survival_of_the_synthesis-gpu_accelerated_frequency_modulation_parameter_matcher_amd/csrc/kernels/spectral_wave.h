@@ -46,13 +46,15 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
     static_assert(sizeof...(LISTS) == (BUCKET ? 1 : 0) + (OBJ == kObjLogMagnitude ? 1 : 0) + (WGT ? 1 : 0), "the BUCKET instantiation takes the lists, the log ones the floor, the weighted ones their table, the others nothing");
     static_assert((OBJ == kObjMagnitude && !WGT) || MODE == 1, "the objective belongs to the fitness epilogue");
     static_assert(!WGT || WIN, "the weighted forms exist with a window only");
-    [[maybe_unused]] const auto bk = trailing<SelLists>(BktNoLists{}, lists...);
+    using Lists = typename bkt_lists_of<LISTS...>::type; // (SelLists or SelListsTwoLevel: the lookup travels in the type)
+    constexpr int LK = bkt_lookup_of<Lists>;
+    [[maybe_unused]] const auto bk = trailing<Lists>(BktNoLists{}, lists...);
     [[maybe_unused]] const float floor_eps = trailing<float>(0.0f, lists...);
     [[maybe_unused]] const float *__restrict__ const wgt_u = trailing<const float *>(nullptr, lists...);
     constexpr int N = 1 << LOG2N, M = N / 2, E = M / kWave, H = E / 2;
     static_assert(LOG2N == 9 || LOG2N == 10, "wavefront-per-row FFT is for N <= 1024");
     static_assert(!BUCKET || (MODE == 1 && W > 1 && !SEG), "keys are filed by the wide fitness kernel only");
-    __shared__ uint32_t bnd_s[BUCKET ? 2 * kBktMaxBuckets : 1];
+    __shared__ __attribute__((aligned(8))) uint32_t bnd_s[BUCKET ? 2 * kBktMaxBuckets : 1]; // (kBktTwoLevel reads whole keys)
     __shared__ float2 lds_all[W][M + M / 8 + 1];
     __shared__ uint32_t next_s;
     const int lane = threadIdx.x & (kWave - 1);
@@ -110,11 +112,17 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
     }
     const uint32_t seg_rows = SEG ? seg_target_rows(target) : 1u;
     if constexpr (BUCKET) {
-        if (wave == W - 1) bkt_bounds(bk.slot, bk.buckets, bnd_s, lane); // (a wavefront of the workgroup's last rows)
+        if (wave == W - 1) bkt_bounds<LK>(bk.slot, bk.buckets, bnd_s, lane); // (a wavefront of the workgroup's last rows)
     }
     if constexpr (MODE == 1 || W > 1) __syncthreads(); // (the only workgroup barrier: target, row counter and bounds are there)
     if (ind >= p_len) return;
+    [[maybe_unused]] uint64_t bkt_end = 0ull; // the last closed bound, wavefront-uniform (kBktTwoLevel)
+    if constexpr (BUCKET) bkt_end = bkt_last<LK>(bnd_s, bk.buckets);
 
+    // (Window and twiddles stay BEHIND the barrier.  Asked for in front of it - pinned there, or the compiler sinks the
+    // loads to their first use - they COST 0.5 us per generation, every round of eight.  Supposed, not shown: the slot
+    // scan's loads and the target's copy then return behind 18 more loads per lane, and the barrier stands later.
+    // profiles/r30_experiments.md)
     float4 wv[WIN ? Q : 1];
     if constexpr (WIN) {
 #pragma unroll
@@ -214,7 +222,7 @@ __global__ __launch_bounds__(W *kWave) void k_fft(const float *__restrict__ audi
             if constexpr (BUCKET) {
                 // (uniform by construction; said to the compiler so that key and bucket stay in scalar registers)
                 const uint32_t kb = __builtin_amdgcn_readfirstlane(order_bits(acc));
-                bkt_visit(bk, bnd_s, ((uint64_t)kb << 32) | ind, blockIdx.x % kSelListShards, lane, bkt);
+                bkt_visit<LK>(bk, bnd_s, bkt_end, ((uint64_t)kb << 32) | ind, blockIdx.x % kSelListShards, lane, bkt);
             }
         }
         wave_lds_sync<W == 1>(); // orders this row's LDS reads before the next row's writes

@@ -817,6 +817,21 @@ int sots_stage_bucket_fitness(sots_ctx *ctx)
     return SOTS_OK;
 }
 
+// what sots_stage_bucket_fitness filed, as it lies in device memory (tests of the filing itself)
+int sots_read_select_lists(sots_ctx *ctx, uint32_t *counts, uint32_t counts_len, uint64_t *keys, uint32_t keys_len)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    if (!lists_possible(ctx) || !ctx->lists_ready) return SOTS_FAIL(ctx, SOTS_ERR_STATE, "no keys filed: sots_stage_bucket_fitness comes first");
+    const uint32_t b = select_splitter_count(ctx->num_cus);
+    if (!counts || !keys || counts_len != b * kSelListShards || keys_len != b * kSelListCap)
+        return SOTS_FAIL(ctx, SOTS_ERR_SIZE, "select lists: %u counters and %u keys needed, got %u and %u", b * kSelListShards, b * kSelListCap, counts_len, keys_len);
+    if (int rc = engine_bind(*ctx)) return rc;
+    SOTS_HIP(ctx, hipMemcpyAsync(counts, counter_set(ctx, ctx->spl_cur), (size_t)counts_len * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SOTS_HIP(ctx, hipMemcpyAsync(keys, ctx->sel_lists, (size_t)keys_len * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    SOTS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SOTS_OK;
+}
+
 int sots_stage_rotate(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);

@@ -1734,6 +1734,15 @@ static Spectral spectral_choice(uint32_t p, uint32_t log2n, uint32_t num_cus)
     return has_log2n(WaveSizes{}, log2n) ? Spectral::wave : Spectral::none;
 }
 
+// The lookup of every launch that files keys (kernels/sel_keys.h), the spectral kernel's and the staged k_bucket_fitness's
+// alike, so that a staged and a fused run of one population file by the same code: two levels up to 65 536 rows, where they
+// won every round (1.4-1.5 us of 113-115 per generation, profiles/r30_experiments.md), all bounds against every key above,
+// where the two levels lost 4.4 us of 212 at 131 072 rows (profiles/r19_experiments.md).  The buckets are the same either way.
+#ifndef SOTS_BKT_TWO_LEVEL_MAX_P
+#define SOTS_BKT_TWO_LEVEL_MAX_P 65536u // (0u: the build variant that files flat at every size)
+#endif
+static bool bkt_two_level(uint32_t p) { return p <= SOTS_BKT_TWO_LEVEL_MAX_P; }
+
 // a workgroup per row: as many workgroups as rows, at most four per CU (they loop)
 static uint32_t big_grid(uint32_t p, uint32_t num_cus)
 {
@@ -1868,8 +1877,11 @@ static hipError_t launch_fused(hipStream_t st, const float *audio, const float *
         else {
             if (!window || !select_lists_apply(p, log2n, num_cus) || lists->buckets != select_splitter_count(num_cus) || !lists->slot || !lists->cnt || !lists->lists)
                 return hipErrorInvalidValue;
-            return launch_resident(k_fft<10, 1, true, W, false, true, OBJ, WGT, SelLists, FL...>, W * kWave, groups_of(p, W), num_cus, &oc->wide[3], st,
-                                   audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, *lists, fl...);
+            const auto file = [&](auto l) { // (l: the lists, typed by the lookup)
+                return launch_resident(k_fft<10, 1, true, W, false, true, OBJ, WGT, decltype(l), FL...>, W * kWave, groups_of(p, W), num_cus, &oc->wide[3], st,
+                                       audio, nullptr, target, fitness, twiddle, window, p, inv_n, inv_wf, pitch, l, fl...);
+            };
+            return bkt_two_level(p) ? file(SelListsTwoLevel{*lists}) : file(*lists);
         }
     }
     // f(bool_constant<WIN>{}): with the window, or without one where that form exists
@@ -2174,19 +2186,21 @@ size_t select_counters_bytes() { return (size_t)kSelListMaxBuckets * kSelListSha
 // bkt_visit over an array of fitness values: a wavefront takes 64 consecutive keys, one after the other (the visit is
 // a wavefront's, its key uniform)
 constexpr uint32_t kBktThreads = 256;
+template <int LK>
 static __global__ __launch_bounds__(kBktThreads) void k_bucket_fitness(const float *__restrict__ fin, uint32_t p_len, SelLists bk)
 {
-    __shared__ uint32_t bnd_s[2 * kBktMaxBuckets];
+    __shared__ __attribute__((aligned(8))) uint32_t bnd_s[2 * kBktMaxBuckets];
     const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1);
-    if (tid < kWave) bkt_bounds(bk.slot, bk.buckets, bnd_s, lane);
+    if (tid < kWave) bkt_bounds<LK>(bk.slot, bk.buckets, bnd_s, lane);
     __syncthreads();
+    const uint64_t last = bkt_last<LK>(bnd_s, bk.buckets);
     const uint32_t first = __builtin_amdgcn_readfirstlane(blockIdx.x * kBktThreads + (tid & ~(kWave - 1)));
     const uint32_t idx = first + lane;
     const uint32_t bits = idx < p_len ? order_bits(fin[idx]) : 0u;
     BktPend pd = {0ull, kBktNone, 0u};
     for (uint32_t l = 0; l < kWave && first + l < p_len; ++l) {
         const uint32_t kb = (uint32_t)__builtin_amdgcn_readlane((int)bits, (int)l);
-        bkt_visit(bk, bnd_s, ((uint64_t)kb << 32) | (first + l), (first / kWave) % kSelListShards, lane, pd);
+        bkt_visit<LK>(bk, bnd_s, last, ((uint64_t)kb << 32) | (first + l), (first / kWave) % kSelListShards, lane, pd);
     }
     bkt_flush(bk, pd, lane);
 }
@@ -2194,7 +2208,9 @@ static __global__ __launch_bounds__(kBktThreads) void k_bucket_fitness(const flo
 hipError_t launch_bucket_fitness(hipStream_t st, const float *fitness, uint32_t p, const SelLists &lists)
 {
     if (lists.buckets < 2 || lists.buckets > kBktMaxBuckets || !lists.slot || !lists.cnt || !lists.lists) return hipErrorInvalidValue;
-    k_bucket_fitness<<<(p + kBktThreads - 1) / kBktThreads, kBktThreads, 0, st>>>(fitness, p, lists);
+    const uint32_t grid = (p + kBktThreads - 1) / kBktThreads;
+    if (bkt_two_level(p)) k_bucket_fitness<kBktTwoLevel><<<grid, kBktThreads, 0, st>>>(fitness, p, lists);
+    else k_bucket_fitness<kBktFlat><<<grid, kBktThreads, 0, st>>>(fitness, p, lists);
     return hipGetLastError();
 }
 
