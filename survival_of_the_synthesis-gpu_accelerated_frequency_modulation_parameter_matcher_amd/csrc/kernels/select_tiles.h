@@ -12,7 +12,7 @@ namespace sots { namespace {
 
 // ------------------------------------------------------------------------------------
 // Selection for the fused generation loop: the best `need` rows IN ORDER and nothing else.
-// The next recombination reads whole parent blocks only (recombine_source, sots_kernels.hip;
+// The next recombination reads whole parent blocks only (recombine_source, variation.h;
 // ocl_program.cl:99-112), so inside sots_execute_generations the order of the other rows is
 // never looked at; the full order is produced (by launch_sort, from the untouched unsorted half)
 // when somebody reads the population.  Rows 0..need-1 are bit-identical to the full sort's.

@@ -33,7 +33,7 @@ struct PopDims {
     uint32_t block_shift;  // log2(block) when block is a power of two, else kNoPow2
     uint32_t npb;          // parent blocks: max(1, num_parents / block)
     uint32_t npb_mask;     // npb - 1 when npb is a power of two, else kNoPow2
-    // rows 0 .. survivors-1 of the sorted half pass through variation as they are (make_gene, sots_kernels.hip); a
+    // rows 0 .. survivors-1 of the sorted half pass through variation as they are (make_gene, kernels/variation.h); a
     // setting of the context or batch (sots_set_survivors), 0 = the reference's strategy
     uint32_t survivors;
 };

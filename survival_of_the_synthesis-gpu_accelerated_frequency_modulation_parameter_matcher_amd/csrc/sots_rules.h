@@ -271,7 +271,7 @@ inline MutateConsts mutate_consts(uint32_t num_dimensions)
 }
 
 // ---- the rows of a sorted half ----
-// Rows that the next recombination reads (recombine_source, sots_kernels.hip):
+// Rows that the next recombination reads (recombine_source, kernels/variation.h):
 // whole blocks of parents, floor(numParents / block) of them, at least one.  Immigrants go to the
 // tail of THESE rows: with numParents not a multiple of the block, rows between the last whole
 // block and numParents are never read and immigrants written there would be dead.

@@ -1,6 +1,6 @@
 // sots_track.h -- the run record a context (one chunk) and a batch (max_chunks chunks) keep on the device: best-ever
 // individual, per-generation history ring, and the small read-back the stop rules look at.  Host side only; the kernel is
-// k_track (sots_kernels.hip).  Internal to libsots_hip.so.
+// k_track (kernels/track.h).  Internal to libsots_hip.so.
 #pragma once
 
 #include <hip/hip_runtime.h>

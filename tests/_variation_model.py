@@ -1,4 +1,4 @@
-"""An independent model of variation (recombine_source, mutate_gene, make_gene of csrc/sots_kernels.hip), NumPy only.
+"""An independent model of variation (recombine_source, mutate_gene, make_gene of csrc/kernels/variation.h), NumPy only.
 
 recombine() is written as the reference words it (ocl_program.cl:130-137), as a scatter in 64-bit integers: gene g of local
 individual l of block b GOES TO local individual (l + g (b + 1)) mod B, and block b copies parent block b mod
