@@ -274,7 +274,8 @@ int sots_get_voice_feedback(const sots_ctx *ctx, float index[8]);
  * Variation, selection, the run record, batch, queue, carried rows and survivors are generic in D and serve the voice;
  * sots_render_overlap_add and the match report render each row with its own beta.  sots_render_graph_continuous and
  * sots_render_graph_feedback take beta from the context and refuse a context whose mask is not 0 (SOTS_ERR_STATE; the
- * text names sots_render_overlap_add).  Islands do not take the voice. */
+ * text names sots_render_overlap_add); sots_render_graph_genes renders such a voice phase-continuously, every row with its
+ * own beta.  Islands do not take the voice. */
 int sots_create_graph_genes(const sots_config *cfg, const sots_voice_graph *graph, uint32_t feedback_genes, sots_ctx **out);
 int sots_get_voice_feedback_genes(const sots_ctx *ctx, uint32_t *feedback_genes);
 
@@ -505,6 +506,7 @@ int sots_render_continuous(sots_ctx *ctx, const float *values, size_t values_byt
  *   sots_render_continuous         the four fixed voices                   carried, 15.17 words   one voice
  *   sots_render_graph_continuous   the graph voice, waveforms, no feedback carried, 15.17 words   one voice
  *   sots_render_graph_feedback     the graph voice, waveforms, feedback    carried, words + h1 h2 one voice
+ *   sots_render_graph_genes        ... and feedback indices that are genes carried, words + h1 h2 one voice, beta per sample
  *
  * The work goes in passes of samples_per_pass output samples (0: the library's choice, the most that keeps the phase words
  * of a pass, one per operator and sample, within 96 MiB: 2^22 samples up to 6 operators, 3 592 192 for 7, 3 145 728 for 8);
@@ -562,6 +564,42 @@ typedef struct sots_render_graph_feedback_args {
 } sots_render_graph_feedback_args;
 int sots_render_graph_feedback(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
                                const sots_render_graph_feedback_args *args, float *out, uint64_t out_samples);
+
+/* ---- ... whose feedback indices are genes (new) ----
+ * sots_render_graph_feedback for a context of sots_create_graph_genes: a track as the matcher writes it for that voice,
+ * rendered as ONE voice whose oscillators never restart and whose feedback index follows the rows.  The args struct and its
+ * flags are those of sots_render_graph_feedback, and everything of that call holds: inputs, row position of sample n, HOLD /
+ * SOTS_RENDER_GLIDE, fix(), S and +0 at n >= S, gene scaling, A_j, c, cur_j, the phase recurrence, the carrier sum and its
+ * division, h1 = h2 = +0 at sample 0, chain_form and relax_cap, passes and what a pass carries.  What differs:
+ *   Row width.  values is [num_rows][D] with D = 2 OPS + E, the context's D.  Genes 0 .. 2 OPS - 1 mean what they mean in
+ *     every graph voice; gene 2 OPS + r is the index of the operator with the r-th set bit of the mask, ascending.
+ *   The index at sample n.  For an operator j of the mask, with q its gene column:
+ *       g_q(n)  the raw gene at n: the row's (HOLD) or v_k + t (v_k+1 - v_k) (GLIDE), as any gene
+ *       p(n)    = pmin_q + g_q(n) (pmax_q - pmin_q)
+ *       beta_j(n) = p(n) > 0 ? fminf(p(n), 2) : +0     (NaN, negative values and -0 give +0; values above 2 give 2)
+ *       B_j(n)  = beta_j(n) * K                        (one fp32 product, uncontracted)
+ *     and the chain step at n uses B_j(n): z = Phi_j(n) + fix(B_j(n) * g) mod 2^32.  Nothing else changes.
+ *   A gene operator ALWAYS runs the chain, as in the voice itself, also where beta_j(n) = +0.  In the rendering that cannot be
+ *     seen in the bits: fix(+0 * g) = 0 for every g (|g| <= 1), so z = Phi_j(n), the word wraps and is never clamped, and
+ *     t_j(n) = shape(w_j, Phi_j(n) >> 17), the feed-forward value.
+ *   The other operators keep the context's index (sots_set_voice_feedback); those with beta_j != 0 run the chain with their
+ *     constant B_j as in sots_render_graph_feedback.  The operators that run a chain ("flagged") are the mask's and these.
+ * Anchors, both bit for bit.  (a) On a context whose mask is 0 the call is sots_render_graph_feedback: the same launches with
+ * the same arguments.  (b) A track whose effective index is the constant b_j on every gene operator (a gene range [b_j, b_j]
+ * and any finite gene value, HOLD or GLIDE) renders to what sots_render_graph_feedback gives for a context of
+ * sots_create_graph with the same graph, waveforms and ranges and sots_set_voice_feedback = b_j on those operators, fed the
+ * same rows without their gene columns; b_j anywhere in [0, 2], 0 included.
+ * The chain has one solution whether B is one constant or a value per sample: the carry into it is given and every sample is
+ * a function of the two before it and of its own B.  The bits do not depend on chain_form, relax_cap, tiles, grids or passes;
+ * tests/_render_graph_genes_model.py states it in NumPy, the chain twice.
+ *   chain_form 0  the library's choice per operator: an operator of the mask is relaxed, whatever its rows hold (at every
+ *                 index up to 1.5 the relaxation was measured faster, and at 2 it cost what the serial form costs; nothing in
+ *                 between was measured); every other flagged operator by the rule of sots_render_graph_feedback.
+ * A pass holds what it holds there, with the flagged operators counted as FB.
+ * SOTS_ERR_STATE for a context of a fixed voice; SOTS_ERR_INVALID and SOTS_ERR_SIZE as sots_render_graph_feedback, under this
+ * call's name, with D the context's: values_bytes != num_rows * D * 4 is SOTS_ERR_SIZE. */
+int sots_render_graph_genes(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
+                            const sots_render_graph_feedback_args *args, float *out, uint64_t out_samples);
 
 /* ---- per-stage device timing (feeds Benchmarker::addTimer, Benchmarker.hpp:109-130) ---- */
 int sots_timing_enable(sots_ctx *ctx, int enabled);

@@ -74,7 +74,7 @@ EXPORTS = [
     "sots_set_objective_weights", "sots_get_objective_weights", "sots_batch_set_objective_weights",
     "sots_group_set_objective_weights",
     "sots_render_overlap_add", "sots_batch_set_target_audio_hop", "sots_batch_queue_targets_audio_hop",
-    "sots_render_continuous", "sots_render_graph_continuous", "sots_render_graph_feedback",
+    "sots_render_continuous", "sots_render_graph_continuous", "sots_render_graph_feedback", "sots_render_graph_genes",
     "sots_batch_queue_set_carry", "sots_batch_queue_get_carry",
     "sots_batch_set_analysis", "sots_batch_get_analysis", "sots_batch_analyse_audio_hop", "sots_batch_queue_score_audio_hop",
     "sots_create_graph", "sots_batch_create_graph", "sots_get_voice_graph",
@@ -374,6 +374,7 @@ def load():
     L.sots_render_continuous.argtypes = [vp, vp, sz, u32, C.POINTER(RenderContinuousArgs), vp, C.c_uint64]
     L.sots_render_graph_continuous.argtypes = [vp, vp, sz, u32, C.POINTER(RenderContinuousArgs), vp, C.c_uint64]
     L.sots_render_graph_feedback.argtypes = [vp, vp, sz, u32, C.POINTER(RenderGraphFeedbackArgs), vp, C.c_uint64]
+    L.sots_render_graph_genes.argtypes = [vp, vp, sz, u32, C.POINTER(RenderGraphFeedbackArgs), vp, C.c_uint64]
     L.sots_batch_set_target_audio_hop.argtypes = [vp, vp, u32, u32, u32]
     L.sots_batch_queue_targets_audio_hop.argtypes = [vp, vp, C.c_uint64, u32, u32]
     L.sots_batch_queue_set_carry.argtypes = [vp, u32, u32]
@@ -635,6 +636,13 @@ class HipES:
         (0: the library's choice).  Neither changes a bit of the result."""
         args = RenderGraphFeedbackArgs(C.sizeof(RenderGraphFeedbackArgs), hop, RENDER_GLIDE if glide else 0, samples_per_pass, chain_form, relax_cap)
         return self._render(self.L.sots_render_graph_feedback, values, hop, out_samples, args)
+
+    # -- ... whose feedback indices are genes --
+    def render_graph_genes(self, values, hop, glide=False, samples_per_pass=0, chain_form=0, relax_cap=0, out_samples=None):
+        """render_graph_feedback for a context of feedback_genes=...: values[M][2 x operators + E], every row with its own
+        indices, held or glided like every gene.  With a mask of 0 it is render_graph_feedback."""
+        args = RenderGraphFeedbackArgs(C.sizeof(RenderGraphFeedbackArgs), hop, RENDER_GLIDE if glide else 0, samples_per_pass, chain_form, relax_cap)
+        return self._render(self.L.sots_render_graph_genes, values, hop, out_samples, args)
 
     # -- stages --
     def recombine(self):

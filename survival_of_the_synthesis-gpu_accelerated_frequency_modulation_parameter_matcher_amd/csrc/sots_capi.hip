@@ -390,10 +390,11 @@ int record_generation(sots_ctx *ctx)
 // What the three entry points share once their checks have passed: the passes.  `who` names the entry point in a refusal;
 // cap: the most samples its scratch lets a pass hold; layout(samples): its pass struct (ContPass, GraphPass) for passes of so
 // many samples, with .lay and whatever else is its own filled in; state_words: the words from lay.carry on that a pass
-// leaves for the next, cleared before the first; launch(pass) enqueues one pass.
+// leaves for the next, cleared before the first; launch(pass, rows) enqueues one pass, whose `rows` rows from pass.row_base on
+// are on the device.  width: the floats of a row of `values`, the context's D for every voice but one (render_graph_passes).
 template <class LAYOUT, class LAUNCH>
-int render_passes(sots_ctx *ctx, const char *who, const float *values, uint32_t num_rows, uint32_t hop, uint32_t flags, uint32_t samples_per_pass,
-                  uint64_t cap, uint32_t state_words, float *out, uint64_t out_samples, LAYOUT layout, LAUNCH launch)
+int render_passes(sots_ctx *ctx, const char *who, const float *values, uint32_t width, uint32_t num_rows, uint32_t hop, uint32_t flags,
+                  uint32_t samples_per_pass, uint64_t cap, uint32_t state_words, float *out, uint64_t out_samples, LAYOUT layout, LAUNCH launch)
 {
     const uint32_t N = ctx->N, D = ctx->D;
     const uint64_t covered = (uint64_t)(num_rows - 1u) * hop + N, want = out_samples < covered ? out_samples : covered;
@@ -423,10 +424,10 @@ int render_passes(sots_ctx *ctx, const char *who, const float *values, uint32_t 
         cont_position((uint32_t)s0, N / 2u, hop, num_rows, k0, r);
         cont_position((uint32_t)s0 + count - 1u, N / 2u, hop, num_rows, k1, r);
         k1 = k1 + 1u < num_rows ? k1 + 1u : num_rows - 1u; // (the row after: the second half of a hop, the far end of a glide)
-        SOTS_HIP(ctx, hipMemcpyAsync(ctx->render.values, values + (size_t)k0 * D, (size_t)(k1 - k0 + 1u) * D * sizeof(float),
+        SOTS_HIP(ctx, hipMemcpyAsync(ctx->render.values, values + (size_t)k0 * width, (size_t)(k1 - k0 + 1u) * width * sizeof(float),
                                      hipMemcpyHostToDevice, ctx->stream));
         ps.row_base = k0, ps.n0 = (uint32_t)s0, ps.count = count;
-        SOTS_HIP(ctx, launch(ps));
+        SOTS_HIP(ctx, launch(ps, k1 - k0 + 1u));
         // (stream order keeps the next pass off the scratch until this copy has read it)
         SOTS_HIP(ctx, hipMemcpyAsync(out + s0, ctx->render.out, (size_t)count * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     }
@@ -435,29 +436,58 @@ int render_passes(sots_ctx *ctx, const char *who, const float *values, uint32_t 
     return SOTS_OK;
 }
 
-// the operator-graph voice: the flagged operators (beta != 0), their B_j and the form of each one's chain.  None flagged: no
-// chain launch, and hist, behind the eight carries, is neither cleared nor touched.
+// the operator-graph voice: the flagged operators (beta != 0, or the index a gene), their B_j and the form of each one's
+// chain.  None flagged: no chain launch, and hist, behind the eight carries, is neither cleared nor touched.
+// With gene operators (sots_render_graph_genes alone gets here with any) a row of `values` is D = 2 OPS + E floats, and the
+// track is split on the host before the first pass: the rows' first 2 OPS floats, which go to the device as the rows of every
+// graph voice do, so that reduce, apply and mix are the kernels of every graph voice; and their E gene columns, which a pass
+// puts behind its rows on the device for the chains (GraphGenes).  Both parts of a pass's rows fit the D floats per row that
+// render_passes reserves.
 int render_graph_passes(sots_ctx *ctx, const char *who, const float *values, uint32_t num_rows, uint32_t hop, uint32_t flags,
                         uint32_t samples_per_pass, uint32_t chain_form, uint32_t relax_cap, float *out, uint64_t out_samples)
 {
-    const uint32_t ops = ctx->graph.num_operators;
+    const uint32_t ops = ctx->graph.num_operators, D = ctx->D;
     GraphPass fb{};
     scale_feedback(ctx->feedback, ops, fb.scaled);
-    for (uint32_t j = 0; j < ops; ++j) {
-        if (ctx->feedback[j] == 0.0f) continue;
-        fb.fb_mask |= 1u << j;
-        const uint32_t form = chain_form ? chain_form : graph_feedback_form(ctx->feedback[j]);
-        if (form == kChainRelax) fb.forms |= 1u << j;
-    }
+    const GraphGeneOps go = graph_gene_ops(ops, ctx->feedback_genes, ctx->feedback);
+    fb.fb_mask = go.flagged;
+    for (uint32_t j = 0; j < ops; ++j)
+        if ((go.flagged >> j & 1u) && graph_genes_form(chain_form, go.genes >> j & 1u, ctx->feedback[j]) == kChainRelax) fb.forms |= 1u << j;
     fb.relax_cap = relax_cap ? relax_cap : kRelaxCapLibrary;
+    GraphGenes gn{};
+    gn.first = 2u * ops, gn.count = D - gn.first, gn.mask = go.genes;
+    for (uint32_t j = 0; j < kGraphMaxOps; ++j) gn.column[j] = go.column[j];
+    std::vector<float> split; // [num_rows][2 OPS], then [num_rows][E]; alive until the last pass's copies have been waited for
+    const float *rows = values, *columns = nullptr;
+    if (gn.mask) {
+        split.resize((size_t)num_rows * D);
+        float *front = split.data(), *back = front + (size_t)num_rows * gn.first;
+        for (size_t r = 0; r < num_rows; ++r) {
+            memcpy(front + r * gn.first, values + r * D, gn.first * sizeof(float));
+            memcpy(back + r * gn.count, values + r * D + gn.first, gn.count * sizeof(float));
+        }
+        rows = front, columns = back;
+    }
     const uint32_t flagged = (uint32_t)__builtin_popcount(fb.fb_mask);
-    return render_passes(
-        ctx, who, values, num_rows, hop, flags, samples_per_pass, graph_feedback_max_pass(ops, flagged), fb.fb_mask ? 8u + 16u : 8u, out, out_samples,
+    size_t behind = 0; // where the gene columns of a pass lie in the context's buffer of rows: behind the most rows a pass has
+    const int rc = render_passes(
+        ctx, who, rows, gn.first, num_rows, hop, flags, samples_per_pass, graph_feedback_max_pass(ops, flagged), fb.fb_mask ? 8u + 16u : 8u, out,
+        out_samples,
         [&](uint32_t samples) {
             fb.lay = graph_layout(ops, flagged, samples);
+            behind = ((size_t)(samples / hop) + 3u) * gn.first;
             return fb;
         },
-        [&](const GraphPass &ps) { return launch_graph_pass(ctx->stream, ctx->graph, ctx->waveforms, ps, ctx->num_cus); });
+        [&](const GraphPass &ps, uint32_t pass_rows) {
+            if (!gn.mask) return launch_graph_pass(ctx->stream, ctx->graph, ctx->waveforms, ps, ctx->num_cus);
+            gn.rows = ctx->render.values + behind;
+            if (hipError_t e = hipMemcpyAsync(ctx->render.values + behind, columns + (size_t)ps.row_base * gn.count,
+                                              (size_t)pass_rows * gn.count * sizeof(float), hipMemcpyHostToDevice, ctx->stream))
+                return e;
+            return launch_graph_pass(ctx->stream, ctx->graph, ctx->waveforms, ps, ctx->num_cus, &gn);
+        });
+    if (rc != SOTS_OK && gn.mask) (void)hipStreamSynchronize(ctx->stream); // (a copy out of `split` may still be under way)
+    return rc;
 }
 
 } // namespace
@@ -1263,14 +1293,14 @@ int sots_render_continuous(sots_ctx *ctx, const float *values, size_t values_byt
     if (int rc = engine_bind(*ctx)) return rc;
     const uint32_t kind = ctx->cfg.synth_kind;
     return render_passes(
-        ctx, "sots_render_continuous", values, num_rows, args->hop, args->flags, args->samples_per_pass, kContMaxPass, kContMaxStages * kContMaxChains,
+        ctx, "sots_render_continuous", values, ctx->D, num_rows, args->hop, args->flags, args->samples_per_pass, kContMaxPass, kContMaxStages * kContMaxChains,
         out, out_samples,
         [&](uint32_t samples) {
             ContPass ps{};
             ps.lay = cont_layout(kind, samples);
             return ps;
         },
-        [&](const ContPass &ps) { return launch_continuous_pass(ctx->stream, kind, ps, ctx->num_cus); });
+        [&](const ContPass &ps, uint32_t) { return launch_continuous_pass(ctx->stream, kind, ps, ctx->num_cus); });
 }
 
 int sots_render_graph_continuous(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows,
@@ -1293,6 +1323,16 @@ int sots_render_graph_feedback(sots_ctx *ctx, const float *values, size_t values
                                                  ctx->feedback_genes));
     if (int rc = engine_bind(*ctx)) return rc;
     return render_graph_passes(ctx, "sots_render_graph_feedback", values, num_rows, args->hop, args->flags, args->samples_per_pass, args->chain_form,
+                               args->relax_cap, out, out_samples);
+}
+
+int sots_render_graph_genes(sots_ctx *ctx, const float *values, size_t values_bytes, uint32_t num_rows, const sots_render_graph_feedback_args *args,
+                            float *out, uint64_t out_samples)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    SOTS_REFUSE(ctx, render_graph_genes_check(ctx->cfg.synth_kind, args, ctx->N, ctx->D, values, values_bytes, num_rows, out, out_samples));
+    if (int rc = engine_bind(*ctx)) return rc;
+    return render_graph_passes(ctx, "sots_render_graph_genes", values, num_rows, args->hop, args->flags, args->samples_per_pass, args->chain_form,
                                args->relax_cap, out, out_samples);
 }
 

@@ -1,7 +1,8 @@
 // sots_render.h -- overlap-add resynthesis of a parameter track (sots_render.hip) and its phase-continuous
-// rendering (sots_render_continuous.hip), for the operator-graph voice with or without feedback operators
-// sots_render_graph.hip (4.16, 4.17).  Internal to libsots_hip.so; the public boundary is sots_render_overlap_add /
-// sots_render_continuous / sots_render_graph_continuous / sots_render_graph_feedback in include/sots_hip.h.
+// rendering (sots_render_continuous.hip), for the operator-graph voice with or without feedback operators,
+// fixed or genes, sots_render_graph.hip (4.16, 4.17, 4.19).  Internal to libsots_hip.so; the public boundary is
+// sots_render_overlap_add / sots_render_continuous / sots_render_graph_continuous / sots_render_graph_feedback /
+// sots_render_graph_genes in include/sots_hip.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -144,8 +145,25 @@ struct GraphPass {
     uint32_t forms;     // bit j: operator j's chain runs as a relaxation (else serially)
     uint32_t relax_cap; // sweeps per tile before a tile is finished serially, 1..4096 (read where fb_mask != 0)
 };
+// A voice whose feedback indices are genes (sots_create_graph_genes): a row of the track is D = 2 x operators
+// + E floats.  The pass's rows reach the device in two parts: their first 2 x operators floats in GraphPass::values, which is
+// all that reduce, apply and mix look at - they are the kernels of every graph voice, unchanged - and their E gene columns in
+// `rows`, E floats per row of the same rows (row_base ...), which only the chains look at.  An operator of `mask` takes B at
+// sample n from its column, held or glided and scaled by pass.sp as any gene: effective_feedback(p) K.  Every operator of mask
+// is flagged in the pass's fb_mask; the other flagged operators keep pass.scaled.  This stands beside GraphPass and not in it:
+// GraphPass is an argument by value of every kernel of the file, and the kernels of a voice without gene operators stay what
+// they were, byte for byte.  Only the chain launches of a voice with gene operators take it, kernels of their own.
+struct GraphGenes {
+    const float *rows;  // the gene columns of the pass's rows, `count` floats each
+    uint32_t count;     // E
+    uint32_t first;     // 2 x operators: gene column q of a row of D is rows[q - first], and its range pass.sp.pmin/pmax[q]
+    uint32_t mask;      // the operators whose index is a gene
+    uint32_t column[8]; // by operator: q; read where the operator's bit of mask is set
+};
 // every level of one pass with its chains, and the mix; the carries (lay.carry) and, where fb_mask != 0, hist are the
-// caller's to clear before the first pass.  waveforms: the eight codes (sots_set_voice_waveforms).
-hipError_t launch_graph_pass(hipStream_t st, const sots_voice_graph &graph, const uint32_t waveforms[8], const GraphPass &pass, uint32_t num_cus);
+// caller's to clear before the first pass.  waveforms: the eight codes (sots_set_voice_waveforms).  genes: null, or with a
+// mask of 0, for a voice without gene operators.
+hipError_t launch_graph_pass(hipStream_t st, const sots_voice_graph &graph, const uint32_t waveforms[8], const GraphPass &pass, uint32_t num_cus,
+                             const GraphGenes *genes = nullptr);
 
 } // namespace sots

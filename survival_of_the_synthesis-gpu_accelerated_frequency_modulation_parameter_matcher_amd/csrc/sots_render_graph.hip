@@ -37,6 +37,12 @@
 // Sweep k makes at least the first k samples final, so after relax_cap sweeps lane 0 finishes the tile from sample relax_cap.
 // No workgroup waits for another, no atomics, no scratch.  Every fp32 expression is the definition's (include/sots_hip.h),
 // uncontracted; tests/_render_graph_continuous_model.py and tests/_render_graph_feedback_model.py state the whole in NumPy.
+//
+// A voice whose feedback indices are genes (sots_render_graph_genes; GraphGenes, sots_render.h): a gene
+// operator's B is a value per sample, made from the gene columns of the pass's rows like a frequency or a level.  Neither the
+// scans nor the chain's exactness use the constancy of B.  Reduce, apply and mix are the kernels of every graph voice, fed the
+// rows' first 2 OPS floats; only the chains are kernels of the voice's own (.._genes).  tests/_render_graph_genes_model.py
+// states it.
 #include <type_traits>
 
 #include "sots_render.h"
@@ -64,17 +70,19 @@ struct GraphSample {
     float t;
     bool lerp;
 };
-__device__ inline GraphSample graph_sample(const GraphPass &ps, uint32_t d, uint32_t n)
+// (rows: the pass's rows, d floats each, from row_base on)
+__device__ inline GraphSample graph_sample(const GraphPass &ps, const float *rows, uint32_t d, uint32_t n)
 {
     uint32_t k, r;
     cont_position(n, ps.half_n, ps.hop, ps.num_rows, k, r);
     GraphSample s;
     s.lerp = ps.glide && r != 0u;
     if (!ps.glide) k += 2u * r >= ps.hop ? 1u : 0u;
-    s.a = ps.values + (size_t)(k - ps.row_base) * d;
+    s.a = rows + (size_t)(k - ps.row_base) * d;
     s.t = s.lerp ? (float)r / (float)ps.hop : 0.0f;
     return s;
 }
+__device__ inline GraphSample graph_sample(const GraphPass &ps, uint32_t d, uint32_t n) { return graph_sample(ps, ps.values, d, n); }
 // parameter g of the sample, scaled as the graph voice scales it: no folding of the ranges
 __device__ inline float graph_param(const GraphPass &ps, const GraphSample &s, uint32_t d, uint32_t g)
 {
@@ -418,6 +426,142 @@ template <bool TABLE> __global__ __launch_bounds__(kContThreads) void k_graph_ch
     if (n == 0) hist[0] = c1, hist[1] = c2;
 }
 
+// ---- the chains of a voice whose feedback indices are genes ----
+// The two forms above with B a value per sample.  They are kernels of their own, their text beside the forms' above and not
+// shared with it: a body that both call compiles the kernels above to other code (the same instructions in another order),
+// and a voice without gene operators is to launch what it launched before, byte for byte (tools/codeobj_diff.py).
+// An operator of gn.mask (a kernel argument: the branch is wavefront-uniform) takes B per sample from the gene columns of the
+// pass's rows, made by all lanes outside the chain and kept in a register and in LDS; the other operators of the launch keep
+// their constant.  No global access inside a chain.
+
+// B of gene operator j at pass sample `at`: the gene of the sample's rows, held or glided and scaled as any gene, made
+// effective, times K - one fp32 product.  A sample behind the pass's end takes the pass's last sample's rows.
+__device__ inline float graph_gene_scaled(const GraphPass &ps, const GraphGenes &gn, uint32_t j, uint32_t at)
+{
+    const uint32_t q = gn.column[j];
+    const GraphSample s = graph_sample(ps, gn.rows, gn.count, ps.n0 + (at < ps.count ? at : ps.count - 1u));
+    float v = s.a[q - gn.first];
+    if (s.lerp) v = v + s.t * (s.a[q - gn.first + gn.count] - v);
+    return effective_feedback(ps.sp.pmin[q] + v * (ps.sp.pmax[q] - ps.sp.pmin[q])) * kFeedbackScale;
+}
+
+// serial form: k_graph_chain_serial with the block's 256 values of B, four per lane, in LDS beside the phase words
+template <bool TABLE> __global__ __launch_bounds__(64) void k_graph_chain_serial_genes(GraphPass ps, GraphGenes gn, uint32_t shapes, uint32_t chain_ops)
+{
+    __shared__ float tab_s[TABLE ? kWavetableSize : 4];
+    __shared__ uint32_t phi_s[kSerialBlock];
+    __shared__ float big_s[kSerialBlock];
+    __shared__ float t_s[kSerialBlock];
+    const uint32_t j = chain_ops >> (3u * blockIdx.x) & 7u, w = shapes >> (3u * j) & 7u, lane = threadIdx.x;
+    if (TABLE && waveform_reads_table(w)) {
+        for (uint32_t i = lane; i < kWavetableSize / 4u; i += 64u)
+            reinterpret_cast<float4 *>(tab_s)[i] = reinterpret_cast<const float4 *>(ps.wavetable)[i];
+    }
+    const uint32_t *phi = ps.words + (size_t)j * ps.lay.stride;
+    float *t = graph_tbuf(ps, j), *hist = graph_hist(ps, j);
+    const uint32_t count = ps.count;
+    const bool gene = gn.mask >> j & 1u;
+    const float scaled = ps.scaled[j];
+    float h1 = hist[0], h2 = hist[1];
+    uint4 next = graph_load_words(phi, 4u * lane, count);
+    for (uint32_t base = 0; base < count; base += kSerialBlock) {
+        phi_s[4u * lane] = next.x, phi_s[4u * lane + 1u] = next.y, phi_s[4u * lane + 2u] = next.z, phi_s[4u * lane + 3u] = next.w;
+#pragma unroll
+        for (uint32_t e = 0; e < 4u; ++e) big_s[4u * lane + e] = gene ? graph_gene_scaled(ps, gn, j, base + 4u * lane + e) : scaled;
+        __syncthreads();
+        if (base + kSerialBlock < count) next = graph_load_words(phi, base + kSerialBlock + 4u * lane, count); // in flight under the chain
+        const uint32_t len = count - base < kSerialBlock ? count - base : kSerialBlock;
+        if (lane == 0) {
+            for (uint32_t n = 0; n < len; ++n) {
+                const float v = graph_step<TABLE>(w, phi_s[n], big_s[n], h1, h2, tab_s);
+                t_s[n] = v;
+                h2 = h1, h1 = v;
+            }
+        }
+        __syncthreads();
+        const uint32_t first = base + 4u * lane;
+        if (first + 4u <= count) {
+            *reinterpret_cast<float4 *>(t + first) = make_float4(t_s[4u * lane], t_s[4u * lane + 1u], t_s[4u * lane + 2u], t_s[4u * lane + 3u]);
+        } else {
+#pragma unroll
+            for (uint32_t e = 0; e < 4u; ++e)
+                if (first + e < count) t[first + e] = t_s[4u * lane + e];
+        }
+    }
+    if (lane == 0) hist[0] = h1, hist[1] = h2;
+}
+
+// relaxation: k_graph_chain_relax with this lane's sample's B made once per tile, before the sweeps, and kept in a register;
+// the in-order finish reads it from LDS
+template <bool TABLE>
+__global__ __launch_bounds__(kContThreads) void k_graph_chain_relax_genes(GraphPass ps, GraphGenes gn, uint32_t shapes, uint32_t chain_ops)
+{
+    __shared__ float tab_s[TABLE ? kWavetableSize : 4];
+    __shared__ float t_s[2][kRelaxTile];
+    __shared__ uint32_t phi_s[kRelaxTile];
+    __shared__ float big_s[kRelaxTile];
+    __shared__ uint32_t flag_s[2][kContWaves];
+    const uint32_t j = chain_ops >> (3u * blockIdx.x) & 7u, w = shapes >> (3u * j) & 7u, n = threadIdx.x;
+    if (TABLE && waveform_reads_table(w)) cont_load_table(tab_s, ps.wavetable);
+    const uint32_t *phi = ps.words + (size_t)j * ps.lay.stride;
+    float *t = graph_tbuf(ps, j), *hist = graph_hist(ps, j);
+    const uint32_t count = ps.count, cap = ps.relax_cap;
+    const bool gene = gn.mask >> j & 1u;
+    float c1 = hist[0], c2 = hist[1];
+    for (uint32_t base = 0; base < count; base += kRelaxTile) {
+        const uint32_t len = count - base < kRelaxTile ? count - base : kRelaxTile;
+        const bool live = n < len;
+        const uint32_t p = live ? phi[base + n] : 0u;
+        const float scaled = gene ? graph_gene_scaled(ps, gn, j, base + n) : ps.scaled[j];
+        float mine = graph_shape<TABLE>(w, p >> 17, tab_s);
+        phi_s[n] = p;
+        big_s[n] = scaled;
+        t_s[0][n] = mine;
+        __syncthreads();
+        const uint32_t limit = cap < len ? cap : len;
+        uint32_t cur = 0;
+        bool settled = false;
+        for (uint32_t s = 0; s < limit; ++s) {
+            const float *src = t_s[cur];
+            const float a = n >= 1u ? src[n - 1u] : c1;
+            const float b = n >= 2u ? src[n - 2u] : (n == 1u ? c1 : c2);
+            const float v = graph_step<TABLE>(w, p, scaled, a, b, tab_s);
+            const bool changed = live && __float_as_uint(v) != __float_as_uint(mine);
+            t_s[cur ^ 1u][n] = v;
+            mine = v;
+            const bool wave_changed = __ballot(changed) != 0ull;
+            if ((n & 63u) == 0u) flag_s[s & 1u][n >> 6] = wave_changed ? 1u : 0u;
+            __syncthreads();
+            cur ^= 1u;
+            uint32_t any = 0;
+#pragma unroll
+            for (int q = 0; q < kContWaves; ++q) any |= flag_s[s & 1u][q];
+            if (any == 0u) {
+                settled = true;
+                break;
+            }
+        }
+        if (!settled && limit < len) {
+            if (n == 0) {
+                float *fin = t_s[cur];
+                float h1 = fin[limit - 1u], h2 = limit >= 2u ? fin[limit - 2u] : c1;
+                for (uint32_t i = limit; i < len; ++i) {
+                    const float v = graph_step<TABLE>(w, phi_s[i], big_s[i], h1, h2, tab_s);
+                    fin[i] = v;
+                    h2 = h1, h1 = v;
+                }
+            }
+            __syncthreads();
+        }
+        const float *fin = t_s[cur];
+        if (live) t[base + n] = fin[n];
+        const float e1 = fin[len - 1u], e2 = len >= 2u ? fin[len - 2u] : c1;
+        c1 = e1, c2 = e2;
+        __syncthreads(); // the next tile writes t_s, phi_s, big_s and flag_s
+    }
+    if (n == 0) hist[0] = c1, hist[1] = c2;
+}
+
 // f(TABLE, FB) with the two decided at run time as compile-time constants
 template <class F> hipError_t graph_pick(bool table, bool fb, F f)
 {
@@ -442,7 +586,9 @@ hipError_t graph_level(hipStream_t st, const GraphPass &ps, const GraphTopo &tp,
 }
 
 // the chains of the operators in `set` (a bit mask, all of one level), serially or as relaxations
-hipError_t graph_chains(hipStream_t st, const GraphPass &ps, const GraphTopo &tp, const uint32_t codes[8], uint32_t set, bool relax)
+// (gn: null for a voice without gene operators)
+hipError_t graph_chains(hipStream_t st, const GraphPass &ps, const GraphTopo &tp, const uint32_t codes[8], uint32_t set, bool relax,
+                        const GraphGenes *gn)
 {
     uint32_t chain_ops = 0, in_launch = 0;
     bool table = false;
@@ -452,7 +598,15 @@ hipError_t graph_chains(hipStream_t st, const GraphPass &ps, const GraphTopo &tp
         table = table || waveform_reads_table(codes[j]);
     }
     if (in_launch == 0) return hipSuccess;
-    if (relax) {
+    if (gn) {
+        if (relax) {
+            if (table) k_graph_chain_relax_genes<true><<<in_launch, kContThreads, 0, st>>>(ps, *gn, tp.shapes, chain_ops);
+            else k_graph_chain_relax_genes<false><<<in_launch, kContThreads, 0, st>>>(ps, *gn, tp.shapes, chain_ops);
+        } else {
+            if (table) k_graph_chain_serial_genes<true><<<in_launch, 64, 0, st>>>(ps, *gn, tp.shapes, chain_ops);
+            else k_graph_chain_serial_genes<false><<<in_launch, 64, 0, st>>>(ps, *gn, tp.shapes, chain_ops);
+        }
+    } else if (relax) {
         if (table) k_graph_chain_relax<true><<<in_launch, kContThreads, 0, st>>>(ps, tp.shapes, chain_ops);
         else k_graph_chain_relax<false><<<in_launch, kContThreads, 0, st>>>(ps, tp.shapes, chain_ops);
     } else {
@@ -464,7 +618,8 @@ hipError_t graph_chains(hipStream_t st, const GraphPass &ps, const GraphTopo &tp
 
 } // namespace
 
-hipError_t launch_graph_pass(hipStream_t st, const sots_voice_graph &graph, const uint32_t waveforms[8], const GraphPass &ps, uint32_t num_cus)
+hipError_t launch_graph_pass(hipStream_t st, const sots_voice_graph &graph, const uint32_t waveforms[8], const GraphPass &ps, uint32_t num_cus,
+                             const GraphGenes *genes)
 {
     if (!ps.values || !ps.wavetable || !ps.words || !ps.out || ps.num_rows == 0 || ps.hop == 0 || ps.hop > 2u * ps.half_n) return hipErrorInvalidValue;
     if (voice_graph_check(&graph)) return hipErrorInvalidValue;
@@ -473,6 +628,15 @@ hipError_t launch_graph_pass(hipStream_t st, const sots_voice_graph &graph, cons
     const GraphLayout &lay = ps.lay;
     // what the kernels' 32-bit indices and the scratch layout rest on
     if (ps.fb_mask >> ops) return hipErrorInvalidValue;
+    // a voice with gene operators: every one of them is flagged, and its column is the one the rules give it
+    const GraphGenes *gn = genes && genes->mask ? genes : nullptr;
+    if (gn) {
+        if (!gn->rows || (gn->mask & ~ps.fb_mask) || gn->first != 2u * ops || gn->count != feedback_gene_count(gn->mask) ||
+            gn->first + gn->count > SOTS_MAX_DIMS)
+            return hipErrorInvalidValue;
+        for (uint32_t j = 0; j < ops; ++j)
+            if ((gn->mask >> j & 1u) && gn->column[j] != feedback_gene_column(ops, gn->mask, j)) return hipErrorInvalidValue;
+    }
     if (ps.count > graph_feedback_max_pass(ops, flagged) || ps.count > lay.stride || (lay.stride & 3u) || (uint64_t)ps.n0 + ps.count > (1ull << 31))
         return hipErrorInvalidValue;
     const uint32_t tiles = (ps.count + kContTile - 1u) / kContTile;
@@ -504,9 +668,9 @@ hipError_t launch_graph_pass(hipStream_t st, const sots_voice_graph &graph, cons
         });
         if (e != hipSuccess) return e;
         const uint32_t chains = level_mask & ps.fb_mask;
-        e = graph_chains(st, ps, tp, codes, chains & ~ps.forms, false);
+        e = graph_chains(st, ps, tp, codes, chains & ~ps.forms, false, gn);
         if (e != hipSuccess) return e;
-        e = graph_chains(st, ps, tp, codes, chains & ps.forms, true);
+        e = graph_chains(st, ps, tp, codes, chains & ps.forms, true, gn);
         if (e != hipSuccess) return e;
     }
     bool table = false; // some carrier's value is made from its phase word by a shape that reads the table

@@ -172,7 +172,8 @@ inline uint32_t feedback_gene_column(uint32_t ops, uint32_t feedback_genes, uint
     return 2u * ops + feedback_gene_count(feedback_genes & ((1u << j) - 1u));
 }
 // The effective index of a scaled gene p: NaN and everything not above 0 give +0, everything above 2 gives 2
-inline float effective_feedback(float p) { return p > 0.0f ? (p < kFeedbackMax ? p : kFeedbackMax) : 0.0f; }
+// (constexpr: the renderer's chain kernels make it per sample, sots_render_graph.hip)
+constexpr float effective_feedback(float p) { return p > 0.0f ? (p < kFeedbackMax ? p : kFeedbackMax) : 0.0f; }
 // What a mask other than 0 adds to config_check, for a checked graph: the mask lies within the operators, the genes fit a
 // row, the configuration counts them, and each gene column's range lies in [0, 2] in ascending order
 inline Fault voice_feedback_genes_check(const sots_config &cfg, const sots_voice_graph &graph, uint32_t feedback_genes)
@@ -509,20 +510,62 @@ constexpr uint32_t kRelaxCapMax = 4096, kRelaxCapLibrary = 1024;
 // was the fastest or within a percent of it at every index.
 constexpr float kRelaxBetaMax = 1.5f;
 inline uint32_t graph_feedback_form(float beta) { return beta <= kRelaxBetaMax ? kChainRelax : kChainSerial; }
-// sots_render_graph_feedback: what it refuses before anything touches the device; those of render_graph_continuous_check
-// without the feedback one, and the two of its own arguments.
-inline Fault render_graph_feedback_check(uint32_t kind, const sots_render_graph_feedback_args *args, uint32_t n, uint32_t d, const void *values,
-                                         size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples, uint32_t feedback_genes = 0)
+// What sots_render_graph_feedback and sots_render_graph_genes refuse alike before anything touches the device, under the name
+// `who`: those of render_graph_continuous_check without the feedback one, and the two of their own arguments.
+inline Fault render_graph_chain_check(const char *who, uint32_t kind, uint32_t feedback_genes, const sots_render_graph_feedback_args *args, uint32_t n,
+                                      uint32_t d, const void *values, size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples)
 {
-    const char *who = "sots_render_graph_feedback";
     if (const Fault f = render_graph_voice_check(who, kind, feedback_genes)) return f;
     if (const Fault f = render_cont_args_check(who, "sots_render_graph_feedback_args", args, n)) return f;
     if (args->chain_form > kChainRelax)
-        return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: chain_form %u is not a form (0 = the library's choice, 1 = serial, 2 = relaxation)",
-                     args->chain_form);
-    if (args->relax_cap > kRelaxCapMax)
-        return fault(SOTS_ERR_INVALID, "sots_render_graph_feedback: relax_cap %u outside 0..%u", args->relax_cap, kRelaxCapMax);
+        return fault(SOTS_ERR_INVALID, "%s: chain_form %u is not a form (0 = the library's choice, 1 = serial, 2 = relaxation)", who, args->chain_form);
+    if (args->relax_cap > kRelaxCapMax) return fault(SOTS_ERR_INVALID, "%s: relax_cap %u outside 0..%u", who, args->relax_cap, kRelaxCapMax);
     return render_cont_track_check(who, args->hop, n, d, values, values_bytes, num_rows, out, out_samples);
+}
+// sots_render_graph_feedback: all of them, a context whose feedback indices are genes among them
+inline Fault render_graph_feedback_check(uint32_t kind, const sots_render_graph_feedback_args *args, uint32_t n, uint32_t d, const void *values,
+                                         size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples, uint32_t feedback_genes = 0)
+{
+    return render_graph_chain_check("sots_render_graph_feedback", kind, feedback_genes, args, n, d, values, values_bytes, num_rows, out, out_samples);
+}
+
+// ---- ... whose feedback indices are genes (sots_render_graph_genes) ----
+// The operators whose chain a rendering runs ("flagged"): the gene operators, whatever their rows hold, and the others with
+// beta_j != 0.  Per operator: whether it is flagged, whether its index is a gene, and the gene's column in a row of D.
+struct GraphGeneOps {
+    uint32_t flagged, genes;       // bit masks; genes is a subset of flagged
+    uint32_t column[kGraphMaxOps]; // by operator; 0 where the operator's index is no gene
+};
+inline GraphGeneOps graph_gene_ops(uint32_t ops, uint32_t feedback_genes, const float feedback[8])
+{
+    GraphGeneOps g{};
+    for (uint32_t j = 0; j < ops && j < kGraphMaxOps; ++j) {
+        if (feedback_genes >> j & 1u) {
+            g.genes |= 1u << j, g.flagged |= 1u << j;
+            g.column[j] = feedback_gene_column(ops, feedback_genes, j);
+        } else if (feedback[j] != 0.0f) {
+            g.flagged |= 1u << j;
+        }
+    }
+    return g;
+}
+// The form of a flagged operator's chain.  chain_form 1 and 2 force it.  Under the library's choice a fixed-index operator keeps
+// graph_feedback_form(beta_j); a gene operator gets the relaxation (with the cap kRelaxCapLibrary where none is given),
+// whatever its rows hold.  No rule on the rows is needed: in profiles/r27_render_graph_feedback.json the relaxation at cap 1024
+// beat the serial form at every index up to 1.5, and at 2, where every tile takes its thousand sweeps, it cost what the
+// serial form costs (311.5 against 310.3 ms).  Nothing between 1.5 and 2 was measured.  On a track whose index varies over
+// [0, 2] from row to row the relaxation took 0.19 to 0.27 of the serial form's time (profiles/r31_render_graph_genes.json).
+inline uint32_t graph_genes_form(uint32_t chain_form, bool gene, float beta)
+{
+    if (chain_form != kChainLibrary) return chain_form;
+    return gene ? kChainRelax : graph_feedback_form(beta);
+}
+// sots_render_graph_genes: what it refuses before anything touches the device; those of render_graph_feedback_check under its
+// own name, without the refusal of a gene mask.  d: the context's genes per row, 2 OPS + E.
+inline Fault render_graph_genes_check(uint32_t kind, const sots_render_graph_feedback_args *args, uint32_t n, uint32_t d, const void *values,
+                                      size_t values_bytes, uint32_t num_rows, const void *out, uint64_t out_samples)
+{
+    return render_graph_chain_check("sots_render_graph_genes", kind, 0, args, n, d, values, values_bytes, num_rows, out, out_samples);
 }
 
 // ---- run record, stop rules ----

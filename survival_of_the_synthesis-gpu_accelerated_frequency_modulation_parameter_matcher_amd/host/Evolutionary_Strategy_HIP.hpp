@@ -58,7 +58,8 @@ struct Evolutionary_Strategy_HIP_Arguments
     std::vector<float> voiceFeedback;
     // ... or, for the operators in this mask, a gene of the individual (type.HIP.voiceFeedbackGenes; sots_create_graph_genes,
     // DESIGN.md 4.18): numDimensions = 2 x num_operators + the set bits, the genes' ranges behind the others.  Only with the
-    // graph voice and not with renderMode 3 to 6: the constructor throws before any device work; the library refuses the rest.
+    // graph voice and not with renderMode 3 to 6 (7 and 8 render it): the constructor throws before any device work; the
+    // library refuses the rest.
     uint32_t voiceFeedbackGenes = 0;
     bool fusedGenerations = true;     // executeAllGenerations uses the fused kernel loop
     // general.isBenchmarking (parameters.json:7, main.cpp:85).  true: every launch is bracketed by a
@@ -161,7 +162,8 @@ struct Evolutionary_Strategy_HIP_Arguments
     //                 chunk centre), 2 = phase-continuous with the parameters interpolated between the centres.  Takes effect
     //                 only with renderMatch; 1 and 2 are not available with deviceKernelArithmetic.  3 and 4 are 1 and 2 for the
     //                 operator-graph voice (sots_render_graph_continuous) and need it.  5 and 6 are 3 and 4 for a
-    //                 graph voice with feedback indices (sots_render_graph_feedback).
+    //                 graph voice with feedback indices (sots_render_graph_feedback).  7 and 8 are 5 and 6 for a
+    //                 graph voice whose feedback indices may be genes (sots_render_graph_genes).
     //   matchPath   : sots_match writes the parameter track there, one CSV row per chunk (Match_track.hpp)
     uint32_t hopSize = 0;
     bool renderMatch = false;
@@ -351,7 +353,8 @@ public:
     // With renderMode 1 or 2 the same track goes through sots_render_continuous instead: the same length, one voice from the
     // first sample to the last, chunk i's parameters reached at its centre i hop + N/2.  With 3 or 4 (the operator-graph
     // voice) through sots_render_graph_continuous, which is the same for a voice graph, and with 5 or 6 through
-    // sots_render_graph_feedback, which is the same for a voice graph with feedback indices.
+    // sots_render_graph_feedback, which is the same for a voice graph with feedback indices, and with 7 or 8
+    // through sots_render_graph_genes, which is the same for a voice graph with voiceFeedbackGenes.
     void renderMatch(std::vector<float> &out)
     {
         const uint32_t d = population.numDimensions, chunks = (uint32_t)bestPerChunk_.size();
@@ -359,12 +362,13 @@ public:
         if (!chunks) return;
         std::vector<float> values((size_t)chunks * d);
         for (uint32_t c = 0; c < chunks; ++c) std::copy(bestPerChunk_[c].begin(), bestPerChunk_[c].begin() + d, values.begin() + (size_t)c * d);
-        if (args_.renderMode == 5u || args_.renderMode == 6u) {
+        if (args_.renderMode >= 5u && args_.renderMode <= 8u) {
             sots_render_graph_feedback_args fa{};
             fa.struct_size = sizeof fa;
             fa.hop = hop_;
-            fa.flags = args_.renderMode == 6u ? (uint32_t)SOTS_RENDER_GLIDE : 0u;
-            check(sots_render_graph_feedback(ctx_, values.data(), values.size() * sizeof(float), chunks, &fa, out.data(), out.size()), "renderMatch");
+            fa.flags = args_.renderMode == 6u || args_.renderMode == 8u ? (uint32_t)SOTS_RENDER_GLIDE : 0u;
+            const auto render = args_.renderMode >= 7u ? sots_render_graph_genes : sots_render_graph_feedback;
+            check(render(ctx_, values.data(), values.size() * sizeof(float), chunks, &fa, out.data(), out.size()), "renderMatch");
             return;
         }
         if (args_.renderMode != 0u) {
@@ -423,7 +427,9 @@ public:
         if (graphVoice && args_.deviceKernelArithmetic)
             throw std::runtime_error("Evolutionary_Strategy_HIP: deviceKernelArithmetic is not available with the operator-graph voice");
         if (!graphVoice && args_.renderMode >= 3u)
-            throw std::runtime_error(args_.renderMode >= 5u
+            throw std::runtime_error(args_.renderMode >= 7u
+                                         ? "Evolutionary_Strategy_HIP: renderMode 7 and 8 (sots_render_graph_genes) need the operator-graph voice"
+                                     : args_.renderMode >= 5u
                                          ? "Evolutionary_Strategy_HIP: renderMode 5 and 6 (sots_render_graph_feedback) need the operator-graph voice"
                                          : "Evolutionary_Strategy_HIP: renderMode 3 and 4 (sots_render_graph_continuous) need the operator-graph voice");
         if (!graphVoice && !args_.voiceWaveforms.empty())
@@ -432,9 +438,10 @@ public:
             throw std::runtime_error("Evolutionary_Strategy_HIP: voiceFeedback needs the operator-graph voice");
         if (!graphVoice && args_.voiceFeedbackGenes)
             throw std::runtime_error("Evolutionary_Strategy_HIP: voiceFeedbackGenes need the operator-graph voice");
-        if (args_.voiceFeedbackGenes && args_.renderMode >= 3u)
+        if (args_.renderMode > 8u) throw std::runtime_error("Evolutionary_Strategy_HIP: renderMode must be 0 to 8");
+        if (args_.voiceFeedbackGenes && args_.renderMode >= 3u && args_.renderMode <= 6u)
             throw std::runtime_error("Evolutionary_Strategy_HIP: renderMode 3 to 6 take the feedback index from the voice, not from the row: "
-                                     "voiceFeedbackGenes are rendered by renderMode 0 (sots_render_overlap_add)");
+                                     "voiceFeedbackGenes are rendered by renderMode 0 (sots_render_overlap_add) and 7, 8 (sots_render_graph_genes)");
         cfg_.workgroup_size = args_.workgroupX * args_.workgroupY * args_.workgroupZ;
         cfg_.device = args_.deviceOrdinal;
         cfg_.gid_base = args_.gidBase;

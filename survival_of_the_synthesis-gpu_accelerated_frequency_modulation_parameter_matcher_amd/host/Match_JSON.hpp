@@ -203,26 +203,36 @@ inline bool readHopSizeKey(const Json &h, uint32_t audioLength, uint32_t &hopSiz
 // parameters held from chunk centre to chunk centre) or "continuousGlide" (2: the same with the parameters interpolated
 // between the centres); for the operator-graph voice "graphContinuous" (3) and "graphContinuousGlide" (4): the same two
 // through sots_render_graph_continuous, and "graphFeedback" (5) and "graphFeedbackGlide" (6): the same two
-// through sots_render_graph_feedback, which renders a voice with type.HIP.voiceFeedback too.  Returns whether
-// the key was there; throws - before any device work - on anything else.
+// through sots_render_graph_feedback, which renders a voice with type.HIP.voiceFeedback too, and "graphGenes"
+// (7) and "graphGenesGlide" (8): the same two through sots_render_graph_genes, which renders a voice with
+// type.HIP.voiceFeedbackGenes too, every chunk with its own feedback indices.  Returns whether the key was there; throws -
+// before any device work - on anything else.
 inline bool readRenderModeKey(const Json &h, uint32_t &renderMode)
 {
     if (!h.has("renderMode")) return false;
     const Json &v = h["renderMode"];
-    const char *names[] = {"overlapAdd", "continuous", "continuousGlide", "graphContinuous", "graphContinuousGlide", "graphFeedback", "graphFeedbackGlide"};
+    const char *names[] = {"overlapAdd",    "continuous",         "continuousGlide", "graphContinuous", "graphContinuousGlide",
+                           "graphFeedback", "graphFeedbackGlide", "graphGenes",      "graphGenesGlide"};
     if (v.kind == Json::String)
-        for (uint32_t m = 0; m < 7; ++m)
+        for (uint32_t m = 0; m < 9; ++m)
             if (v.str == names[m]) return renderMode = m, true;
     throw std::runtime_error("parameters.json: type.HIP.renderMode must be \"overlapAdd\", \"continuous\" or \"continuousGlide\" (with type.HIP.synth "
-                             "\"graph\": \"overlapAdd\", \"graphContinuous\" or \"graphContinuousGlide\", \"graphFeedback\" or \"graphFeedbackGlide\")" +
+                             "\"graph\": \"overlapAdd\", \"graphContinuous\" or \"graphContinuousGlide\", \"graphFeedback\" or \"graphFeedbackGlide\", "
+                             "\"graphGenes\" or \"graphGenesGlide\")" +
                              (v.kind == Json::String ? ", not \"" + v.str + "\"" : std::string()));
 }
 // renderMode "graphContinuous" / "graphContinuousGlide" belong to the operator-graph voice, and to one without feedback
 // (sots_render_graph_continuous refuses a feedback index other than 0: no scan computes that recurrence); "graphFeedback" /
-// "graphFeedbackGlide" belong to the operator-graph voice, with or without feedback.  Throws - before any device work -
-// otherwise; the feedback is looked at only where the match is rendered.
+// "graphFeedbackGlide" belong to the operator-graph voice, with or without feedback; "graphGenes" / "graphGenesGlide" to the
+// operator-graph voice, with or without voiceFeedbackGenes.  Throws - before any device work - otherwise; the feedback is
+// looked at only where the match is rendered.
 inline void checkGraphRenderMode(uint32_t renderMode, bool graphVoice, bool renderMatch, const std::vector<float> &voiceFeedback)
 {
+    if (renderMode == 7u || renderMode == 8u) {
+        if (!graphVoice)
+            throw std::runtime_error("parameters.json: type.HIP.renderMode \"graphGenes\" and \"graphGenesGlide\" need type.HIP.synth \"graph\"");
+        return;
+    }
     if (renderMode == 5u || renderMode == 6u) {
         if (!graphVoice)
             throw std::runtime_error("parameters.json: type.HIP.renderMode \"graphFeedback\" and \"graphFeedbackGlide\" need type.HIP.synth \"graph\"");
@@ -409,8 +419,9 @@ inline bool readVoiceFeedbackKey(const Json &h, bool graphVoice, uint32_t operat
 // the others.  Returns whether the key is there; mask receives bit j for operator j.  Throws - before any device work -
 // without type.HIP.synth "graph", on anything but a list of `operators` entries that are 0 or 1, on an operator that also has
 // a voiceFeedback other than 0, on more than 16 genes, on numDimensions / paramMins / paramMaxs that do not count the genes,
-// and on any "graph..." renderMode (those renderers take the index from the voice, not from the row; "overlapAdd" renders
-// every row with its own).  The ranges themselves are the library's rule.
+// and on the renderModes "graphContinuous" to "graphFeedbackGlide" (those renderers take the index from the voice, not from
+// the row; "overlapAdd" renders every row with its own, and so do "graphGenes" / "graphGenesGlide", phase-continuously).  The
+// ranges themselves are the library's rule.
 inline bool readVoiceFeedbackGenesKey(const Json &h, bool graphVoice, uint32_t operators, const std::vector<float> &voiceFeedback, uint32_t numDimensions,
                                       size_t numParamMins, size_t numParamMaxs, uint32_t renderMode, uint32_t &mask)
 {
@@ -440,7 +451,7 @@ inline bool readVoiceFeedbackGenesKey(const Json &h, bool graphVoice, uint32_t o
                                  std::to_string(numDimensions) + ", " + std::to_string(numParamMins) + " and " + std::to_string(numParamMaxs));
     static const char *const modes[] = {"", "", "", "graphContinuous", "graphContinuousGlide", "graphFeedback", "graphFeedbackGlide"};
     if (m && renderMode >= 3u && renderMode <= 6u)
-        throw std::runtime_error(what + ": every row has its own feedback index, which type.HIP.renderMode \"" + modes[renderMode] + "\" cannot render (\"overlapAdd\" does)");
+        throw std::runtime_error(what + ": every row has its own feedback index, which type.HIP.renderMode \"" + modes[renderMode] + "\" cannot render (\"overlapAdd\" does, and \"graphGenes\" renders it phase-continuously)");
     mask = m;
     return true;
 }

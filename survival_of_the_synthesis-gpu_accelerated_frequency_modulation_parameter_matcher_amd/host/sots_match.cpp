@@ -22,6 +22,8 @@
 //                 are "graphContinuous" and "graphContinuousGlide" (sots_render_graph_continuous): the same rendering for
 //                 any voice graph and its waveforms, not with a "voiceFeedback" other than 0; refused with any other synth.
 //                 "graphFeedback" and "graphFeedbackGlide" (sots_render_graph_feedback) are those two with any "voiceFeedback".
+//                 "graphGenes" and "graphGenesGlide" (sots_render_graph_genes) are those two with "voiceFeedbackGenes" too: every
+//                 chunk's match with its own feedback indices, held or interpolated like its other parameters.
 //   "voiceGraph"  with "synth": "graph", the operator-graph voice (sots_create_graph): {"operators": n, "modulators":
 //                 [[...], ...], "carriers": [...]} - modulators[j] lists the operators that modulate operator j (each
 //                 below j), carriers the operators that are heard; gene 2j is operator j's frequency, gene 2j+1 its level,
@@ -34,7 +36,8 @@
 //   "voiceFeedbackGenes" with "voiceGraph": one 0 or 1 per operator; 1 makes that operator's feedback index a gene of the
 //                 individual (sots_create_graph_genes): "numDimensions" is 2 n + the number of 1s, "paramMins" / "paramMaxs"
 //                 carry the genes' ranges, within [0, 2], behind the others, and "matchPath" writes the index per chunk with
-//                 the other columns.  Not on an operator with a "voiceFeedback" other than 0, not with a "graph..." renderMode.
+//                 the other columns.  Not on an operator with a "voiceFeedback" other than 0; of the "graph..." renderModes only
+//                 "graphGenes" and "graphGenesGlide" (sots_render_graph_genes) render such a match.
 //   "voiceFeedback" with "voiceGraph": one feedback index in [0, 2] per operator, 0 (the default) for none: the operator's phase
 //                 is offset by index x W / 2 pi x the mean of its own last two values (sots_set_voice_feedback), so that a
 //                 sine operator emits a harmonic series whose brightness follows the index.  Used wherever the waveforms are.
