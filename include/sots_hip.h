@@ -80,7 +80,11 @@ enum sots_sort_mode {
                               * sort; rows S..P-1 are produced, from the still intact unsorted half, by the first
                               * call that looks at them (read/write population, any sots_stage_*, packing more
                               * than S elites).  A population outside 1024 < P <= 131072 or with S > P/2 is sorted in full.
-                              * Calls that WRITE rows (stages, write_population, init) end the pending state. */
+                              * Calls that WRITE rows (stages, write_population, init) end the pending state.
+                              * Settings (target, objective, weights, survivors, arithmetic, voice, select plan, splitters,
+                              * sots_set_generation, sots_track), the renderers, sots_inject_immigrants_* (the rows it writes
+                              * are placed rows) and every refused call neither produce nor drop the rows; a generation of
+                              * either loop and sots_stage_recombine read rows 0..S-1 only and write every row anew. */
     SOTS_SORT_FULL = 1,      /* the reference's behaviour: every generation sorts all P rows
                               * (ocl_program.cl:664-711, Evolutionary_Strategy.hpp:108-124) */
     SOTS_SORT_TOP_ONLY = 2   /* like 0 but rows S..P-1 are never produced (their content is unspecified; packing more
@@ -287,7 +291,8 @@ int sots_set_target_spectrum(sots_ctx *ctx, const float *magnitudes, uint32_t nu
 /* ---- population (initPopulationCL ...OpenCL.hpp:369-378; write/readPopulationData :403-430) ---- */
 int sots_init_population(sots_ctx *ctx, uint32_t chunk_index);
 /* any pointer may be NULL; byte counts must equal P*D*4 (values, steps) and P*4 (fitness).
- * Reads and writes address the CURRENT rotation half. */
+ * Reads and writes address the CURRENT rotation half.  The byte counts are checked before anything changes: a refused
+ * sots_write_population (SOTS_ERR_SIZE) leaves rows, pending state and stored splitters as they were. */
 int sots_write_population(sots_ctx *ctx, const float *values, size_t values_bytes,
                           const float *steps, size_t steps_bytes,
                           const float *fitness, size_t fitness_bytes);
@@ -334,7 +339,11 @@ int sots_execute_generation(sots_ctx *ctx);
  * (executeAllGenerations, ...OpenCL.hpp:542-547) */
 int sots_execute_generations(sots_ctx *ctx, uint32_t n);
 
-int sots_set_sort_mode(sots_ctx *ctx, uint32_t mode); /* enum sots_sort_mode */
+/* enum sots_sort_mode.  The new mode decides what happens to rows a selection has left out: leaving SOTS_SORT_TOP_ONLY, or
+ * SOTS_SORT_LAZY_TAIL for SOTS_SORT_FULL, while they are outstanding produces them now; entering SOTS_SORT_TOP_ONLY keeps them
+ * outstanding (unspecified until the mode is left again).  Where a write has ended the pending state in between, leaving
+ * SOTS_SORT_TOP_ONLY produces nothing: rows S..P-1 stay what the write left.  Setting the mode in force again changes nothing. */
+int sots_set_sort_mode(sots_ctx *ctx, uint32_t mode);
 int sots_set_select_plan(sots_ctx *ctx, uint32_t plan); /* enum sots_select_plan */
 /* The splitters the next SPLITTERS selection reads (one per compute unit: sots_select_splitter_count), for tests and
  * diagnostics: keys are (order-preserving fitness bits << 32) | row index; any values are allowed. */
@@ -345,7 +354,9 @@ int sots_read_select_splitters(sots_ctx *ctx, uint64_t *keys, uint32_t count);
  * between the splitters the next sots_stage_select reads - what the fused loop's spectral kernel does as it computes the
  * fitness - so that this sots_stage_select takes its buckets from the lists.  Anything that replaces rows, fitness,
  * splitters, target, plan or sort mode in between drops the lists again.  SOTS_ERR_STATE where a slot holds more than
- * 256 splitters, or with SOTS_SELECT_LISTS=0 in the environment of sots_create (the selection then always streams). */
+ * 256 splitters, or with SOTS_SELECT_LISTS=0 in the environment of sots_create (the selection then always streams).
+ * Like every sots_stage_* it looks at all P rows: rows a lazy selection has left out are produced first (under
+ * SOTS_SORT_TOP_ONLY they are not, and what is filed for them is as unspecified as they are). */
 int sots_stage_bucket_fitness(sots_ctx *ctx);
 /* What sots_stage_bucket_fitness filed, for tests of the filing itself (SOTS_ERR_STATE unless it was the last thing to
  * touch the lists).  With B = sots_select_splitter_count: counts[B * 16] - counter s of bucket j at j * 16 + s, every key

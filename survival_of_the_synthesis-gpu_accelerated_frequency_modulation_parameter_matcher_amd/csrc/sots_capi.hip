@@ -669,6 +669,8 @@ int sots_write_population(sots_ctx *ctx, const float *values, size_t values_byte
                           size_t steps_bytes, const float *fitness, size_t fitness_bytes)
 {
     SOTS_REQUIRE_CTX(ctx);
+    // refused before anything changes: settle_tail ends a pending state, which under SOTS_SORT_TOP_ONLY cannot come back
+    SOTS_REFUSE(ctx, population_bytes_check(ctx->P, ctx->D, values, values_bytes, steps, steps_bytes, fitness, fitness_bytes));
     if (int rc = settle_tail(ctx)) return rc;
     return copy_population(ctx, ctx->rot, true, (void *)values, values_bytes, (void *)steps, steps_bytes,
                            (void *)fitness, fitness_bytes);
@@ -819,7 +821,7 @@ int sots_stage_sort(sots_ctx *ctx)
 int sots_stage_select(sots_ctx *ctx)
 {
     SOTS_REQUIRE_CTX(ctx);
-    const bool lists = ctx->lists_ready; // (filed from the half this selection reads: settle_tail writes the other one)
+    const bool lists = ctx->lists_ready; // (filed from the half this selection reads, after its tail had been completed)
     if (int rc = settle_tail(ctx)) return rc;
     if (int rc = engine_bind(*ctx)) return rc;
     const uint32_t src = ctx->rot, dst = ctx->rot ^ 1u, need = selected_rows(ctx);
@@ -840,6 +842,9 @@ int sots_stage_bucket_fitness(sots_ctx *ctx)
     SOTS_REQUIRE_CTX(ctx);
     if (!lists_possible(ctx)) return SOTS_FAIL(ctx, SOTS_ERR_STATE, "no key lists here: %u splitters per slot, SOTS_SELECT_LISTS=%d", select_splitter_count(ctx->num_cus), (int)ctx->use_lists);
     if (int rc = engine_bind(*ctx)) return rc;
+    // it looks at every row's fitness: the rows a lazy selection left out are produced first (the sots_stage_select that
+    // follows would produce them AFTER their stale fitness had been filed)
+    if (int rc = complete_tail(ctx)) return rc;
     SelLists sl;
     if (int rc = open_lists(ctx, &sl)) return rc;
     SOTS_HIP(ctx, launch_bucket_fitness(ctx->stream, ctx->fit(ctx->rot), ctx->P, sl));

@@ -299,3 +299,31 @@ def test_two_islands_exchange_every_generation_with_lists(pkg, O):
                 assert np.array_equal(x, y, equal_nan=True), f"island {r} after {25 * (chunk + 1)} generations"
     for g in groups:
         g.close()
+
+
+def test_bucket_fitness_files_the_rows_a_lazy_selection_left_out(pkg, O):
+    """A fused generation under SORT_LAZY_TAIL leaves rows S..P-1 of the current half to the first call that looks at them.
+    sots_stage_bucket_fitness looks at every row's fitness: it must produce them first.  By its code it used to file the
+    stale fitness those rows still held, and the sots_stage_select behind it - which completes the tail - then ranked
+    keys of rows that no longer existed (found by reading, while the sequence test's rules were written down).  (Reduced from a sequence of tests/test_gpu_state_machine.py's kind: execute_generations,
+    bucket_fitness, select, rotate under plan SPLITTERS, no read between.)"""
+    parents, offspring = 1024, 3072
+    a, _ = make_pair(pkg, O, parents, offspring, 0, 10)
+    b, _ = make_pair(pkg, O, parents, offspring, 0, 10)
+    tgt, _ = target_audio(O, 0, a.N)
+    b.set_sort_mode(pkg.capi.SORT_FULL)
+    a.set_select_plan(pkg.capi.SELECT_SPLITTERS)
+    for es in (a, b):
+        es.set_target_audio(tgt)
+        es.init_population(0)
+    a.execute_generations(2)
+    a.bucket_fitness()
+    counts, _ = a.read_select_lists()
+    a.select(); a.rotate()
+    b.execute_generation(); b.execute_generation()
+    b.sort(); b.rotate()
+    assert counts.sum() <= a.P  # (every key of a closed bucket is counted, the open bucket counts nothing)
+    for x, y in zip(a.read_population(), b.read_population()):
+        assert np.array_equal(x, y, equal_nan=True)
+    a.close()
+    b.close()

@@ -214,3 +214,27 @@ def test_exchange_inside_the_sort_kernel_equals_the_two_launches(pkg, O, kind, p
         assert np.array_equal(x, y, equal_nan=True)
     # the exchange is used once
     assert not np.all(packs[1] == -3.0)
+
+
+def test_a_refused_write_population_leaves_a_top_only_tail_completable(pkg, O):
+    """A refused call changes nothing.  sots_write_population used to end the pending state before it looked at its byte
+    counts: under SORT_TOP_ONLY the rows S..P-1 could then never be produced, and leaving the mode completed nothing.
+    (Reduced from a sequence of tests/test_gpu_state_machine.py: TOP_ONLY, execute_generations, a write_population of the
+    wrong size, LAZY_TAIL, read.)"""
+    parents, offspring = 1024, 3072
+    full = make(pkg, O, parents, offspring)
+    full.init_population(0)
+    full.execute_generations(2)
+    want = full.read_population()
+    es = make(pkg, O, parents, offspring)
+    es.set_sort_mode(pkg.capi.SORT_TOP_ONLY)
+    es.init_population(0)
+    es.execute_generations(2)
+    with pytest.raises(pkg.SotsError) as e:
+        es.write_population(values=np.zeros((es.P - 1, es.D), np.float32))
+    assert e.value.code == -4  # SOTS_ERR_SIZE
+    es.set_sort_mode(pkg.capi.SORT_LAZY_TAIL)
+    for x, y in zip(es.read_population(), want):
+        assert np.array_equal(x, y)
+    es.close()
+    full.close()
