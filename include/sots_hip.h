@@ -283,6 +283,31 @@ int sots_get_voice_feedback(const sots_ctx *ctx, float index[8]);
 int sots_create_graph_genes(const sots_config *cfg, const sots_voice_graph *graph, uint32_t feedback_genes, sots_ctx **out);
 int sots_get_voice_feedback_genes(const sots_ctx *ctx, uint32_t *feedback_genes);
 
+/* The synthesis FORM of the operator-graph voice (new): which kernel computes the audio.  The three never
+ * differ in a bit of any output - audio, fitness, populations, run record, rendered matches: every value sees the
+ * operations of the definition above in the sample-by-sample order, unfused, in either kernel.
+ *   LANES          a lane per individual (the only form until now): its time does not depend on how many lanes are alive.
+ *   TIME_PARALLEL  the time axis in the lanes, for a few individuals per CU: per operator a wavefront that turns a block
+ *                  of 64 increments into 64 phases, lane = individual, and one or two that evaluate everything else,
+ *                  lane = sample.  A workgroup holds at most sots_graph_time_parallel_capacity() individuals; a larger
+ *                  share of the rows is taken in several groups - correct, not necessarily fast.
+ *   AUTO (default) TIME_PARALLEL where a CU's share of the rows of a launch fits one group and is at most the measured
+ *                  limit, LANES elsewhere.
+ * Whatever is requested, a voice with any feedback index other than 0 (sots_set_voice_feedback) or with feedback genes
+ * (sots_create_graph_genes) runs LANES: a feedback operator's value is a serial chain through a table read.
+ * sots_set_graph_synth_form clears nothing - not the run record, not the stored splitters, not the target.  It refuses a
+ * fixed voice (SOTS_ERR_STATE) and an unknown code (SOTS_ERR_INVALID).  sots_get_graph_synth_form gives the request and
+ * `effective`: what the next synthesis of the context's own population would launch, LANES or TIME_PARALLEL, recomputed
+ * from the current state (either pointer may be NULL, not both). */
+enum sots_graph_synth_form { SOTS_GRAPH_FORM_AUTO = 0, SOTS_GRAPH_FORM_LANES = 1, SOTS_GRAPH_FORM_TIME_PARALLEL = 2 };
+int sots_set_graph_synth_form(sots_ctx *ctx, uint32_t form); /* enum sots_graph_synth_form */
+int sots_get_graph_synth_form(const sots_ctx *ctx, uint32_t *requested, uint32_t *effective);
+/* The individuals a workgroup of the TIME_PARALLEL form holds for this graph (0: the form does not take it) and the
+ * graph's levels (0 for an unmodulated operator, else one more than its deepest modulator; the count is the largest + 1).
+ * Either output may be NULL.  A malformed graph is refused with the graph rule's own text (sots_last_error(NULL)).  Pure
+ * host code: no device, no handle. */
+int sots_graph_time_parallel_capacity(const sots_voice_graph *graph, uint32_t *individuals_per_workgroup, uint32_t *levels);
+
 /* ---- target (replaces setTargetAudio, ...OpenCL.hpp:563-570; Objective::calculateFFT,
  *      Evolutionary_Strategy.hpp:524-542) ---- */
 int sots_set_target_audio(sots_ctx *ctx, const float *audio, uint32_t num_samples);
@@ -759,6 +784,10 @@ int sots_batch_get_voice_feedback(const sots_batch *b, float index[8]);
 int sots_batch_create_graph_genes(const sots_config *cfg, const sots_voice_graph *graph, uint32_t feedback_genes, uint32_t max_chunks,
                                   sots_batch **out);
 int sots_batch_get_voice_feedback_genes(const sots_batch *b, uint32_t *feedback_genes);
+/* sots_set_graph_synth_form for a graph-voice batch (new), in sots_batch_execute_* and sots_batch_queue_run alike: the same
+ * rules and refusals; nothing is cleared.  `effective` is for one launch of all max_chunks x P rows of the batch. */
+int sots_batch_set_graph_synth_form(sots_batch *b, uint32_t form);
+int sots_batch_get_graph_synth_form(const sots_batch *b, uint32_t *requested, uint32_t *effective);
 /* row 0 (the best) of every active chunk: values [active][D], fitness [active] (either may be NULL); blocking */
 int sots_batch_read_best(sots_batch *b, float *values, size_t values_bytes, float *fitness, size_t fitness_bytes);
 /* one active chunk's current half; byte counts as sots_read_population; blocking */

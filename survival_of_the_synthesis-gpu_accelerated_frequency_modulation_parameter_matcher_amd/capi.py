@@ -81,7 +81,11 @@ EXPORTS = [
     "sots_set_voice_waveforms", "sots_get_voice_waveforms", "sots_batch_set_voice_waveforms", "sots_batch_get_voice_waveforms",
     "sots_set_voice_feedback", "sots_get_voice_feedback", "sots_batch_set_voice_feedback", "sots_batch_get_voice_feedback",
     "sots_create_graph_genes", "sots_batch_create_graph_genes", "sots_get_voice_feedback_genes", "sots_batch_get_voice_feedback_genes",
+    "sots_set_graph_synth_form", "sots_get_graph_synth_form", "sots_batch_set_graph_synth_form", "sots_batch_get_graph_synth_form",
+    "sots_graph_time_parallel_capacity",
 ]
+GRAPH_FORM_AUTO, GRAPH_FORM_LANES, GRAPH_FORM_TIME_PARALLEL = 0, 1, 2  # enum sots_graph_synth_form
+GRAPH_FORM_NAMES = {"auto": GRAPH_FORM_AUTO, "lanes": GRAPH_FORM_LANES, "timeParallel": GRAPH_FORM_TIME_PARALLEL}
 ANALYSIS_HOST, ANALYSIS_DEVICE = 0, 1  # enum sots_analysis
 QUEUE_NO_CHUNK = 0xFFFFFFFF
 RENDER_WINDOWED = 1
@@ -142,6 +146,17 @@ def as_voice_graph(graph):
     if graph is None or isinstance(graph, VoiceGraph):
         return graph
     return make_voice_graph(graph["operators"], graph["modulators"], graph["carriers"])
+
+
+def graph_time_parallel_capacity(graph):
+    """(individuals per workgroup, levels) of the graph voice's time-parallel synthesis form for this graph
+    (sots_graph_time_parallel_capacity: host only, no device needed); the library's rule refuses a malformed graph"""
+    cap, levels = C.c_uint32(), C.c_uint32()
+    L = load()
+    rc = L.sots_graph_time_parallel_capacity(C.byref(as_voice_graph(graph)), C.byref(cap), C.byref(levels))
+    if rc != 0:
+        raise SotsError(rc, L.sots_last_error(None).decode())
+    return cap.value, levels.value
 
 
 def _waveform_codes(waveforms):
@@ -398,6 +413,11 @@ def load():
     L.sots_batch_create_graph_genes.argtypes = [C.POINTER(Config), C.POINTER(VoiceGraph), u32, u32, C.POINTER(vp)]
     L.sots_get_voice_feedback_genes.argtypes = [vp, C.POINTER(u32)]
     L.sots_batch_get_voice_feedback_genes.argtypes = [vp, C.POINTER(u32)]
+    L.sots_set_graph_synth_form.argtypes = [vp, u32]
+    L.sots_get_graph_synth_form.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    L.sots_batch_set_graph_synth_form.argtypes = [vp, u32]
+    L.sots_batch_get_graph_synth_form.argtypes = [vp, C.POINTER(u32), C.POINTER(u32)]
+    L.sots_graph_time_parallel_capacity.argtypes = [C.POINTER(VoiceGraph), C.POINTER(u32), C.POINTER(u32)]
     _lib = L
     return L
 
@@ -534,6 +554,18 @@ class HipES:
         mask = C.c_uint32()
         self._check(self.L.sots_get_voice_feedback_genes(self._h, C.byref(mask)))
         return mask.value
+
+    def set_graph_synth_form(self, form):
+        """GRAPH_FORM_AUTO (default), GRAPH_FORM_LANES or GRAPH_FORM_TIME_PARALLEL (enum sots_graph_synth_form), or a
+        GRAPH_FORM_NAMES name: which synthesis kernel the graph voice runs - the same audio bit for bit either way, and
+        nothing is cleared"""
+        self._check(self.L.sots_set_graph_synth_form(self._h, GRAPH_FORM_NAMES.get(form, form)))
+
+    def graph_synth_form(self):
+        """(requested, effective): effective is what the next synthesis of the handle's own rows would launch"""
+        requested, effective = C.c_uint32(), C.c_uint32()
+        self._check(self.L.sots_get_graph_synth_form(self._h, C.byref(requested), C.byref(effective)))
+        return requested.value, effective.value
 
     def info(self):
         i = Info()
@@ -970,6 +1002,18 @@ class HipBatch:
         mask = C.c_uint32()
         self._check(self.L.sots_batch_get_voice_feedback_genes(self._h, C.byref(mask)))
         return mask.value
+
+    def set_graph_synth_form(self, form):
+        """GRAPH_FORM_AUTO (default), GRAPH_FORM_LANES or GRAPH_FORM_TIME_PARALLEL (enum sots_graph_synth_form), or a
+        GRAPH_FORM_NAMES name: which synthesis kernel the graph voice runs - the same audio bit for bit either way, and
+        nothing is cleared"""
+        self._check(self.L.sots_batch_set_graph_synth_form(self._h, GRAPH_FORM_NAMES.get(form, form)))
+
+    def graph_synth_form(self):
+        """(requested, effective): effective is what the next synthesis of the handle's own rows would launch"""
+        requested, effective = C.c_uint32(), C.c_uint32()
+        self._check(self.L.sots_batch_get_graph_synth_form(self._h, C.byref(requested), C.byref(effective)))
+        return requested.value, effective.value
 
     def read_best(self):
         """(values[active][D], fitness[active]): row 0 of every active chunk"""

@@ -315,6 +315,18 @@ int sots_batch_get_voice_feedback_genes(const sots_batch *b, uint32_t *feedback_
     return engine_get_voice_feedback_genes(*b, feedback_genes);
 }
 
+int sots_batch_set_graph_synth_form(sots_batch *b, uint32_t form)
+{
+    BATCH_REQUIRE(b);
+    return engine_set_graph_synth_form(*b, form);
+}
+
+int sots_batch_get_graph_synth_form(const sots_batch *b, uint32_t *requested, uint32_t *effective)
+{
+    BATCH_REQUIRE(b);
+    return engine_get_graph_synth_form(*b, b->rows(), requested, effective);
+}
+
 void sots_batch_destroy(sots_batch *b) { free_batch(b); }
 
 const char *sots_batch_last_error(const sots_batch *b) { return err_of(b).c_str(); }

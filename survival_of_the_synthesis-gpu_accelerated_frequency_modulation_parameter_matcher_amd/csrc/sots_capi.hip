@@ -575,6 +575,28 @@ int sots_get_voice_feedback_genes(const sots_ctx *ctx, uint32_t *feedback_genes)
     return engine_get_voice_feedback_genes(*ctx, feedback_genes);
 }
 
+int sots_set_graph_synth_form(sots_ctx *ctx, uint32_t form)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    return engine_set_graph_synth_form(*ctx, form);
+}
+
+int sots_get_graph_synth_form(const sots_ctx *ctx, uint32_t *requested, uint32_t *effective)
+{
+    SOTS_REQUIRE_CTX(ctx);
+    return engine_get_graph_synth_form(*ctx, ctx->P, requested, effective);
+}
+
+// pure host code: the plan rule of sots_rules.h
+int sots_graph_time_parallel_capacity(const sots_voice_graph *graph, uint32_t *individuals_per_workgroup, uint32_t *levels)
+{
+    if (const Fault f = voice_graph_check(graph)) return SOTS_FAIL(nullptr, f.code, "%s", f.text);
+    const GraphTpPlan plan = graph_tp_plan(*graph);
+    if (individuals_per_workgroup) *individuals_per_workgroup = plan.capacity;
+    if (levels) *levels = plan.levels;
+    return SOTS_OK;
+}
+
 int sots_get_voice_graph(const sots_ctx *ctx, sots_voice_graph *graph)
 {
     SOTS_REQUIRE_CTX(ctx);

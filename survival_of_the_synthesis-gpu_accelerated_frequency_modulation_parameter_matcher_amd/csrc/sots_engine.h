@@ -57,6 +57,7 @@ struct Engine {
     uint32_t waveforms[8] = {0}; // ... and its operators' waveform codes (sots_set_voice_waveforms; all sine until set)
     float feedback[8] = {0};     // ... and their feedback indices (sots_set_voice_feedback; +0, no feedback, until set)
     uint32_t feedback_genes = 0; // ... and the operators whose index is a gene instead (sots_create_graph_genes; theirs above stays +0)
+    uint32_t graph_form = SOTS_GRAPH_FORM_AUTO; // ... and the synthesis form asked for (sots_set_graph_synth_form): a preference, no state depends on it
     PopDims pd{};
     MutateConsts mc{};
     SynthParams sp{};
@@ -211,6 +212,23 @@ inline int engine_get_voice_feedback_genes(const Engine &e, uint32_t *feedback_g
     return SOTS_OK;
 }
 
+// The synthesis form of the graph voice: a preference that changes no bit of any output, so nothing is cleared.
+// own_rows: the rows of one synthesis of the handle's own population(s), for `effective`.
+inline int engine_set_graph_synth_form(Engine &e, uint32_t form)
+{
+    SOTS_REFUSE(e, graph_synth_form_check(e.cfg.synth_kind, form));
+    e.graph_form = form;
+    return SOTS_OK;
+}
+inline int engine_get_graph_synth_form(const Engine &e, uint64_t own_rows, uint32_t *requested, uint32_t *effective)
+{
+    SOTS_REFUSE(e, graph_synth_form_check(e.cfg.synth_kind, SOTS_GRAPH_FORM_AUTO));
+    if (!requested && !effective) return SOTS_FAIL(e, SOTS_ERR_INVALID, "graph synthesis form: null arguments");
+    if (requested) *requested = e.graph_form;
+    if (effective) *effective = graph_synth_form_for(e.graph_form, e.graph, e.feedback, e.feedback_genes, own_rows, e.num_cus);
+    return SOTS_OK;
+}
+
 // ---- objective ----
 // Both setters check everything before anything changes, then leave the objective they replaced in *old: the caller derives
 // what depends on the new one (its target images, its run record) and, where that fails, puts *old back with
@@ -258,6 +276,10 @@ inline hipError_t engine_synthesise(const Engine &e, const float *values, float 
 {
     if (e.synth_arith == SOTS_ARITH_DEVICE_KERNELS)
         return launch_synth_device_arith(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch);
+    // the graph voice makes no individuals (launch_synth refuses a Variation with it): its launcher takes the handle's form
+    if (e.cfg.synth_kind == SOTS_SYNTH_GRAPH && !var)
+        return launch_synth_graph(e.stream, e.graph, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch, e.num_cus, pack_waveforms(e.waveforms),
+                                  e.feedback, e.feedback_genes, e.graph_form);
     return launch_synth(e.stream, e.cfg.synth_kind, values, e.wavetable, audio, e.sp, rows, e.log2n, e.pitch, e.num_cus, var, allow_cut, &e.graph,
                         pack_waveforms(e.waveforms), e.feedback, e.feedback_genes);
 }

@@ -132,10 +132,16 @@ hipError_t launch_synth(hipStream_t st, uint32_t kind, const float *values, cons
 // anything else its shaped sibling.  feedback: the operators' eight checked feedback indices (sots_set_voice_feedback) or
 // null; any index other than 0 launches the feedback sibling, with the codes going through it too.  feedback_genes: the
 // checked mask of sots_create_graph_genes; other than 0, values is [p][2 OPS + popcount] and the gene sibling is launched,
-// with the codes and the fixed indices going through it; 0 launches exactly what is launched without it
+// with the codes and the fixed indices going through it; 0 launches exactly what is launched without it.  form: the handle's
+// enum sots_graph_synth_form; graph_synth_form_for (sots_rules.h) says which kernel these p rows get - LANES launches
+// exactly what was launched before there were forms, TIME_PARALLEL goes to launch_synth_graph_tp
 hipError_t launch_synth_graph(hipStream_t st, const sots_voice_graph &graph, const float *values, const float *wavetable, float *audio,
                               const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus, uint32_t waveforms = 0,
-                              const float *feedback = nullptr, uint32_t feedback_genes = 0);
+                              const float *feedback = nullptr, uint32_t feedback_genes = 0, uint32_t form = SOTS_GRAPH_FORM_LANES);
+// ... its time-parallel form (sots_synth_graph_tp.hip): no feedback, no gene mask; any p (a CU's share beyond the plan's
+// capacity is taken in several groups of rows)
+hipError_t launch_synth_graph_tp(hipStream_t st, const sots_voice_graph &graph, const float *values, const float *wavetable, float *audio,
+                                 const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus, uint32_t waveforms);
 hipError_t launch_window(hipStream_t st, float *audio, const float *window, uint32_t p, uint32_t log2n,
                          uint32_t pitch);
 // audio[P][pitch] -> spectrum[P][N+8]

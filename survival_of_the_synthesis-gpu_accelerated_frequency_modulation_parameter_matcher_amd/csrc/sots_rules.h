@@ -568,6 +568,125 @@ inline Fault render_graph_genes_check(uint32_t kind, const sots_render_graph_fee
     return render_graph_chain_check("sots_render_graph_genes", kind, 0, args, n, d, values, values_bytes, num_rows, out, out_samples);
 }
 
+// ---- time-parallel synthesis of the operator-graph voice (k_synth_graph_tp, sots_synth_graph_tp.hip) ----
+// The PLAN of a checked graph: when each operator runs, how long its output is kept and where its buffers lie.  Computed
+// here and nowhere else; the kernel receives the struct as an argument, so the host's capacity and the kernel's layout
+// cannot disagree.
+// The schedule, in ticks relative to a block's first: operator j SCANS the block at tick_of[j] (a modulated operator first
+// forms its increments from its modulators' outputs) and EVALUATES it at tick_of[j] + 1, which makes its output o_j.
+//   * tick_of[j] >= tick_of[i] + 2 for every modulator i of j (o_i is made strictly before j's scan reads it);
+//   * the MIXER - the carrier with the latest tick, the largest j among equals - sums the carriers in the tick in which it
+//     evaluates, so every other carrier runs at least one tick before it: tick_of[mixer] > tick_of[i];
+//   * the first pass is as soon as possible, 2 x level (graph_levels) and one more for the mixer where another carrier shares
+//     its level; the second, from the last operator down, as late as the readers allow, which shortens the rings.
+// o_j of a block is read until tick last_read = max tick_of[its targets] (a modulator) or tick_of[mixer] + 1 (another
+// carrier), so it needs a RING of depth[j] = last_read - tick_of[j] blocks: the block written depth[j] blocks later lands in
+// the tick after the last read.  The mixer's own output stays in a register: depth 0.  Phases take two blocks per operator.
+// An (individual, block) row is kGraphTpRow floats: 64 samples and 4 of padding, so that the scan's 16-byte accesses of
+// neighbouring lanes fall on different banks (k_synth_tp's row).
+constexpr uint32_t kGraphTpRow = 64 + 4;
+constexpr uint32_t kGraphTpLdsBytes = 31 * 1024; // beside the 128 KiB table
+struct GraphTpPlan {
+    uint32_t ops, levels;
+    uint32_t capacity;   // individuals per workgroup; 0: the graph's rows do not fit
+    uint32_t rows;       // LDS rows per individual: 2 per operator (phases) + the ring depths
+    uint32_t lag;        // ticks beyond the number of blocks: tick_of[mixer] + 1
+    uint32_t mixer, num_carriers;
+    uint32_t evaluators; // evaluating wavefronts per operator: 2 up to five operators, else 1 (at most 16 wavefronts)
+    uint32_t tick_of[kGraphMaxOps], depth[kGraphMaxOps];
+    uint32_t phase_off[kGraphMaxOps], ring_off[kGraphMaxOps]; // in floats, for `capacity` individuals per block
+};
+inline GraphTpPlan graph_tp_plan(const sots_voice_graph &g)
+{
+    GraphTpPlan p{};
+    const GraphLevels lv = graph_levels(g);
+    const uint32_t ops = g.num_operators < kGraphMaxOps ? g.num_operators : kGraphMaxOps;
+    p.ops = ops;
+    p.levels = lv.count;
+    p.evaluators = ops <= 5u ? 2u : 1u;
+    for (uint32_t j = 0; j < ops; ++j) {
+        p.tick_of[j] = 2u * lv.level_of[j];
+        if (g.carriers >> j & 1u) {
+            ++p.num_carriers;
+            if (p.num_carriers == 1u || p.tick_of[j] >= p.tick_of[p.mixer]) p.mixer = j;
+        }
+    }
+    for (uint32_t j = 0; j < ops; ++j)
+        if ((g.carriers >> j & 1u) && j != p.mixer && p.tick_of[j] == p.tick_of[p.mixer]) {
+            ++p.tick_of[p.mixer];
+            break;
+        }
+    // as late as the readers allow, from the last operator down (a reader has a larger index, or is the mixer)
+    for (uint32_t j = ops; j-- > 0;) {
+        if (j == p.mixer) continue;
+        uint32_t latest = ~0u;
+        if (g.carriers >> j & 1u) latest = p.tick_of[p.mixer] - 1u;
+        for (uint32_t k = j + 1; k < ops; ++k)
+            if ((g.modulators[k] >> j & 1u) && p.tick_of[k] - 2u < latest) latest = p.tick_of[k] - 2u;
+        if (latest != ~0u && latest > p.tick_of[j]) p.tick_of[j] = latest;
+    }
+    p.lag = p.tick_of[p.mixer] + 1u;
+    p.rows = 2u * ops;
+    for (uint32_t j = 0; j < ops; ++j) {
+        if (j == p.mixer) continue;
+        uint32_t last_read = 0;
+        if (g.carriers >> j & 1u) last_read = p.tick_of[p.mixer] + 1u;
+        for (uint32_t k = j + 1; k < ops; ++k)
+            if ((g.modulators[k] >> j & 1u) && p.tick_of[k] > last_read) last_read = p.tick_of[k];
+        p.depth[j] = last_read > p.tick_of[j] ? last_read - p.tick_of[j] : 0u;
+        p.rows += p.depth[j];
+    }
+    p.capacity = kGraphTpLdsBytes / (p.rows * kGraphTpRow * (uint32_t)sizeof(float));
+    if (p.capacity > 64u) p.capacity = 64u; // (a lane per individual in the scans)
+    uint32_t at = 0;
+    for (uint32_t j = 0; j < ops; ++j) {
+        p.phase_off[j] = at;
+        at += 2u * p.capacity * kGraphTpRow;
+        p.ring_off[j] = at;
+        at += p.depth[j] * p.capacity * kGraphTpRow;
+    }
+    return p;
+}
+// LDS bytes of a plan's buffers (<= kGraphTpLdsBytes)
+inline uint32_t graph_tp_bytes(const GraphTpPlan &p) { return p.rows * p.capacity * kGraphTpRow * (uint32_t)sizeof(float); }
+
+// Where AUTO takes the time-parallel form: a CU's share of the rows of at most this many individuals, by operator count
+// (index OPS; 0: never).  From profiles/r33_graph_time_parallel.json, one job on one MI355X, the two forms alternating over
+// three rounds on one context: the largest share up to which the form beat the lane form in every round by more than the lane
+// leg's own round-to-round spread, in synthesis launch time and per generation, at N = 1024 and 2048 and at every measured
+// share below it.  For the operator counts measured it did at every share that fits one group - the entries are the
+// capacities of 2op (19), chain3 and two_mods (11), fan3 (8) and triple (5) - and nowhere near: the closest leg is 2op at a
+// share of 19 and N = 1024, 67 against 103 us per launch with a lane spread below 1.  A graph that holds
+// fewer than its count's entry stops at its own capacity.  Graphs of 5, 7 and 8 operators were NOT measured: AUTO keeps the
+// lane form for them until they are.
+constexpr uint32_t kGraphTpAutoShare[kGraphMaxOps + 1] = {0, 0, 19, 11, 8, 0, 5, 0, 0};
+// The form that a synthesis of `rows` rows launches (SOTS_GRAPH_FORM_LANES or SOTS_GRAPH_FORM_TIME_PARALLEL): read by the
+// launcher and by the getters.  Feedback - an index other than 0 or a gene mask - and a graph whose plan holds nobody keep
+// the lane form whatever is requested; a forced TIME_PARALLEL takes any number of rows (in several groups per CU where the
+// share exceeds the capacity); AUTO takes it where the share fits one group and is at most the measured limit.
+inline uint32_t graph_synth_form_for(uint32_t requested, const sots_voice_graph &g, const float *feedback, uint32_t feedback_genes, uint64_t rows,
+                                     uint32_t num_cus)
+{
+    if (requested == SOTS_GRAPH_FORM_LANES || feedback_genes) return SOTS_GRAPH_FORM_LANES;
+    if (feedback)
+        for (uint32_t j = 0; j < kGraphMaxOps && j < g.num_operators; ++j)
+            if (feedback[j] != 0.0f) return SOTS_GRAPH_FORM_LANES;
+    const GraphTpPlan p = graph_tp_plan(g);
+    if (p.capacity == 0) return SOTS_GRAPH_FORM_LANES;
+    if (requested == SOTS_GRAPH_FORM_TIME_PARALLEL) return SOTS_GRAPH_FORM_TIME_PARALLEL;
+    const uint32_t cus = num_cus ? num_cus : 256u;
+    const uint64_t share = (rows + cus - 1u) / cus;
+    return share <= p.capacity && share <= kGraphTpAutoShare[p.ops] ? SOTS_GRAPH_FORM_TIME_PARALLEL : SOTS_GRAPH_FORM_LANES;
+}
+// sots_set_graph_synth_form / sots_get_graph_synth_form: a fixed voice has no forms; an unknown code
+inline Fault graph_synth_form_check(uint32_t kind, uint32_t form)
+{
+    if (kind != SOTS_SYNTH_GRAPH) return fault(SOTS_ERR_STATE, "graph synthesis form: the handle runs a fixed voice (synth_kind %u)", kind);
+    if (form > SOTS_GRAPH_FORM_TIME_PARALLEL)
+        return fault(SOTS_ERR_INVALID, "graph synthesis form: %u is not a form (0 = auto, 1 = lanes, 2 = time-parallel)", form);
+    return Fault{};
+}
+
 // ---- run record, stop rules ----
 constexpr uint64_t kTrackMaxRecords = 1ull << 24; // chunks x history_capacity (1.5 GiB of records)
 // sots_track / sots_batch_track: known flags, a history with a period and room, and no more than kTrackMaxRecords records

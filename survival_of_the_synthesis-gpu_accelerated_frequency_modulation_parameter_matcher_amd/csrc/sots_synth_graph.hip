@@ -381,9 +381,12 @@ hipError_t launch_ops(hipStream_t st, const GraphMasks &gm, const float *values,
 
 hipError_t launch_synth_graph(hipStream_t st, const sots_voice_graph &graph, const float *values, const float *wavetable, float *audio,
                               const SynthParams &sp, uint32_t p, uint32_t log2n, uint32_t pitch, uint32_t num_cus, uint32_t waveforms,
-                              const float *feedback, uint32_t feedback_genes)
+                              const float *feedback, uint32_t feedback_genes, uint32_t form)
 {
     if (p == 0 || log2n < 8 || pitch < (1u << log2n) || pitch % 4u != 0) return hipErrorInvalidValue; // (a flush is 32 samples; 16-byte stores)
+    // the time axis in the lanes (k_synth_graph_tp, sots_synth_graph_tp.hip) where the rule gives these rows to it
+    if (graph_synth_form_for(form, graph, feedback, feedback_genes, p, num_cus) == SOTS_GRAPH_FORM_TIME_PARALLEL)
+        return launch_synth_graph_tp(st, graph, values, wavetable, audio, sp, p, log2n, pitch, num_cus, waveforms);
     GraphMasks gm;
     gm.carriers = graph.carriers;
     for (int j = 0; j < 8; ++j) gm.modulators[j] = graph.modulators[j];

@@ -61,6 +61,9 @@ struct Evolutionary_Strategy_HIP_Arguments
     // graph voice and not with renderMode 3 to 6 (7 and 8 render it): the constructor throws before any device work; the
     // library refuses the rest.
     uint32_t voiceFeedbackGenes = 0;
+    // ... and which synthesis kernel the graph voice runs (type.HIP.graphSynthForm; sots_set_graph_synth_form, DESIGN.md
+    // 4.20): enum sots_graph_synth_form, the same audio bit for bit.  Only with the graph voice, as the waveforms.
+    uint32_t graphSynthForm = 0;
     bool fusedGenerations = true;     // executeAllGenerations uses the fused kernel loop
     // general.isBenchmarking (parameters.json:7, main.cpp:85).  true: every launch is bracketed by a
     // hipEvent pair and lands in the CSV under the reference's stage names (an event pair costs
@@ -239,6 +242,8 @@ private:
         if (!args_.voiceFeedback.empty() &&
             sots_batch_set_voice_feedback(batch_, args_.voiceFeedback.data(), (uint32_t)args_.voiceFeedback.size()) != SOTS_OK)
             throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_batch_set_voice_feedback: ") + sots_batch_last_error(batch_));
+        if (args_.graphSynthForm != 0u && sots_batch_set_graph_synth_form(batch_, args_.graphSynthForm) != SOTS_OK)
+            throw std::runtime_error(std::string("Evolutionary_Strategy_HIP: sots_batch_set_graph_synth_form: ") + sots_batch_last_error(batch_));
     }
     void check(int rc, const char *what) const
     {
@@ -438,6 +443,8 @@ public:
             throw std::runtime_error("Evolutionary_Strategy_HIP: voiceFeedback needs the operator-graph voice");
         if (!graphVoice && args_.voiceFeedbackGenes)
             throw std::runtime_error("Evolutionary_Strategy_HIP: voiceFeedbackGenes need the operator-graph voice");
+        if (!graphVoice && args_.graphSynthForm)
+            throw std::runtime_error("Evolutionary_Strategy_HIP: graphSynthForm needs the operator-graph voice");
         if (args_.renderMode > 8u) throw std::runtime_error("Evolutionary_Strategy_HIP: renderMode must be 0 to 8");
         if (args_.voiceFeedbackGenes && args_.renderMode >= 3u && args_.renderMode <= 6u)
             throw std::runtime_error("Evolutionary_Strategy_HIP: renderMode 3 to 6 take the feedback index from the voice, not from the row: "
@@ -483,6 +490,7 @@ public:
             check(sots_set_voice_waveforms(ctx_, args_.voiceWaveforms.data(), (uint32_t)args_.voiceWaveforms.size()), "sots_set_voice_waveforms");
         if (!args_.voiceFeedback.empty())
             check(sots_set_voice_feedback(ctx_, args_.voiceFeedback.data(), (uint32_t)args_.voiceFeedback.size()), "sots_set_voice_feedback");
+        if (args_.graphSynthForm != 0u) check(sots_set_graph_synth_form(ctx_, args_.graphSynthForm), "sots_set_graph_synth_form");
         if (args_.fullSortEveryGeneration)
             for (uint32_t i = 0; i < numIslands(); ++i)
                 check(sots_set_sort_mode(group_ ? sots_group_island(group_, i) : ctx_, SOTS_SORT_FULL), "sots_set_sort_mode");

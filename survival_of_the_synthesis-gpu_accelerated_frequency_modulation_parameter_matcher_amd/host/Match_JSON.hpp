@@ -456,4 +456,21 @@ inline bool readVoiceFeedbackGenesKey(const Json &h, bool graphVoice, uint32_t o
     return true;
 }
 
+// type.HIP.graphSynthForm (sots_set_graph_synth_form, include/sots_hip.h): which synthesis kernel the graph
+// voice runs, "auto" (the default), "lanes" or "timeParallel" - the same audio bit for bit.  Returns whether the key is
+// there.  Throws - before any device work - without type.HIP.synth "graph" and on any other value.
+inline bool readGraphSynthFormKey(const Json &h, bool graphVoice, uint32_t &form)
+{
+    if (!h.has("graphSynthForm")) return false;
+    const std::string what = "parameters.json: type.HIP.graphSynthForm";
+    if (!graphVoice) throw std::runtime_error(what + " needs type.HIP.synth \"graph\"");
+    const Json &v = h["graphSynthForm"];
+    const std::string s = v.kind == Json::String ? v.str : std::string();
+    if (s == "auto") form = SOTS_GRAPH_FORM_AUTO;
+    else if (s == "lanes") form = SOTS_GRAPH_FORM_LANES;
+    else if (s == "timeParallel") form = SOTS_GRAPH_FORM_TIME_PARALLEL;
+    else throw std::runtime_error(what + " must be \"auto\", \"lanes\" or \"timeParallel\"");
+    return true;
+}
+
 #endif

@@ -41,6 +41,8 @@
 //   "voiceFeedback" with "voiceGraph": one feedback index in [0, 2] per operator, 0 (the default) for none: the operator's phase
 //                 is offset by index x W / 2 pi x the mean of its own last two values (sots_set_voice_feedback), so that a
 //                 sine operator emits a harmonic series whose brightness follows the index.  Used wherever the waveforms are.
+//   "graphSynthForm" with "voiceGraph": "auto" (the default), "lanes" or "timeParallel": which synthesis kernel the graph
+//                 voice runs (sots_set_graph_synth_form) - the same audio bit for bit; refused with any other synth.
 //   "matchPath"   a CSV of the parameter track, one row per chunk:
 //                 chunk,start_sample,generations,fitness,u0..u{D-1},p0..p{D-1} - u the unit-range genes (%.9g: the fp32
 //                 bits), p the scaled parameters; with returnBestEver the best-ever individual of each chunk.
@@ -181,6 +183,8 @@ int main(int argc, char *argv[])
             // ... or chosen operators' indices as genes of the individual: "voiceFeedbackGenes", a 0 or 1 per operator (Match_JSON.hpp)
             (void)readVoiceFeedbackGenesKey(h, graphVoice, args.voiceGraph.num_operators, args.voiceFeedback, args.es_args.pop.numDimensions,
                                             args.es_args.paramMin.size(), args.es_args.paramMax.size(), args.renderMode, args.voiceFeedbackGenes);
+            // ... and which synthesis kernel it runs: "graphSynthForm", "auto", "lanes" or "timeParallel" (Match_JSON.hpp)
+            (void)readGraphSynthFormKey(h, graphVoice, args.graphSynthForm);
             // "graphContinuous" / "graphContinuousGlide" rendering: the graph voice's, without feedback (Match_JSON.hpp)
             checkGraphRenderMode(args.renderMode, graphVoice, args.renderMatch, args.voiceFeedback);
         }
